@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: env-steps/sec of the full K-Bot joystick training iteration (rollout + PPO update).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 For N > 1 either launch it under torchrun (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
 ... bench.py --gpus N ...) or call it directly: it then starts its N ranks itself (a torch.distributed.run child process,
 before this process touches the GPU) and exits with the child's status. Ranks talk over RCCL (backend "nccl").
@@ -9,7 +9,9 @@ before this process touches the GPU) and exits with the child's status. Ranks ta
 One "step" = one training iteration over 8192 envs per GPU (BASELINE.json configs[1]; weak scaling): a 100-control-step
 rollout (policy forward, 5 physics substeps, observations, terminations/resets, rewards) followed by GAE and
 3 passes x 16 minibatches of BPTT + AdamW (launch hyper-parameters train.py:1761-1791, hidden 256).
-Rank 0 prints ONE JSON line; `roofline` and `cpu_baseline` are measured in the same run (N = 1 for the CPU leg).
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs) and
+prints the line; everything else it can measure - `roofline` (one extra instrumented iteration), `cpu_baseline` (N = 1), the
+non-headline legs - runs only with --full, in the same run, and is null in the line otherwise.
 """
 from __future__ import annotations
 
@@ -27,6 +29,7 @@ PEAK_FP32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md chip table
 PEAK_HBM_GBS = 8000.0
 ENV_BYTES_PER_ENVSTEP = 13.3e3  # state r/w + per-env params + trajectory rows
 PATH_BYTES_PER_ENVSTEP = 169e3  # rollout 13.3 KB + update 156 KB (trajectory re-reads + BPTT stash, 3 passes) per env-step
+DUMP_MAX_ELEMENTS = 1_200_000   # --dump-outputs: per array; 13 float32 arrays stay under 64 MB in all
 
 
 def nn_flops_per_envstep(H: int, num_passes: int) -> float:
@@ -37,6 +40,35 @@ def nn_flops_per_envstep(H: int, num_passes: int) -> float:
     critic = 475 * H + lstm + H
     fwd = 2.0 * (actor + critic)
     return fwd * (1 + 3 * num_passes)
+
+
+def dump_outputs(task, out_dir: str) -> int:
+    """--dump-outputs: what the timed path hands its caller after its last step, as float32 `<out_dir>/<name>.npy`: the updated parameters,
+    their AdamW moments and the update's metrics, and the rollout's trajectory (rewards, values, log-probs, GAE advantages / targets, done
+    flags, actions, actor / critic observation rows; [T(+1)][N](x dim), this rank's envs). An array of more than DUMP_MAX_ELEMENTS elements
+    is written as the elements at DUMP_MAX_ELEMENTS of its flat indices, drawn without replacement by a generator seeded with its size and
+    sorted: the same arguments give the same sample in every build. The inputs are seeded and the headline's update reduces in fixed order,
+    so two runs with the same arguments write the same arrays bit for bit (`metrics`, the logged loss terms that feed nothing back, to
+    rounding: the library still sums them with atomics). Returns the bytes written."""
+    import numpy as np
+    import torch
+    tr = task.traj
+    outs = dict(params=task.params, adam_m=task.opt_m, adam_v=task.opt_v, metrics=task.metrics, reward=tr.reward, value=tr.value, log_prob=tr.logp,
+                advantage=tr.adv, target=tr.target, done=tr.done, action=tr.action, actor_obs=tr.actor_obs, critic_obs=tr.critic_obs)
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    total = 0
+    for name, t in outs.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(flat.numel()).choice(flat.numel(), DUMP_MAX_ELEMENTS, replace=False))
+            a = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+        else:
+            a = t.detach().float().cpu().numpy()
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        total += os.path.getsize(path)
+    return total
 
 
 def cpu_baseline(repeats: int = 3):
@@ -222,7 +254,7 @@ def leg_variant(args, cfg_kw, wl) -> dict:
     """Child process: the headline workload with kbj_config.gemm_bf16x3, timed like the headline."""
     import torch
     from kbot_joystick_amd.host.task import HumanoidWalkingTask, launch_config
-    task = HumanoidWalkingTask(launch_config(gemm_bf16x3=True, **cfg_kw, **wl), device=torch.device("cuda", 0))
+    task = HumanoidWalkingTask(launch_config(gemm_bf16x3=True, **dict(cfg_kw, deterministic=False), **wl), device=torch.device("cuda", 0))
     for _ in range(max(1, min(args.warmup, 2))):
         task.train_iteration()
     torch.cuda.synchronize()
@@ -276,6 +308,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--envs-per-gpu", type=int, default=ENVS_PER_GPU)
     ap.add_argument("--hidden", type=int, default=256)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the instrumented roofline iteration (roofline, roofline_secondary, "
+                         "hbm_whole_path, allreduce_ms_per_iteration), the non-headline legs and the CPU baseline; a plain run reports them as null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0) as float32 DIR/<name>.npy, 64 MB at most in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--config", type=int, default=1, choices=[1, 3, 4],
                     help="BASELINE.json configs[i] workload: 1 = the metric's (kbot-headless, flat, fixed command); 3 = UnifiedCommand "
@@ -329,7 +366,9 @@ def main():
     wl_name = {1: "kbot-headless, {n} envs/GPU, flat ground, fixed joystick command (0.5,0,0)",
                3: "kbot-headless, {n} envs/GPU, flat ground, UnifiedCommand 6-mode sampler",
                4: "kbot (full), {n} envs/GPU, sine terrain (A 0.05 m, L 2 m), UnifiedCommand sampler, pushes + all randomizers"}[args.config]
-    cfg_kw = dict(num_envs=args.envs_per_gpu * world, hidden_size=args.hidden, seed=0, allreduce=args.allreduce)
+    # the update's reductions in fixed order (kbj_config.deterministic) instead of fp32 / fp64 atomics: with the same arguments every run computes
+    # the same outputs bit for bit (+2 % per step). The bf16 x3 variant has no fixed-order form and keeps the atomics.
+    cfg_kw = dict(num_envs=args.envs_per_gpu * world, hidden_size=args.hidden, seed=0, allreduce=args.allreduce, deterministic=not args.gemm_bf16x3)
     if args.leg:       # child process of a one-GPU bench.py: one non-headline leg, one JSON object
         if world != 1:
             sys.exit("bench.py: --leg is the one-GPU child of bench.py")
@@ -375,6 +414,9 @@ def main():
         dist_util.FORCE_COLLECTIVE = True                                  # world size 1 would skip the collective
         forced = dict(ms_per_step_no_process_group=round(plain / args.steps * 1e3, 2))
     elapsed = timed_steps(args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(task, args.dump_outputs)
+        print(f"bench.py: wrote the last timed step's outputs to {args.dump_outputs} ({dumped / 1e6:.1f} MB)", file=sys.stderr, flush=True)
     rank_ms = [elapsed / args.steps * 1e3]
     if world > 1:
         ts = [torch.zeros(1, device="cuda", dtype=torch.float64) for _ in range(world)]
@@ -390,19 +432,21 @@ def main():
     env_steps = args.envs_per_gpu * world * task.T * args.steps
     value = env_steps / elapsed
 
-    # ---- roofline leg: one extra iteration with HIP-event timing inside the library (rank 0) ----
+    # ---- roofline leg (--full): one extra iteration with HIP-event timing inside the library (rank 0) ----
     roofline = roofline2 = hbm = None
-    if rank == 0:
-        task.ctx.profile_begin()
-        dist_util.TIMING = []          # events around every gradient all-reduce of the instrumented iteration
-    task.train_iteration()   # every rank takes part (gradient all-reduce); only rank 0 is instrumented
-    torch.cuda.synchronize()
-    allreduce_ms, allreduce_calls = 0.0, 0
-    if rank == 0:
+    allreduce_ms = allreduce_calls = None
+    if args.full:
+        if rank == 0:
+            task.ctx.profile_begin()
+            dist_util.TIMING = []          # events around every gradient all-reduce of the instrumented iteration
+        task.train_iteration()   # every rank takes part (gradient all-reduce); only rank 0 is instrumented
+        torch.cuda.synchronize()
+        allreduce_ms, allreduce_calls = 0.0, 0
+    if args.full and rank == 0:
         allreduce_calls = len(dist_util.TIMING)
         allreduce_ms = float(sum(a.elapsed_time(b) for a, b in dist_util.TIMING))
         dist_util.TIMING = None
-    if rank == 0:
+    if args.full and rank == 0:
         prof = task.ctx.profile_end()
         nn_s = prof["nn_ms"] * 1e-3
         env_s = prof["env_step_ms"] * 1e-3
@@ -450,7 +494,7 @@ def main():
     # checkpoints. A hard fault or hang in either costs its own object, not the line.
     variant = train_loop = None
     rollout_steps = task.T
-    if not args.gemm_bf16x3 and not args.no_variants and not args.force_collective and world == 1:
+    if args.full and not args.gemm_bf16x3 and not args.no_variants and not args.force_collective and world == 1:
         # (one GPU only: a multi-rank job reports its headline and nothing else)
         task.ctx.synchronize(); task.close(); task = None      # the headline context goes first: the child has the GPU to itself
         torch.cuda.empty_cache()
@@ -461,7 +505,8 @@ def main():
         if train_loop.get("value"):
             train_loop["vs_headline"] = round(train_loop["value"] / value, 4)
     if forced is not None:      # third leg: the actor's gradient slice all-reduced on a second stream under the critic's tail
-        forced.update(ms_per_step_forced_allreduce=round(elapsed / args.steps * 1e3, 2), allreduce_ms_per_iteration=round(allreduce_ms, 3),
+        forced.update(ms_per_step_forced_allreduce=round(elapsed / args.steps * 1e3, 2),
+                      allreduce_ms_per_iteration=None if allreduce_ms is None else round(allreduce_ms, 3),
                       allreduce_calls_per_iteration=allreduce_calls)
         task.config.overlap_allreduce = True
         forced["ms_per_step_forced_allreduce_overlapped"] = round(timed_steps(1, args.steps) / args.steps * 1e3, 2)
@@ -475,25 +520,25 @@ def main():
             dist.destroy_process_group()
         return
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline()
     out = {
         "metric": "env-steps/sec (whole node), K-Bot joystick 8192 envs @1/2/4/8 MI355X",
-        "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
         "ms_per_step": round(elapsed / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32" if not args.gemm_bf16x3 else "f32 (backward GEMMs: exact 3-way bf16 split of the fp32 operands, fp32 accumulation)", "data": "synthetic",
         "variant": "headline: plain fp32-MFMA kernels" if not args.gemm_bf16x3 else "NOT THE HEADLINE: --gemm-bf16x3 (kbj_config.gemm_bf16x3)",
         "config": {"workload": ("[variant gemm_bf16x3] " if args.gemm_bf16x3 else "") + wl_name.format(n=args.envs_per_gpu) + ", full iteration: "
                                f"100-step rollout + PPO update (batch 512/GPU, 3 passes, LSTM hidden {args.hidden}, depth 2)",
                    "envs_per_gpu": args.envs_per_gpu, "rollout_steps": rollout_steps, "batch_size_per_gpu": cfg.batch_size, "num_passes": cfg.num_passes,
-                   "hidden_size": args.hidden, "baseline_config": args.config, "parallelism": f"env-sharded dp{world}, grad all-reduce {'per optimizer step' if args.allreduce == 'per_step' else 'once per pass (accumulated)'}"
+                   "hidden_size": args.hidden, "baseline_config": args.config, "deterministic_update": bool(cfg.deterministic), "parallelism": f"env-sharded dp{world}, grad all-reduce {'per optimizer step' if args.allreduce == 'per_step' else 'once per pass (accumulated)'}"
                                   + (f" [{args.backend}{', ranks share GPU 0' if args.share_gpu else ''}]" if world > 1 else "")},
         "roofline": roofline, "roofline_secondary": roofline2, "cpu_baseline": cpu,
         # data-parallel exchange: ranks in the process group (1 = no collective runs), gradient all-reduce time of one iteration (HIP events
         # around every dist.all_reduce of the instrumented iteration, rank 0) and the whole-path HBM fraction
         "rccl_ranks": pg_ranks, "rccl_ranks_counted_by_allreduce": pg_counted, "collective_backend": pg_backend,
         "rank_ms_per_step": {"min": round(min(rank_ms), 2), "max": round(max(rank_ms), 2)}, "forced_collective": forced,
-        "allreduce_ms_per_iteration": round(allreduce_ms, 3), "allreduce_calls_per_iteration": allreduce_calls,
+        "allreduce_ms_per_iteration": None if allreduce_ms is None else round(allreduce_ms, 3), "allreduce_calls_per_iteration": allreduce_calls,
         "hbm_whole_path": hbm,
         "variant_gemm_bf16x3": variant,
         # the number launch() delivers: the same workload through the reference-shaped training loop (logging + validation + checkpoints)

@@ -284,14 +284,14 @@ def test_bench_launches_its_own_ranks():
 
 
 def test_bench_line_carries_the_child_process_legs():
-    """`bench.py --gpus 1` (the driver's own invocation, at a small size): after the headline is measured the two NON-headline legs run in child
+    """`bench.py --gpus 1 --full` (at a small size): after the headline is measured the two NON-headline legs run in child
     processes - `variant_gemm_bf16x3` and `train_loop` (launch() with logging, validation rollouts and background checkpoints) - and a leg that
     dies costs its own object, never the line."""
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--envs-per-gpu", "512", "--hidden", "64", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--loop-iterations", "30"]
+           "--full", "--no-cpu-baseline", "--loop-iterations", "30"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -310,13 +310,13 @@ def test_bench_line_carries_the_child_process_legs():
 
 
 def test_bench_forced_collective_on_one_gpu():
-    """`bench.py --gpus 1 --force-collective`: the RCCL leg (backend nccl, world size 1, gradient all-reduce forced) timed beside the run
+    """`bench.py --gpus 1 --force-collective --full`: the RCCL leg (backend nccl, world size 1, gradient all-reduce forced) timed beside the run
     without a process group and the overlapped exchange, in one process; the rank count of the line comes from the process group and an
-    all-reduce of ones, not from the environment."""
+    all-reduce of ones, not from the environment; the all-reduce time comes from --full's instrumented iteration."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29547")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-collective", "--envs-per-gpu", "1024", "--hidden", "64",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-collective", "--full", "--envs-per-gpu", "1024", "--hidden", "64",
                           "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -327,6 +327,39 @@ def test_bench_forced_collective_on_one_gpu():
         assert fc[k] > 0
     assert abs(rec["ms_per_step"] - fc["ms_per_step_forced_allreduce"]) < 1e-6
     assert rec["rank_ms_per_step"]["min"] <= rec["rank_ms_per_step"]["max"]
+
+
+def test_plain_bench_run_reports_the_headline_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: one JSON line with the headline fields and none of what needs
+    runs of its own (roofline, all-reduce timing, CPU baseline, child legs: null); DIR holds the last timed step's outputs as float32 .npy
+    files, 64 MB at most. The headline's update reduces in fixed order, so two runs with the same arguments compute the same: after a
+    warm-up and two timed iterations every array is bit-identical (the logged metrics, still summed with atomics, to rounding)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--envs-per-gpu", "512", "--hidden", "64", "--steps", "2",
+                              "--warmup", "1", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=env)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        rec = json.loads(lines[0])
+        assert rec["value"] > 0 and rec["unit"] == "env-steps/s" and rec["higher_is_better"] is True and rec["dtype"] == "f32"
+        assert rec["steps"] == 2 and rec["full"] is False and abs(rec["value"] - 512 * 100 / (rec["ms_per_step"] * 1e-3)) < 1e-3 * rec["value"]
+        assert rec["config"]["deterministic_update"] is True
+        for k in ("roofline", "roofline_secondary", "hbm_whole_path", "allreduce_ms_per_iteration", "cpu_baseline", "variant_gemm_bf16x3", "train_loop"):
+            assert rec[k] is None, k
+        files = sorted(glob.glob(str(d / "*.npy")))
+        assert sum(os.path.getsize(f) for f in files) <= 64e6
+        arrs = {os.path.basename(f)[:-4]: np.load(f) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        dumps.append(arrs)
+    a, b = dumps
+    assert set(a) == set(b) >= {"params", "metrics", "reward", "done", "action", "actor_obs", "critic_obs"}
+    assert a["reward"].shape == (100, 512) and a["action"].shape == (100, 512, L.NU)
+    for k in sorted(set(a) - {"metrics"}):
+        assert a[k].shape == b[k].shape and np.array_equal(a[k], b[k]), k
+    assert np.allclose(a["metrics"], b["metrics"], rtol=1e-5, atol=1e-7)
 
 
 def test_python_termination_and_observation_terms():

@@ -7,10 +7,10 @@ import pytest
 
 from kbot_joystick_amd.spec import compiler, constants as K, layout as L
 
-REF = "/root/reference/robot"
+# robot.mjcf + metadata.json of the reference's robot/<name>/ (the only files the compiler reads), stored as test fixtures
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "robot")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference assets are only present in the build container")
 @pytest.mark.parametrize("name", ["kbot", "kbot-headless"])
 def test_committed_blob_matches_compiler(name):
     m = compiler.compile_model(os.path.join(REF, name))

@@ -55,7 +55,7 @@ def main():
         git = None
     cmd = os.environ.get("KBJ_PROFILE_CMD") or ""
     m_steps, m_warm = re.search(r"--steps\s+(\d+)", cmd), re.search(r"--warmup\s+(\d+)", cmd)
-    iters = (int(m_steps.group(1)) if m_steps else 3) + (int(m_warm.group(1)) if m_warm else 1) + 1      # + bench.py's instrumented roofline iteration
+    iters = (int(m_steps.group(1)) if m_steps else 3) + (int(m_warm.group(1)) if m_warm else 1) + ("--full" in cmd.split())   # + the instrumented roofline iteration of bench.py --full
     out["_meta"] = dict(source_fingerprint=source_fingerprint(), git=git, command=cmd or None, iterations=iters)
     json.dump(out, sys.stdout, indent=1)
     print()
