@@ -71,21 +71,9 @@ def test_policy_step_matches_oracle(H, N):                                      
 
 
 def _synthetic_traj(torch, buffers, N, T, H, seed=0, mirror=False, depth=2):
-    g = torch.Generator(device="cpu").manual_seed(seed)
+    from tests import helpers
     tr = buffers.TrajBuffers(T, N, H, depth, "cuda:0", mirror=mirror)
-    tr.actor_obs[:, :, :65] = (torch.randn(T + 1, N, 65, generator=g) * 0.5).cuda()
-    tr.critic_obs[:, :, :475] = (torch.randn(T + 1, N, 475, generator=g) * 0.5).cuda()
-    tr.action.copy_(torch.randn(T, N, 20, generator=g) * 0.3)
-    done = (torch.rand(T, N, generator=g) < 0.15).float() * torch.where(torch.rand(T, N, generator=g) < 0.5, -1.0, 1.0)
-    tr.aux[:T, :, L.AUX["DONE"]] = done.cuda()
-    tr.reward.copy_(torch.rand(T, N, generator=g))
-    tr.carry0_actor_hc.copy_(torch.randn(depth, 2, N, H, generator=g) * 0.3)
-    tr.carry0_critic_hc.copy_(torch.randn(depth, 2, N, H, generator=g) * 0.3)
-    tr.carry0_lpf.copy_(torch.randn(N, 20, generator=g) * 0.2)
-    if mirror:
-        tr.carry0_actor_mirror_hc.copy_(torch.randn(depth, 2, N, H, generator=g) * 0.3)
-        tr.carry0_critic_mirror_hc.copy_(torch.randn(depth, 2, N, H, generator=g) * 0.3)
-        tr.carry0_lpf_mirror.copy_(torch.randn(N, 20, generator=g) * 0.2)
+    helpers.fill_traj(tr, helpers.synthetic_arrays(N, T, H, seed, depth, mirror))       # the same draws as CPU tensors: shared with the oracle-only tests
     return tr
 
 
