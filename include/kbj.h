@@ -170,6 +170,22 @@ int kbj_rollout(kbj_ctx* ctx, const float* params_d, kbj_carry* carry, uint32_t 
  * mode. 0 restores sampling. (kbj_policy_step takes the flag per call.) */
 int kbj_set_rollout_argmax(kbj_ctx* ctx, int argmax);
 
+/* ---- episode metrics ------------------------------------------------------------------------ */
+/* replaces: the episode metrics of the reference's logger (episodic return, episode length, which termination ended the episodes, the
+ * per-episode sum of every reward term). That logger is ksim's, un-vendored: its metric list is UPSTREAM MEMORY, not a cited line.
+ * An episode outlives a rollout (up to max_episode_steps = 600 control steps against 100), so the sums are carried per env ACROSS calls in
+ * acc_d [N][KBJ_EACC_SIZE] fp32, device memory of the caller like kbj_carry (zero it once; save it with the env state), updated in place.
+ * For every env n independently, for t = 0 .. T-1 in ascending order:
+ *   acc[RETURN] += reward[t][n];  acc[LENGTH] += 1;  acc[TERM + k] += reward_comps[t][n][k] (skipped when traj->reward_comps_d is NULL);
+ *   if aux[t][n][KBJ_AUX_DONE] != 0 the episode ends here: it enters the call's statistics with its cause (kbj_model.h KBJ_EPST_*: the
+ *   sign of DONE, and for a failure the env kernel's own height test on the record's BASEZ / LFZ / RFZ) and the row's 14 sums return to 0.
+ * The accumulations are plain fp32 adds in exactly this order (a float32 loop on the host reproduces acc_d bit for bit). stats_d
+ * [KBJ_EPST_SIZE] doubles is OVERWRITTEN with the statistics of the episodes that finished inside this trajectory; the reduction over
+ * the envs runs in double, in a fixed order, without atomics: the same inputs give bit-identical results on every call.
+ * Reads traj->aux_d, traj->reward_d and, if present, traj->reward_comps_d (call it behind kbj_rollout / kbj_rewards and whatever the host
+ * adds to the rewards); asynchronous on the context's stream. acc_d and reward_comps_d must be 16-byte aligned. */
+int kbj_episode_stats(kbj_ctx* ctx, const kbj_traj* traj, float* acc_d, double* stats_d);
+
 /* ---- PPO update, rows a9, a12, a13 ---------------------------------------------------------- */
 /* replaces: ksim GAE (gamma, lam: train.py:1769-1770). done from aux; adv_d/target_d [T][N] */
 int kbj_gae(kbj_ctx* ctx, const kbj_traj* traj, float* adv_d, float* target_d);

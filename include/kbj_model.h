@@ -270,6 +270,33 @@ enum {
   KBJ_QSTATE_SIZE     = 80
 };
 
+/* ---- episode accounting (kbj_episode_stats) ----
+ * Per-env accumulator row ("EACC" record, fp32, owned by the caller on the device like kbj_carry): what the env's RUNNING episode has
+ * collected so far; carried from one rollout to the next, zeroed when the episode ends. */
+enum {
+  KBJ_EACC_RETURN = 0,   /* sum of reward since the episode started */
+  KBJ_EACC_LENGTH = 1,   /* control steps since the episode started (integer valued) */
+  KBJ_EACC_TERM   = 2,   /* [12] sums of the unscaled reward terms, KBJ_REW_* order (stay 0 without kbj_traj.reward_comps_d) */
+  KBJ_EACC_SIZE   = 16   /* 64-byte rows; the two spare floats are left as they are */
+};
+/* One call's result ("EPST" record, doubles): statistics of the episodes that FINISHED inside the trajectory. The cause slots double as
+ * the cause codes. With no finished episode RETURN_MIN = +inf, RETURN_MAX = -inf, LENGTH_MAX = 0; spare slots are 0. */
+enum {
+  KBJ_EPST_EPISODES        = 0,   /* episodes that finished in this trajectory = the sum of the next three */
+  KBJ_EPST_FAIL_HEIGHT     = 1,   /* done < 0 and BASEZ - fminf(LFZ, RFZ) < unhealthy_z (the env kernel's own fp32 expression) */
+  KBJ_EPST_FAIL_OTHER      = 2,   /* done < 0 otherwise (tilt only, or a user Termination term's -1) */
+  KBJ_EPST_TRUNCATED       = 3,   /* done > 0 (episode length, or a user term's +1) */
+  KBJ_EPST_RETURN_SUM      = 4,   /* over the finished episodes: sum of the fp32 episodic return, */
+  KBJ_EPST_RETURN_SUMSQ    = 5,   /* of its square (taken in double), */
+  KBJ_EPST_RETURN_MIN      = 6,   /* its minimum */
+  KBJ_EPST_RETURN_MAX      = 7,   /* and maximum */
+  KBJ_EPST_LENGTH_SUM      = 8,   /* sum of the episode lengths (control steps), */
+  KBJ_EPST_LENGTH_MAX      = 9,   /* the longest, */
+  KBJ_EPST_FAIL_LENGTH_SUM = 10,  /* the sum over the done < 0 episodes only */
+  KBJ_EPST_TERM_SUM        = 12,  /* [12] sum over the finished episodes of the episodic reward-term sums, KBJ_REW_* order */
+  KBJ_EPST_SIZE            = 32
+};
+
 /* reward component order (train.py:1225-1256) */
 enum {
   KBJ_REW_LINVEL = 0, KBJ_REW_ANGVEL, KBJ_REW_ROLL_PITCH, KBJ_REW_BASE_HEIGHT, KBJ_REW_ARM_POS,

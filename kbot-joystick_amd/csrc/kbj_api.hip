@@ -169,6 +169,7 @@ int kbj_destroy(kbj_ctx* ctx) {
   if (ctx->ep_d) hipFree(ctx->ep_d);
   if (ctx->es_d) hipFree(ctx->es_d);
   if (ctx->rcarry_d) hipFree(ctx->rcarry_d);
+  if (ctx->epst_part_d) hipFree(ctx->epst_part_d);
   if (ctx->ev0) hipEventDestroy(ctx->ev0);
   if (ctx->ev1) hipEventDestroy(ctx->ev1);
   for (int k = 0; k < 32; ++k) if (ctx->ev_pool[k]) hipEventDestroy(ctx->ev_pool[k]);

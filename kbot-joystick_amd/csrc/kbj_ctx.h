@@ -45,6 +45,8 @@ struct kbj_ctx {
   uint32_t seed = 0;
   int rollout_argmax = 0;       // kbj_set_rollout_argmax: kbj_rollout acts with the distribution's mode (validation rollouts, train.py:1564)
   float* qstate_next = nullptr; // kbj_env_record_state: where the next kbj_env_step writes its state record (one-shot)
+  double* epst_part_d = nullptr;  // kbj_episode_stats: workgroup partials [epst_part_blocks][KBJ_EPST_SIZE], allocated by the first call
+  int epst_part_blocks = 0;
   // NN workspace (kbj_nn.hip)
   void* nn_ws = nullptr;
   size_t nn_ws_bytes = 0;

@@ -1,7 +1,9 @@
 // kbj_env.hip — HIP kernels + C-ABI entry points of the environment side of the hot path:
-// kbj_env_reset_all / kbj_env_step (one wavefront = one env, state in LDS; kbj_env_*.h) and kbj_rewards.
+// kbj_env_reset_all / kbj_env_step (one wavefront = one env, state in LDS; kbj_env_*.h), kbj_rewards and kbj_episode_stats
+// (kbj_episode_stats.h).
 #include <hip/hip_runtime.h>
 #include "kbj_env_task.h"
+#include "kbj_episode_stats.h"
 #include "kbj_ctx.h"
 
 using namespace kbj;
@@ -414,6 +416,28 @@ int kbj_rewards(kbj_ctx* ctx, const float* aux_d, int T, float* reward_d, float*
   hipLaunchKernelGGL(rewards_kernel, dim3((N + 63) / 64), dim3(64), 0, ctx->stream, ctx->model_d, ctx->cfg_d, aux_d, T, N, ctx->rcarry_d,
                      reward_d, comps_d);
   KBJ_CHECK_LAUNCH(ctx, "rewards_kernel");
+  return 0;
+}
+
+int kbj_episode_stats(kbj_ctx* ctx, const kbj_traj* tr, float* acc_d, double* stats_d) {
+  if (!ctx || !tr || !acc_d || !stats_d) return kbj_fail(ctx, "kbj_episode_stats: null argument");
+  if (!tr->aux_d || !tr->reward_d || tr->T <= 0 || tr->N <= 0) return kbj_fail(ctx, "kbj_episode_stats: the trajectory needs aux_d, reward_d and positive T, N");
+  if ((reinterpret_cast<uintptr_t>(acc_d) | reinterpret_cast<uintptr_t>(tr->reward_comps_d)) & 15)
+    return kbj_fail(ctx, "kbj_episode_stats: acc_d and reward_comps_d must be 16-byte aligned");
+  KBJ_HIP(ctx, hipSetDevice(ctx->device));
+  kbj_nn_drop_prefetch(ctx);
+  const int blocks = (tr->N + EPST_ENVS - 1) / EPST_ENVS;
+  if (blocks > ctx->epst_part_blocks) {   // first call of the context (or a wider trajectory than any before): never per call
+    if (ctx->epst_part_d) KBJ_HIP(ctx, hipFree(ctx->epst_part_d));
+    ctx->epst_part_d = nullptr; ctx->epst_part_blocks = 0;
+    KBJ_HIP(ctx, hipMalloc(&ctx->epst_part_d, (size_t)blocks * KBJ_EPST_SIZE * sizeof(double)));
+    ctx->epst_part_blocks = blocks;
+  }
+  hipLaunchKernelGGL(episode_stats_kernel, dim3(blocks), dim3(EPST_THREADS), 0, ctx->stream, tr->aux_d, tr->reward_d, tr->reward_comps_d, tr->T, tr->N,
+                     ctx->cfg_h.unhealthy_z, acc_d, ctx->epst_part_d);
+  KBJ_CHECK_LAUNCH(ctx, "episode_stats_kernel");
+  hipLaunchKernelGGL(episode_stats_reduce_kernel, dim3(1), dim3(EPST_THREADS), 0, ctx->stream, ctx->epst_part_d, blocks, stats_d);
+  KBJ_CHECK_LAUNCH(ctx, "episode_stats_reduce_kernel");
   return 0;
 }
 

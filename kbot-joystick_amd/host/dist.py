@@ -2,7 +2,10 @@
 (RCCL over xGMI on the GPU job, gloo in the CPU tests). The 1/world scale is applied inside kbj_adamw_step."""
 from __future__ import annotations
 
+import numpy as np
 import torch
+
+from ..spec import layout as L
 
 
 def env_shard(num_envs_total: int, rank: int, world_size: int) -> tuple[int, int]:
@@ -57,3 +60,42 @@ def global_advantage_sums(adv_minibatch: torch.Tensor, world_size: int) -> torch
         import torch.distributed as dist
         dist.all_reduce(sums, op=dist.ReduceOp.SUM)
     return sums
+
+
+# kbj_episode_stats vectors (kbj_model.h KBJ_EPST_*): every slot is a count or a sum over the finished episodes, except these three
+_EPST_MIN, _EPST_MAX, _EPST_LENGTH_MAX = L.EPST["RETURN_MIN"], L.EPST["RETURN_MAX"], L.EPST["LENGTH_MAX"]
+
+
+def empty_episode_stats() -> np.ndarray:
+    """The KBJ_EPST vector of no finished episode: zeros, RETURN_MIN = +inf, RETURN_MAX = -inf."""
+    v = np.zeros(L.EPST["SIZE"], np.float64)
+    v[_EPST_MIN], v[_EPST_MAX] = np.inf, -np.inf
+    return v
+
+
+def combine_episode_stats(vectors) -> np.ndarray:
+    """Statistics of the union of the episode sets that the given KBJ_EPST vectors describe (other ranks' envs, or later rollouts): counts
+    and sums add up in list order, in float64; minimum, maximum and longest episode are taken over the list. Pure host arithmetic, the same
+    that reduce_episode_stats performs with collectives."""
+    out = empty_episode_stats()
+    for v in vectors:
+        v = np.asarray(v, np.float64)
+        lo, hi, longest = min(out[_EPST_MIN], v[_EPST_MIN]), max(out[_EPST_MAX], v[_EPST_MAX]), max(out[_EPST_LENGTH_MAX], v[_EPST_LENGTH_MAX])
+        out = out + v
+        out[_EPST_MIN], out[_EPST_MAX], out[_EPST_LENGTH_MAX] = lo, hi, longest
+    return out
+
+
+def reduce_episode_stats(vec: torch.Tensor, world_size: int) -> torch.Tensor:
+    """combine_episode_stats over the data-parallel ranks: `vec` [..., EPST SIZE] float64 holds this rank's KBJ_EPST vector(s); returns the
+    vector(s) of all ranks' envs together. ONE SUM all-reduce over the counts and sums, ONE MAX all-reduce over (max, -min, longest).
+    Collective: every rank calls it, at logging cadence (HumanoidWalkingTask.episode_stats()), never inside the update."""
+    if world_size > 1 or FORCE_COLLECTIVE:
+        import torch.distributed as dist
+        ext = torch.stack([vec[..., _EPST_MAX], -vec[..., _EPST_MIN], vec[..., _EPST_LENGTH_MAX]], dim=-1).contiguous()
+        vec = vec.clone()
+        vec[..., _EPST_MIN] = 0.0; vec[..., _EPST_MAX] = 0.0       # summed with the rest, overwritten below: keep them finite
+        dist.all_reduce(vec, op=dist.ReduceOp.SUM)
+        dist.all_reduce(ext, op=dist.ReduceOp.MAX)
+        vec[..., _EPST_MAX], vec[..., _EPST_MIN], vec[..., _EPST_LENGTH_MAX] = ext[..., 0], -ext[..., 1], ext[..., 2]
+    return vec

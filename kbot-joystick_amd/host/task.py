@@ -84,6 +84,11 @@ class HumanoidWalkingTaskConfig:
     terrain_amplitude: float = 0.05         # metres; the surface definition is this build's own
     terrain_wavelength: float = 2.0
     log_reward_components: bool = False     # keep the 12 unscaled reward terms of every rollout for logging (39 MB at 8192 x 100)
+    # episode accounting on the device (kbj_episode_stats): episodic return, true episode length, termination causes and - with
+    # log_reward_components - the per-episode sum of every reward term, carried per env across rollouts and through checkpoints;
+    # read with task.episode_stats(), merged into scalars() / validate(). Off (the default; KBJ_EPISODE_STATS in the environment overrides
+    # it, for A/B runs with tools/ab_bench.py): nothing is allocated, launched or logged.
+    episode_stats: bool = dataclasses.field(default_factory=lambda: os.environ.get("KBJ_EPISODE_STATS", "0") not in ("0", ""))
     # keep qpos / qvel of every env-step (kbj_traj.qstate_d, 262 MB at 8192 x 100): the Python reward terms (extra_rewards) then see a
     # ksim-shaped `host.trajectory.Trajectory` - trajectory.qpos / .qvel / .xpos / .xquat / .obs[...] / .command["unified_command"] as the
     # reference's reward classes read them (train.py:138-506) - instead of the narrower TrajectoryView of the aux record
@@ -179,6 +184,31 @@ def cosine_decay_lr(config: HumanoidWalkingTaskConfig, count: int) -> float:
     frac = min(max(count, 0), config.lr_decay_steps) / config.lr_decay_steps
     cosine = 0.5 * (1.0 + math.cos(math.pi * frac))
     return config.learning_rate * ((1.0 - config.lr_final_multiplier) * cosine + config.lr_final_multiplier)
+
+
+def episode_stats_scalars(vec, ctrl_dt: float, prefix: str = "episode/", terms: bool = False) -> dict:
+    """One KBJ_EPST vector (kbj_model.h; layout.EPST) as logger scalars. Means over the finished episodes are omitted when there are none
+    (and the time to failure when none of them failed): a mean of nothing is not a number worth plotting."""
+    E = L.EPST
+    n = float(vec[E["EPISODES"]])
+    out = {prefix + "count": n}
+    if n <= 0:
+        return out
+    mean = float(vec[E["RETURN_SUM"]]) / n
+    out[prefix + "return_mean"] = mean
+    out[prefix + "return_std"] = math.sqrt(max(float(vec[E["RETURN_SUMSQ"]]) / n - mean * mean, 0.0))
+    out[prefix + "return_min"], out[prefix + "return_max"] = float(vec[E["RETURN_MIN"]]), float(vec[E["RETURN_MAX"]])
+    out[prefix + "length_s_mean"] = float(vec[E["LENGTH_SUM"]]) / n * ctrl_dt
+    out[prefix + "length_s_max"] = float(vec[E["LENGTH_MAX"]]) * ctrl_dt
+    fails = float(vec[E["FAIL_HEIGHT"]] + vec[E["FAIL_OTHER"]])
+    if fails > 0:
+        out[prefix + "time_to_failure_s_mean"] = float(vec[E["FAIL_LENGTH_SUM"]]) / fails * ctrl_dt
+    for key, slot in (("frac_fail_height", "FAIL_HEIGHT"), ("frac_fail_other", "FAIL_OTHER"), ("frac_truncated", "TRUNCATED")):
+        out[prefix + key] = float(vec[E[slot]]) / n
+    if terms:
+        for k, name in enumerate(constants.REWARD_NAMES):
+            out[f"{prefix}reward/{name}"] = float(vec[E["TERM_SUM"] + k]) / n
+    return out
 
 
 def launch_config(**overrides) -> HumanoidWalkingTaskConfig:
@@ -278,6 +308,18 @@ class HumanoidWalkingTask:
                              "(extra_observations={name: (term, 'actor' | 'critic' | 'both')})")
         self.traj = TrajBuffers(self.T, self.N, self.H, self.kcfg.depth, self.device, mirror=self.mirror, reward_comps=config.log_reward_components,
                                 ld_actor=self.ld_actor, ld_critic=self.ld_critic, record_state=config.record_state)
+        # episode accounting (config.episode_stats): per-env accumulator rows next to the env state, one call's result, and on the host the
+        # last rollout's vector and the totals since creation / resume. The result comes back through a pinned buffer behind the kernel
+        # (no sync in the loop); it is folded into the totals when the next rollout starts or when somebody asks.
+        self.ep_acc = self.ep_stats = None
+        if config.episode_stats:
+            self.ep_acc = torch.zeros(self.N, L.EACC["SIZE"], device=self.device)
+            self.ep_stats = torch.zeros(L.EPST["SIZE"], dtype=torch.float64, device=self.device)
+            self._ep_host = torch.zeros(L.EPST["SIZE"], dtype=torch.float64).pin_memory()
+            self._ep_event = torch.cuda.Event()
+            self._ep_pending = False
+            self._ep_last = dist_util.empty_episode_stats()
+            self._ep_total = dist_util.empty_episode_stats()
         self.opt_step = 0
         self.iteration = 0
         self._perm_gen = torch.Generator(device="cpu")
@@ -315,6 +357,45 @@ class HumanoidWalkingTask:
         if self.extra_rewards:
             from .traj_view import apply_extra_rewards
             self.extra_reward_means = apply_extra_rewards(self.extra_rewards, self._extra_carries, self.trajectory(), self.traj.reward)
+        if self.ep_acc is not None:               # behind the user rewards, so that they count; user terminations are in the DONE column already
+            self._fold_episode_stats()
+            self.ctx.episode_stats(self.traj.c, self.ep_acc, self.ep_stats)
+            self._ep_host.copy_(self.ep_stats, non_blocking=True)
+            self._ep_event.record()
+            self._ep_pending = True
+
+    def _fold_episode_stats(self):
+        """The last kbj_episode_stats result, once its copy has landed, becomes `_ep_last` and joins the totals."""
+        if self._ep_pending:
+            self._ep_event.synchronize()
+            self._ep_last = self._ep_host.numpy().copy()
+            self._ep_total = dist_util.combine_episode_stats([self._ep_total, self._ep_last])
+            self._ep_pending = False
+
+    def episode_stats_vectors(self):
+        """(last, total): this rank's raw KBJ_EPST vectors (float64 numpy, layout.EPST) behind episode_stats() - the episodes that finished in
+        the last rollout and all since creation / resume."""
+        if self.ep_acc is None:
+            raise B.KbjError("episode_stats_vectors() needs HumanoidWalkingTaskConfig.episode_stats=True")
+        self._fold_episode_stats()
+        return self._ep_last.copy(), self._ep_total.copy()
+
+    def episode_stats(self) -> dict:
+        """Episode metrics (needs `episode_stats=True` in the config): `episode/...` over the episodes that finished in the LAST rollout,
+        `episode_total/...` over all that finished since the task was created or resumed - count, return mean / std / min / max, length
+        and time to failure in seconds, fractions per termination cause and, with `log_reward_components`, the mean episodic sum of every
+        reward term. In a multi-rank job the vectors are reduced over the ranks (dist.reduce_episode_stats): every rank must call it."""
+        if self.ep_acc is None:
+            raise B.KbjError("episode_stats() needs HumanoidWalkingTaskConfig.episode_stats=True")
+        self._fold_episode_stats()
+        last, total = self._ep_last, self._ep_total
+        if self.world_size > 1 or dist_util.FORCE_COLLECTIVE:
+            both = dist_util.reduce_episode_stats(torch.from_numpy(np.stack([last, total])).to(self.device), self.world_size).cpu().numpy()
+            last, total = both[0], both[1]
+        terms = self.traj.comps is not None
+        out = episode_stats_scalars(last, self.config.ctrl_dt, "episode/", terms)
+        out.update(episode_stats_scalars(total, self.config.ctrl_dt, "episode_total/", terms))
+        return out
 
     def trajectory(self):
         """The last rollout as the Python reward terms see it: with `config.record_state` a ksim-shaped `host.trajectory.Trajectory`
@@ -608,6 +689,9 @@ class HumanoidWalkingTask:
         if self.mirror:
             extras.update(actor_mirror_hc=self.carry.actor_mirror_hc.cpu().numpy(), critic_mirror_hc=self.carry.critic_mirror_hc.cpu().numpy(),
                           lpf_mirror=self.carry.lpf_mirror.cpu().numpy())
+        if self.ep_acc is not None:      # episodes in flight and the totals so far (the last rollout's own vector is not state)
+            self._fold_episode_stats()
+            extras.update(ep_acc=self.ep_acc.cpu().numpy(), ep_total=self._ep_total.copy())
         # carries of Python StatefulReward terms (extra_rewards): tensors (or tuples / lists of tensors) per term name
         import numpy as np
         for name, carry in self._extra_carries.items():
@@ -671,6 +755,17 @@ class HumanoidWalkingTask:
         self._command_started = self.iteration > 0      # a resumed run's row 0 already carries the user command term's commands
         self._resets_started = self.iteration > 0       # ... and its env rows the user Reset terms' state
         x = z["extras"]
+        if self.ep_acc is not None:
+            # episode accounting: the members when the saved run kept them (same env count), else from zero - episodes already running
+            # are then counted from here on (an old checkpoint, a run saved with the switch off, a model-only file)
+            self._ep_pending = False
+            self._ep_last = dist_util.empty_episode_stats()
+            if "ep_acc" in x and "ep_total" in x and tuple(x["ep_acc"].shape) == tuple(self.ep_acc.shape) and x["ep_total"].shape == (L.EPST["SIZE"],):
+                self.ep_acc.copy_(torch.from_numpy(np.ascontiguousarray(x["ep_acc"], np.float32)))
+                self._ep_total = np.array(x["ep_total"], np.float64)
+            else:
+                self.ep_acc.zero_()
+                self._ep_total = dist_util.empty_episode_stats()
         if "es" not in x:
             return            # a model-only checkpoint (e.g. written by the reference): parameters and optimizer only
         if x["es"].shape[0] != self.N:
@@ -776,6 +871,10 @@ class HumanoidWalkingTask:
                 _capture(vctx, t + 1)
         if not fused:
             vctx.rewards(tr.aux, T, tr.reward, tr.comps)
+        if self.ep_acc is not None:     # the same kernel on the validation trajectory: every validation starts its episodes afresh
+            vacc = torch.zeros(num_envs, L.EACC["SIZE"], device=self.device)
+            vstats = torch.zeros(L.EPST["SIZE"], dtype=torch.float64, device=self.device)
+            vctx.episode_stats(tr.c, vacc, vstats)
         vctx.synchronize()
         done = tr.done
         fails, succ = float((done < 0).sum()), float((done > 0).sum())
@@ -783,6 +882,8 @@ class HumanoidWalkingTask:
                "valid/episode_length_s": float(T * num_envs / max(1.0, fails + succ + num_envs) * self.config.ctrl_dt), "valid/value_mean": float(tr.value.mean())}
         for name, v in zip(constants.REWARD_NAMES, tr.comps.mean(dim=(0, 1)).cpu().tolist()):
             out[f"valid/reward/{name}"] = v
+        if self.ep_acc is not None:
+            out.update(episode_stats_scalars(vstats.cpu().numpy(), self.config.ctrl_dt, "valid/episode/", terms=True))
         return out
 
     def close_validation(self):
@@ -836,6 +937,8 @@ class HumanoidWalkingTask:
         if self.traj.comps is not None:
             for name, v in self.reward_components().items():
                 out[f"reward/{name}"] = v
+        if self.ep_acc is not None:      # the result came back behind the kernel: the sync above is already past it
+            out.update(self.episode_stats())
         return out
 
     def export_actor(self, path: str):
