@@ -85,6 +85,7 @@ int kbj_create(kbj_ctx** out, const void* model_blob, size_t model_bytes, const 
   kbj_ctx* ctx = new kbj_ctx();
   std::memcpy(&ctx->model_h, model_blob, sizeof(kbj_model));
   ctx->cfg_h = *cfg;
+  ctx->set = kbj_read_settings(ctx->cfg_h);
   std::string why;
   if (!topology_ok(ctx->model_h, why)) { delete ctx; return kbj_fail(nullptr, "kbj_create: " + why); }
   {
@@ -127,19 +128,13 @@ int kbj_create(kbj_ctx** out, const void* model_blob, size_t model_bytes, const 
   // (6.66 -> 6.61 ms per minibatch then). Round 6 (default): the critic's chain runs on the CALLER's stream (kbj_nn.hip Sched::critic_on_caller: no
   // queue hop between the optimizer step and the chain's two ends), stream2 carries the actor's chain and gets the normal priority - it has
   // ~0.3 ms of slack and should not take CUs from the critic where they compete (measured: normal 354.7 / high 355.3 ms, then 350.7 / 350.9).
-  {
-    int lo = 0, hi = 0;
-    KBJ_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    const char* cl = getenv("KBJ_CRITIC_LANE");
-    const bool critic_on_stream2 = cl && std::string(cl) == "2nd";
-    KBJ_TRY(hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, critic_on_stream2 ? hi : (lo + hi) / 2));
-  }
+  int prio_least = 0, prio_greatest = 0;
+  KBJ_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+  KBJ_TRY(hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, ctx->set.sched.critic_on_caller ? (prio_least + prio_greatest) / 2 : prio_greatest));
   // The side lanes carry work that hangs off the critical chain of the update (weight-gradient GEMMs, bias sums) and the critic of the
   // rollout: lowest queue priority, so that when a dX GEMM of the chain and a dW GEMM compete for CUs the chain's workgroups go first.
   // Nearly zero-sum (the dX GEMMs finish in 520 instead of 756 us, but the displaced dW GEMMs then run beside the backward recurrences,
   // which slow from 895 to 1209 us): 6.91 -> 6.86 ms per minibatch, 444.2 -> 441.8 ms per iteration.
-  int prio_least = 0, prio_greatest = 0;
-  KBJ_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
   for (int n = 0; n < 2; ++n) {
     KBJ_TRY(hipStreamCreateWithPriority(&ctx->side[n], hipStreamNonBlocking, prio_least));
     KBJ_TRY(hipEventCreateWithFlags(&ctx->ev_side[n], hipEventDisableTiming));

@@ -19,6 +19,46 @@ inline int kbj_kind_gemm_x3(int tm, bool a_kc, bool b_kc, bool gen) {
   return gen ? KBJ_KIND_GEMM_X3_SMALL_GEN : KBJ_KIND_GEMM_X3_SMALL;
 }
 
+// Formulation switches of the schedule. A test process builds contexts under different settings; every non-default value below is exercised
+// by a parity test (tests/test_gpu_switches.py) and README.md lists exactly these. `deterministic` comes from kbj_config (KBJ_DETERMINISTIC=1
+// forces it on).
+struct Sched {
+  bool fold_actor = true;          // KBJ_FOLD_ACTOR=0: actor input projection as its own GEMM (65 -> H -> 4H) instead of folded into layer 0
+  bool fold_critic = true;         // KBJ_FOLD_CRITIC=0: critic layer-0 backward through dX0 instead of Z = dG0^T obs
+  bool fuse_ih = true;             // KBJ_SEQ_FUSE=0: input products x W_ih^T as GEMM launches in front of the forward recurrences
+  bool fuse_obs = true;            // KBJ_SEQ_FUSE_OBS=0: the folded actor layer 0 as a GEMM launch instead of inside its recurrence
+  bool fused_critic_head = true;   // KBJ_FUSED_CRITIC_HEAD=0: critic head as output GEMM + value kernel + loss kernel + K = 1 GEMM
+  bool rollout_step = true;        // KBJ_ROLLOUT_STEP=0: rollout layers as [x | h] gate GEMM + cell kernel instead of lstm_step_kernel
+  bool one_stream = false;         // KBJ_ONE_STREAM=1: the whole update on the caller's stream (no lanes); forced for wide layers whose two recurrences would not be resident together
+  bool debug_sync = false;         // KBJ_DEBUG=1: kbj_ppo_grad synchronises and reports device-side errors at the call that caused them
+  bool deterministic = false;      // fixed-order reductions instead of fp32 / fp64 atomics (bit-reproducible update)
+  bool bwd16 = true;               // KBJ_BWD16=0: backward recurrences on the 32-row x 32-unit form of rounds 1-4 (lstm_seq_bwd_kernel) instead of 16-row x 64-unit
+                                   // tiles with the partner-major contraction (kbj_lstm_bwd16.h: 620 instead of 907 us per launch in situ)
+  bool critic_on_caller = true;    // KBJ_CRITIC_LANE=2nd: the critic's chain on the context's SECOND stream (rounds 1-5). Default (round 6): the critic - the longer
+                                   // chain, the one a minibatch waits for - runs on the caller's stream, so that nothing between the optimizer step and the
+                                   // critic's first kernel, nor between its last kernel and the next optimizer step, crosses a queue (a cross-queue event wait
+                                   // costs 10-25 us on this runtime); the actor's chain, which has ~0.3 ms of slack, takes the second stream and the hops.
+                                   // kbj_create gives the second stream its queue priority from this same value
+  bool gemm_x3 = false;            // kbj_config.gemm_bf16x3 / KBJ_GEMM_X3=1: the GEMM launches that are eligible (the update's input gradients, weight-gradient
+                                   // pairs and critic input projection, the rollout's [x | h] gate GEMMs) on the bf16 matrix cores through the exact three-way
+                                   // operand split (kbj_gemm.h gemm_x3_kernel); not the default, not the headline
+};
+
+struct KbjSettings {
+  Sched sched;
+  int seq_timeout_ms = 0;          // wall-clock bound of the recurrences' inter-workgroup waits (kbj_lstm_seq.h seq_wait): 2 s by default, KBJ_SEQ_TIMEOUT_MS=n
+                                   // (clamped to 1..30000) overrides, 20 ms under fault injection
+  // fault injection for the tests (KBJ_DEBUG_DROP_SEQ_WG = n, KBJ_DEBUG_DROP_SEQ_BWD_WG = n): the context's next n forward / backward recurrence
+  // launches run with one workgroup missing, so its partners' bounded spins expire and the timeout / fail-stop path is exercised on real
+  // hardware. Counted down per affected launch.
+  int seq_drop = 0, seq_drop_bwd = 0;
+  // diagnostics: per-step clock stamps of one workgroup of one recurrence launch, 1 + net + 2 * layer picks the launch
+  bool seq_stamps = false; int stamp_sel = 1;     // KBJ_SEQ_STAMPS (forward)
+  bool seq_bstamps = false; int bstamp_sel = 0;   // KBJ_SEQ_BSTAMPS (backward; needs the bstamps build)
+};
+
+KbjSettings kbj_read_settings(const kbj_config& cfg);   // kbj_nn.hip
+
 struct kbj_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -35,6 +75,7 @@ struct kbj_ctx {
   int ev_next = 0;
   kbj_model model_h;
   kbj_config cfg_h;
+  KbjSettings set;              // the environment's say about this context (kbj_read_settings, once, in kbj_create); the fault-injection counters count down here
   kbj_model* model_d = nullptr;
   kbj_config* cfg_d = nullptr;
   void* pc_d = nullptr;         // kbj::PhysConst (kbj_env_core.h): solver / impedance / terrain constants derived from the config, computed at create

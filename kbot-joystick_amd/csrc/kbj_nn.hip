@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <algorithm>
+#include <type_traits>
 #include "kbj_ctx.h"
 #include "kbj_gemm.h"
 #include "kbj_nn_kernels.h"
@@ -27,43 +28,23 @@ struct TrainBufs {  // per net, minibatch-sized
   float *obs, *X0, *G[MAXD], *Hm[MAXD], *Hout[MAXD], *Cm[MAXD], *TanhC[MAXD], *Out, *dOut, *dHa, *dHb, *dGl[MAXD];
 };
 
-// Formulation switches of the schedule. Read from the environment ONCE PER CONTEXT (kbj_create), so that a test process can build contexts
-// under different settings; every non-default value below is exercised by a parity test (tests/test_gpu_switches.py) and README.md lists
-// exactly these. `deterministic` comes from kbj_config (KBJ_DETERMINISTIC=1 forces it on).
-struct Sched {
-  bool fold_actor = true;          // KBJ_FOLD_ACTOR=0: actor input projection as its own GEMM (65 -> H -> 4H) instead of folded into layer 0
-  bool fold_critic = true;         // KBJ_FOLD_CRITIC=0: critic layer-0 backward through dX0 instead of Z = dG0^T obs
-  bool fuse_ih = true;             // KBJ_SEQ_FUSE=0: input products x W_ih^T as GEMM launches in front of the forward recurrences
-  bool fuse_obs = true;            // KBJ_SEQ_FUSE_OBS=0: the folded actor layer 0 as a GEMM launch instead of inside its recurrence
-  bool fused_critic_head = true;   // KBJ_FUSED_CRITIC_HEAD=0: critic head as output GEMM + value kernel + loss kernel + K = 1 GEMM
-  bool rollout_step = true;        // KBJ_ROLLOUT_STEP=0: rollout layers as [x | h] gate GEMM + cell kernel instead of lstm_step_kernel
-  bool one_stream = false;         // KBJ_ONE_STREAM=1: the whole update on the caller's stream (no lanes)
-  bool debug_sync = false;         // KBJ_DEBUG=1: kbj_ppo_grad synchronises and reports device-side errors at the call that caused them
-  bool deterministic = false;      // fixed-order reductions instead of fp32 / fp64 atomics (bit-reproducible update)
-  bool bwd16 = true;               // KBJ_BWD16=0: backward recurrences on the 32-row x 32-unit form of rounds 1-4 (lstm_seq_bwd_kernel) instead of 16-row x 64-unit
-                                   // tiles with the partner-major contraction (kbj_lstm_bwd16.h: 620 instead of 907 us per launch in situ)
-  bool critic_on_caller = true;    // KBJ_CRITIC_LANE=2nd: the critic's chain on the context's SECOND stream (rounds 1-5). Default (round 6): the critic - the longer
-                                   // chain, the one a minibatch waits for - runs on the caller's stream, so that nothing between the optimizer step and the
-                                   // critic's first kernel, nor between its last kernel and the next optimizer step, crosses a queue (a cross-queue event wait
-                                   // costs 10-25 us on this runtime); the actor's chain, which has ~0.3 ms of slack, takes the second stream and the hops
-  bool gemm_x3 = false;            // kbj_config.gemm_bf16x3 / KBJ_GEMM_X3=1: the GEMM launches that are eligible (the update's input gradients, weight-gradient
-                                   // pairs and critic input projection, the rollout's [x | h] gate GEMMs) on the bf16 matrix cores through the exact three-way
-                                   // operand split (kbj_gemm.h gemm_x3_kernel); not the default, not the headline
+// where every leaf sits in the flat parameter vector of a given hidden size
+struct ParamLayout {
+  NetOff net[2];
+  size_t nparams = 0, nactor = 0;
+  int D = 2;
 };
-bool env_flag(const char* name, bool dflt) { const char* v = getenv(name); return v ? atoi(v) != 0 : dflt; }
 
-constexpr int MAX_PAD_DESC = 2 * (4 + 3 * MAXD);
-
-struct NnWs {
-  Sched sched;
-  int H = 0, N = 0, B = 0, T = 0, D = 2;
+struct NnWs : ParamLayout {   // (the base: the layout at the kernels' H)
+  Sched& sched;               // the context's (kbj_ctx::set)
+  explicit NnWs(Sched& s) : sched(s) {}
+  int H = 0, N = 0, B = 0, T = 0;
   // hidden_size is free (train.py:78-81); the kernels tile hidden units in groups of 64. Hu = the caller's value, H = the kernels'.
   // Hu != H: every entry point that takes parameters, carries or a gradient converts at the boundary (zero padding is exact for this
   // network: a padded unit has zero weights and bias, so its gates are sigma(0), tanh(0), its cell stays 0, its output 0, and every
   // gradient into or out of it is 0) and runs the H-wide schedule on the internal copies below.
   int Hu = 0;
-  bool inner = false;                 // set while an entry point runs on the internal copies
-  size_t unparams = 0, unactor = 0;   // parameter counts in the caller's layout
+  ParamLayout user;                   // the caller's layout (Hu)
   PadDesc* pad_desc = nullptr; int npad = 0;
   float *pparams = nullptr, *pgrad = nullptr;
   float *phc[4] = {nullptr, nullptr, nullptr, nullptr}, *pc0[4] = {nullptr, nullptr, nullptr, nullptr};   // carries / trajectory start carries [D][2][N][H]
@@ -73,8 +54,6 @@ struct NnWs {
   size_t skws_cap[4] = {0, 0, 0, 0};
   float* detp[4] = {nullptr, nullptr, nullptr, nullptr};   // [512][1024] floats each
   double* detd = nullptr;                                    // [512][2] doubles (advantage statistics, gradient norm)
-  NetOff net[2];
-  size_t nparams = 0, nactor = 0;
   // rollout scratch
   float *rX[4] = {nullptr, nullptr, nullptr, nullptr}, *rG[4] = {nullptr, nullptr, nullptr, nullptr}, *rOut[4] = {nullptr, nullptr, nullptr, nullptr};
   float* joint_bias_d = nullptr;
@@ -99,6 +78,7 @@ struct NnWs {
   const double* ext_adv_sums = nullptr;   // kbj_set_advantage_sums: (sum adv, sum adv^2, count) on the device, used instead of the minibatch's own statistics
   unsigned* seq_counters = nullptr;  // per row-group arrival counters of the persistent LSTM kernels
   unsigned* seq_err = nullptr;       // spin-timeout flag
+  unsigned seq_timeout_ticks = 0;    // KbjSettings::seq_timeout_ms in wall_clock64 ticks of this device
   bool counters_clean = false;       // the hand-off counters were cleared at the tail of the last kbj_ppo_grad (per lane, behind its last recurrence): the next call skips its own clear
   bool sumsq_clean = false;          // stats[10] (the gradient's sum of squares) has been zeroed by kbj_ppo_grad's own clear and not used since: kbj_adamw_step skips its memset
   int seq_grid = 0, seq_slots = 0;   // workgroups of one recurrence launch / resident workgroups of the worst-fitting recurrence kernel (kbj_recurrence_residency)
@@ -109,12 +89,13 @@ struct NnWs {
 
 NnWs* ws_of(kbj_ctx* ctx) { return reinterpret_cast<NnWs*>(ctx->nn_ws); }
 
-void layout_params(NnWs& w, int H, int D, int extra_actor = 0, int extra_critic = 0) {
-  w.D = D;
+ParamLayout layout_params(const kbj_config& c, int H) {
+  ParamLayout p;
+  const int D = p.D = c.depth;
   size_t off = 0;
   for (int n = 0; n < 2; ++n) {
-    NetOff& o = w.net[n];
-    o.nin = n == 0 ? KBJ_NOBS_ACTOR + extra_actor : KBJ_NOBS_CRITIC + extra_critic;     // user observation columns behind the reference's (kbj_model.h)
+    NetOff& o = p.net[n];
+    o.nin = n == 0 ? KBJ_NOBS_ACTOR + c.extra_obs_actor : KBJ_NOBS_CRITIC + c.extra_obs_critic;     // user observation columns behind the reference's (kbj_model.h)
     o.ld_obs = KBJ_LD_OF(o.nin);
     o.nout = n == 0 ? 2 * KBJ_NU : 1;
     o.w_in = off; off += (size_t)H * o.nin;
@@ -126,10 +107,15 @@ void layout_params(NnWs& w, int H, int D, int extra_actor = 0, int extra_critic 
     }
     o.w_out = off; off += (size_t)o.nout * H;
     o.b_out = off; off += o.nout;
-    if (n == 0) w.nactor = off;
+    if (n == 0) p.nactor = off;
   }
-  w.nparams = off;
+  p.nparams = off;
+  return p;
 }
+
+// the carries of net n (0 actor, 1 critic, 2 / 3 their mirror branches) in a kbj_carry, the start carries in a kbj_traj
+template <class C> auto& carry_hc(C& c, int n) { return n == 0 ? c.actor_hc_d : n == 1 ? c.critic_hc_d : n == 2 ? c.actor_mirror_hc_d : c.critic_mirror_hc_d; }
+template <class T> auto& traj_carry0(T& t, int n) { return n == 0 ? t.carry0_actor_hc_d : n == 1 ? t.carry0_critic_hc_d : n == 2 ? t.carry0_actor_mirror_hc_d : t.carry0_critic_mirror_hc_d; }
 
 // Mirror of the packed observation rows as (source index, multiplier, offset) per element (mirror_rows_kernel).
 // Follows the index/sign lists of the reference's mirror_obs functions (train.py:1574-1756); element order = the obs packing
@@ -188,7 +174,6 @@ template <class T> int dalloc(kbj_ctx* ctx, NnWs& w, T** p, size_t count) {
   return 0;
 }
 
-thread_local int g_gemm_x3 = 0;     // set by kbj_ppo_grad from the context's schedule for the duration of the call (the wrappers below have no context)
 constexpr int g_fold_sk = 8;        // k slices of the small W_ih0^T Z product of the folded input projections
 #ifndef KBJ_SPLITK_WGS
 #define KBJ_SPLITK_WGS 768   // re-swept in round 5 under the four-launches-together schedule: 256 / 384 / 512 / 768 / 1024 -> 6.10 / 6.0 / 5.96 / 5.86 / 5.95 ms per minibatch
@@ -199,8 +184,24 @@ constexpr int DETP_ROWS = 512, DETP_COLS = 4 * 512;   // (columns: one gate row 
 // lane index of a stream of this context (deterministic-mode workspaces are per lane: launches on different lanes overlap)
 int lane_of(kbj_ctx* ctx, hipStream_t s) { return s == ctx->stream ? 0 : (s == ctx->stream2 ? 1 : (s == ctx->side[0] ? 2 : 3)); }
 // split-K slab workspace of the lane of stream s, grown on demand (deterministic mode only; null otherwise = atomics)
-float* sk_workspace(kbj_ctx* ctx, hipStream_t s, size_t floats);
-float* det_partials(kbj_ctx* ctx, hipStream_t s);
+float* sk_workspace(kbj_ctx* ctx, hipStream_t s, size_t floats) {
+  NnWs& w = *ws_of(ctx);
+  if (!w.sched.deterministic) return nullptr;
+  const int l = lane_of(ctx, s);
+  if (w.skws_cap[l] < floats) {   // grows during the first calls only; nothing may still be reading the old slab
+    hipDeviceSynchronize();
+    if (w.skws[l]) hipFree(w.skws[l]);
+    w.skws[l] = nullptr; w.skws_cap[l] = 0;
+    void* q = nullptr;
+    if (hipMalloc(&q, floats * sizeof(float)) != hipSuccess) { kbj_fail(ctx, "hipMalloc (deterministic split-K workspace)"); return nullptr; }
+    w.skws[l] = reinterpret_cast<float*>(q); w.skws_cap[l] = floats;
+  }
+  return w.skws[l];
+}
+float* det_partials(kbj_ctx* ctx, hipStream_t s) {
+  NnWs& w = *ws_of(ctx);
+  return w.sched.deterministic ? w.detp[lane_of(ctx, s)] : nullptr;
+}
 
 inline dim3 g1(size_t n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
 
@@ -209,14 +210,14 @@ void linear_fwd(hipStream_t s, const float* x, int lda, const float* W, int ldw,
   GemmArgs g{x, W, y, bias, M, N, K, lda, ldw, ldy, beta, 1, nullptr};
   gemm_launch<true, true>(s, g);
 }
-// dx = dy W   (dy [M][K=nout] , W [K][N])
-void linear_bwd_input(hipStream_t s, const float* dy, int lddy, const float* W, int ldw, float* dx, int lddx, int M, int N, int K, int beta, int tile = -1) {
+// dx = dy W   (dy [M][K=nout] , W [K][N]). x3 here and below: the caller's Sched::gemm_x3
+void linear_bwd_input(hipStream_t s, bool x3, const float* dy, int lddy, const float* W, int ldw, float* dx, int lddx, int M, int N, int K, int beta, int tile = -1) {
   GemmArgs g{dy, W, dx, nullptr, M, N, K, lddy, ldw, lddx, beta, 1, nullptr};
-  g.x3 = g_gemm_x3;
-  gemm_launch<true, false>(s, g, g_gemm_x3 ? -1 : tile);   // tile = 2: 64 x 128 tiles (kbj_gemm.h: few 128 x 128 tiles quantise badly)
+  g.x3 = x3;
+  gemm_launch<true, false>(s, g, x3 ? -1 : tile);   // tile = 2: 64 x 128 tiles (kbj_gemm.h: few 128 x 128 tiles quantise badly)
 }
 // dW[Nout][Nin] += dy^T x  (dy [R][Nout], x [R][Nin]); split-K over the R samples with atomics (dW pre-zeroed by the caller)
-void linear_bwd_weight(kbj_ctx* ctx, hipStream_t s, const float* dy, int lddy, const float* x, int ldx, float* dW, int lddw, int Nout, int Nin, int R) {
+void linear_bwd_weight(kbj_ctx* ctx, hipStream_t s, bool x3, const float* dy, int lddy, const float* x, int ldx, float* dW, int lddw, int Nout, int Nin, int R) {
   // the long contraction (R = T*B samples) is split over the grid: 128x128 tiles when the output allows it, ~768 workgroups
   bool big = Nout >= 128 && Nin >= 128;
   int ts = big ? 128 : 64;
@@ -225,17 +226,17 @@ void linear_bwd_weight(kbj_ctx* ctx, hipStream_t s, const float* dy, int lddy, c
   sk = std::max(2, std::min(sk, (R + 255) / 256));
   GemmArgs g{dy, x, dW, nullptr, Nout, Nin, R, lddy, ldx, lddw, 1, sk, nullptr};  // always the split-K path: accumulates into dW
   g.skws = sk_workspace(ctx, s, (size_t)sk * Nout * Nin);
-  g.x3 = g_gemm_x3;
+  g.x3 = x3;
   gemm_launch<false, false>(s, g, big ? 1 : 0);
 }
 
 // two weight gradients that share dy in one launch: dW1 += dy^T x1, dW2 += dy^T x2 (x1, x2 [R][Nin] with the same ld)
-void linear_bwd_weight2(kbj_ctx* ctx, hipStream_t s, const float* dy, int lddy, const float* x1, const float* x2, int ldx, float* dW1, float* dW2, int lddw, int Nout, int Nin, int R) {
+void linear_bwd_weight2(kbj_ctx* ctx, hipStream_t s, bool x3, const float* dy, int lddy, const float* x1, const float* x2, int ldx, float* dW1, float* dW2, int lddw, int Nout, int Nin, int R) {
   bool big = Nout >= 128 && Nin >= 128;
   int ts = big ? 128 : 64;
   if (Nin % ts != 0) {  // the column split must fall on a tile boundary
-    linear_bwd_weight(ctx, s, dy, lddy, x1, ldx, dW1, lddw, Nout, Nin, R);
-    linear_bwd_weight(ctx, s, dy, lddy, x2, ldx, dW2, lddw, Nout, Nin, R);
+    linear_bwd_weight(ctx, s, x3, dy, lddy, x1, ldx, dW1, lddw, Nout, Nin, R);
+    linear_bwd_weight(ctx, s, x3, dy, lddy, x2, ldx, dW2, lddw, Nout, Nin, R);
     return;
   }
   int tiles = ((Nout + ts - 1) / ts) * (2 * Nin / ts);
@@ -244,7 +245,7 @@ void linear_bwd_weight2(kbj_ctx* ctx, hipStream_t s, const float* dy, int lddy, 
   GemmArgs g{dy, x1, dW1, nullptr, Nout, 2 * Nin, R, lddy, ldx, lddw, 1, sk, nullptr};
   g.B2 = x2; g.C2 = dW2; g.n1 = Nin;
   g.skws = sk_workspace(ctx, s, (size_t)sk * Nout * 2 * Nin);
-  g.x3 = g_gemm_x3;
+  g.x3 = x3;
   gemm_launch<false, false>(s, g, big ? 1 : 0);
 }
 // column sums of X [M][N] (ld) added to out[N]: atomics over 512 row slices, or (deterministic) per-slice partials + ordered reduce
@@ -265,77 +266,54 @@ constexpr int SEQ_FUSED_MAX_H = 256;
 constexpr int SEQ_MAX_H = 512;
 constexpr int SEQ_COUNTER_WORDS = 256;   // hand-off words per recurrence launch (one per workgroup): the grid of a launch may not exceed it
 constexpr int SEQ_COUNTER_TOTAL = 2 * MAXD * 4 * SEQ_COUNTER_WORDS;   // all launches of one call (forward + backward, MAXD layers, 4 nets): ONE clear
-// fault injection for the tests (KBJ_DEBUG_DROP_SEQ_WG = n at kbj_create): the next n forward-recurrence launches run with one
-// workgroup missing, so its partners' bounded spins expire and the timeout / fail-stop path is exercised on real hardware
-int g_seq_drop = 0;
-int g_seq_drop_bwd = 0;   // the same for the backward recurrences (KBJ_DEBUG_DROP_SEQ_BWD_WG = n)
-unsigned g_seq_timeout_ticks = SEQ_TIMEOUT_MS * 100000u;   // wall_clock64 ticks; set per context in kbj_nn_create
-template <int H, int UW> void seq_fwd_launch(hipStream_t s, const SeqFwdArgs& a0) {
+
+// The run-time hidden size H in {64, 128, ..., SEQ_MAX_H} as a compile-time constant: returns f(std::integral_constant<int, H>()), and false
+// for any other H. f returns whether it has a kernel for that size (those built up to SEQ_FUSED_MAX_H only: `if constexpr` in f).
+template <int HC = 64, class F> bool dispatch_hidden(int H, F&& f) {
+  if constexpr (HC > SEQ_MAX_H) return false;
+  else return H == HC ? f(std::integral_constant<int, HC>()) : dispatch_hidden<HC + 64>(H, f);
+}
+
+int seq_fwd(kbj_ctx* ctx, hipStream_t st, int H, const SeqFwdArgs& a0) {   // a0.counters: zeroed by the caller
   SeqFwdArgs a = a0;
-  a.timeout_ticks = g_seq_timeout_ticks;
-  int grid = (H / (SEQ_UNITS * UW)) * ((a.B + SEQ_ROWS - 1) / SEQ_ROWS);
-  if (g_seq_drop > 0 && grid > 1) { --g_seq_drop; --grid; }
-  if constexpr (H <= SEQ_FUSED_MAX_H) {
-    if (a.X && a.ldx == KBJ_LD_ACTOR) { hipLaunchKernelGGL((lstm_seq_fwd_kernel<H, UW, true, KBJ_LD_ACTOR>), dim3(grid), dim3(256 * UW), 0, s, a); return; }   // gates from the observation rows
-    if (a.X) { hipLaunchKernelGGL((lstm_seq_fwd_kernel<H, UW, true>), dim3(grid), dim3(256 * UW), 0, s, a); return; }   // input projection fused
-  }
-  hipLaunchKernelGGL((lstm_seq_fwd_kernel<H, UW, false>), dim3(grid), dim3(256 * UW), 0, s, a);   // (wide layers: the schedule never passes X, kbj_nn_create)
-}
-template <int H, int UW> void seq_bwd_launch(hipStream_t s, const SeqBwdArgs& a0) {
-  SeqBwdArgs a = a0;
-  a.timeout_ticks = g_seq_timeout_ticks;
-  int grid = (H / (SEQ_UNITS * UW)) * ((a.B + SEQ_ROWS - 1) / SEQ_ROWS);
-  if constexpr (H <= SEQ_FUSED_MAX_H) hipLaunchKernelGGL((lstm_seq_bwd_kernel<H, UW>), dim3(grid), dim3(256 * UW), 0, s, a);
-  else hipLaunchKernelGGL((lstm_seq_bwd_wide_kernel<H, UW>), dim3(grid), dim3(256 * UW), 0, s, a);
-}
-int seq_fwd(kbj_ctx* ctx, hipStream_t st, int H, const SeqFwdArgs& a) {   // a.counters: zeroed by the caller
+  a.timeout_ticks = ws_of(ctx)->seq_timeout_ticks;
   KbjKernelTimer timer(st, a.X ? (a.ldx == KBJ_LD_ACTOR ? KBJ_KIND_SEQ_FWD_OBS : KBJ_KIND_SEQ_FWD_FUSED) : KBJ_KIND_SEQ_FWD, 2.0 * a.T * a.B * 4.0 * H * (H + (a.X ? (a.kx ? a.kx : H) : 0)));
-  switch (H) {
-    case 64: seq_fwd_launch<64, SEQ_UW>(st, a); break;
-    case 128: seq_fwd_launch<128, SEQ_UW>(st, a); break;
-    case 192: seq_fwd_launch<192, SEQ_UW>(st, a); break;
-    case 256: seq_fwd_launch<256, SEQ_UW>(st, a); break;
-    case 320: seq_fwd_launch<320, SEQ_UW>(st, a); break;
-    case 384: seq_fwd_launch<384, SEQ_UW>(st, a); break;
-    case 448: seq_fwd_launch<448, SEQ_UW>(st, a); break;
-    case 512: seq_fwd_launch<512, SEQ_UW>(st, a); break;
-    default: return kbj_fail(ctx, "persistent LSTM kernels are built for hidden sizes 64, 128, ..., 512");
-  }
-  return 0;
-}
-template <int H> void seq_bwd16_launch(hipStream_t s, const SeqBwdArgs& a0) {
-  SeqBwdArgs a = a0;
-  a.timeout_ticks = g_seq_timeout_ticks;
-  int grid = (H / BWD16_UNITS) * ((a.B + BWD16_ROWS - 1) / BWD16_ROWS);
-  if (g_seq_drop_bwd > 0 && grid > 1 && H > BWD16_UNITS) { --g_seq_drop_bwd; --grid; }   // fault injection (a launch without partners has nobody to time out)
-  hipLaunchKernelGGL((lstm_seq_bwd16_kernel<H>), dim3(grid), dim3(BWD16_NTH), 0, s, a);
+  const bool built = dispatch_hidden(H, [&](auto hc) {
+    constexpr int HC = decltype(hc)::value, UW = SEQ_UW;
+    int grid = (HC / (SEQ_UNITS * UW)) * ((a.B + SEQ_ROWS - 1) / SEQ_ROWS);
+    if (ctx->set.seq_drop > 0 && grid > 1) { --ctx->set.seq_drop; --grid; }   // fault injection (KbjSettings::seq_drop)
+    const dim3 block(256 * UW);
+    if constexpr (HC <= SEQ_FUSED_MAX_H) {
+      if (a.X && a.ldx == KBJ_LD_ACTOR) { hipLaunchKernelGGL((lstm_seq_fwd_kernel<HC, UW, true, KBJ_LD_ACTOR>), dim3(grid), block, 0, st, a); return true; }   // gates from the observation rows
+      if (a.X) { hipLaunchKernelGGL((lstm_seq_fwd_kernel<HC, UW, true>), dim3(grid), block, 0, st, a); return true; }   // input projection fused
+    }
+    hipLaunchKernelGGL((lstm_seq_fwd_kernel<HC, UW, false>), dim3(grid), block, 0, st, a);   // (wide layers: the schedule never passes X, kbj_read_settings)
+    return true;
+  });
+  return built ? 0 : kbj_fail(ctx, "seq_fwd: the persistent LSTM kernels are built for hidden sizes 64, 128, ..., 512");
 }
 // row groups of a backward-recurrence launch (deterministic mode: rows of its per-row-group bias partials)
 int seq_bwd_row_groups(int B, bool tiles16) { return tiles16 ? (B + BWD16_ROWS - 1) / BWD16_ROWS : (B + SEQ_ROWS - 1) / SEQ_ROWS; }
-int seq_bwd(kbj_ctx* ctx, hipStream_t st, int H, const SeqBwdArgs& a, bool tiles16 = false) {   // a.counters: zeroed by the caller
+int seq_bwd(kbj_ctx* ctx, hipStream_t st, int H, const SeqBwdArgs& a0, bool tiles16 = false) {   // a0.counters: zeroed by the caller
+  SeqBwdArgs a = a0;
+  a.timeout_ticks = ws_of(ctx)->seq_timeout_ticks;
   KbjKernelTimer timer(st, tiles16 ? KBJ_KIND_SEQ_BWD16 : KBJ_KIND_SEQ_BWD, 2.0 * a.T * a.B * 4.0 * H * H);
-  if (tiles16) {
-    switch (H) {
-      case 64: seq_bwd16_launch<64>(st, a); break;
-      case 128: seq_bwd16_launch<128>(st, a); break;
-      case 192: seq_bwd16_launch<192>(st, a); break;
-      case 256: seq_bwd16_launch<256>(st, a); break;
-      default: return kbj_fail(ctx, "lstm_seq_bwd16_kernel is built for hidden sizes 64, 128, 192, 256");
+  const bool built = dispatch_hidden(H, [&](auto hc) {
+    constexpr int HC = decltype(hc)::value, UW = SEQ_UW;
+    if (tiles16) {
+      if constexpr (HC <= SEQ_FUSED_MAX_H) {
+        int grid = (HC / BWD16_UNITS) * ((a.B + BWD16_ROWS - 1) / BWD16_ROWS);
+        if (ctx->set.seq_drop_bwd > 0 && grid > 1 && HC > BWD16_UNITS) { --ctx->set.seq_drop_bwd; --grid; }   // fault injection (a launch without partners has nobody to time out)
+        hipLaunchKernelGGL((lstm_seq_bwd16_kernel<HC>), dim3(grid), dim3(BWD16_NTH), 0, st, a);
+        return true;
+      } else return false;
     }
-    return 0;
-  }
-  switch (H) {
-    case 64: seq_bwd_launch<64, SEQ_UW>(st, a); break;
-    case 128: seq_bwd_launch<128, SEQ_UW>(st, a); break;
-    case 192: seq_bwd_launch<192, SEQ_UW>(st, a); break;
-    case 256: seq_bwd_launch<256, SEQ_UW>(st, a); break;
-    case 320: seq_bwd_launch<320, SEQ_UW>(st, a); break;
-    case 384: seq_bwd_launch<384, SEQ_UW>(st, a); break;
-    case 448: seq_bwd_launch<448, SEQ_UW>(st, a); break;
-    case 512: seq_bwd_launch<512, SEQ_UW>(st, a); break;
-    default: return kbj_fail(ctx, "persistent LSTM kernels are built for hidden sizes 64, 128, ..., 512");
-  }
-  return 0;
+    const dim3 grid((HC / (SEQ_UNITS * UW)) * ((a.B + SEQ_ROWS - 1) / SEQ_ROWS)), block(256 * UW);
+    if constexpr (HC <= SEQ_FUSED_MAX_H) hipLaunchKernelGGL((lstm_seq_bwd_kernel<HC, UW>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((lstm_seq_bwd_wide_kernel<HC, UW>), grid, block, 0, st, a);
+    return true;
+  });
+  return built ? 0 : kbj_fail(ctx, "seq_bwd: the persistent LSTM kernels are built for hidden sizes 64, 128, ..., 512 (lstm_seq_bwd16_kernel: up to 256)");
 }
 
 // resident workgroups per CU of the recurrence kernel that fits worst, over EVERY recurrence kernel the schedule may launch for this
@@ -367,41 +345,17 @@ int lstm_step(kbj_ctx* ctx, hipStream_t st, int H, const StepArgs& a) {
   const int nug = H / (SEQ_UNITS * 2), nrg = (a.M + SEQ_ROWS - 1) / SEQ_ROWS;
   const int nch = std::max(1, std::min(nrg, 256 / nug));
   dim3 grid(nug * nch), block(512);
-  switch (H * 2 + (obs ? 1 : 0)) {
-    case 128: hipLaunchKernelGGL((lstm_step_kernel<64, 2>), grid, block, 0, st, a); break;
-    case 129: hipLaunchKernelGGL((lstm_step_kernel<64, 2, KBJ_LD_ACTOR>), grid, block, 0, st, a); break;
-    case 256: hipLaunchKernelGGL((lstm_step_kernel<128, 2>), grid, block, 0, st, a); break;
-    case 257: hipLaunchKernelGGL((lstm_step_kernel<128, 2, KBJ_LD_ACTOR>), grid, block, 0, st, a); break;
-    case 384: hipLaunchKernelGGL((lstm_step_kernel<192, 2>), grid, block, 0, st, a); break;
-    case 385: hipLaunchKernelGGL((lstm_step_kernel<192, 2, KBJ_LD_ACTOR>), grid, block, 0, st, a); break;
-    case 512: hipLaunchKernelGGL((lstm_step_kernel<256, 2>), grid, block, 0, st, a); break;
-    case 513: hipLaunchKernelGGL((lstm_step_kernel<256, 2, KBJ_LD_ACTOR>), grid, block, 0, st, a); break;
-    default: return kbj_fail(ctx, "LSTM step kernels are built for hidden_size 64, 128, 192, 256");
-  }
-  return 0;
+  const bool built = dispatch_hidden(H, [&](auto hc) {
+    constexpr int HC = decltype(hc)::value;
+    if constexpr (HC <= SEQ_FUSED_MAX_H) {
+      if (obs) hipLaunchKernelGGL((lstm_step_kernel<HC, 2, KBJ_LD_ACTOR>), grid, block, 0, st, a);
+      else hipLaunchKernelGGL((lstm_step_kernel<HC, 2>), grid, block, 0, st, a);
+      return true;
+    } else return false;
+  });
+  return built ? 0 : kbj_fail(ctx, "lstm_step: the LSTM step kernels are built for hidden_size 64, 128, 192, 256");
 }
 
-}  // namespace
-
-namespace {
-float* sk_workspace(kbj_ctx* ctx, hipStream_t s, size_t floats) {
-  NnWs& w = *ws_of(ctx);
-  if (!w.sched.deterministic) return nullptr;
-  const int l = lane_of(ctx, s);
-  if (w.skws_cap[l] < floats) {   // grows during the first calls only; nothing may still be reading the old slab
-    hipDeviceSynchronize();
-    if (w.skws[l]) hipFree(w.skws[l]);
-    w.skws[l] = nullptr; w.skws_cap[l] = 0;
-    void* q = nullptr;
-    if (hipMalloc(&q, floats * sizeof(float)) != hipSuccess) { kbj_fail(ctx, "hipMalloc (deterministic split-K workspace)"); return nullptr; }
-    w.skws[l] = reinterpret_cast<float*>(q); w.skws_cap[l] = floats;
-  }
-  return w.skws[l];
-}
-float* det_partials(kbj_ctx* ctx, hipStream_t s) {
-  NnWs& w = *ws_of(ctx);
-  return w.sched.deterministic ? w.detp[lane_of(ctx, s)] : nullptr;
-}
 }  // namespace
 
 int kbj_nn_check_errors(kbj_ctx* ctx) {
@@ -460,43 +414,73 @@ void kbj_nn_drop_prefetch(kbj_ctx* ctx) {
   w->prefetched_idx = nullptr; w->prefetched_traj = nullptr;
 }
 
-int kbj_nn_create(kbj_ctx* ctx) {
-  NnWs* w = new NnWs();
-  ctx->nn_ws = w;
+// THE place where the environment is read (besides kbj_rollout's per-call KBJ_ROLLOUT_PIPELINE): once per context, at the top of kbj_create
+KbjSettings kbj_read_settings(const kbj_config& c) {
+  auto flag = [](const char* name, bool dflt) { const char* v = getenv(name); return v ? atoi(v) != 0 : dflt; };
+  auto number = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
+  KbjSettings set;
+  Sched& sc = set.sched;
+  const bool wide = c.hidden_size > SEQ_FUSED_MAX_H;   // (SEQ_FUSED_MAX_H is a multiple of 64: the same answer for the padded size)
+  sc.fold_actor = flag("KBJ_FOLD_ACTOR", true); sc.fold_critic = flag("KBJ_FOLD_CRITIC", true);
+  sc.fuse_ih = flag("KBJ_SEQ_FUSE", true); sc.fuse_obs = sc.fuse_ih && flag("KBJ_SEQ_FUSE_OBS", true);
+  sc.fused_critic_head = flag("KBJ_FUSED_CRITIC_HEAD", true); sc.rollout_step = flag("KBJ_ROLLOUT_STEP", true);
+  sc.one_stream = flag("KBJ_ONE_STREAM", false); sc.debug_sync = flag("KBJ_DEBUG", false);
+  sc.deterministic = c.deterministic != 0 || flag("KBJ_DETERMINISTIC", false);
+  { const char* cl = getenv("KBJ_CRITIC_LANE"); sc.critic_on_caller = !(cl && std::string(cl) == "2nd"); }
+  sc.bwd16 = flag("KBJ_BWD16", true) && !wide;   // wide layers keep lstm_seq_bwd_wide_kernel
+  sc.gemm_x3 = (c.gemm_bf16x3 != 0 || flag("KBJ_GEMM_X3", false)) && !sc.deterministic;   // (the deterministic split-K slabs stay on the exact kernel)
+  if (wide) sc.fuse_ih = sc.fuse_obs = sc.rollout_step = false;   // wide layers (SEQ_FUSED_MAX_H above)
+  set.seq_drop = number("KBJ_DEBUG_DROP_SEQ_WG", 0);
+  set.seq_drop_bwd = number("KBJ_DEBUG_DROP_SEQ_BWD_WG", 0);
+  set.seq_timeout_ms = (set.seq_drop > 0 || set.seq_drop_bwd > 0) ? 20 : (int)SEQ_TIMEOUT_MS;
+  if (getenv("KBJ_SEQ_TIMEOUT_MS")) set.seq_timeout_ms = std::max(1, std::min(30000, number("KBJ_SEQ_TIMEOUT_MS", 0)));
+  set.seq_stamps = getenv("KBJ_SEQ_STAMPS") != nullptr; set.stamp_sel = number("KBJ_SEQ_STAMPS", 1);
+  set.seq_bstamps = getenv("KBJ_SEQ_BSTAMPS") != nullptr; set.bstamp_sel = number("KBJ_SEQ_BSTAMPS", 0);
+  return set;
+}
+
+namespace {
+
+// ---- kbj_nn_create, step by step (each: 0 or kbj_fail) ----
+int nn_layouts(kbj_ctx* ctx, NnWs* w) {
   const kbj_config& c = ctx->cfg_h;
   w->Hu = c.hidden_size; w->H = (c.hidden_size + 63) / 64 * 64; w->N = c.num_envs; w->B = c.batch_size; w->T = c.rollout_len;
   if (w->B <= 0 || w->B > w->N) return kbj_fail(ctx, "kbj_create: batch_size must be in [1, num_envs]");
-  layout_params(*w, w->H, ctx->cfg_h.depth, ctx->cfg_h.extra_obs_actor, ctx->cfg_h.extra_obs_critic);
-  size_t N = w->N, H = w->H, B = w->B, T = w->T;
-  w->unparams = w->nparams; w->unactor = w->nactor;
-  if (w->padded()) {
-    NnWs u;
-    layout_params(u, w->Hu, c.depth, c.extra_obs_actor, c.extra_obs_critic);
-    w->unparams = u.nparams; w->unactor = u.nactor;
-    std::vector<PadDesc> pd;
-    const int Hu = w->Hu, Hi = w->H;
-    for (int n = 0; n < 2; ++n) {
-      const NetOff &a = u.net[n], &b = w->net[n];
-      pd.push_back(PadDesc{a.w_in, b.w_in, 1, Hu, Hi, a.nin, a.nin});
-      pd.push_back(PadDesc{a.b_in, b.b_in, 1, Hu, Hi, 1, 1});
-      for (int l = 0; l < w->D; ++l) {
-        pd.push_back(PadDesc{a.w_ih[l], b.w_ih[l], 4, Hu, Hi, Hu, Hi});
-        pd.push_back(PadDesc{a.w_hh[l], b.w_hh[l], 4, Hu, Hi, Hu, Hi});
-        pd.push_back(PadDesc{a.b[l], b.b[l], 4, Hu, Hi, 1, 1});
-      }
-      pd.push_back(PadDesc{a.w_out, b.w_out, 1, a.nout, a.nout, Hu, Hi});
-      pd.push_back(PadDesc{a.b_out, b.b_out, 1, a.nout, a.nout, 1, 1});
-    }
-    w->npad = (int)pd.size();
-    if (dalloc(ctx, *w, &w->pad_desc, pd.size())) return -1;
-    if (hipMemcpy(w->pad_desc, pd.data(), pd.size() * sizeof(PadDesc), hipMemcpyHostToDevice) != hipSuccess) return kbj_fail(ctx, "hipMemcpy pad descriptors");
-    if (dalloc(ctx, *w, &w->pparams, w->nparams) || dalloc(ctx, *w, &w->pgrad, w->nparams)) return -1;
-    const bool mir = c.actor_mirror_loss_scale != 0.0f || c.critic_mirror_loss_scale != 0.0f;
-    for (int k = 0; k < (mir ? 4 : 2); ++k)
-      if (dalloc(ctx, *w, &w->phc[k], (size_t)2 * w->D * N * H) || dalloc(ctx, *w, &w->pc0[k], (size_t)2 * w->D * N * H)) return -1;
-  }
+  static_cast<ParamLayout&>(*w) = layout_params(c, w->H);
+  w->user = layout_params(c, w->Hu);
   w->mirror = c.actor_mirror_loss_scale != 0.0f || c.critic_mirror_loss_scale != 0.0f;
   w->nnets = w->mirror ? 4 : 2;
+  return 0;
+}
+
+// free hidden_size: descriptors of every leaf's place in the two layouts, internal copies of parameters, gradient and carries
+int nn_padding(kbj_ctx* ctx, NnWs* w) {
+  if (!w->padded()) return 0;
+  std::vector<PadDesc> pd;
+  const int Hu = w->Hu, Hi = w->H;
+  for (int n = 0; n < 2; ++n) {
+    const NetOff &a = w->user.net[n], &b = w->net[n];
+    pd.push_back(PadDesc{a.w_in, b.w_in, 1, Hu, Hi, a.nin, a.nin});
+    pd.push_back(PadDesc{a.b_in, b.b_in, 1, Hu, Hi, 1, 1});
+    for (int l = 0; l < w->D; ++l) {
+      pd.push_back(PadDesc{a.w_ih[l], b.w_ih[l], 4, Hu, Hi, Hu, Hi});
+      pd.push_back(PadDesc{a.w_hh[l], b.w_hh[l], 4, Hu, Hi, Hu, Hi});
+      pd.push_back(PadDesc{a.b[l], b.b[l], 4, Hu, Hi, 1, 1});
+    }
+    pd.push_back(PadDesc{a.w_out, b.w_out, 1, a.nout, a.nout, Hu, Hi});
+    pd.push_back(PadDesc{a.b_out, b.b_out, 1, a.nout, a.nout, 1, 1});
+  }
+  w->npad = (int)pd.size();
+  if (dalloc(ctx, *w, &w->pad_desc, pd.size())) return -1;
+  if (hipMemcpy(w->pad_desc, pd.data(), pd.size() * sizeof(PadDesc), hipMemcpyHostToDevice) != hipSuccess) return kbj_fail(ctx, "hipMemcpy pad descriptors");
+  if (dalloc(ctx, *w, &w->pparams, w->nparams) || dalloc(ctx, *w, &w->pgrad, w->nparams)) return -1;
+  for (int k = 0; k < w->nnets; ++k)
+    if (dalloc(ctx, *w, &w->phc[k], (size_t)2 * w->D * w->N * w->H) || dalloc(ctx, *w, &w->pc0[k], (size_t)2 * w->D * w->N * w->H)) return -1;
+  return 0;
+}
+
+int nn_rollout_scratch(kbj_ctx* ctx, NnWs* w) {
+  const size_t N = w->N, H = w->H;
   for (int n = 0; n < w->nnets; ++n) {
     if (dalloc(ctx, *w, &w->rX[n], N * H)) return -1;
     if (dalloc(ctx, *w, &w->rG[n], N * 4 * H)) return -1;
@@ -505,7 +489,12 @@ int kbj_nn_create(kbj_ctx* ctx) {
   }
   if (dalloc(ctx, *w, &w->joint_bias_d, KBJ_NU)) return -1;
   if (hipMemcpy(w->joint_bias_d, ctx->model_h.joint_bias, KBJ_NU * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return kbj_fail(ctx, "hipMemcpy joint_bias");
-  size_t R = T * B;
+  return 0;
+}
+
+// the mirror branches' tables and buffers (rollout rows and minibatch), then everything a minibatch pass works in
+int nn_training_buffers(kbj_ctx* ctx, NnWs* w) {
+  const size_t N = w->N, H = w->H, B = w->B, T = w->T, R = T * B;
   if (w->mirror) {
     std::vector<MirrorEntry> ta, tc;
     build_mirror_tables(ctx->model_h, ta, tc, ctx->cfg_h.extra_obs_actor, ctx->cfg_h.extra_obs_critic);
@@ -550,76 +539,62 @@ int kbj_nn_create(kbj_ctx* ctx) {
   if (hipMemset(w->Weff, 0, (size_t)4 * H * w->net[0].ld_obs * sizeof(float)) != hipSuccess) return kbj_fail(ctx, "hipMemset Weff");
   if (dalloc(ctx, *w, &w->seq_counters, SEQ_COUNTER_TOTAL)) return -1;   // [phase: forward layer l = l, backward layer l = D + l][net][row group x unit group]
   if (dalloc(ctx, *w, &w->seq_err, 4)) return -1;
-  if (getenv("KBJ_SEQ_STAMPS")) { if (dalloc(ctx, *w, &w->seq_stamps, (size_t)T * 6)) return -1; }
-  if (getenv("KBJ_SEQ_BSTAMPS")) { if (dalloc(ctx, *w, &w->seq_bstamps, (size_t)T * 10 + 768)) return -1; }
+  if (ctx->set.seq_stamps && dalloc(ctx, *w, &w->seq_stamps, (size_t)T * 6)) return -1;
+  if (ctx->set.seq_bstamps && dalloc(ctx, *w, &w->seq_bstamps, (size_t)T * 10 + 768)) return -1;
   if (hipMemset(w->seq_err, 0, 4 * sizeof(unsigned)) != hipSuccess) return kbj_fail(ctx, "hipMemset seq_err");
-  {
-    Sched& sc = w->sched;
-    sc.fold_actor = env_flag("KBJ_FOLD_ACTOR", true); sc.fold_critic = env_flag("KBJ_FOLD_CRITIC", true);
-    sc.fuse_ih = env_flag("KBJ_SEQ_FUSE", true); sc.fuse_obs = sc.fuse_ih && env_flag("KBJ_SEQ_FUSE_OBS", true);
-    sc.fused_critic_head = env_flag("KBJ_FUSED_CRITIC_HEAD", true); sc.rollout_step = env_flag("KBJ_ROLLOUT_STEP", true);
-    sc.one_stream = env_flag("KBJ_ONE_STREAM", false); sc.debug_sync = env_flag("KBJ_DEBUG", false);
-    sc.deterministic = c.deterministic != 0 || env_flag("KBJ_DETERMINISTIC", false);
-    { const char* cl = getenv("KBJ_CRITIC_LANE"); sc.critic_on_caller = !(cl && std::string(cl) == "2nd"); }
-    sc.bwd16 = env_flag("KBJ_BWD16", true) && H <= (size_t)SEQ_FUSED_MAX_H;   // wide layers keep lstm_seq_bwd_wide_kernel
-    sc.gemm_x3 = (c.gemm_bf16x3 != 0 || env_flag("KBJ_GEMM_X3", false)) && !sc.deterministic;   // (the deterministic split-K slabs stay on the exact kernel)
-    if (H > (size_t)SEQ_FUSED_MAX_H) sc.fuse_ih = sc.fuse_obs = sc.rollout_step = false;   // wide layers (SEQ_FUSED_MAX_H above)
-    if (sc.deterministic) {
-      for (int l = 0; l < 4; ++l) if (dalloc(ctx, *w, &w->detp[l], (size_t)DETP_ROWS * DETP_COLS)) return -1;
-      if (dalloc(ctx, *w, &w->detd, 2 * 512)) return -1;
-    }
+  return 0;
+}
+
+int nn_deterministic_workspaces(kbj_ctx* ctx, NnWs* w) {
+  if (!w->sched.deterministic) return 0;
+  for (int l = 0; l < 4; ++l) if (dalloc(ctx, *w, &w->detp[l], (size_t)DETP_ROWS * DETP_COLS)) return -1;
+  return dalloc(ctx, *w, &w->detd, 2 * 512);
+}
+
+// Residency of the persistent recurrences: the workgroups of one launch spin on each other, and kbj_ppo_grad keeps TWO launches
+// (actor-type and critic-type net, one per stream; the mirror branches queue behind them on the same two streams) in flight, so
+// 2 x grid workgroups must be resident at once. Every other kernel of the schedule (GEMMs, heads) terminates on its own, so it can
+// only delay a recurrence workgroup, never starve it. Slots = the occupancy query's answer for the WORST-fitting recurrence kernel
+// of this hidden size. Independently, a launch owns SEQ_COUNTER_WORDS hand-off words (one per workgroup): a larger grid would write
+// into the next launch's block, so it is refused whatever the occupancy says.
+int nn_residency_check(kbj_ctx* ctx, NnWs* w) {
+  const int H = w->H, B = w->B;
+  const int grid = ((B + SEQ_ROWS - 1) / SEQ_ROWS) * (H / (SEQ_UNITS * SEQ_UW));
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, ctx->device) != hipSuccess) return kbj_fail(ctx, "hipGetDeviceProperties");
+  const int cus = prop.multiProcessorCount;
+  int per_cu = 0;
+  hipError_t oe = hipSuccess;
+  if (!dispatch_hidden(H, [&](auto hc) { oe = seq_min_blocks_per_cu<decltype(hc)::value>(&per_cu); return true; }))
+    return kbj_fail(ctx, "kbj_create: hidden_size above 512 (persistent LSTM kernels)");
+  if (oe != hipSuccess || per_cu < 1) return kbj_fail(ctx, "kbj_create: occupancy query of the persistent LSTM kernels failed");
+  const long slots = (long)per_cu * cus;
+  w->seq_grid = grid; w->seq_slots = (int)slots;
+  char msg[320];
+  if (grid > SEQ_COUNTER_WORDS) {
+    snprintf(msg, sizeof(msg), "kbj_create: a persistent LSTM launch would need %d workgroups (batch_size / 32 x hidden_size / 32), the hand-off "
+             "counters hold %d per launch: lower batch_size", grid, SEQ_COUNTER_WORDS);
+    return kbj_fail(ctx, msg);
   }
-  g_seq_drop = getenv("KBJ_DEBUG_DROP_SEQ_WG") ? atoi(getenv("KBJ_DEBUG_DROP_SEQ_WG")) : 0;
-  g_seq_drop_bwd = getenv("KBJ_DEBUG_DROP_SEQ_BWD_WG") ? atoi(getenv("KBJ_DEBUG_DROP_SEQ_BWD_WG")) : 0;
-  {   // wall-clock bound of the recurrences' inter-workgroup waits (kbj_lstm_seq.h seq_wait): 2 s by default, KBJ_SEQ_TIMEOUT_MS=n overrides,
-      // 20 ms under fault injection
-    int wall_khz = 0;
-    if (hipDeviceGetAttribute(&wall_khz, hipDeviceAttributeWallClockRate, ctx->device) != hipSuccess || wall_khz <= 0) wall_khz = 100000;
-    long ms = (g_seq_drop > 0 || g_seq_drop_bwd > 0) ? 20 : (long)SEQ_TIMEOUT_MS;
-    if (getenv("KBJ_SEQ_TIMEOUT_MS")) ms = std::max(1, std::min(30000, atoi(getenv("KBJ_SEQ_TIMEOUT_MS"))));
-    g_seq_timeout_ticks = (unsigned)std::min<long long>(0xFFFFFFFFll, (long long)ms * wall_khz);
-  }
-  // Residency of the persistent recurrences: the workgroups of one launch spin on each other, and kbj_ppo_grad keeps TWO launches
-  // (actor-type and critic-type net, one per stream; the mirror branches queue behind them on the same two streams) in flight, so
-  // 2 x grid workgroups must be resident at once. Every other kernel of the schedule (GEMMs, heads) terminates on its own, so it can
-  // only delay a recurrence workgroup, never starve it. Slots = the occupancy query's answer for the WORST-fitting recurrence kernel
-  // of this hidden size. Independently, a launch owns SEQ_COUNTER_WORDS hand-off words (one per workgroup): a larger grid would write
-  // into the next launch's block, so it is refused whatever the occupancy says.
-  {
-    const int grid = (int)((B + SEQ_ROWS - 1) / SEQ_ROWS) * (int)(H / (SEQ_UNITS * SEQ_UW));
-    int per_cu = 0, cus = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, ctx->device) != hipSuccess) return kbj_fail(ctx, "hipGetDeviceProperties");
-    cus = prop.multiProcessorCount;
-    hipError_t oe = hipSuccess;
-    switch ((int)H) {
-      case 64: oe = seq_min_blocks_per_cu<64>(&per_cu); break;
-      case 128: oe = seq_min_blocks_per_cu<128>(&per_cu); break;
-      case 192: oe = seq_min_blocks_per_cu<192>(&per_cu); break;
-      case 256: oe = seq_min_blocks_per_cu<256>(&per_cu); break;
-      case 320: oe = seq_min_blocks_per_cu<320>(&per_cu); break;
-      case 384: oe = seq_min_blocks_per_cu<384>(&per_cu); break;
-      case 448: oe = seq_min_blocks_per_cu<448>(&per_cu); break;
-      case 512: oe = seq_min_blocks_per_cu<512>(&per_cu); break;
-      default: return kbj_fail(ctx, "kbj_create: hidden_size above 512 (persistent LSTM kernels)");
-    }
-    if (oe != hipSuccess || per_cu < 1) return kbj_fail(ctx, "kbj_create: occupancy query of the persistent LSTM kernels failed");
-    const long slots = (long)per_cu * cus;
-    w->seq_grid = grid; w->seq_slots = (int)slots;
-    char msg[320];
-    if (grid > SEQ_COUNTER_WORDS) {
-      snprintf(msg, sizeof(msg), "kbj_create: a persistent LSTM launch would need %d workgroups (batch_size / 32 x hidden_size / 32), the hand-off "
-               "counters hold %d per launch: lower batch_size", grid, SEQ_COUNTER_WORDS);
-      return kbj_fail(ctx, msg);
-    }
-    if (H > SEQ_FUSED_MAX_H && 2L * grid > slots) w->sched.one_stream = true;   // wide layers: one recurrence at a time
-    if ((w->sched.one_stream ? 1L : 2L) * grid > slots) {
-      snprintf(msg, sizeof(msg), "kbj_create: %s persistent LSTM launches need %ld resident workgroups, the device holds %ld "
-               "(%d per CU x %d CUs): lower batch_size", w->sched.one_stream ? "the" : "two concurrent", (w->sched.one_stream ? 1L : 2L) * grid, slots, per_cu, cus);
-      return kbj_fail(ctx, msg);
-    }
+  if (H > SEQ_FUSED_MAX_H && 2L * grid > slots) w->sched.one_stream = true;   // wide layers: one recurrence at a time
+  if ((w->sched.one_stream ? 1L : 2L) * grid > slots) {
+    snprintf(msg, sizeof(msg), "kbj_create: %s persistent LSTM launches need %ld resident workgroups, the device holds %ld "
+             "(%d per CU x %d CUs): lower batch_size", w->sched.one_stream ? "the" : "two concurrent", (w->sched.one_stream ? 1L : 2L) * grid, slots, per_cu, cus);
+    return kbj_fail(ctx, msg);
   }
   return 0;
+}
+
+}  // namespace
+
+int kbj_nn_create(kbj_ctx* ctx) {
+  NnWs* w = new NnWs(ctx->set.sched);
+  ctx->nn_ws = w;
+  if (nn_layouts(ctx, w) || nn_padding(ctx, w) || nn_rollout_scratch(ctx, w) || nn_training_buffers(ctx, w) || nn_deterministic_workspaces(ctx, w)) return -1;
+  int wall_khz = 0;   // the settings' bound of the recurrences' waits in this device's wall_clock64 ticks
+  if (hipDeviceGetAttribute(&wall_khz, hipDeviceAttributeWallClockRate, ctx->device) != hipSuccess || wall_khz <= 0) wall_khz = 100000;
+  w->seq_timeout_ticks = (unsigned)std::min<long long>(0xFFFFFFFFll, (long long)ctx->set.seq_timeout_ms * wall_khz);
+  return nn_residency_check(ctx, w);
 }
 
 void kbj_nn_destroy(kbj_ctx* ctx) {
@@ -689,10 +664,10 @@ int policy_nets(kbj_ctx* ctx, hipStream_t s, const float* params_d, int net_lo, 
   const int N = w.N, H = w.H;
   const bool fused_any = w.sched.rollout_step;
   const float* obs_base[2] = {actor_obs_d, critic_obs_d};
-  float* hc[4] = {carry->actor_hc_d, carry->critic_hc_d, carry->actor_mirror_hc_d, carry->critic_mirror_hc_d};
   HeadParams hp{c.min_std, c.max_std, c.var_scale, c.lpf_alpha, w.net[0].ld_obs};
   for (int n = net_lo; n < net_hi; ++n) {
     const int k = n & 1;
+    float* const hc = carry_hc(*carry, n);
     const NetOff& o = w.net[k];
     const float* obs = obs_base[k] + (size_t)n0 * o.ld_obs;
     float* obs_m = n >= 2 ? w.rObsM[k] + (size_t)n0 * o.ld_obs : nullptr;
@@ -712,17 +687,17 @@ int policy_nets(kbj_ctx* ctx, hipStream_t s, const float* params_d, int net_lo, 
     }
     const float* x = X;
     for (int l = 0; l < w.D; ++l) {
-      float* cc = hc[n] + (size_t)(2 * l + 1) * N * H + (size_t)n0 * H;
+      float* cc = hc + (size_t)(2 * l + 1) * N * H + (size_t)n0 * H;
       if (fused) {
-        const float* h_in = h_plane(w, hc[n], n, l, n0, parity != 0);
-        float* h_out = h_plane(w, hc[n], n, l, n0, parity == 0);
+        const float* h_in = h_plane(w, hc, n, l, n0, parity != 0);
+        float* h_out = h_plane(w, hc, n, l, n0, parity == 0);
         StepArgs sa{x, H, 0, params_d + o.w_ih[l], H, params_d + o.w_hh[l], params_d + o.b[l], h_in, h_out, cc, cnt};
         if (l == 0 && folded) { sa.X = obs; sa.ldx = o.ld_obs; sa.kx = o.nin; sa.Wih = weff; sa.ldw = o.ld_obs; sa.bias = w.beff; }
         if (lstm_step(ctx, s, H, sa)) return -1;
         x = h_out;
         continue;
       }
-      float* h = hc[n] + (size_t)(2 * l) * N * H + (size_t)n0 * H;
+      float* h = hc + (size_t)(2 * l) * N * H + (size_t)n0 * H;
       {  // gates = [x | h] [W_ih | W_hh]^T + b as ONE launch over the concatenated contraction (no read-modify-write of G)
         GemmArgs g{x, params_d + o.w_ih[l], G, params_d + o.b[l], cnt, 4 * H, 2 * H, H, H, 4 * H, 0, 1, nullptr};
         g.A2 = h; g.B2 = params_d + o.w_hh[l]; g.k1 = H;
@@ -755,15 +730,15 @@ int policy_nets(kbj_ctx* ctx, hipStream_t s, const float* params_d, int net_lo, 
 // carry <- 0 where done, for the nets [net_lo, net_hi) and env rows [n0, n0 + cnt); parity as policy_nets: which copy of the h planes is live
 void carry_reset_nets(kbj_ctx* ctx, hipStream_t s, int net_lo, int net_hi, int n0, int cnt, kbj_carry* carry, const float* done_d, int done_stride, int parity) {
   NnWs& w = *ws_of(ctx);
-  float* hc[4] = {carry->actor_hc_d, carry->critic_hc_d, carry->actor_mirror_hc_d, carry->critic_mirror_hc_d};
   float* lpf[4] = {carry->lpf_d, nullptr, carry->lpf_mirror_d, nullptr};
   const bool partner = parity != 0 && w.sched.rollout_step;
   for (int k = net_lo; k < net_hi; ++k) {
+    float* const hc = carry_hc(*carry, k);
     CarryPlanes cp;
     cp.n = 2 * w.D;
     for (int l = 0; l < w.D; ++l) {
-      cp.p[2 * l] = h_plane(w, hc[k], k, l, n0, partner);
-      cp.p[2 * l + 1] = hc[k] + (size_t)(2 * l + 1) * w.N * w.H + (size_t)n0 * w.H;
+      cp.p[2 * l] = h_plane(w, hc, k, l, n0, partner);
+      cp.p[2 * l + 1] = hc + (size_t)(2 * l + 1) * w.N * w.H + (size_t)n0 * w.H;
     }
     hipLaunchKernelGGL(carry_reset_kernel, dim3((cnt + 3) / 4), dim3(256), 0, s, cp, cnt, w.H, lpf[k] ? lpf[k] + (size_t)n0 * KBJ_NU : nullptr, done_d + (size_t)n0 * done_stride, done_stride);
   }
@@ -772,10 +747,9 @@ void carry_reset_nets(kbj_ctx* ctx, hipStream_t s, int net_lo, int net_hi, int n
 // the h planes of nets [net_lo, net_hi) back from their ping-pong partners into the caller's arrays
 int carry_h_home(kbj_ctx* ctx, hipStream_t s, int net_lo, int net_hi, kbj_carry* carry) {
   NnWs& w = *ws_of(ctx);
-  float* hc[4] = {carry->actor_hc_d, carry->critic_hc_d, carry->actor_mirror_hc_d, carry->critic_mirror_hc_d};
   for (int k = net_lo; k < net_hi; ++k)
     for (int l = 0; l < w.D && net_uses_step_kernel(w, k); ++l)
-      KBJ_HIP(ctx, hipMemcpyAsync(hc[k] + (size_t)(2 * l) * w.N * w.H, w.rH[k][l], (size_t)w.N * w.H * sizeof(float), hipMemcpyDeviceToDevice, s));
+      KBJ_HIP(ctx, hipMemcpyAsync(carry_hc(*carry, k) + (size_t)(2 * l) * w.N * w.H, w.rH[k][l], (size_t)w.N * w.H * sizeof(float), hipMemcpyDeviceToDevice, s));
   return 0;
 }
 
@@ -798,82 +772,28 @@ void repitch_hc(kbj_ctx* ctx, hipStream_t s, const float* src, float* dst, int w
 kbj_carry pad_carry(kbj_ctx* ctx, hipStream_t s, const kbj_carry& c) {
   NnWs& w = *ws_of(ctx);
   kbj_carry p = c;
-  float* const* src[4] = {&c.actor_hc_d, &c.critic_hc_d, &c.actor_mirror_hc_d, &c.critic_mirror_hc_d};
-  float** dst[4] = {&p.actor_hc_d, &p.critic_hc_d, &p.actor_mirror_hc_d, &p.critic_mirror_hc_d};
   for (int k = 0; k < 4; ++k)
-    if (*src[k] && w.phc[k]) { repitch_hc(ctx, s, *src[k], w.phc[k], w.Hu, w.H); *dst[k] = w.phc[k]; }
+    if (carry_hc(c, k) && w.phc[k]) { repitch_hc(ctx, s, carry_hc(c, k), w.phc[k], w.Hu, w.H); carry_hc(p, k) = w.phc[k]; }
   return p;
 }
 void unpad_carry(kbj_ctx* ctx, hipStream_t s, const kbj_carry& c) {
   NnWs& w = *ws_of(ctx);
-  float* user[4] = {c.actor_hc_d, c.critic_hc_d, c.actor_mirror_hc_d, c.critic_mirror_hc_d};
   for (int k = 0; k < 4; ++k)
-    if (user[k] && w.phc[k]) repitch_hc(ctx, s, w.phc[k], user[k], w.H, w.Hu);
+    if (carry_hc(c, k) && w.phc[k]) repitch_hc(ctx, s, w.phc[k], carry_hc(c, k), w.H, w.Hu);
 }
 // the trajectory with its start carries as H-wide internal copies
 kbj_traj pad_traj_carry0(kbj_ctx* ctx, hipStream_t s, const kbj_traj& tr) {
   NnWs& w = *ws_of(ctx);
   kbj_traj p = tr;
-  float* const* src[4] = {&tr.carry0_actor_hc_d, &tr.carry0_critic_hc_d, &tr.carry0_actor_mirror_hc_d, &tr.carry0_critic_mirror_hc_d};
-  float** dst[4] = {&p.carry0_actor_hc_d, &p.carry0_critic_hc_d, &p.carry0_actor_mirror_hc_d, &p.carry0_critic_mirror_hc_d};
   for (int k = 0; k < 4; ++k)
-    if (*src[k] && w.pc0[k]) { repitch_hc(ctx, s, *src[k], w.pc0[k], w.Hu, w.H); *dst[k] = w.pc0[k]; }
+    if (traj_carry0(tr, k) && w.pc0[k]) { repitch_hc(ctx, s, traj_carry0(tr, k), w.pc0[k], w.Hu, w.H); traj_carry0(p, k) = w.pc0[k]; }
   return p;
 }
-struct InnerScope { NnWs& w; explicit InnerScope(NnWs& ws) : w(ws) { w.inner = true; } ~InnerScope() { w.inner = false; } };
 
-}  // namespace
-
-extern "C" {
-
-int kbj_mirror_table(const void* model_blob, size_t model_bytes, int critic, int32_t* src_h, float* mul_h, float* add_h) {
-  if (!model_blob || !src_h || !mul_h || !add_h || model_bytes != sizeof(kbj_model)) return kbj_fail(nullptr, "kbj_mirror_table: bad argument");
-  std::vector<MirrorEntry> ta, tc;
-  build_mirror_tables(*reinterpret_cast<const kbj_model*>(model_blob), ta, tc);
-  const std::vector<MirrorEntry>& t = critic ? tc : ta;
-  for (size_t k = 0; k < t.size(); ++k) { src_h[k] = t[k].src; mul_h[k] = t[k].mul; add_h[k] = t[k].add; }
-  return (int)t.size();
-}
-
-size_t kbj_param_count(const kbj_config* cfg) { NnWs w; layout_params(w, cfg->hidden_size, cfg->depth, cfg->extra_obs_actor, cfg->extra_obs_critic); return w.nparams; }
-size_t kbj_actor_param_count(const kbj_config* cfg) { NnWs w; layout_params(w, cfg->hidden_size, cfg->depth, cfg->extra_obs_actor, cfg->extra_obs_critic); return w.nactor; }
-
-int kbj_init_params(kbj_ctx* ctx, uint32_t seed, float* params_d) {
-  if (!ctx || !params_d) return kbj_fail(ctx, "kbj_init_params: null argument");
-  KBJ_HIP(ctx, hipSetDevice(ctx->device));
+// ---- the H-wide bodies of the entry points below (arguments validated; a padded context passes its internal copies) ----
+int policy_step_body(kbj_ctx* ctx, const float* params_d, const float* actor_obs_d, const float* critic_obs_d, kbj_carry* carry, uint32_t seed,
+                     uint32_t step_index, int argmax, float* action_d, float* logp_d, float* value_d) {
   NnWs& w = *ws_of(ctx);
-  NnWs u;                                // the caller's layout: fan-ins and offsets follow its hidden_size, not the kernels' padded one
-  layout_params(u, w.Hu, w.D, ctx->cfg_h.extra_obs_actor, ctx->cfg_h.extra_obs_critic);
-  int H = w.Hu;
-  uint32_t leaf = 0;
-  auto fill = [&](size_t off, size_t n, int fan_in) {
-    hipLaunchKernelGGL(init_uniform_kernel, g1(n), dim3(256), 0, ctx->stream, params_d + off, n, 1.0f / std::sqrt((float)fan_in), seed, leaf++);
-  };
-  for (int n = 0; n < 2; ++n) {
-    const NetOff& o = u.net[n];
-    fill(o.w_in, (size_t)H * o.nin, o.nin); fill(o.b_in, H, o.nin);
-    for (int l = 0; l < w.D; ++l) { fill(o.w_ih[l], (size_t)4 * H * H, H); fill(o.w_hh[l], (size_t)4 * H * H, H); fill(o.b[l], (size_t)4 * H, H); }
-    fill(o.w_out, (size_t)o.nout * H, H); fill(o.b_out, o.nout, H);
-  }
-  KBJ_CHECK_LAUNCH(ctx, "init_uniform_kernel");
-  return 0;
-}
-
-int kbj_policy_step(kbj_ctx* ctx, const float* params_d, const float* actor_obs_d, const float* critic_obs_d, kbj_carry* carry, uint32_t seed,
-                    uint32_t step_index, int argmax, float* action_d, float* logp_d, float* value_d) {
-  if (!ctx || !params_d || !actor_obs_d || !critic_obs_d || !carry || !action_d || !logp_d || !value_d) return kbj_fail(ctx, "kbj_policy_step: null argument");
-  KBJ_HIP(ctx, hipSetDevice(ctx->device));
-  NnWs& w = *ws_of(ctx);
-  if (w.mirror && (!carry->actor_mirror_hc_d || !carry->critic_mirror_hc_d || !carry->lpf_mirror_d))
-    return kbj_fail(ctx, "kbj_policy_step: the mirror losses are enabled, the carry needs the mirror-branch arrays");
-  if (w.padded() && !w.inner) {
-    InnerScope in(w);
-    pad_params(ctx, ctx->stream, params_d, w.pparams);
-    kbj_carry pc = pad_carry(ctx, ctx->stream, *carry);
-    const int rc = kbj_policy_step(ctx, w.pparams, actor_obs_d, critic_obs_d, &pc, seed, step_index, argmax, action_d, logp_d, value_d);
-    unpad_carry(ctx, ctx->stream, *carry);
-    return rc;
-  }
   kbj_nn_drop_prefetch(ctx);   // action / logp / value may be trajectory rows
   KbjTimed timed(ctx, true);
   repitch_input_weights(ctx, ctx->stream, params_d);
@@ -884,46 +804,9 @@ int kbj_policy_step(kbj_ctx* ctx, const float* params_d, const float* actor_obs_
   return 0;
 }
 
-int kbj_carry_reset(kbj_ctx* ctx, kbj_carry* carry, const float* done_d, int done_stride) {
-  if (!ctx || !carry || !done_d) return kbj_fail(ctx, "kbj_carry_reset: null argument");
-  KBJ_HIP(ctx, hipSetDevice(ctx->device));
+int rollout_body(kbj_ctx* ctx, const float* params_d, kbj_carry* carry, uint32_t seed, uint32_t first_step_index, kbj_traj* tr) {
   NnWs& w = *ws_of(ctx);
-  if (w.mirror && (!carry->actor_mirror_hc_d || !carry->critic_mirror_hc_d || !carry->lpf_mirror_d)) return kbj_fail(ctx, "kbj_carry_reset: mirror-branch carry arrays are NULL");
-  if (w.padded() && !w.inner) {
-    InnerScope in(w);
-    kbj_carry pc = pad_carry(ctx, ctx->stream, *carry);
-    const int rc = kbj_carry_reset(ctx, &pc, done_d, done_stride);
-    unpad_carry(ctx, ctx->stream, *carry);
-    return rc;
-  }
-  carry_reset_nets(ctx, ctx->stream, 0, w.nnets, 0, w.N, carry, done_d, done_stride, 0);
-  KBJ_CHECK_LAUNCH(ctx, "carry_reset_kernel");
-  return 0;
-}
-
-int kbj_rollout(kbj_ctx* ctx, const float* params_d, kbj_carry* carry, uint32_t seed, uint32_t first_step_index, kbj_traj* tr) {
-  if (!ctx || !params_d || !carry || !tr) return kbj_fail(ctx, "kbj_rollout: null argument");
-  KBJ_HIP(ctx, hipSetDevice(ctx->device));
-  NnWs& w = *ws_of(ctx);
-  int N = w.N, H = w.H, T = tr->T;
-  if (tr->N != N || T <= 0) return kbj_fail(ctx, "kbj_rollout: trajectory shape does not match the context");
-  if (w.padded() && !w.inner) {   // the H-wide schedule on internal copies; the caller's start-carry snapshot is taken here, at its own width
-    InnerScope in(w);
-    const size_t ub = (size_t)2 * w.D * N * w.Hu * sizeof(float);
-    float* c0[4] = {tr->carry0_actor_hc_d, tr->carry0_critic_hc_d, tr->carry0_actor_mirror_hc_d, tr->carry0_critic_mirror_hc_d};
-    float* cu[4] = {carry->actor_hc_d, carry->critic_hc_d, carry->actor_mirror_hc_d, carry->critic_mirror_hc_d};
-    for (int k = 0; k < w.nnets; ++k) {
-      if (!c0[k] || !cu[k]) return kbj_fail(ctx, "kbj_rollout: carry / trajectory start-carry array is NULL");
-      KBJ_HIP(ctx, hipMemcpyAsync(c0[k], cu[k], ub, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    pad_params(ctx, ctx->stream, params_d, w.pparams);
-    kbj_carry pc = pad_carry(ctx, ctx->stream, *carry);
-    kbj_traj pt = *tr;
-    pt.carry0_actor_hc_d = w.pc0[0]; pt.carry0_critic_hc_d = w.pc0[1]; pt.carry0_actor_mirror_hc_d = w.pc0[2]; pt.carry0_critic_mirror_hc_d = w.pc0[3];
-    const int rc = kbj_rollout(ctx, w.pparams, &pc, seed, first_step_index, &pt);
-    unpad_carry(ctx, ctx->stream, *carry);
-    return rc;
-  }
+  const int N = w.N, H = w.H, T = tr->T;
   hipStream_t s = ctx->stream;
   kbj_nn_drop_prefetch(ctx);
   size_t la = w.net[0].ld_obs, lc = w.net[1].ld_obs, lx = KBJ_AUX_SIZE;
@@ -981,6 +864,90 @@ int kbj_rollout(kbj_ctx* ctx, const float* params_d, kbj_carry* carry, uint32_t 
   return kbj_rewards(ctx, tr->aux_d, T, tr->reward_d, tr->reward_comps_d);
 }
 
+}  // namespace
+
+extern "C" {
+
+int kbj_mirror_table(const void* model_blob, size_t model_bytes, int critic, int32_t* src_h, float* mul_h, float* add_h) {
+  if (!model_blob || !src_h || !mul_h || !add_h || model_bytes != sizeof(kbj_model)) return kbj_fail(nullptr, "kbj_mirror_table: bad argument");
+  std::vector<MirrorEntry> ta, tc;
+  build_mirror_tables(*reinterpret_cast<const kbj_model*>(model_blob), ta, tc);
+  const std::vector<MirrorEntry>& t = critic ? tc : ta;
+  for (size_t k = 0; k < t.size(); ++k) { src_h[k] = t[k].src; mul_h[k] = t[k].mul; add_h[k] = t[k].add; }
+  return (int)t.size();
+}
+
+size_t kbj_param_count(const kbj_config* cfg) { return layout_params(*cfg, cfg->hidden_size).nparams; }
+size_t kbj_actor_param_count(const kbj_config* cfg) { return layout_params(*cfg, cfg->hidden_size).nactor; }
+
+int kbj_init_params(kbj_ctx* ctx, uint32_t seed, float* params_d) {
+  if (!ctx || !params_d) return kbj_fail(ctx, "kbj_init_params: null argument");
+  KBJ_HIP(ctx, hipSetDevice(ctx->device));
+  NnWs& w = *ws_of(ctx);
+  const ParamLayout& u = w.user;         // the caller's layout: fan-ins and offsets follow its hidden_size, not the kernels' padded one
+  int H = w.Hu;
+  uint32_t leaf = 0;
+  auto fill = [&](size_t off, size_t n, int fan_in) {
+    hipLaunchKernelGGL(init_uniform_kernel, g1(n), dim3(256), 0, ctx->stream, params_d + off, n, 1.0f / std::sqrt((float)fan_in), seed, leaf++);
+  };
+  for (int n = 0; n < 2; ++n) {
+    const NetOff& o = u.net[n];
+    fill(o.w_in, (size_t)H * o.nin, o.nin); fill(o.b_in, H, o.nin);
+    for (int l = 0; l < w.D; ++l) { fill(o.w_ih[l], (size_t)4 * H * H, H); fill(o.w_hh[l], (size_t)4 * H * H, H); fill(o.b[l], (size_t)4 * H, H); }
+    fill(o.w_out, (size_t)o.nout * H, H); fill(o.b_out, o.nout, H);
+  }
+  KBJ_CHECK_LAUNCH(ctx, "init_uniform_kernel");
+  return 0;
+}
+
+int kbj_policy_step(kbj_ctx* ctx, const float* params_d, const float* actor_obs_d, const float* critic_obs_d, kbj_carry* carry, uint32_t seed,
+                    uint32_t step_index, int argmax, float* action_d, float* logp_d, float* value_d) {
+  if (!ctx || !params_d || !actor_obs_d || !critic_obs_d || !carry || !action_d || !logp_d || !value_d) return kbj_fail(ctx, "kbj_policy_step: null argument");
+  KBJ_HIP(ctx, hipSetDevice(ctx->device));
+  NnWs& w = *ws_of(ctx);
+  if (w.mirror && (!carry->actor_mirror_hc_d || !carry->critic_mirror_hc_d || !carry->lpf_mirror_d))
+    return kbj_fail(ctx, "kbj_policy_step: the mirror losses are enabled, the carry needs the mirror-branch arrays");
+  if (!w.padded()) return policy_step_body(ctx, params_d, actor_obs_d, critic_obs_d, carry, seed, step_index, argmax, action_d, logp_d, value_d);
+  pad_params(ctx, ctx->stream, params_d, w.pparams);
+  kbj_carry pc = pad_carry(ctx, ctx->stream, *carry);
+  const int rc = policy_step_body(ctx, w.pparams, actor_obs_d, critic_obs_d, &pc, seed, step_index, argmax, action_d, logp_d, value_d);
+  unpad_carry(ctx, ctx->stream, *carry);
+  return rc;
+}
+
+int kbj_carry_reset(kbj_ctx* ctx, kbj_carry* carry, const float* done_d, int done_stride) {
+  if (!ctx || !carry || !done_d) return kbj_fail(ctx, "kbj_carry_reset: null argument");
+  KBJ_HIP(ctx, hipSetDevice(ctx->device));
+  NnWs& w = *ws_of(ctx);
+  if (w.mirror && (!carry->actor_mirror_hc_d || !carry->critic_mirror_hc_d || !carry->lpf_mirror_d)) return kbj_fail(ctx, "kbj_carry_reset: mirror-branch carry arrays are NULL");
+  kbj_carry pc = w.padded() ? pad_carry(ctx, ctx->stream, *carry) : *carry;
+  carry_reset_nets(ctx, ctx->stream, 0, w.nnets, 0, w.N, &pc, done_d, done_stride, 0);   // (the body: H wide)
+  if (w.padded()) unpad_carry(ctx, ctx->stream, *carry);
+  KBJ_CHECK_LAUNCH(ctx, "carry_reset_kernel");
+  return 0;
+}
+
+int kbj_rollout(kbj_ctx* ctx, const float* params_d, kbj_carry* carry, uint32_t seed, uint32_t first_step_index, kbj_traj* tr) {
+  if (!ctx || !params_d || !carry || !tr) return kbj_fail(ctx, "kbj_rollout: null argument");
+  KBJ_HIP(ctx, hipSetDevice(ctx->device));
+  NnWs& w = *ws_of(ctx);
+  if (tr->N != w.N || tr->T <= 0) return kbj_fail(ctx, "kbj_rollout: trajectory shape does not match the context");
+  if (!w.padded()) return rollout_body(ctx, params_d, carry, seed, first_step_index, tr);
+  // the H-wide schedule on internal copies; the caller's start-carry snapshot is taken here, at its own width
+  const size_t ub = (size_t)2 * w.D * w.N * w.Hu * sizeof(float);
+  for (int k = 0; k < w.nnets; ++k) {
+    if (!traj_carry0(*tr, k) || !carry_hc(*carry, k)) return kbj_fail(ctx, "kbj_rollout: carry / trajectory start-carry array is NULL");
+    KBJ_HIP(ctx, hipMemcpyAsync(traj_carry0(*tr, k), carry_hc(*carry, k), ub, hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  pad_params(ctx, ctx->stream, params_d, w.pparams);
+  kbj_carry pc = pad_carry(ctx, ctx->stream, *carry);
+  kbj_traj pt = *tr;
+  for (int k = 0; k < 4; ++k) traj_carry0(pt, k) = w.pc0[k];
+  const int rc = rollout_body(ctx, w.pparams, &pc, seed, first_step_index, &pt);
+  unpad_carry(ctx, ctx->stream, *carry);
+  return rc;
+}
+
 int kbj_gae(kbj_ctx* ctx, const kbj_traj* tr, float* adv_d, float* target_d) {
   if (!ctx || !tr || !adv_d || !target_d) return kbj_fail(ctx, "kbj_gae: null argument");
   KBJ_HIP(ctx, hipSetDevice(ctx->device));
@@ -1006,15 +973,14 @@ int head_gathers(kbj_ctx* ctx, hipStream_t st, const kbj_traj* tr, const int32_t
   else hipLaunchKernelGGL(gather_rows_kernel, g1((size_t)R * lda), dim3(256), 0, st, tr->actor_obs_d, idx, T, N, B, lda, lda, lda, w.tb[0].obs);
   GatherSmallArgs gs{tr->action_d, nullptr, nullptr, nullptr, nullptr, tr->aux_d, w.act, w.logp_old, w.val_old, w.adv, w.target, w.keep};
   hipLaunchKernelGGL(gather_small_kernel, g1((size_t)R), dim3(256), 0, st, gs, idx, T, N, B, KBJ_NU + 4, KBJ_NU + 5);   // keep flags: all the recurrences need of these
-  const float* carry0[4] = {tr->carry0_actor_hc_d, tr->carry0_critic_hc_d, tr->carry0_actor_mirror_hc_d, tr->carry0_critic_mirror_hc_d};
-  if (w.mirror && (!carry0[2] || !carry0[3] || !tr->carry0_lpf_mirror_d))
+  if (w.mirror && (!traj_carry0(*tr, 2) || !traj_carry0(*tr, 3) || !tr->carry0_lpf_mirror_d))
     return kbj_fail(ctx, "PPO pass: the mirror losses are enabled, the trajectory needs the mirror-branch carries");
   GatherCarryArgs gc;
   gc.nplanes = 0;
   for (int n = 0; n < w.nnets; ++n)
     for (int l = 0; l < D; ++l) {  // carry at the start of the trajectory: [N][H] planes h, c of every layer
-      gc.src[gc.nplanes] = carry0[n] + (size_t)(2 * l) * N * H; gc.dst[gc.nplanes++] = w.tb[n].Hm[l];
-      gc.src[gc.nplanes] = carry0[n] + (size_t)(2 * l + 1) * N * H; gc.dst[gc.nplanes++] = w.tb[n].Cm[l];
+      gc.src[gc.nplanes] = traj_carry0(*tr, n) + (size_t)(2 * l) * N * H; gc.dst[gc.nplanes++] = w.tb[n].Hm[l];
+      gc.src[gc.nplanes] = traj_carry0(*tr, n) + (size_t)(2 * l + 1) * N * H; gc.dst[gc.nplanes++] = w.tb[n].Cm[l];
     }
   gc.nlpf = 0;
   gc.src[gc.nplanes] = tr->carry0_lpf_d; gc.dst[gc.nplanes] = w.lpf0; gc.nlpf++;
@@ -1114,7 +1080,7 @@ int ppo_forward_nets(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, co
       hipLaunchKernelGGL(mirror_rows_kernel, g1((size_t)R * w.net[k].ld_obs), dim3(256), 0, ns[k], w.tb[k].obs, w.tb[2 + k].obs, (size_t)R, w.net[k].ld_obs, w.mtab[k]);
   // ---- forward through time: actor on the caller's stream, critic on the context's second stream (the recurrences are
   // latency bound, so the two nets overlap) ----
-  static const int stamp_sel = getenv("KBJ_SEQ_STAMPS") ? atoi(getenv("KBJ_SEQ_STAMPS")) : 1;   // diagnostics build: 1 + net + 2 * layer picks the stamped forward launch
+  const int stamp_sel = ctx->set.stamp_sel;   // diagnostics build: 1 + net + 2 * layer picks the stamped forward launch
   const int stamp_net = (stamp_sel - 1) & 1, stamp_layer = ((stamp_sel - 1) >> 1) & 1;
   // forward: the K = H input projections (x W_ih^T + b) run inside the persistent recurrence, their MFMAs placed around the flag poll and
   // the h-tile fetch where the matrix pipe idles (kbj_lstm_seq.h FUSE): a fused launch takes 1.11 instead of 0.88 ms, the 0.41-0.48 ms
@@ -1176,24 +1142,10 @@ int ppo_forward_nets(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, co
   return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int kbj_ppo_forward(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const int32_t* env_idx_d, int B, kbj_ppo_vars* out) {
-  if (!ctx || !params_d || !tr || !env_idx_d || !out || !out->logp_d || !out->value_d) return kbj_fail(ctx, "kbj_ppo_forward: null argument");
-  KBJ_HIP(ctx, hipSetDevice(ctx->device));
+int ppo_forward_body(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const int32_t* env_idx_d, kbj_ppo_vars* out) {
   NnWs& w = *ws_of(ctx);
   const kbj_config& c = ctx->cfg_h;
-  if (B != w.B) return kbj_fail(ctx, "kbj_ppo_forward: B must equal config.batch_size");
-  if (tr->T != w.T || tr->N != w.N) return kbj_fail(ctx, "kbj_ppo_forward: trajectory shape does not match the context");
-  if (w.padded() && !w.inner) {
-    InnerScope in(w);
-    pad_params(ctx, ctx->stream, params_d, w.pparams);
-    kbj_traj pt = pad_traj_carry0(ctx, ctx->stream, *tr);
-    return kbj_ppo_forward(ctx, w.pparams, &pt, env_idx_d, B, out);
-  }
-  const int T = tr->T, H = w.H, R = T * B, D = w.D;
+  const int T = tr->T, H = w.H, B = w.B, R = T * B, D = w.D;
   hipStream_t ns[2];
   if (ppo_forward_nets(ctx, params_d, tr, env_idx_d, nullptr, nullptr, nullptr, false, ns)) return -1;
   hipStream_t s = ns[0];   // the actor's lane
@@ -1218,36 +1170,18 @@ int kbj_ppo_forward(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, con
   return 0;
 }
 
-int kbj_ppo_grad(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const int32_t* env_idx_d, int B, const float* adv_d, const float* target_d,
-                 float* grad_d, float* metrics_d) {
-  if (!ctx || !params_d || !tr || !env_idx_d || !adv_d || !target_d || !grad_d || !metrics_d) return kbj_fail(ctx, "kbj_ppo_grad: null argument");
-  KBJ_HIP(ctx, hipSetDevice(ctx->device));
+int ppo_grad_body(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const int32_t* env_idx_d, const float* adv_d, const float* target_d,
+                  float* grad_d, float* metrics_d) {
   NnWs& w = *ws_of(ctx);
   const kbj_config& c = ctx->cfg_h;
   const Sched& sc = w.sched;
-  if (B != w.B) return kbj_fail(ctx, "kbj_ppo_grad: B must equal config.batch_size");
-  int T = tr->T, N = tr->N, H = w.H;
-  if (T != w.T || N != w.N) return kbj_fail(ctx, "kbj_ppo_grad: trajectory shape does not match the context");
-  hipStream_t s = ctx->stream;
-  if (w.padded() && !w.inner) {
-    InnerScope in(w);
-    pad_params(ctx, s, params_d, w.pparams);
-    kbj_traj pt = pad_traj_carry0(ctx, s, *tr);
-    const int rc = kbj_ppo_grad(ctx, w.pparams, &pt, env_idx_d, B, adv_d, target_d, w.pgrad, metrics_d);
-    if (rc) return rc;
-    unpad_params(ctx, s, w.pgrad, grad_d);          // the poison markers of a timed-out recurrence sit on real elements: they travel
-    KBJ_HIP(ctx, hipEventRecord(ctx->ev_actor_grad, s));   // the caller's actor slice is final only now
-    KBJ_CHECK_LAUNCH(ctx, "pad_params_kernel");
-    return 0;
-  }
-  const int R = T * B, D = w.D;
+  const int T = tr->T, H = w.H, B = w.B, R = T * B, D = w.D;
   KbjTimed timed(ctx, true);
   const bool one_stream = sc.one_stream, fold_actor = sc.fold_actor, fold_critic = sc.fold_critic;
   hipStream_t ns[2];
-  struct X3Scope { X3Scope(int v) { g_gemm_x3 = v; } ~X3Scope() { g_gemm_x3 = 0; } } x3scope(sc.gemm_x3 ? 1 : 0);   // backward-pass GEMMs only
   if (ppo_forward_nets(ctx, params_d, tr, env_idx_d, adv_d, target_d, grad_d, true, ns)) return -1;
-  s = ns[0];   // from here on "s" = the actor's lane (the caller's stream or the context's second one, Sched::critic_on_caller)
-  static const int bstamp_sel = getenv("KBJ_SEQ_BSTAMPS") ? atoi(getenv("KBJ_SEQ_BSTAMPS")) : 0;   // diagnostics build only
+  hipStream_t s = ns[0];   // "s" = the actor's lane (the caller's stream or the context's second one, Sched::critic_on_caller)
+  const int bstamp_sel = ctx->set.bstamp_sel;   // diagnostics build only
   // Without the mirror branches the critic's one-output head, the value half of the loss and the head's backward are ONE kernel on the
   // critic's lane (critic_head_kernel: ~30 us instead of two degenerate GEMMs and three small kernels, ~220 us, on the longer chain).
   const bool fused_critic_head = sc.fused_critic_head && !w.mirror && w.net[1].nout == 1;
@@ -1270,14 +1204,12 @@ int kbj_ppo_grad(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const 
     const NetOff& oc = w.net[1];
     TrainBufs& tc = w.tb[1];
     const dim3 grid(2048), block(256);
-#define KBJ_CRITIC_HEAD(V) hipLaunchKernelGGL((critic_head_kernel<V>), grid, block, 0, ns[1], tc.Hout[D - 1], params_d + oc.w_out, params_d + oc.b_out, w.val_old, w.target, \
-                                              pp, R, w.value, w.dvalue, tc.dOut, tc.dHa, w.stats + 2)
-    switch (H / 64) {
-      case 1: KBJ_CRITIC_HEAD(1); break; case 2: KBJ_CRITIC_HEAD(2); break; case 3: KBJ_CRITIC_HEAD(3); break; case 4: KBJ_CRITIC_HEAD(4); break;
-      case 5: KBJ_CRITIC_HEAD(5); break; case 6: KBJ_CRITIC_HEAD(6); break; case 7: KBJ_CRITIC_HEAD(7); break; case 8: KBJ_CRITIC_HEAD(8); break;
-      default: return kbj_fail(ctx, "critic_head_kernel: hidden size above 512");
-    }
-#undef KBJ_CRITIC_HEAD
+    const bool built = dispatch_hidden(H, [&](auto hc) {
+      hipLaunchKernelGGL((critic_head_kernel<decltype(hc)::value / 64>), grid, block, 0, ns[1], tc.Hout[D - 1], params_d + oc.w_out, params_d + oc.b_out, w.val_old, w.target,
+                         pp, R, w.value, w.dvalue, tc.dOut, tc.dHa, w.stats + 2);
+      return true;
+    });
+    if (!built) return kbj_fail(ctx, "kbj_ppo_grad: critic_head_kernel is built for hidden sizes 64, 128, ..., 512");
     if (one_stream) hipLaunchKernelGGL(ppo_loss_kernel, g1(R), dim3(256), 0, s, w.logp, w.value, w.ent, w.logp_old, w.val_old, w.adv, w.target, w.stats, pp, R, w.dlogp, w.dvalue,
                                        w.stats + 2, 1);   // (the actor's launch above was a no-op in this diagnostic mode)
   } else {
@@ -1320,10 +1252,10 @@ int kbj_ppo_grad(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const 
   for (int n = 0; n < w.nnets; ++n) {
     const NetOff& o = w.net[n & 1];
     TrainBufs& t = w.tb[n];
-    if (!(n == 1 && fused_critic_head)) linear_bwd_input(ns[n & 1], t.dOut, 40, params_d + o.w_out, H, t.dHa, H, R, H, o.nout, 0);
+    if (!(n == 1 && fused_critic_head)) linear_bwd_input(ns[n & 1], sc.gemm_x3, t.dOut, 40, params_d + o.w_out, H, t.dHa, H, R, H, o.nout, 0);
     if (n == 1 && critic_fork_recorded) hipStreamWaitEvent(ctx->side[1], ctx->ev_side[1], 0);   // recorded with the metrics fork above
     else fork_side(n);
-    linear_bwd_weight(ctx, side_of(n), t.dOut, 40, t.Hout[D - 1], H, grad_d + o.w_out, H, o.nout, H, R);
+    linear_bwd_weight(ctx, side_of(n), sc.gemm_x3, t.dOut, 40, t.Hout[D - 1], H, grad_d + o.w_out, H, o.nout, H, R);
     colsum_acc(ctx, side_of(n), t.dOut, R, o.nout, 40, grad_d + o.b_out);
     dh_above[n] = t.dHa; dx_out[n] = t.dHb;
   }
@@ -1357,7 +1289,7 @@ int kbj_ppo_grad(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const 
   auto launch_dw_pair = [&](hipStream_t st, int n, int l) {
     const NetOff& o = w.net[n & 1];
     TrainBufs& t = w.tb[n];
-    linear_bwd_weight2(ctx, st, t.dGl[l], 4 * H, t.Hm[l], l == 0 ? t.X0 : t.Hout[l - 1], H, grad_d + o.w_hh[l], grad_d + o.w_ih[l], H, 4 * H, H, R);
+    linear_bwd_weight2(ctx, st, sc.gemm_x3, t.dGl[l], 4 * H, t.Hm[l], l == 0 ? t.X0 : t.Hout[l - 1], H, grad_d + o.w_hh[l], grad_d + o.w_ih[l], H, 4 * H, H, R);
   };
   for (int l = D - 1; l >= 0; --l) {
     for (int n = 0; n < w.nnets; ++n) {
@@ -1401,7 +1333,7 @@ int kbj_ppo_grad(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const 
         GemmArgs g{t.dGl[0], t.Hm[0], grad_d + o.w_hh[0], nullptr, 4 * H, H + o.nin, R, 4 * H, H, H, 1, sk, nullptr};
         g.B2 = t.obs; g.C2 = Z; g.n1 = H; g.ldb2 = o.ld_obs; g.ldc2 = o.ld_obs;
         g.skws = sk_workspace(ctx, ws, (size_t)sk * 4 * H * (H + o.nin));
-        g.x3 = g_gemm_x3;
+        g.x3 = sc.gemm_x3;
         gemm_launch<false, false>(ws, g, ts == 128 ? 1 : 0);
         // dW_in += W_ih0^T Z, dW_ih0 += Z W_in^T (the bias terms follow from db_0 at the end)
         // (a 4H-deep contraction on a handful of output tiles: split over k so that it is a short kernel, not a 130 us tail on 32 workgroups)
@@ -1417,7 +1349,7 @@ int kbj_ppo_grad(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const 
         continue;
       }
       // the input gradient as ONE product on the net's own lane, behind the recurrence (it is the next layer's input)
-      linear_bwd_input(s, t.dGl[l], 4 * H, params_d + o.w_ih[l], H, dx_out[n], H, R, H, 4 * H, 0, H <= 256 ? 2 : -1);
+      linear_bwd_input(s, sc.gemm_x3, t.dGl[l], 4 * H, params_d + o.w_ih[l], H, dx_out[n], H, R, H, 4 * H, 0, H <= 256 ? 2 : -1);
       if (l > 0) pending_dw.push_back(PendingDW{n, l});   // issued in the next pass of the layer loop, behind layer l - 1's recurrence
       else {
         fork_side(n);   // the weight gradients start behind the input gradient
@@ -1433,7 +1365,7 @@ int kbj_ppo_grad(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const 
     TrainBufs& t = w.tb[n];
     hipStream_t s = ns[n & 1];
     if (!(fold_actor && ((n & 1) == 0 || fold_critic))) {   // input projection (dh_above now holds dX0)
-      linear_bwd_weight(ctx, s, dh_above[n], H, t.obs, o.ld_obs, grad_d + o.w_in, o.nin, H, o.nin, R);
+      linear_bwd_weight(ctx, s, sc.gemm_x3, dh_above[n], H, t.obs, o.ld_obs, grad_d + o.w_in, o.nin, H, o.nin, R);
       colsum_acc(ctx, s, dh_above[n], R, H, H, grad_d + o.b_in);
     }
     if (!one_stream) {
@@ -1472,6 +1404,41 @@ int kbj_ppo_grad(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const 
 #endif
   KBJ_CHECK_LAUNCH(ctx, "kbj_ppo_grad");
   if (sc.debug_sync) return kbj_synchronize(ctx);   // KBJ_DEBUG=1: surface a hand-off timeout at the call that caused it
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kbj_ppo_forward(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const int32_t* env_idx_d, int B, kbj_ppo_vars* out) {
+  if (!ctx || !params_d || !tr || !env_idx_d || !out || !out->logp_d || !out->value_d) return kbj_fail(ctx, "kbj_ppo_forward: null argument");
+  KBJ_HIP(ctx, hipSetDevice(ctx->device));
+  NnWs& w = *ws_of(ctx);
+  if (B != w.B) return kbj_fail(ctx, "kbj_ppo_forward: B must equal config.batch_size");
+  if (tr->T != w.T || tr->N != w.N) return kbj_fail(ctx, "kbj_ppo_forward: trajectory shape does not match the context");
+  if (!w.padded()) return ppo_forward_body(ctx, params_d, tr, env_idx_d, out);
+  pad_params(ctx, ctx->stream, params_d, w.pparams);
+  kbj_traj pt = pad_traj_carry0(ctx, ctx->stream, *tr);
+  return ppo_forward_body(ctx, w.pparams, &pt, env_idx_d, out);
+}
+
+int kbj_ppo_grad(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const int32_t* env_idx_d, int B, const float* adv_d, const float* target_d,
+                 float* grad_d, float* metrics_d) {
+  if (!ctx || !params_d || !tr || !env_idx_d || !adv_d || !target_d || !grad_d || !metrics_d) return kbj_fail(ctx, "kbj_ppo_grad: null argument");
+  KBJ_HIP(ctx, hipSetDevice(ctx->device));
+  NnWs& w = *ws_of(ctx);
+  if (B != w.B) return kbj_fail(ctx, "kbj_ppo_grad: B must equal config.batch_size");
+  if (tr->T != w.T || tr->N != w.N) return kbj_fail(ctx, "kbj_ppo_grad: trajectory shape does not match the context");
+  if (!w.padded()) return ppo_grad_body(ctx, params_d, tr, env_idx_d, adv_d, target_d, grad_d, metrics_d);
+  hipStream_t s = ctx->stream;
+  pad_params(ctx, s, params_d, w.pparams);
+  kbj_traj pt = pad_traj_carry0(ctx, s, *tr);
+  const int rc = ppo_grad_body(ctx, w.pparams, &pt, env_idx_d, adv_d, target_d, w.pgrad, metrics_d);
+  if (rc) return rc;
+  unpad_params(ctx, s, w.pgrad, grad_d);          // the poison markers of a timed-out recurrence sit on real elements: they travel
+  KBJ_HIP(ctx, hipEventRecord(ctx->ev_actor_grad, s));   // the caller's actor slice is final only now
+  KBJ_CHECK_LAUNCH(ctx, "pad_params_kernel");
   return 0;
 }
 
@@ -1537,11 +1504,11 @@ int kbj_adamw_step(kbj_ctx* ctx, float* params_d, float* m_d, float* v_d, const 
   if (!w.sumsq_clean) KBJ_HIP(ctx, hipMemsetAsync(sumsq, 0, sizeof(double), s));
   w.sumsq_clean = false;
   double* part = w.sched.deterministic ? w.detd : nullptr;
-  hipLaunchKernelGGL(sumsq_kernel, dim3(512), dim3(256), 0, s, grad_d, w.unparams, grad_scale, sumsq, part);
+  hipLaunchKernelGGL(sumsq_kernel, dim3(512), dim3(256), 0, s, grad_d, w.user.nparams, grad_scale, sumsq, part);
   if (part) hipLaunchKernelGGL(reduce_double_kernel, dim3(1), dim3(64), 0, s, part, 512, 1, sumsq);
   AdamParams ap{c.learning_rate, c.adam_b1, c.adam_b2, c.adam_eps, c.weight_decay, c.max_grad_norm,
                 (float)(1.0 - std::pow((double)c.adam_b1, (double)step)), (float)(1.0 - std::pow((double)c.adam_b2, (double)step)), grad_scale};
-  hipLaunchKernelGGL(adamw_kernel, g1(w.unparams), dim3(256), 0, s, params_d, m_d, v_d, grad_d, w.unparams, sumsq, ap, w.seq_err);
+  hipLaunchKernelGGL(adamw_kernel, g1(w.user.nparams), dim3(256), 0, s, params_d, m_d, v_d, grad_d, w.user.nparams, sumsq, ap, w.seq_err);
   KBJ_CHECK_LAUNCH(ctx, "adamw_kernel");
   return 0;
 }
