@@ -17,6 +17,8 @@
 // section 5), every VALU instruction in this loop is matrix time lost.
 // Work items are ordered n-tile fastest and handed out so that the workgroups of one XCD (blockIdx % 8) own a contiguous
 // range: the operand panel shared by neighbouring tiles is fetched into one L2, not eight.
+// Every form below (layouts, tiles, fast / guarded loads, k1, n1, a_idx, split-K with atomics and slabs, the x3 kernels and gemm_x3_form) is
+// checked per call site against a double-precision reference at ragged shapes by tools/gemm_check (tests/test_gpu_tools.py).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>

@@ -7,13 +7,16 @@ driver's `-m gpu` run:
   This is what lets tests/test_emu_env.py (CPU) speak for the register solver the GPU runs.
 * tools/gemm_bench 10: the operand range of the bf16 x3 split GEMM (kbj_config.gemm_bf16x3): as accurate as the exact fp32-MFMA kernel for
   operands scaled anywhere in 2^-100 .. 2^100, bounded loss below 2^-110 where the split's lower pieces enter the bf16 subnormal range.
+* tools/gemm_check: every form of the GEMM launcher (csrc/kbj_gemm.h), named after its call site in kbj_nn.hip, against a full double-precision
+  reference at ragged shapes inside NaN / bit-pattern guard bands - bit for bit on integer operands, within the derived fp32 bound on reals;
+  `gemm_check --plan` (no device, runs in the CPU suite) proves that the integer inputs satisfy the bit-exactness precondition.
 """
 import os
 import subprocess
 
 import pytest
 
-pytestmark = pytest.mark.gpu
+gpu = pytest.mark.gpu      # per test: the --plan test below needs no device
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOOLS = os.path.join(ROOT, "tools")
@@ -24,6 +27,7 @@ def _run(cmd, timeout=600):
     return out.returncode, out.stdout, out.stderr
 
 
+@gpu
 def test_wave_primitives_and_arrow_solve_bit_identical_to_the_emulation():
     rc, so, se = _run(["make", "-C", os.path.join(TOOLS, "wave_test"), "-s"])
     assert rc == 0, (so[-500:], se[-1500:])
@@ -39,6 +43,7 @@ def test_wave_primitives_and_arrow_solve_bit_identical_to_the_emulation():
     assert m and float(m.group(1)) < 1e-6 and float(m.group(2)) < 2e-6, solve     # relative to max |x| over 256 random arrow systems
 
 
+@gpu
 def test_gemm_bf16x3_operand_range():
     rc, so, se = _run(["make", "-C", TOOLS, "-s", "gemm_bench"])
     assert rc == 0, (so[-500:], se[-1500:])
@@ -48,3 +53,51 @@ def test_gemm_bf16x3_operand_range():
     assert len(rows) == 24 and all(l.rstrip().endswith("ok") or "bounded loss" in l for l in rows), so
     strict = [l for l in rows if "bounded loss" not in l]
     assert len(strict) == 16                                       # every operand scale in 2^-100 .. 2^100: as accurate as the exact kernel
+
+
+GEMM_CHECK_FORMS = ("linear_fwd", "rollout_gates", "critic_input_projection", "g2a", "linear_bwd_input", "linear_bwd_weight", "linear_bwd_weight2",
+                    "g1a")
+
+
+def _gemm_check_plan():
+    rc, so, se = _run(["make", "-C", TOOLS, "-s", "gemm_check"])
+    assert rc == 0, (so[-500:], se[-1500:])
+    rc, so, se = _run([os.path.join(TOOLS, "gemm_check"), "--plan"], timeout=300)
+    return rc, so, se
+
+
+def _case_lines(so):
+    return [l for l in so.splitlines() if l.startswith("case ")]
+
+
+def test_gemm_check_plan_inputs_satisfy_the_exactness_precondition():
+    """No device: the tool enumerates its case table, builds the integer inputs and verifies that sum |a||b| + |bias| + |C0| < 2^24 for every
+    output element, i.e. that the reference alone entitles the GPU test to demand bit-identical results."""
+    rc, so, se = _gemm_check_plan()
+    assert rc == 0 and "GEMM CHECK PLAN OK" in so, (so[-2000:], se[-500:])
+    cases = _case_lines(so)
+    count = [l for l in so.splitlines() if l.startswith("cases ")]
+    assert len(count) == 1 and int(count[0].split()[1]) == len(cases) > 0
+    assert not any("FAIL" in l for l in so.splitlines()), [l for l in so.splitlines() if "FAIL" in l][:20]
+    for form in GEMM_CHECK_FORMS:                                   # every call site of kbj_nn.hip, as issued and with x3 = 1
+        mine = [l for l in cases if l.split()[2] == form]
+        assert any(" x3=0->" in l for l in mine) and any(" x3=1->" in l for l in mine), form
+    x3 = [l for l in cases if " x3=1->" in l]
+    for kind in ("x3-plain(TM=1)", "x3-plain(TM=2)", "x3-GEN(TM=1)", "x3-GEN(TM=2)", "exact-kernel("):   # all four instantiations and the fallback
+        assert any(kind in l for l in x3), kind
+
+
+@gpu
+def test_gemm_check_every_form_against_the_double_reference():
+    rc, so, se = _gemm_check_plan()
+    assert rc == 0, (so[-2000:], se[-500:])
+    planned = int([l for l in so.splitlines() if l.startswith("cases ")][0].split()[1])
+    rc, so, se = _run([os.path.join(TOOLS, "gemm_check")], timeout=300)
+    lines = so.splitlines()
+    failing = [l for l in lines if "FAIL" in l]
+    assert rc == 0 and "GEMM CHECK PASSED" in so, (failing[:40], so[-1500:], se[-500:])
+    cases = _case_lines(so)
+    assert len(cases) == planned, (len(cases), planned)
+    for form in GEMM_CHECK_FORMS:
+        assert any(l.split()[2] == form for l in cases), form
+    assert not failing, failing[:40]
