@@ -140,6 +140,15 @@ int kbj_policy_step(kbj_ctx* ctx, const float* params_d, const float* actor_obs_
                     uint32_t seed, uint32_t step_index, int argmax, float* action_d, float* logp_d, float* value_d);
 /* carry <- initial carry where done (train.py:1502-1506): done_d [N] float (aux KBJ_AUX_DONE column, stride in floats) */
 int kbj_carry_reset(kbj_ctx* ctx, kbj_carry* carry, const float* done_d, int done_stride);
+/* replaces: the bootstrap value every PPO stack takes at the end of a rollout - run_critic (train.py:1381-1433) on the observation that FOLLOWS the
+ * last step (UPSTREAM MEMORY: ksim's GAE is un-vendored). The critic's value of ONE observation row critic_obs_d
+ * [N][ld_critic] from the critic carries in `carry` (only carry->critic_hc_d is read): value_d [N]. Nothing the caller owns is written besides
+ * value_d - the step runs on a copy of the carries inside the context, no net advances. The launches are those kbj_policy_step makes for
+ * its critic, so value_d is bit-identical to what kbj_policy_step would write from the same carries and row. Needs a context created with
+ * kbj_config.gae_tail_value = 1 (the carry copy is allocated then); call it where the carries are at rest: behind kbj_rollout, kbj_policy_step
+ * or kbj_carry_reset. Hosts that drive the steps themselves call it behind their last kbj_carry_reset with observation row T and
+ * kbj_traj.value_tail_d, BEFORE the update changes the parameters. */
+int kbj_critic_value(kbj_ctx* ctx, const float* params_d, const float* critic_obs_d, const kbj_carry* carry, float* value_d);
 
 /* ---- rollout, §3.2 ------------------------------------------------------------------------- */
 typedef struct kbj_traj {
@@ -160,9 +169,13 @@ typedef struct kbj_traj {
   float* reward_comps_d;     /* optional [T][N][12]: unscaled reward terms of the rollout (logging), or NULL */
   float* qstate_d;           /* optional [T][N][KBJ_QSTATE_SIZE]: qpos / qvel after every step + the positions its last forward pass ran on (the
                               * fields a ksim Trajectory carries for user reward terms: trajectory.qpos / .qvel / .xpos / .xquat, train.py:262-506), or NULL */
+  float* value_tail_d;       /* optional [N]: the critic's value of observation row T from the carries after the last step (kbj_config.gae_tail_value:
+                              * kbj_rollout writes it, kbj_gae bootstraps the last row from it), or NULL. Untouched while gae_tail_value is 0 */
 } kbj_traj;
 /* replaces: ksim's jitted rollout scan (vmap over envs, scan over T). Copies observation row T to row 0,
- * snapshots the carry, then T x (policy_step, env_step, carry_reset), then rewards. */
+ * snapshots the carry, then T x (policy_step, env_step, carry_reset), then rewards. With kbj_config.gae_tail_value = 1 and a non-NULL
+ * traj->value_tail_d it also runs the critic once more, on observation row T with a COPY of the carries the last carry reset left (the
+ * caller's carries do not advance), with the rollout's parameters: exactly kbj_critic_value below. */
 int kbj_rollout(kbj_ctx* ctx, const float* params_d, kbj_carry* carry, uint32_t seed, uint32_t first_step_index, kbj_traj* traj);
 
 /* replaces: `argmax=True` of sample_action during ksim's validation rollouts (train.py:1564, valid_every_n_steps train.py:1789): the following
@@ -187,7 +200,20 @@ int kbj_set_rollout_argmax(kbj_ctx* ctx, int argmax);
 int kbj_episode_stats(kbj_ctx* ctx, const kbj_traj* traj, float* acc_d, double* stats_d);
 
 /* ---- PPO update, rows a9, a12, a13 ---------------------------------------------------------- */
-/* replaces: ksim GAE (gamma, lam: train.py:1769-1770). done from aux; adv_d/target_d [T][N] */
+/* replaces: ksim GAE (gamma, lam: train.py:1769-1770). done from aux; adv_d/target_d [T][N].
+ * Per env n, for t = T-1 .. 0, with d = aux[t][n][KBJ_AUX_DONE], v = value[t][n], r = reward[t][n] and A_T = 0:
+ *   d < 0, or d > 0 with gae_bootstrap_truncation == 0:  delta = r - v                          A_t = delta   (terminal: the chain is cut)
+ *   d > 0 with gae_bootstrap_truncation == 1:            delta = r + gamma v - v                A_t = delta   (truncation: cut, but bootstrapped)
+ *   d == 0, t < T-1:                                     delta = r + gamma value[t+1][n] - v    A_t = delta + gamma lam A_{t+1}
+ *   d == 0, t == T-1:                                    delta = r + gamma vn - v               A_t = delta
+ *                                                        vn = traj->value_tail_d[n] if gae_tail_value == 1, else v
+ *   adv = A_t, target = A_t + v.
+ * Both switches are kbj_config fields, default 0 (this build's conventions: every non-zero DONE is terminal, V_T := V_{T-1}); with both at 0
+ * the kernel of the earlier releases runs, bit for bit. At a truncation v stands in for the value of the terminal observation, which is never
+ * recorded (the env kernel resets in place: observation row t+1 already belongs to the next episode) - so a truncation in the LAST row
+ * follows the truncation rule, not the tail rule (row T is a post-reset observation there). A user Termination term that writes +1 into the
+ * DONE column gets the same treatment. gae_tail_value == 1 with traj->value_tail_d == NULL is an error: nothing is launched, the context
+ * stays usable. tests/gae_ref.py restates this table in float64. */
 int kbj_gae(kbj_ctx* ctx, const kbj_traj* traj, float* adv_d, float* target_d);
 /* replaces: the loss/grad of one minibatch: get_ppo_variables under grad (BPTT through T LSTM steps,
  * train.py:1435-1524) + ksim's clipped PPO loss. env_idx_d [B] int32 env indices of the minibatch.

@@ -148,7 +148,12 @@ typedef struct kbj_config {
                                 EXACT three-way split of their fp32 operands (6 bf16 products per fp32 product, fp32 accumulation): measured more
                                 accurate than the fp32-MFMA chain and faster. Default 0: the plain fp32-MFMA kernels, which is
                                 what every headline number of this library is measured with. Ignored in deterministic mode. */
-  float dt;                  /* 0.004 */
+  int32_t gae_bootstrap_truncation; /* kbj_gae at a TRUNCATION (KBJ_AUX_DONE > 0: the episode-length "success" termination, or a user term's +1):
+                                0 (default) = a terminal state like a failure, delta = r - V(s_t); 1 = bootstrap through it with V(s_t) standing
+                                in for the unrecorded terminal observation, delta = r + gamma V(s_t) - V(s_t). The advantage chain is cut either way. */
+  int32_t gae_tail_value;    /* kbj_gae at the END of a rollout: 0 (default) = V_T := V_{T-1}; 1 = V_T = kbj_traj.value_tail_d, the critic's value of
+                                observation row T from the post-rollout carries (kbj_rollout / kbj_critic_value write it). 0 or 1, kbj.h kbj_gae */
+  float dt;                 /* 0.004 */
   float ctrl_dt;             /* 0.02  */
   float solver_tolerance;    /* 1e-8 */
   float latency_lo, latency_hi; /* seconds (0.003, 0.01) */

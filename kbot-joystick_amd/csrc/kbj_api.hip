@@ -62,6 +62,12 @@ int kbj_check_config(const kbj_config* cfg, char* why, size_t why_bytes) {
     return fail("hidden_size must be in 1..512 (multiples of 64 run unpadded; above 256 on the wide, untuned schedule) and depth in 1..4 (train.py:78-85 defaults 128 / 2, launch 256 / 2)");
   if (cfg->extra_obs_actor < 0 || cfg->extra_obs_actor > KBJ_MAX_EXTRA_OBS || cfg->extra_obs_critic < 0 || cfg->extra_obs_critic > KBJ_MAX_EXTRA_OBS)
     return fail("extra_obs_actor / extra_obs_critic must be in 0.." + std::to_string(KBJ_MAX_EXTRA_OBS));
+  if (cfg->gae_bootstrap_truncation != 0 && cfg->gae_bootstrap_truncation != 1)
+    return fail("gae_bootstrap_truncation must be 0 (a truncation ends the return like a failure) or 1 (bootstrap through it with V(s_t)), not " +
+                std::to_string(cfg->gae_bootstrap_truncation));
+  if (cfg->gae_tail_value != 0 && cfg->gae_tail_value != 1)
+    return fail("gae_tail_value must be 0 (V_T := V_{T-1}) or 1 (V_T = the critic's value of observation row T, kbj_traj.value_tail_d), not " +
+                std::to_string(cfg->gae_tail_value));
   const unsigned long long lim = 1ull << 31;
   const unsigned long long Hp = (unsigned long long)((cfg->hidden_size + 63) / 64 * 64), T = (unsigned long long)cfg->rollout_len;
   const unsigned long long B = (unsigned long long)(cfg->batch_size > 0 ? cfg->batch_size : cfg->num_envs), N = (unsigned long long)cfg->num_envs;

@@ -63,6 +63,7 @@ struct NnWs : ParamLayout {   // (the base: the layout at the kernels' H)
   MirrorEntry* mtab[2] = {nullptr, nullptr};
   float *rObsM[2] = {nullptr, nullptr};   // rollout: mirrored observation rows [N][ld]
   float* rH[4][MAXD] = {};                  // rollout: the h planes' ping-pong partners [N][H] per (net, layer)
+  float* tail_hc = nullptr;                 // kbj_config.gae_tail_value: the critic carry copy [D][2][N][H] that kbj_critic_value / the rollout's tail pass steps instead of the caller's
   float *y_m = nullptr, *sd_m = nullptr, *value_m = nullptr, *lpf0_m = nullptr, *dy = nullptr, *dy_m = nullptr, *dvalue_m = nullptr, *zeroR = nullptr;
   // training
   TrainBufs tb[4];
@@ -487,6 +488,7 @@ int nn_rollout_scratch(kbj_ctx* ctx, NnWs* w) {
     if (dalloc(ctx, *w, &w->rOut[n], N * 40)) return -1;
     for (int l = 0; l < w->D; ++l) if (dalloc(ctx, *w, &w->rH[n][l], N * H)) return -1;
   }
+  if (ctx->cfg_h.gae_tail_value && dalloc(ctx, *w, &w->tail_hc, 2 * (size_t)w->D * N * H)) return -1;
   if (dalloc(ctx, *w, &w->joint_bias_d, KBJ_NU)) return -1;
   if (hipMemcpy(w->joint_bias_d, ctx->model_h.joint_bias, KBJ_NU * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return kbj_fail(ctx, "hipMemcpy joint_bias");
   return 0;
@@ -646,9 +648,9 @@ const float* fold_actor_weights(kbj_ctx* ctx, hipStream_t s, const float* params
 // load path for that operand (the critic's 8192 x 256 x 475 product ran at 27 TFLOP/s, with four times the load instructions - beside an env kernel
 // that is bound by vector issue). As in the update (ppo_forward_nets): a re-pitched copy with the observation rows' stride, zeros behind column nin,
 // made once per rollout / policy step; the contraction then runs over the padded width (the rows' padding columns hold zeros: host/buffers.py).
-void repitch_input_weights(kbj_ctx* ctx, hipStream_t s, const float* params_d) {
+void repitch_input_weights(kbj_ctx* ctx, hipStream_t s, const float* params_d, int k_lo = 0, int k_hi = 2) {
   NnWs& w = *ws_of(ctx);
-  for (int k = 0; k < 2; ++k) {
+  for (int k = k_lo; k < k_hi; ++k) {
     const NetOff& o = w.net[k];
     if (o.nin == o.ld_obs) continue;
     hipLaunchKernelGGL(repitch_rows_kernel, g1((size_t)w.H * o.ld_obs), dim3(256), 0, s, params_d + o.w_in, w.H, o.nin, o.ld_obs, w.WinP[k]);
@@ -790,6 +792,22 @@ kbj_traj pad_traj_carry0(kbj_ctx* ctx, hipStream_t s, const kbj_traj& tr) {
   return p;
 }
 
+// The critic's value of ONE observation row [N][ld_critic] from a COPY of its carries (kbj_critic_value; the tail pass of kbj_rollout for
+// kbj_config.gae_tail_value): critic_hc_d [D][2][N][hc_width] goes into w.tail_hc (re-pitched when the caller's hidden_size is not the kernels'),
+// then the critic leg of policy_nets steps the copy - the launches kbj_policy_step makes for net 1 (side-lane GEMM tiles, gate GEMM + cell kernel in
+// place, fused value head), so the value is bit-identical to the one a policy step writes from the same carries and row. The critic never runs on
+// the layer-step kernel (net_uses_step_kernel), so no ping-pong partner plane is involved; its scratch rows w.rX[1] / w.rG[1] belong to policy_nets
+// alone (the update and kbj_ppo_prefetch work in w.tb[] and the gather buffers). The caller has run repitch_input_weights for params_d on a
+// stream ordered in front of s. Nets 0, 2 and 3 do not run: no other carry, no low-pass state moves.
+int critic_tail(kbj_ctx* ctx, hipStream_t s, const float* params_d, const float* critic_obs_d, const float* critic_hc_d, int hc_width, float* value_d) {
+  NnWs& w = *ws_of(ctx);   // (w.tail_hc: allocated at kbj_create exactly when gae_tail_value is set; both callers have checked)
+  if (hc_width == w.H) KBJ_HIP(ctx, hipMemcpyAsync(w.tail_hc, critic_hc_d, (size_t)2 * w.D * w.N * w.H * sizeof(float), hipMemcpyDeviceToDevice, s));
+  else repitch_hc(ctx, s, critic_hc_d, w.tail_hc, hc_width, w.H);
+  kbj_carry sc = {};
+  sc.critic_hc_d = w.tail_hc;
+  return policy_nets(ctx, s, params_d, 1, 2, 0, w.N, nullptr, critic_obs_d, &sc, 0, 0, 0, nullptr, nullptr, value_d, 0, nullptr);
+}
+
 // ---- the H-wide bodies of the entry points below (arguments validated; a padded context passes its internal copies) ----
 int policy_step_body(kbj_ctx* ctx, const float* params_d, const float* actor_obs_d, const float* critic_obs_d, kbj_carry* carry, uint32_t seed,
                      uint32_t step_index, int argmax, float* action_d, float* logp_d, float* value_d) {
@@ -855,6 +873,9 @@ int rollout_body(kbj_ctx* ctx, const float* params_d, kbj_carry* carry, uint32_t
     }
     carry_reset_nets(ctx, cs, 1, w.nnets, 0, N, carry, aux_t + KBJ_AUX_DONE, KBJ_AUX_SIZE, (t + 1) & 1);
   }
+  // kbj_config.gae_tail_value: V(s_T) for kbj_gae - the critic once more, on observation row T with a copy of the carries the last reset left, on the
+  // critic's lane in front of the join (under the tail of the last env step's successors: the actor's carry copy-back and kbj_rewards)
+  if (ctx->cfg_h.gae_tail_value && tr->value_tail_d && critic_tail(ctx, cs, params_d, tr->critic_obs_d + (size_t)T * N * lc, carry->critic_hc_d, H, tr->value_tail_d)) return -1;
   KBJ_CHECK_LAUNCH(ctx, "kbj_rollout");
   if (!serial) {   // join the side lane back into the caller's stream
     KBJ_HIP(ctx, hipEventRecord(ctx->ev_side[0], cs));
@@ -927,6 +948,20 @@ int kbj_carry_reset(kbj_ctx* ctx, kbj_carry* carry, const float* done_d, int don
   return 0;
 }
 
+int kbj_critic_value(kbj_ctx* ctx, const float* params_d, const float* critic_obs_d, const kbj_carry* carry, float* value_d) {
+  if (!ctx || !params_d || !critic_obs_d || !carry || !carry->critic_hc_d || !value_d) return kbj_fail(ctx, "kbj_critic_value: null argument");
+  KBJ_HIP(ctx, hipSetDevice(ctx->device));
+  NnWs& w = *ws_of(ctx);
+  if (!w.tail_hc) return kbj_fail(ctx, "kbj_critic_value: the context was created with kbj_config.gae_tail_value = 0 (the carry copy it steps is allocated for 1 only)");
+  kbj_nn_drop_prefetch(ctx);   // value_d may be a trajectory array
+  const float* p = params_d;
+  if (w.padded()) { pad_params(ctx, ctx->stream, params_d, w.pparams); p = w.pparams; }   // (of the carries only the critic's is read: critic_tail re-pitches it into its copy)
+  repitch_input_weights(ctx, ctx->stream, p, 1, 2);
+  if (critic_tail(ctx, ctx->stream, p, critic_obs_d, carry->critic_hc_d, w.Hu, value_d)) return -1;
+  KBJ_CHECK_LAUNCH(ctx, "kbj_critic_value");
+  return 0;
+}
+
 int kbj_rollout(kbj_ctx* ctx, const float* params_d, kbj_carry* carry, uint32_t seed, uint32_t first_step_index, kbj_traj* tr) {
   if (!ctx || !params_d || !carry || !tr) return kbj_fail(ctx, "kbj_rollout: null argument");
   KBJ_HIP(ctx, hipSetDevice(ctx->device));
@@ -952,7 +987,15 @@ int kbj_gae(kbj_ctx* ctx, const kbj_traj* tr, float* adv_d, float* target_d) {
   if (!ctx || !tr || !adv_d || !target_d) return kbj_fail(ctx, "kbj_gae: null argument");
   KBJ_HIP(ctx, hipSetDevice(ctx->device));
   const kbj_config& c = ctx->cfg_h;
+  if (c.gae_tail_value && !tr->value_tail_d)
+    return kbj_fail(ctx, "kbj_gae: kbj_config.gae_tail_value = 1 needs kbj_traj.value_tail_d (kbj_rollout / kbj_critic_value fill it), it is NULL");
   kbj_nn_drop_prefetch(ctx);
+  if (c.gae_bootstrap_truncation || c.gae_tail_value) {   // the selectable boundary conventions (kbj.h); the default below is untouched by them
+    hipLaunchKernelGGL(gae_boundary_kernel, g1(tr->N, 64), dim3(64), 0, ctx->stream, tr->value_d, tr->reward_d, tr->aux_d, c.gae_tail_value ? tr->value_tail_d : nullptr,
+                       tr->T, tr->N, c.gamma, c.lam, (int)c.gae_bootstrap_truncation, adv_d, target_d);
+    KBJ_CHECK_LAUNCH(ctx, "gae_boundary_kernel");
+    return 0;
+  }
   hipLaunchKernelGGL(gae_kernel, g1(tr->N, 64), dim3(64), 0, ctx->stream, tr->value_d, tr->reward_d, tr->aux_d, tr->T, tr->N, c.gamma, c.lam, adv_d, target_d);
   KBJ_CHECK_LAUNCH(ctx, "gae_kernel");
   return 0;

@@ -566,6 +566,31 @@ __global__ void gae_kernel(const float* __restrict__ value, const float* __restr
     adv[r] = last; target[r] = last + v;
   }
 }
+// The selectable boundary conventions (kbj.h kbj_gae, kbj_config.gae_bootstrap_truncation / gae_tail_value): the same reverse scan with the
+// table's cases spelled out. boot_trunc: a truncation (DONE > 0) bootstraps from V(s_t) - the terminal observation is not recorded - and still
+// cuts the chain; value_tail [N] non-null: V_T of the envs still running in the last row (a truncation there follows the truncation rule).
+// Launched only when a switch is on: with both off kbj_gae runs gae_kernel above, so the default stays bit-identical by construction.
+__global__ void gae_boundary_kernel(const float* __restrict__ value, const float* __restrict__ reward, const float* __restrict__ aux,
+                                    const float* __restrict__ value_tail, int T, int N, float gamma, float lam, int boot_trunc,
+                                    float* __restrict__ adv, float* __restrict__ target) {
+  int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  float last = 0;
+  for (int t = T - 1; t >= 0; --t) {
+    size_t r = (size_t)t * N + n;
+    const float d = aux[r * KBJ_AUX_SIZE + KBJ_AUX_DONE];
+    const float v = value[r];
+    if (d != 0) {   // the episode ends here: nothing of the next episode's advantages flows back
+      last = (d > 0 && boot_trunc) ? reward[r] + gamma * v - v : reward[r] - v;
+    } else if (t + 1 < T) {
+      last = reward[r] + gamma * value[r + N] - v + gamma * lam * last;
+    } else {
+      const float vn = value_tail ? value_tail[n] : v;
+      last = reward[r] + gamma * vn - v;
+    }
+    adv[r] = last; target[r] = last + v;
+  }
+}
 
 // ---- AdamW with global-norm clipping (optax.adamw, train.py:1059-1077) -------------------------------------------------
 __global__ void sumsq_kernel(const float* __restrict__ g, size_t n, float scale, double* __restrict__ out, double* __restrict__ part) {

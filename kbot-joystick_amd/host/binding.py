@@ -31,7 +31,7 @@ class Traj(C.Structure):
                 ("action_d", C.c_void_p), ("logp_d", C.c_void_p), ("value_d", C.c_void_p), ("reward_d", C.c_void_p),
                 ("carry0_actor_hc_d", C.c_void_p), ("carry0_critic_hc_d", C.c_void_p), ("carry0_lpf_d", C.c_void_p),
                 ("carry0_actor_mirror_hc_d", C.c_void_p), ("carry0_critic_mirror_hc_d", C.c_void_p),
-                ("carry0_lpf_mirror_d", C.c_void_p), ("reward_comps_d", C.c_void_p), ("qstate_d", C.c_void_p)]
+                ("carry0_lpf_mirror_d", C.c_void_p), ("reward_comps_d", C.c_void_p), ("qstate_d", C.c_void_p), ("value_tail_d", C.c_void_p)]
 
 
 class PpoVars(C.Structure):
@@ -76,6 +76,7 @@ SIGNATURES = {
     "kbj_mirror_table": (_i, [_vp, _sz, _i, _vp, _vp, _vp]),
     "kbj_policy_step": (_i, [_vp, _vp, _vp, _vp, C.POINTER(Carry), _u32, _u32, _i, _vp, _vp, _vp]),
     "kbj_carry_reset": (_i, [_vp, C.POINTER(Carry), _vp, _i]),
+    "kbj_critic_value": (_i, [_vp, _vp, _vp, C.POINTER(Carry), _vp]),
     "kbj_rollout": (_i, [_vp, _vp, C.POINTER(Carry), _u32, _u32, C.POINTER(Traj)]),
     "kbj_set_rollout_argmax": (_i, [_vp, _i]),
     "kbj_recurrence_residency": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
@@ -258,6 +259,11 @@ class Context:
 
     def carry_reset(self, carry: Carry, done, stride):
         self.call("kbj_carry_reset", C.byref(carry), _ptr(done), stride)
+
+    def critic_value(self, params, critic_obs, carry: Carry, value):
+        """kbj_critic_value: the critic's value [N] of ONE observation row [N, ld_critic] from the critic carries in `carry`; no carry advances.
+        Needs a context with kbj_config.gae_tail_value = 1."""
+        self.call("kbj_critic_value", _ptr(params), _ptr(critic_obs), C.byref(carry), _ptr(value))
 
     def rollout(self, params, carry: Carry, seed, first_step_index, traj: Traj):
         self.call("kbj_rollout", _ptr(params), C.byref(carry), seed, first_step_index, C.byref(traj))

@@ -54,6 +54,8 @@ class TrajBuffers:
         self.comps = z(T, N, 12) if reward_comps else None   # unscaled reward terms (train.py:1224-1256 order)
         # per-step state record (kbj_model.h KBJ_QSTATE_*): what host/trajectory.Trajectory turns into ksim's qpos / qvel / xpos / xquat
         self.qstate = z(T, N, L.QSTATE["SIZE"]) if record_state else None
+        # V(s_T) of kbj_config.gae_tail_value (kbj_traj.value_tail_d): always there, 4 N bytes; the library reads and writes it only with the switch on
+        self.value_tail = z(N)
         mptr = [None, None, None]
         if mirror:
             self.carry0_actor_mirror_hc = z(depth, 2, N, H)
@@ -63,7 +65,7 @@ class TrajBuffers:
         self.c = B.Traj(T, N, self.actor_obs.data_ptr(), self.critic_obs.data_ptr(), self.aux.data_ptr(), self.action.data_ptr(),
                         self.logp.data_ptr(), self.value.data_ptr(), self.reward.data_ptr(), self.carry0_actor_hc.data_ptr(),
                         self.carry0_critic_hc.data_ptr(), self.carry0_lpf.data_ptr(), *mptr, self.comps.data_ptr() if reward_comps else None,
-                        self.qstate.data_ptr() if record_state else None)
+                        self.qstate.data_ptr() if record_state else None, self.value_tail.data_ptr())
 
     @property
     def done(self) -> torch.Tensor:

@@ -89,6 +89,13 @@ class HumanoidWalkingTaskConfig:
     # read with task.episode_stats(), merged into scalars() / validate(). Off (the default; KBJ_EPISODE_STATS in the environment overrides
     # it, for A/B runs with tools/ab_bench.py): nothing is allocated, launched or logged.
     episode_stats: bool = dataclasses.field(default_factory=lambda: os.environ.get("KBJ_EPISODE_STATS", "0") not in ("0", ""))
+    # GAE boundary conventions (include/kbj.h kbj_gae). Both off by default - this build's choice: every termination ends the
+    # return, V_T := V_{T-1} - and selectable, because SURVEY B.2 believes ksim bootstraps through the episode-length "success" termination:
+    # bootstrap_on_truncation: at DONE = +1 (time-out, or a user term's +1) delta = r + gamma V(s_t) - V(s_t) instead of r - V(s_t);
+    # bootstrap_tail_value: the last row bootstraps from the critic's value of observation row T (one more critic step per rollout) instead of
+    # from V_{T-1}. KBJ_GAE_TRUNCATION / KBJ_GAE_TAIL in the environment override the defaults (A/B runs with tools/ab_bench.py).
+    bootstrap_on_truncation: bool = dataclasses.field(default_factory=lambda: os.environ.get("KBJ_GAE_TRUNCATION", "0") not in ("0", ""))
+    bootstrap_tail_value: bool = dataclasses.field(default_factory=lambda: os.environ.get("KBJ_GAE_TAIL", "0") not in ("0", ""))
     # keep qpos / qvel of every env-step (kbj_traj.qstate_d, 262 MB at 8192 x 100): the Python reward terms (extra_rewards) then see a
     # ksim-shaped `host.trajectory.Trajectory` - trajectory.qpos / .qvel / .xpos / .xquat / .obs[...] / .command["unified_command"] as the
     # reference's reward classes read them (train.py:138-506) - instead of the narrower TrajectoryView of the aux record
@@ -143,7 +150,8 @@ class HumanoidWalkingTaskConfig:
                   lam=self.lam, learning_rate=self.learning_rate, weight_decay=self.adam_weight_decay, switch_prob=self.ctrl_dt / 5,
                   actor_mirror_loss_scale=self.actor_mirror_loss_scale, critic_mirror_loss_scale=self.critic_mirror_loss_scale,
                   lpf_alpha=self.ctrl_dt / (self.ctrl_dt + 1.0 / (2.0 * math.pi * self.cutoff_frequency)), deterministic=int(bool(self.deterministic)),
-                  extra_obs_actor=int(self.extra_actor_obs), extra_obs_critic=int(self.extra_critic_obs), gemm_bf16x3=int(bool(self.gemm_bf16x3)))
+                  extra_obs_actor=int(self.extra_actor_obs), extra_obs_critic=int(self.extra_critic_obs), gemm_bf16x3=int(bool(self.gemm_bf16x3)),
+                  gae_bootstrap_truncation=int(bool(self.bootstrap_on_truncation)), gae_tail_value=int(bool(self.bootstrap_tail_value)))
         if not (0 <= self.extra_actor_obs <= L.MAX_EXTRA_OBS and 0 <= self.extra_critic_obs <= L.MAX_EXTRA_OBS):
             raise ValueError(f"extra_actor_obs / extra_critic_obs must be in 0..{L.MAX_EXTRA_OBS}")
         if self.allreduce not in ("per_step", "per_pass"):
@@ -531,6 +539,8 @@ class HumanoidWalkingTask:
             if self.extra_observations:
                 observe(t + 1, view)
             c.carry_reset(self.carry.c, tr.aux[t].data_ptr() + done_col, L.AUX["SIZE"])
+        if self.kcfg.gae_tail_value:          # V(s_T) for GAE, as kbj_rollout computes it: row T, the carries the last reset left, the rollout's parameters
+            c.critic_value(self.params, tr.critic_obs[T], self.carry.c, tr.value_tail)
         c.rewards(tr.aux, T, tr.reward, tr.comps)
 
     def update(self):
@@ -823,6 +833,7 @@ class HumanoidWalkingTask:
         if getattr(self, "_valid", None) is None or self._valid[0] != key:
             vcfg = self.config.to_kbj(num_envs) if num_envs % self.config.batch_size == 0 else dataclasses.replace(self.config, batch_size=num_envs).to_kbj(num_envs)
             vcfg.rollout_len = T
+            vcfg.gae_bootstrap_truncation = vcfg.gae_tail_value = 0      # validation never runs GAE: no tail pass, no carry copy
             if self.command_term is not None:
                 vcfg.command_mode = 1
             vctx = B.Context(self.model_blob, vcfg, self.device.index or 0, torch.cuda.current_stream().cuda_stream)

@@ -60,6 +60,7 @@ class Config(C.Structure):
         ("solver_iterations", i32), ("ls_iterations", i32), ("hidden_size", i32), ("depth", i32),
         ("batch_size", i32), ("num_passes", i32), ("command_mode", i32), ("enable_randomizers", i32),
         ("enable_pushes", i32), ("enable_noise", i32), ("max_episode_steps", i32), ("solver_newton", i32), ("deterministic", i32), ("extra_obs_actor", i32), ("extra_obs_critic", i32), ("gemm_bf16x3", i32),
+        ("gae_bootstrap_truncation", i32), ("gae_tail_value", i32),
         ("dt", f32), ("ctrl_dt", f32), ("solver_tolerance", f32), ("latency_lo", f32), ("latency_hi", f32),
         ("drop_action_prob", f32), ("fixed_command", f32 * NCMD),
         ("vx_lo", f32), ("vx_hi", f32), ("vy_lo", f32), ("vy_hi", f32), ("wz_lo", f32), ("wz_hi", f32),
@@ -124,6 +125,7 @@ def default_config(**overrides) -> Config:
     c.hidden_size, c.depth, c.batch_size, c.num_passes = 256, 2, 512, 3           # train.py:1773,82-85,1764-1765
     c.command_mode, c.enable_randomizers, c.enable_pushes, c.enable_noise = 0, 1, 1, 1
     c.solver_newton = 1
+    c.gae_bootstrap_truncation, c.gae_tail_value = 0, 0   # this build's GAE boundaries: every DONE terminal, V_T := V_{T-1}
     c.max_episode_steps = 600                                                     # 12 s, train.py:1268
     c.dt, c.ctrl_dt, c.solver_tolerance = 0.004, 0.02, 1e-6   # fp32 gradient noise floor sits above MuJoCo's 1e-8
     c.latency_lo, c.latency_hi, c.drop_action_prob = 0.003, 0.01, 0.05            # train.py:1780-1781

@@ -4,7 +4,8 @@ import torch
 from kbot_joystick_amd.host.task import HumanoidWalkingTask, launch_config
 from kbot_joystick_amd.spec import layout as L
 cfg = launch_config(num_envs=8192, robot="kbot", terrain="sine", seed=3, actor_mirror_loss_scale=1.0, critic_mirror_loss_scale=0.01,
-                    use_lr_decay=True, lr_decay_steps=48 * 60, log_reward_components=True)
+                    use_lr_decay=True, lr_decay_steps=48 * 60, log_reward_components=True,
+                    bootstrap_on_truncation=True, bootstrap_tail_value=True)
 task = HumanoidWalkingTask(cfg)
 import time; t0 = time.time()
 for it in range(60):
