@@ -92,6 +92,303 @@ def random_actions(model, rng, n, scale=0.3):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# episode ends: every termination cause, the terminal record and the in-step reset, against the oracle
+# (GPU: tests/test_gpu_env.py; the host emulation of the kernel body: tests/test_emu_env.py; the oracle halves alone, which keep
+# the cases alive: tests/test_oracle_task.py)
+# ---------------------------------------------------------------------------------------------------------------------
+# Teacher-forced cases (seed 11, random_actions scale 0.3 from default_rng(0)). `counts`: what the fp32 oracle gives, measured on the
+# CPU and pinned there (tests/test_oracle_task.py), `max_episode` = the most episodes one env has finished (the in-step reset then draws
+# from episode counter max_episode + 1's slots); `floors`: half of the counts, the liveness the GPU test asserts. The threshold
+# config ends episodes while the robot is still in ordinary, contact-stable states (so a normal step's tolerances hold); the default
+# config run long enough to fall puts contact-rich states into the terminal records.
+EPISODE_END_CASES = {
+    "episode ends": dict(N=256, steps=24, cfg=dict(unhealthy_z=0.655, max_tilt_rad=0.12, max_episode_steps=7),
+                         counts=dict(height=960, tilt_only=52, timeout=100, fail_on_timeout=175), max_episode=7,
+                         floors=dict(height=480, tilt_only=26, timeout=50, fail_on_timeout=87)),
+    "falls": dict(N=256, steps=60, cfg=dict(),
+                  counts=dict(height=55, tilt_only=175, timeout=0, fail_on_timeout=0), max_episode=2,
+                  floors=dict(height=27, tilt_only=87, timeout=0, fail_on_timeout=0)),
+}
+# terminations the fp32 oracle gives in the default-config cases of test_teacher_forced_steps_match_oracle: (N, steps, command) -> count
+TEACHER_FORCED_TERMINATIONS = {(128, 30, "sampler"): 5, (8192, 12, "sampler"): 0, (8192, 6, "fixed"): 0, (256, 20, "sampler on jax.random keys"): 0}
+
+# column groups of the completed aux_t record: name -> (first column, width, floor). The floor is a few fp32 roundings of the
+# quantity: velocities and positions as in check_against_oracle_spread (qvel 1e-6, qpos 2e-7); unit quaternion components and heights
+# below 1 m like positions; a PD torque is kp (~100) times a position error plus kd times a velocity error, values up to ~40 N m whose
+# one rounding is 4e-6: 2e-5.
+AUX_RECORD_GROUPS = dict(QVEL=(0, 6, 1e-6), BQUAT=(6, 4, 2e-7), HEIGHTS=(10, 3, 2e-7), FOOTQUAT=(13, 8, 2e-7), ARMQ=(21, 10, 2e-7), CTRL=(31, 20, 2e-5))
+
+
+class Step:
+    """What one control step leaves behind, as host arrays: parameter / state rows, the completed aux_t row, the next rows."""
+    def __init__(self, ep, es, aux_t, actor, critic, aux):
+        self.ep, self.es, self.aux_t, self.actor, self.critic, self.aux = ep, es, aux_t, actor, critic, aux
+
+
+def record_height(aux_t):
+    """The height termination's operand (kbj_env_task.h task_step: xpos[base].z - fminf(xpos[lfoot].z, xpos[rfoot].z)) from a record, in fp64."""
+    from kbot_joystick_amd.spec import layout as L
+    x = aux_t.astype(np.float64)
+    return x[:, L.AUX["BASEZ"]] - np.minimum(x[:, L.AUX["LFZ"]], x[:, L.AUX["RFZ"]])
+
+
+def record_tilt_zz(aux_t):
+    """The tilt termination's expression (kbj_env_task.h task_step: zz = 1 - 2 (qx qx + qy qy), failing below cos(max_tilt_rad)) on a record's
+    base quaternion, in fp64. The record holds the quaternion of the last substep's kinematics, the kernel tests the integrated one: a
+    margin taken here is that of the record, one substep (4 ms) before the state the flag was decided on (zz moves by up to 2e-3 in that
+    substep in the "episode ends" case, 1.7e-2 in "falls"; on the integrated state the smallest fp64 margins are 1.1e-6 and 9.3e-5, measured
+    with a second oracle whose thresholds are off). A flag that flips on the tilt threshold is therefore excused only where the record
+    happens to sit on the threshold too: the exemption is in practice the height test's."""
+    from kbot_joystick_amd.spec import layout as L
+    q = aux_t[:, L.AUX["BQUAT"]:L.AUX["BQUAT"] + 4].astype(np.float64)
+    return 1 - 2 * (q[:, 1] * q[:, 1] + q[:, 2] * q[:, 2])
+
+
+class EpisodeEndAudit:
+    """Accumulates, over the steps of a teacher-forced run, everything about the END of an episode that an implementation of the control
+    step (`got`: the HIP kernel, or its host emulation) must share with the oracle; `got` = None audits the oracle halves alone.
+
+    add() per step, from the identical start state `es0`:
+      * DONE against the fp32 oracle's, sign included. A disagreement is kept for finish(), which excuses it only if it is a failure flag
+        (-1 against the time-out / running value that is due) on an env-step whose fp64 margin to the height or tilt threshold is below
+        4x the largest fp32-vs-fp64 oracle error of that quantity in this run, and at most `max_exempt` of them;
+      * the per-cause counts, from the oracle's flags;
+      * rows that both sides finish: the new episode's parameters and state with the fields and bounds of test_reset_matches_oracle (exact,
+        base quaternion 3e-7: device libm against glibc), the cleared warm start, the re-seeded lagged projected gravity, and the new
+        episode's first actor / critic / aux rows with that test's bounds;
+      * the completed aux_t row by column group, error against the fp64 oracle beside the fp32 oracle's own on the same env-steps,
+        terminal and running rows apart.
+    finish() asserts what needs the whole run and returns the measured figures."""
+
+    def __init__(self, cfg, max_exempt=2, label=""):
+        self.max_steps, self.max_exempt, self.label = int(cfg.max_episode_steps), max_exempt, label
+        self.uz = float(np.float32(cfg.unhealthy_z))                       # the threshold as the fp64 oracle reads it: the fp32 field, widened
+        self.cos_tilt = float(np.cos(np.float64(np.float32(cfg.max_tilt_rad))))
+        self.counts = dict(height=0, tilt_only=0, timeout=0, fail_on_timeout=0)
+        self.oracle_flips, self.max_episode, self.t = 0, 0, 0
+        self.err_height, self.err_zz = 0.0, 0.0                            # largest fp32-vs-fp64 oracle error of the two operands
+        self.margin_height, self.margin_zz = np.inf, np.inf                # smallest fp64 distance to the thresholds
+        self.disagree = []                                                 # (t, env, got, oracle, due, margin_height, margin_zz)
+        self.rec_got = {g: [] for g in AUX_RECORD_GROUPS}
+        self.rec_o32 = {g: [] for g in AUX_RECORD_GROUPS}
+        self.terminal, self.switch = [], []
+        self.reset_rows = 0
+        self.reset_err = dict(quat=0.0, pglag=0.0, actor=0.0, critic=0.0, aux=0.0)
+        self.o32_reset_err = dict(state=0.0, quat=0.0, pglag=0.0, actor=0.0, critic=0.0, aux=0.0)
+
+    def add(self, es0, o32: Step, o64: Step, got: Step = None, switch=None):
+        """One step. Returns the rows whose DONE is the oracle's (all rows where `got` is None)."""
+        from kbot_joystick_amd.spec import layout as L
+        t, self.t = self.t, self.t + 1
+        d32, d64 = o32.aux_t[:, L.AUX["DONE"]], o64.aux_t[:, L.AUX["DONE"]]
+        due = es0[:, L.ES["TIME"]] + 1 >= self.max_steps
+        h64, z64 = self._collect_oracle(o32, o64, d32, d64, due)
+        if got is None:
+            return np.ones_like(due)
+        dg = got.aux_t[:, L.AUX["DONE"]]
+        agree = dg == d32
+        for i in np.nonzero(~agree)[0]:
+            self.disagree.append((t, int(i), float(dg[i]), float(d32[i]), bool(due[i]), float(abs(h64[i] - self.uz)), float(abs(z64[i] - self.cos_tilt))))
+        both = (d32 != 0) & (d64 != 0) & agree
+        if both.any():
+            self._assert_reset_rows(es0, o32, got, both, (self.label, t))
+        self._collect_record(o32, o64, got, agree, (d32 != 0), np.zeros_like(due) if switch is None else switch)
+        return agree
+
+    def _collect_oracle(self, o32, o64, d32, d64, due):
+        """The oracle halves of a step: per-cause counts from the fp32 oracle's flags, fp32 / fp64 flips, the operands' errors and margins,
+        and the two precisions' disagreement on the rows both reset (the yardstick of the post-reset bounds). Returns the fp64 operands."""
+        from kbot_joystick_amd.spec import layout as L
+        h32, h64, z32, z64 = record_height(o32.aux_t), record_height(o64.aux_t), record_tilt_zz(o32.aux_t), record_tilt_zz(o64.aux_t)
+        self.oracle_flips += int((d32 != d64).sum())
+        self.err_height, self.err_zz = max(self.err_height, float(np.abs(h32 - h64).max())), max(self.err_zz, float(np.abs(z32 - z64).max()))
+        self.margin_height = min(self.margin_height, float(np.abs(h64 - self.uz).min()))
+        self.margin_zz = min(self.margin_zz, float(np.abs(z64 - self.cos_tilt).min()))
+        fail, low = d32 == -1, h64 < self.uz
+        self.counts["height"] += int((fail & low).sum())
+        self.counts["tilt_only"] += int((fail & ~low).sum())
+        self.counts["timeout"] += int((d32 == 1).sum())
+        self.counts["fail_on_timeout"] += int((fail & due).sum())
+        assert np.isin(d32, (-1.0, 0.0, 1.0)).all() and not (d32[~due] == 1).any()
+        self.max_episode = max(self.max_episode, int(o32.es[:, L.ES["EPISODE"]].view(np.uint32).max()) - 1)      # env_reset_all starts at counter 1
+        both = (d32 != 0) & (d64 != 0)
+        if both.any():
+            e = self.o32_reset_err
+            cols = np.r_[0:3, 7:27, 28:125, 128:130]
+            bits32, bits64 = o32.es[both][:, cols].view(np.uint32).astype(np.int64), o64.es[both][:, cols].view(np.uint32).astype(np.int64)
+            e["state"] = max(e["state"], float(np.abs(bits32 - bits64).max()), float(np.abs(o32.ep[both] - o64.ep[both]).max()))
+            for k, v in self._reset_errors(o64, o32, both).items():
+                e[k] = max(e[k], v)
+        return h64, z64
+
+    def _assert_reset_rows(self, es0, o32, got, both, lab):
+        """Rows that the oracle and `got` both finish: the new episode, as test_reset_matches_oracle holds kbj_env_reset_all at episode 0."""
+        from kbot_joystick_amd.spec import layout as L
+        self.reset_rows += int(both.sum())
+        o, g = o32.es[both], got.es[both]
+        assert np.array_equal(o32.ep[both], got.ep[both]), lab                                   # the new episode's randomised parameters
+        assert np.array_equal(o[:, 0:3], g[:, 0:3]) and np.array_equal(o[:, 7:27], g[:, 7:27]), lab
+        assert np.abs(o[:, 28:54] - g[:, 28:54]).max() == 0, lab                                 # qvel
+        assert (g[:, 54:80] == 0).all() and (o[:, 54:80] == 0).all(), lab                        # the warm start, cleared
+        assert np.array_equal(o[:, 80:125], g[:, 80:125]), lab                                   # ACT_PREV, command, push block, time
+        assert np.array_equal(o[:, 128:130].view(np.uint32), g[:, 128:130].view(np.uint32)), lab   # episode / step counters ...
+        assert np.array_equal(g[:, 128:130].view(np.uint32), es0[both, 128:130].view(np.uint32) + 1) and (g[:, L.ES["TIME"]] == 0).all(), lab   # ... each + 1, time restarted
+        e = self.reset_err
+        for k, v in self._reset_errors(o32, got, both).items():
+            e[k] = max(e[k], v)
+        assert e["quat"] < 3e-7, (lab, e)                      # cosf / sinf(yaw / 2): device libm vs glibc, 1-2 ulp
+        # The lagged gravity is re-seeded with the projected gravity of the new episode's forward kinematics: a unit vector turned by the
+        # new base quaternion. The two oracle precisions give it bit-identically (pinned in tests/test_oracle_task.py), so no oracle
+        # spread sets this bound. It is the existing bound of the host emulation's reset (tests/test_emu_env.py: the kinematics compose
+        # the rotations in another order), and what the quaternion bound above implies: a rotation is quadratic in the quaternion,
+        # 2 x 3e-7 per component, plus the roundings of the products.
+        assert e["pglag"] < 1e-6, (lab, e)
+        assert e["actor"] < 1e-4 and e["critic"] < 1e-3 and e["aux"] < 1e-4, (lab, e)
+
+    def _collect_record(self, o32, o64, got, agree, terminal, switch):
+        """The completed aux_t row by column group: `got`'s and the fp32 oracle's error against the fp64 oracle on the same env-steps."""
+        ref = o64.aux_t.astype(np.float64)
+        for name, (c0, w, _) in AUX_RECORD_GROUPS.items():
+            self.rec_got[name].append(np.abs(got.aux_t[agree, c0:c0 + w] - ref[agree, c0:c0 + w]).max(1))
+            self.rec_o32[name].append(np.abs(o32.aux_t[agree, c0:c0 + w] - ref[agree, c0:c0 + w]).max(1))
+        self.terminal.append(terminal[agree])
+        self.switch.append(switch[agree])
+
+    @staticmethod
+    def _reset_errors(ref: Step, got: Step, rows):
+        from kbot_joystick_amd.spec import layout as L
+        c0 = ref.critic[rows]
+        return dict(quat=float(np.abs(ref.es[rows, 3:7] - got.es[rows, 3:7]).max()),
+                    pglag=float(np.abs(ref.es[rows, L.ES["PGLAG"]:L.ES["PGLAG"] + 3] - got.es[rows, L.ES["PGLAG"]:L.ES["PGLAG"] + 3]).max()),
+                    actor=float(np.abs(ref.actor[rows] - got.actor[rows]).max()),
+                    critic=float((np.abs(c0 - got.critic[rows]) / (1 + np.abs(c0))).max()),
+                    aux=float(np.abs(ref.aux[rows] - got.aux[rows]).max()))
+
+    def finish(self, floors=None, verbose=True):
+        lab = self.label
+        for name, floor in (floors or {}).items():                # liveness: every cause occurs, from the oracle's flags
+            assert self.counts[name] >= floor, f"{lab}{name}: {self.counts[name]} env-steps, the case needs {floor}"
+        assert self.oracle_flips == 0, f"{lab}the fp32 and fp64 oracle disagree on {self.oracle_flips} DONE flags: the case sits on a threshold"
+        bound_h, bound_z = 4 * self.err_height, 4 * self.err_zz
+        for (t, env, dg, d32, due, mh, mz) in self.disagree:
+            other = d32 if dg == -1 else dg                       # the side that does not report a failure must hold what is due without one
+            ok = (dg == -1) != (d32 == -1) and other == (1.0 if due else 0.0) and (mh < bound_h or mz < bound_z)
+            assert ok, (f"{lab}DONE at step {t}, env {env}: {dg} against the oracle's {d32} (time-out due: {due}); margins height {mh:.2e} (bound {bound_h:.2e}), "
+                        f"tilt {mz:.2e} (bound {bound_z:.2e}). The tilt margin is the record's, one substep before the quaternion the flag is decided on "
+                        f"(record_tilt_zz): a lone tilt failure against a running / timed-out row with the height far from its threshold can be a rounding "
+                        f"flip on the tilt threshold that this margin cannot see - check the integrated state's margin before suspecting the kernel")
+        assert len(self.disagree) <= self.max_exempt, f"{lab}{len(self.disagree)} DONE flags on a threshold differ from the oracle's: {self.disagree}"
+        out = dict(counts=dict(self.counts), max_episode=self.max_episode, reset_rows=self.reset_rows, margin_height=self.margin_height, margin_zz=self.margin_zz,
+                   bound_height=bound_h, bound_zz=bound_z, reset_err=dict(self.reset_err), oracle_reset_err=dict(self.o32_reset_err), exempted=len(self.disagree), record={})
+        if self.terminal:
+            out["record"] = check_record_against_oracle_spread(self.rec_got, self.rec_o32, np.concatenate(self.terminal), np.concatenate(self.switch), label=lab)
+        if verbose:
+            print(f"{lab}episode ends:", out)
+        return out
+
+
+MIN_TERMINAL_ROWS = 100       # below this a sample carries no 99th percentile of its own
+
+
+def check_record_against_oracle_spread(err_got: dict, err_o32: dict, terminal: np.ndarray, switch: np.ndarray, label=""):
+    """The completed aux_t rows by column group (AUX_RECORD_GROUPS), by the rule of check_against_oracle_spread: error against the fp64
+    oracle beside the fp32 oracle's own error on the SAME env-steps, terminal rows (the record of a finished episode, which must hold the
+    state BEFORE the reset) apart from running rows:
+      * median and p99 at most 2x the oracle's, floored at a few fp32 roundings of the quantity;
+      * terminal rows: the extreme value within 2x the oracle's own extreme (same floor) - no solver switch excuses a wrong record there.
+        Where a run has fewer than MIN_TERMINAL_ROWS terminal rows (the 5 of the default-config case), their own quantiles are no
+        yardstick: a p99 is the extreme of anything under 100 samples, and the ratio of two such extremes is not a stable statistic. Only
+        there, the oracle's quantile over ALL rows of the run stands in where it is the larger, and its p99 for the extreme: a terminal
+        record is written before the reset, from the same arithmetic as a running one;
+      * running rows: no heavier tail than the oracle's - the env-steps beyond 2x the oracle's p99.9 number at most 1.5x the oracle's own
+        count + 5, and at most 8 of them on env-steps the oracle does not flag as sitting on a discrete switch of the solver.
+    Returns {group: {"terminal" / "running": (n, p50, p99, max, oracle p50, oracle p99, oracle max)}}."""
+    out = {}
+    for name, (_, _, floor) in AUX_RECORD_GROUPS.items():
+        hh, oo = np.concatenate(err_got[name]), np.concatenate(err_o32[name])
+        out[name] = {}
+        for rows, where in ((terminal, "terminal"), (~terminal, "running")):
+            h, o = hh[rows], oo[rows]
+            if h.size == 0:
+                continue
+            out[name][where] = (int(h.size),) + tuple(float(f"{x:.3g}") for x in (np.median(h), np.quantile(h, 0.99), h.max(), np.median(o), np.quantile(o, 0.99), o.max()))
+            few = where == "terminal" and h.size < MIN_TERMINAL_ROWS
+            for qn, q in (("median", 0.5), ("p99", 0.99)):
+                hq, oq = np.quantile(h, q), max(np.quantile(o, q), np.quantile(oo, q) if few else 0.0)
+                assert hq <= 2 * max(oq, floor), f"{label}aux_t {name} {where} rows {qn}: {hq:.3e} vs oracle fp32 {oq:.3e}"
+            if where == "terminal":
+                omax = max(o.max(), np.quantile(oo, 0.99) if few else 0.0)
+                assert h.max() <= 2 * max(omax, floor), f"{label}aux_t {name} terminal rows max: {h.max():.3e} vs oracle fp32 {omax:.3e} (env-step {int(np.nonzero(rows)[0][h.argmax()])})"
+            else:
+                thr = 2 * max(np.quantile(o, 0.999), floor)
+                nh, no = int((h > thr).sum()), int((o > thr).sum())
+                assert nh <= 1.5 * no + 5, f"{label}aux_t {name} running rows: {nh} env-steps beyond {thr:.2e}, the oracle's fp32 run has {no}"
+                unexplained = int(((h > thr) & ~switch[rows]).sum())
+                assert unexplained <= 8, f"{label}aux_t {name} running rows: {unexplained} outliers beyond {thr:.2e} without a discrete solver switch"
+    return out
+
+
+def teacher_forced_config(N, command):
+    """kbj_config of a case of test_teacher_forced_steps_match_oracle: `command` names a case of EPISODE_END_CASES, or the command source
+    ("sampler"; "fixed": BASELINE configs[1], command_mode 1, (0.5, 0, 0); "sampler on jax.random keys": command_mode 2)."""
+    from kbot_joystick_amd.spec import layout as L
+    kw = dict(EPISODE_END_CASES[command]["cfg"]) if command in EPISODE_END_CASES else {}
+    if command == "fixed":
+        kw = dict(command_mode=1, fixed_command=[0.5] + [0.0] * 15)
+    if command == "sampler on jax.random keys":
+        kw = dict(command_mode=2, switch_prob=0.2)
+    return L.default_config(num_envs=N, batch_size=min(512, N), **kw)
+
+
+def oracle_pair_step(o, o64, act, aux_in):
+    """One teacher-forced control step of the fp32 oracle `o` and, from the same state, of the fp64 oracle `o64`. Returns (ep0, es0, Step fp32,
+    Step fp64, switch): the start state, both results and the env-steps on which the two evaluations differ in the solver's discrete state
+    (active contacts / force-carrying rows / iteration counts, or the iteration cap bites)."""
+    ep0, es0 = o.ep.copy(), o.es.copy()
+    o64.ep[:], o64.es[:] = ep0, es0
+    x32, x64 = aux_in.copy(), aux_in.copy()
+    a64, c64, n64, d64 = o64.step_diag(act, x64)
+    a32, c32, n32, d32 = o.step_diag(act, x32)
+    it = o.config.solver_iterations
+    switch = (d32 != d64).any(1) | (d64[:, 0] >= it) | (d32[:, 0] >= it)
+    return ep0, es0, Step(o.ep.copy(), o.es.copy(), x32, a32, c32, n32), Step(o64.ep.copy(), o64.es.copy(), x64, a64, c64, n64), switch
+
+
+def emu_stepper(model, cfg, seed, lib=None):
+    """The host emulation of the kernel body (tests/emu) as `step(ep0, es0, act, aux_in) -> Step`."""
+    emu = lib or emu_lib()
+    N = cfg.num_envs
+
+    def step(ep0, es0, act, aux_in):
+        from kbot_joystick_amd.spec import layout as L
+        ep, es, x = ep0.copy(), es0.copy(), aux_in.copy()
+        a, c, n = np.zeros((N, L.LD_ACTOR), np.float32), np.zeros((N, L.LD_CRITIC), np.float32), np.zeros((N, L.AUX["SIZE"]), np.float32)
+        emu.kbj_emu_env_step(C.byref(model), C.byref(cfg), C.c_uint32(seed), fptr(ep), fptr(es), fptr(np.ascontiguousarray(act, np.float32)), fptr(x), fptr(a), fptr(c), fptr(n))
+        return Step(ep, es, x, a, c, n)
+    return step
+
+
+def episode_end_run(model, case: str, stepper_factory=None, seed=11, verbose=True):
+    """A case of EPISODE_END_CASES, teacher-forced: the fp32 oracle's state goes into the fp64 oracle and into `stepper_factory(cfg, seed)`'s
+    implementation before every step. Returns (EpisodeEndAudit.finish()'s figures, the audit)."""
+    from oracle import oracle as O
+    spec = EPISODE_END_CASES[case]
+    N = spec["N"]
+    cfg = teacher_forced_config(N, case)
+    o, o64 = O.Oracle(model, cfg, seed=seed, precision="f32"), O.Oracle(model, cfg, seed=seed, precision="f64")
+    _, _, x0 = o.reset_all()
+    step = stepper_factory(cfg, seed) if stepper_factory else None
+    rng = np.random.default_rng(0)
+    audit = EpisodeEndAudit(cfg, label=case + ": ")
+    for t in range(spec["steps"]):
+        act = random_actions(model, rng, N)
+        ep0, es0, s32, s64, switch = oracle_pair_step(o, o64, act, x0)
+        audit.add(es0, s32, s64, step(ep0, es0, act, x0) if step else None, switch)
+        x0 = s32.aux
+    return audit.finish(spec["floors"], verbose=verbose), audit
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # actor-critic / PPO side: the synthetic minibatch problem of tests/test_gpu_nn.py as CPU tensors, so that the oracle half of a
 # parity test (and the CPU-only liveness checks of tests/test_oracle_nn.py) needs no device
 # ---------------------------------------------------------------------------------------------------------------------

@@ -70,6 +70,18 @@ def test_teacher_forced_steps_match_oracle(model, command_mode):
     H.check_error_distribution(errs, label="emu vs oracle ")
 
 
+@pytest.mark.parametrize("case", list(H.EPISODE_END_CASES))
+def test_episode_ends_match_oracle(model, case):
+    """The termination / record / reset tail of task_step on the host, by the audit the GPU test applies to the kernel (helpers.EpisodeEndAudit;
+    cases and liveness: helpers.EPISODE_END_CASES): DONE with its sign for every cause, the terminal aux_t record against the oracle's own
+    fp32-vs-fp64 spread, the in-step reset's parameters, state, warm start, lagged gravity and first observation rows. The body compiled here
+    is the kernel's, so this is also where a wrong tail is bisected without a device: a record written after the reset, a reset drawing
+    from the first episode's RNG slots and a swapped DONE sign each fail it."""
+    fig, _ = H.episode_end_run(model, case, lambda cfg, seed: H.emu_stepper(model, cfg, seed), verbose=False)
+    assert fig["exempted"] == 0                  # the emulation rounds as the oracle's fp32 does wherever a threshold is near at this seed
+    assert fig["reset_rows"] == sum(fig["counts"][k] for k in ("height", "tilt_only", "timeout"))
+
+
 def test_yardstick_oracle_fp32_vs_fp64(model):
     """The tolerance table is the oracle's own fp32-vs-fp64 spread: check the yardstick itself."""
     N = 48

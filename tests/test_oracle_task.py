@@ -1,9 +1,11 @@
 """Hand-computed cases and properties for the oracle's task layer (rewards train.py:125-506, command sampler
 train.py:710-785, episode bookkeeping) — the pieces of the reference that live in-tree."""
 import numpy as np
+import pytest
 
 from kbot_joystick_amd.spec import layout as L
 from oracle import oracle as O
+from tests import helpers as H
 
 A = L.AUX
 
@@ -103,6 +105,53 @@ def test_episode_bookkeeping(model):
     assert (o.es[:, L.ES["TIME"]] == 1).all()               # new episode has advanced one step
     assert (o.es[:, L.ES["EPISODE"]].view(np.uint32) == 2).all()
     assert (o.es[:, L.ES["STEP"]].view(np.uint32) == 6).all()
+
+
+# ---- episode ends: the oracle halves of the GPU cases (tests/test_gpu_env.py::test_teacher_forced_steps_match_oracle) ----------------------
+@pytest.mark.parametrize("case", list(H.EPISODE_END_CASES))
+def test_episode_end_cases_are_alive_on_the_oracle(model, case):
+    """The conditions that make an episode-end case of the GPU parity test a test of the episode's end, on the oracle alone (the GPU test takes
+    its DONE flags, per-cause counts and yardsticks from these very runs): an edit of a seed or a config cannot silently turn it back into
+    a run that sees no termination.
+      * per-cause counts exactly as pinned in helpers.EPISODE_END_CASES (height / tilt-only / time-out / failure on a step whose time-out was
+        also due - the precedence case, which carries -1), the floors the GPU test asserts at about half of them, envs several episodes deep;
+      * the fp32 and the fp64 oracle agree on every DONE flag, and no env-step is closer to the height or tilt threshold than the exemption
+        bound of the GPU test (4x the largest fp32-vs-fp64 error of the operand in the run): the oracle alone exempts none, so an exempted
+        flag on the GPU is the kernel's own rounding on a threshold or a bug - at most 2 are allowed there;
+      * on rows both precisions reset, the new episode's parameters and state are bit-identical (every draw is one fp32 rounding of the same
+        bits; cos / sin of the half yaw round to the same float), the lagged gravity included; the first observation rows agree to a few
+        roundings (measured: actor 1.7e-7, critic 1.4e-6 relative, aux 1.5e-7), 100x inside the bounds the GPU test takes from
+        test_reset_matches_oracle."""
+    spec = H.EPISODE_END_CASES[case]
+    fig, audit = H.episode_end_run(model, case, verbose=False)             # finish(): floors and zero fp32 / fp64 DONE flips
+    assert fig["counts"] == spec["counts"], fig["counts"]
+    for k, floor in spec["floors"].items():
+        assert floor == spec["counts"][k] // 2, (k, floor)
+    assert fig["max_episode"] == spec["max_episode"], fig["max_episode"]
+    assert fig["margin_height"] > fig["bound_height"] > 0 and fig["margin_zz"] > fig["bound_zz"] > 0, fig
+    e = fig["oracle_reset_err"]
+    assert e["state"] == 0 and e["quat"] == 0 and e["pglag"] == 0, e
+    assert e["actor"] < 5e-7 and e["aux"] < 5e-7 and e["critic"] < 5e-6, e          # ~4 fp32 roundings of an O(1) entry; the critic's composite inertias chain the kinematics
+    if case == "episode ends":       # figures the GPU test's description quotes
+        assert 4.0e-6 < fig["margin_height"] < 4.2e-6 and fig["bound_height"] < 2e-6
+
+
+@pytest.mark.parametrize("N,steps,command", [k for k in H.TEACHER_FORCED_TERMINATIONS if k[0] <= 256])
+def test_default_config_cases_terminate_as_pinned(model, N, steps, command):
+    """The default-config cases of the GPU parity test see the terminations pinned in helpers.TEACHER_FORCED_TERMINATIONS (all by tilt) - its
+    liveness line asserts that count. Only the cases of up to 256 envs are replayed here, to keep this suite quick: the two zeros of the
+    8192-env cases (no termination in their 12 and 6 steps) are held by the GPU test alone, which steps their oracle anyway."""
+    cfg = H.teacher_forced_config(N, command)
+    o = O.Oracle(model, cfg, seed=11, precision="f32")
+    _, _, x = o.reset_all()
+    rng = np.random.default_rng(0)
+    ndone = 0
+    for t in range(steps):
+        aux = x.copy()
+        _, _, x = o.step(H.random_actions(model, rng, N), aux)
+        ndone += int((aux[:, A["DONE"]] != 0).sum())
+        assert (aux[:, A["DONE"]] <= 0).all() and (H.record_height(aux) > cfg.unhealthy_z).all()
+    assert ndone == H.TEACHER_FORCED_TERMINATIONS[(N, steps, command)]
 
 
 # ---- a25: jax.random's key handling (kbj_config.command_mode = 2) ------------------------------------------------------------------
