@@ -508,10 +508,28 @@ __global__ void splitk_reduce_kernel(GemmArgs g, int sk, int per) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (size_t)g.M * g.N) return;
   const int m = (int)(i / g.N), n = (int)(i % g.N);
-  float s = 0.0f;
-  for (int ks = 0; ks < sk && (long)ks * per < g.K; ++ks) s += g.skws[((size_t)ks * g.M + m) * g.N + n];
+  // The additions are a chain in slice order (that order is the result); the loads are not: eight slices are fetched together - the slices
+  // are M * N floats apart, every one a miss - and then added one after the other. The slice index of a load is clamped, not tested, so that
+  // no load sits behind a branch; what a clamped load brought is never added.
+  const int full = (g.K + per - 1) / per, nks = sk < full ? sk : full;   // the slices with a non-empty k range
+  const size_t stride = (size_t)g.M * g.N;
+  const float* p = g.skws + i;
   float* c = (g.n1 > 0 && n >= g.n1) ? g.C2 + (size_t)m * (g.ldc2 > 0 ? g.ldc2 : g.ldc) + (n - g.n1) : g.C + (size_t)m * g.ldc + n;
-  *c += s;
+  const float c0 = *c;   // (fetched beside the first slices, not behind the last)
+  float s = 0.0f;
+  for (int k0 = 0; k0 < nks; k0 += 8) {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = p[(size_t)(k0 + j < nks ? k0 + j : nks - 1) * stride];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) if (k0 + j < nks) s += v[j];
+  }
+  *c = c0 + s;
+}
+
+inline void splitk_reduce_launch(hipStream_t s, const GemmArgs& g, int sk) {
+  const int per = ((g.K + sk - 1) / sk + GEMM_BK - 1) / GEMM_BK * GEMM_BK;   // as gemm_f32_kernel slices k
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((size_t)g.M * g.N + 255) / 256)), dim3(256), 0, s, g, sk, per);
 }
 
 template <int MT, int NT, bool A_KC, bool B_KC, int WM = 2, int WN = 2>
@@ -563,10 +581,7 @@ inline void gemm_launch(hipStream_t s, const GemmArgs& g_in, int force_big = -1)
   if (big) gemm_launch_tile<2, 1, A_KC, B_KC, 2, 4>(s, g, wgs);
 #endif
   else gemm_launch_tile<1, 1, A_KC, B_KC>(s, g, wgs);
-  if (sk > 1 && g.skws) {
-    const int per = ((g.K + sk - 1) / sk + GEMM_BK - 1) / GEMM_BK * GEMM_BK;   // as gemm_f32_kernel slices k
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((size_t)g.M * g.N + 255) / 256)), dim3(256), 0, s, g, sk, per);
-  }
+  if (sk > 1 && g.skws) splitk_reduce_launch(s, g, sk);
 }
 
 }  // namespace kbj

@@ -253,7 +253,7 @@ void linear_bwd_weight2(kbj_ctx* ctx, hipStream_t s, bool x3, const float* dy, i
 void colsum_acc(kbj_ctx* ctx, hipStream_t s, const float* X, int M, int N, int ld, float* out) {
   float* part = det_partials(ctx, s);
   hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64, DETP_ROWS), dim3(256), 0, s, X, M, N, ld, out, part);
-  if (part) hipLaunchKernelGGL(reduce_rows_kernel, dim3((N + 255) / 256), dim3(256), 0, s, part, DETP_ROWS, N, out);
+  if (part) reduce_rows_launch(s, part, DETP_ROWS, N, out);
 }
 
 // recurrence workgroups are 8 wavefronts owning 32 hidden units (kbj_lstm_seq.h; the 4-wavefront / 16-unit form of round 1 is gone:
@@ -1106,7 +1106,7 @@ int ppo_forward_nets(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, co
         KBJ_HIP(ctx, hipMemcpyAsync(w.stats + 11, w.ext_adv_sums + 2, sizeof(double), hipMemcpyDeviceToDevice, sm));
       } else {
         hipLaunchKernelGGL(adv_stats_kernel, dim3(32), dim3(256), 0, sm, w.adv, R, w.stats, sc.deterministic ? w.detd : (double*)nullptr);
-        if (sc.deterministic) hipLaunchKernelGGL(reduce_double_kernel, dim3(1), dim3(64), 0, sm, w.detd, 32, 2, w.stats);
+        if (sc.deterministic) reduce_double_launch(sm, w.detd, 32, 2, w.stats);
       }
       KBJ_HIP(ctx, hipMemsetAsync(grad_d, 0, w.nparams * sizeof(float), sm));
       if (sc.fold_actor)
@@ -1314,7 +1314,7 @@ int ppo_grad_body(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const
     const NetOff& oa = w.net[k];
     float* part = det_partials(ctx, st);
     hipLaunchKernelGGL(matvec_t_acc_kernel, dim3((H + 63) / 64, 16), dim3(256), 0, st, params_d + oa.w_ih[0], grad_d + oa.b[0], 4 * H, H, grad_d + oa.b_in, part);
-    if (part) hipLaunchKernelGGL(reduce_rows_kernel, dim3((H + 255) / 256), dim3(256), 0, st, part, 16, H, grad_d + oa.b_in);
+    if (part) reduce_rows_launch(st, part, 16, H, grad_d + oa.b_in);
     hipLaunchKernelGGL(outer_acc_kernel, g1((size_t)4 * H * H), dim3(256), 0, st, grad_d + oa.w_ih[0], grad_d + oa.b[0], params_d + oa.b_in, 4 * H, H);
   };
   bool bias_done[2] = {false, false};
@@ -1343,7 +1343,7 @@ int ppo_grad_body(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const
       if (w.seq_bstamps && bstamp_sel == 1 + n + 2 * l) ba.stamps = w.seq_bstamps;
       const bool tiles16 = sc.bwd16;
       if (seq_bwd(ctx, ns[n & 1], H, ba, tiles16)) return -1;
-      if (ba.db_part) hipLaunchKernelGGL(reduce_rows_kernel, dim3((4 * H + 255) / 256), dim3(256), 0, ns[n & 1], ba.db_part, seq_bwd_row_groups(B, tiles16), 4 * H, grad_d + o.b[l]);
+      if (ba.db_part) reduce_rows_launch(ns[n & 1], ba.db_part, seq_bwd_row_groups(B, tiles16), 4 * H, grad_d + o.b[l]);
     }
     // the layer above's weight gradients, behind THIS layer's recurrence of the same net
     const bool tail_on_own_lane = l == 0 && !w.mirror && fold_actor;   // (the own_lane case below: the pair follows the net's layer-0 work on its lane)
@@ -1548,7 +1548,7 @@ int kbj_adamw_step(kbj_ctx* ctx, float* params_d, float* m_d, float* v_d, const 
   w.sumsq_clean = false;
   double* part = w.sched.deterministic ? w.detd : nullptr;
   hipLaunchKernelGGL(sumsq_kernel, dim3(512), dim3(256), 0, s, grad_d, w.user.nparams, grad_scale, sumsq, part);
-  if (part) hipLaunchKernelGGL(reduce_double_kernel, dim3(1), dim3(64), 0, s, part, 512, 1, sumsq);
+  if (part) reduce_double_launch(s, part, 512, 1, sumsq);
   AdamParams ap{c.learning_rate, c.adam_b1, c.adam_b2, c.adam_eps, c.weight_decay, c.max_grad_norm,
                 (float)(1.0 - std::pow((double)c.adam_b1, (double)step)), (float)(1.0 - std::pow((double)c.adam_b2, (double)step)), grad_scale};
   hipLaunchKernelGGL(adamw_kernel, g1(w.user.nparams), dim3(256), 0, s, params_d, m_d, v_d, grad_d, w.user.nparams, sumsq, ap, w.seq_err);

@@ -287,13 +287,51 @@ __global__ void adv_stats_kernel(const float* __restrict__ adv, int R, double* _
     else { atomicAdd(&stats[0], s1[0]); atomicAdd(&stats[1], s2[0]); }   // stats zeroed by the caller
   }
 }
-// out[j] += sum over blocks b (in order) of part[b * w + j], j < w (w <= 64): the fixed-order second stage of the double-precision sums
-__global__ void reduce_double_kernel(const double* __restrict__ part, int nblocks, int w, double* __restrict__ out) {
-  const int j = threadIdx.x;
-  if (j >= w) return;
+// out[j] += sum over blocks b (in order) of part[b * w + j], j < w (w <= 64): the fixed-order second stage of the double-precision sums.
+// ONE workgroup of 256 threads. The order of the additions is what fixes the bits - a chain from zero over b = 0, 1, ..., then out += s - and a
+// chain of loads that each wait for the one before pays a memory round trip per partial (512 of them between sumsq_kernel and adamw_kernel).
+// So the fetch is separated from the chain: all 256 threads bring RD_CHUNK values at a time into LDS with independent loads (the next chunk's
+// are in flight while this one is added), and thread j < w walks its column of the chunk out of LDS in order.
+constexpr int RD_CHUNK = 1024;   // doubles staged per pass (whole rows of w: RD_CHUNK / w >= 16 rows)
+__global__ __launch_bounds__(256) void reduce_double_kernel(const double* __restrict__ part, int nblocks, int w, double* __restrict__ out) {
+  __shared__ double stage[RD_CHUNK];
+  const int tid = threadIdx.x;
+  if (nblocks <= 0) return;
+  const int rows = RD_CHUNK / w;                       // rows of the partial array per pass
+  const size_t total = (size_t)nblocks * w;
+  double v[RD_CHUNK / 256];
+  // unconditional loads (index clamped into the array): a load under a run-time condition is branched around and waited for one by one
+  auto fetch = [&](int b0) {
+    const size_t base = (size_t)b0 * w;
+#pragma unroll
+    for (int i = 0; i < RD_CHUNK / 256; ++i) { const size_t e = base + tid + 256 * i; v[i] = part[e < total ? e : total - 1]; }
+  };
+  fetch(0);
+  const double o0 = tid < w ? out[tid] : 0.0;
   double s = 0;
-  for (int b = 0; b < nblocks; ++b) s += part[(size_t)b * w + j];
-  out[j] += s;
+  for (int b0 = 0; b0 < nblocks; b0 += rows) {
+#pragma unroll
+    for (int i = 0; i < RD_CHUNK / 256; ++i) stage[tid + 256 * i] = v[i];
+    __syncthreads();
+    if (b0 + rows < nblocks) fetch(b0 + rows);
+    if (tid < w) {
+      const int m = nblocks - b0 < rows ? nblocks - b0 : rows;
+      int r = 0;
+      for (; r + 8 <= m; r += 8) {
+        double x[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) x[i] = stage[(r + i) * w + tid];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) s += x[i];
+      }
+      for (; r < m; ++r) s += stage[r * w + tid];
+    }
+    __syncthreads();
+  }
+  if (tid < w) out[tid] = o0 + s;
+}
+inline void reduce_double_launch(hipStream_t s, const double* part, int nblocks, int w, double* out) {
+  hipLaunchKernelGGL(reduce_double_kernel, dim3(1), dim3(256), 0, s, part, nblocks, w, out);
 }
 struct PpoParams { float clip, vclip, vcoef, ecoef, lrclip, adv_eps; };
 // per sample: coefficients dL/dlogp, dL/dvalue, dL/dentropy(const) and metric partial sums (atomics into metrics_acc[8] doubles)
@@ -531,12 +569,47 @@ __global__ void outer_acc_kernel(float* __restrict__ C, const float* __restrict_
 
 // column sums: out[n] (+)= sum_m X[m][n]  (bias gradients); one block per 64 columns, 256 threads = 4 row phases
 // out[c] += sum over rows p (in order) of part[p][c]: the fixed-order second stage of the fp32 column sums (deterministic mode)
-__global__ void reduce_rows_kernel(const float* __restrict__ part, int nparts, int n, float* __restrict__ out) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= n) return;
+// The chain s = 0; s += part[0][c]; s += part[1][c]; ...; out[c] += s is the result's definition (bit for bit); the fetch is not part of it.
+// A workgroup of 256 threads owns 64 columns: all four wavefronts bring RR_ROWS rows at a time into LDS with independent loads (16 in flight
+// per thread, the next pass's issued before this one's additions), and the first wavefront adds its column out of LDS in row order. One
+// memory round trip per 64 partial rows instead of one per row.
+constexpr int RR_ROWS = 64;
+__global__ __launch_bounds__(256) void reduce_rows_kernel(const float* __restrict__ part, int nparts, int n, float* __restrict__ out) {
+  __shared__ float tile[RR_ROWS][64];
+  const int cl = threadIdx.x & 63, ph = threadIdx.x >> 6, c = blockIdx.x * 64 + cl;
+  if (nparts <= 0) return;
+  const int cc = c < n ? c : n - 1;                    // clamped, so that every load below is unconditional
+  float v[RR_ROWS / 4];
+  auto fetch = [&](int p0) {
+#pragma unroll
+    for (int i = 0; i < RR_ROWS / 4; ++i) { const int p = p0 + ph + 4 * i; v[i] = part[(size_t)(p < nparts ? p : nparts - 1) * n + cc]; }
+  };
+  fetch(0);
+  const float o0 = out[cc];
   float s = 0.0f;
-  for (int p = 0; p < nparts; ++p) s += part[(size_t)p * n + c];
-  out[c] += s;
+  for (int p0 = 0; p0 < nparts; p0 += RR_ROWS) {
+#pragma unroll
+    for (int i = 0; i < RR_ROWS / 4; ++i) tile[ph + 4 * i][cl] = v[i];
+    __syncthreads();
+    if (p0 + RR_ROWS < nparts) fetch(p0 + RR_ROWS);
+    if (ph == 0) {
+      const int m = nparts - p0 < RR_ROWS ? nparts - p0 : RR_ROWS;
+      int r = 0;
+      for (; r + 8 <= m; r += 8) {
+        float x[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) x[i] = tile[r + i][cl];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) s += x[i];
+      }
+      for (; r < m; ++r) s += tile[r][cl];
+    }
+    __syncthreads();
+  }
+  if (ph == 0 && c < n) out[c] = o0 + s;
+}
+inline void reduce_rows_launch(hipStream_t s, const float* part, int nparts, int n, float* out) {
+  hipLaunchKernelGGL(reduce_rows_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, part, nparts, n, out);
 }
 __global__ void colsum_kernel(const float* __restrict__ X, int M, int N, int ld, float* __restrict__ out, float* __restrict__ part) {
   __shared__ float red[4][64];
