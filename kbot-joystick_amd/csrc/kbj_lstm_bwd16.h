@@ -168,7 +168,10 @@ __global__ __launch_bounds__(BWD16_NTH) void lstm_seq_bwd16_kernel(SeqBwdArgs a)
       if (r < B) {
         float* dg = a.dG + ((size_t)t * B + r) * 4 * H + u0 + eunit[i];
         seq_store(dg, d0); seq_store(dg + H, d1); seq_store(dg + 2 * H, d2); seq_store(dg + 3 * H, d3);
-        bsum[i][0] += d0; bsum[i][1] += d1; bsum[i][2] += d2; bsum[i][3] += d3;
+        {
+#pragma clang fp contract(off)   // sums of the dG values as stored, never of an unrounded product (kbj_lstm_seq.h, lstm_seq_bwd_body)
+          bsum[i][0] += d0; bsum[i][1] += d1; bsum[i][2] += d2; bsum[i][3] += d3;
+        }
       }
       dcm[i] = dc * fg;
     }
@@ -190,6 +193,19 @@ __global__ __launch_bounds__(BWD16_NTH) void lstm_seq_bwd16_kernel(SeqBwdArgs a)
       else atomicAdd(a.db + k * H + u0 + u, s);
     }
   }
+}
+
+
+// launch path (host; see kbj_lstm_seq.h): workgroups = unit groups x 16-row groups; `drop` fewer under fault injection. false: no kernel for this H
+inline int seq_bwd16_grid(int H, int B) { return (H / BWD16_UNITS) * ((B + BWD16_ROWS - 1) / BWD16_ROWS); }
+inline bool seq_bwd16_launch(hipStream_t st, int H, const SeqBwdArgs& a, int drop = 0) {
+  return dispatch_hidden(H, [&](auto hc) {
+    constexpr int HC = decltype(hc)::value;
+    if constexpr (HC <= SEQ_FUSED_MAX_H) {
+      hipLaunchKernelGGL((lstm_seq_bwd16_kernel<HC>), dim3(seq_bwd16_grid(HC, a.B) - drop), dim3(BWD16_NTH), 0, st, a);
+      return true;
+    } else return false;
+  });
 }
 
 }  // namespace kbj

@@ -18,6 +18,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
+#include <type_traits>
+#include "kbj_model.h"
 
 namespace kbj {
 
@@ -528,7 +531,13 @@ __device__ __forceinline__ void lstm_seq_bwd_body(const SeqBwdArgs a) {
       seq_store(dg + H, d1);
       seq_store(dg + 2 * H, d2);
       seq_store(dg + 3 * H, d3);
-      bsum[i][0] += d0; bsum[i][1] += d1; bsum[i][2] += d2; bsum[i][3] += d3;
+      {
+        // the bias sums add the dG values AS STORED (each rounded to fp32): a chain of plain additions that the deterministic mode's contract names
+        // (db_part = sums of dG in a fixed order, tools/lstm_check rebuilds it bit for bit). Left to the compiler, the last product of d0..d3 is
+        // contracted into these additions (v_fmac on the unrounded product), so the sums were not those of the stored dG
+#pragma clang fp contract(off)
+        bsum[i][0] += d0; bsum[i][1] += d1; bsum[i][2] += d2; bsum[i][3] += d3;
+      }
       dcm[i] = dc * fg;
     }
     SEQ_BSTAMP(7);
@@ -659,6 +668,70 @@ __global__ __launch_bounds__(256 * UW) void lstm_step_kernel(StepArgs a) {
     }
     // gbuf is rewritten only behind the next group's first barrier, which every wavefront reaches after these reads
   }
+}
+
+
+// ---- launch path (host): hidden-size dispatch and grids, free of any context so that tools/lstm_check launches exactly what kbj_nn.hip launches ----
+// recurrence workgroups are 8 wavefronts owning 32 hidden units (the 4-wavefront / 16-unit form of round 1 is gone:
+// slower in situ at every size)
+constexpr int SEQ_UW = 2;
+// Hidden sizes above this run "wide": the forward recurrence keeps only its W_hh slice in registers (two slices of H / 4 registers each do
+// not fit beyond 256), so the input products are GEMM launches in front of it; the backward recurrence takes the registers it needs
+// (lstm_seq_bwd_wide_kernel); the rollout's layers are [x | h] gate GEMM + cell kernel; and the update runs on one stream when two
+// recurrence launches would not be resident together. Served, not tuned: the launch configuration is 256.
+constexpr int SEQ_FUSED_MAX_H = 256;
+constexpr int SEQ_MAX_H = 512;
+
+// The run-time hidden size H in {64, 128, ..., SEQ_MAX_H} as a compile-time constant: returns f(std::integral_constant<int, H>()), and false
+// for any other H. f returns whether it has a kernel for that size (those built up to SEQ_FUSED_MAX_H only: `if constexpr` in f).
+template <int HC = 64, class F> bool dispatch_hidden(int H, F&& f) {
+  if constexpr (HC > SEQ_MAX_H) return false;
+  else return H == HC ? f(std::integral_constant<int, HC>()) : dispatch_hidden<HC + 64>(H, f);
+}
+
+// workgroups of a forward / 32 x 32 backward recurrence launch: unit groups x row groups
+inline int seq_grid(int H, int B) { return (H / (SEQ_UNITS * SEQ_UW)) * ((B + SEQ_ROWS - 1) / SEQ_ROWS); }
+// forward recurrence; `drop` workgroups fewer than the grid (fault injection only). false: no kernel for this H. a.counters: zeroed by the caller
+inline bool seq_fwd_launch(hipStream_t st, int H, const SeqFwdArgs& a, int drop = 0) {
+  return dispatch_hidden(H, [&](auto hc) {
+    constexpr int HC = decltype(hc)::value, UW = SEQ_UW;
+    const int grid = seq_grid(HC, a.B) - drop;
+    const dim3 block(256 * UW);
+    if constexpr (HC <= SEQ_FUSED_MAX_H) {
+      if (a.X && a.ldx == KBJ_LD_ACTOR) { hipLaunchKernelGGL((lstm_seq_fwd_kernel<HC, UW, true, KBJ_LD_ACTOR>), dim3(grid), block, 0, st, a); return true; }   // gates from the observation rows
+      if (a.X) { hipLaunchKernelGGL((lstm_seq_fwd_kernel<HC, UW, true>), dim3(grid), block, 0, st, a); return true; }   // input projection fused
+    }
+    hipLaunchKernelGGL((lstm_seq_fwd_kernel<HC, UW, false>), dim3(grid), block, 0, st, a);   // (wide layers: the schedule never passes X, kbj_read_settings)
+    return true;
+  });
+}
+// backward recurrence, 32 x 32 tiles (the capped-register kernel up to SEQ_FUSED_MAX_H, the wide one above)
+inline bool seq_bwd_launch(hipStream_t st, int H, const SeqBwdArgs& a) {
+  return dispatch_hidden(H, [&](auto hc) {
+    constexpr int HC = decltype(hc)::value, UW = SEQ_UW;
+    const dim3 grid(seq_grid(HC, a.B)), block(256 * UW);
+    if constexpr (HC <= SEQ_FUSED_MAX_H) hipLaunchKernelGGL((lstm_seq_bwd_kernel<HC, UW>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((lstm_seq_bwd_wide_kernel<HC, UW>), grid, block, 0, st, a);
+    return true;
+  });
+}
+// one LSTM layer step over many rows: grid = unit groups x row chunks, about one workgroup per CU
+inline bool lstm_step_obs(const StepArgs& a) { return a.ldx == KBJ_LD_ACTOR && a.ldw == KBJ_LD_ACTOR; }
+inline int lstm_step_grid(int H, int M) {
+  const int nug = H / (SEQ_UNITS * 2), nrg = (M + SEQ_ROWS - 1) / SEQ_ROWS;
+  return nug * std::max(1, std::min(nrg, 256 / nug));
+}
+inline bool lstm_step_launch(hipStream_t st, int H, const StepArgs& a) {
+  const bool obs = lstm_step_obs(a);
+  const dim3 grid(lstm_step_grid(H, a.M)), block(512);
+  return dispatch_hidden(H, [&](auto hc) {
+    constexpr int HC = decltype(hc)::value;
+    if constexpr (HC <= SEQ_FUSED_MAX_H) {
+      if (obs) hipLaunchKernelGGL((lstm_step_kernel<HC, 2, KBJ_LD_ACTOR>), grid, block, 0, st, a);
+      else hipLaunchKernelGGL((lstm_step_kernel<HC, 2>), grid, block, 0, st, a);
+      return true;
+    } else return false;
+  });
 }
 
 }  // namespace kbj

@@ -256,42 +256,17 @@ void colsum_acc(kbj_ctx* ctx, hipStream_t s, const float* X, int M, int N, int l
   if (part) reduce_rows_launch(s, part, DETP_ROWS, N, out);
 }
 
-// recurrence workgroups are 8 wavefronts owning 32 hidden units (kbj_lstm_seq.h; the 4-wavefront / 16-unit form of round 1 is gone:
-// slower in situ at every size)
-constexpr int SEQ_UW = 2;
-// Hidden sizes above this run "wide": the forward recurrence keeps only its W_hh slice in registers (two slices of H / 4 registers each do
-// not fit beyond 256), so the input products are GEMM launches in front of it; the backward recurrence takes the registers it needs
-// (lstm_seq_bwd_wide_kernel); the rollout's layers are [x | h] gate GEMM + cell kernel; and the update runs on one stream when two
-// recurrence launches would not be resident together. Served, not tuned: the launch configuration is 256.
-constexpr int SEQ_FUSED_MAX_H = 256;
-constexpr int SEQ_MAX_H = 512;
+// SEQ_UW, SEQ_FUSED_MAX_H, SEQ_MAX_H, dispatch_hidden and the grids of the recurrence / step launches: kbj_lstm_seq.h, kbj_lstm_bwd16.h (launch path)
 constexpr int SEQ_COUNTER_WORDS = 256;   // hand-off words per recurrence launch (one per workgroup): the grid of a launch may not exceed it
 constexpr int SEQ_COUNTER_TOTAL = 2 * MAXD * 4 * SEQ_COUNTER_WORDS;   // all launches of one call (forward + backward, MAXD layers, 4 nets): ONE clear
-
-// The run-time hidden size H in {64, 128, ..., SEQ_MAX_H} as a compile-time constant: returns f(std::integral_constant<int, H>()), and false
-// for any other H. f returns whether it has a kernel for that size (those built up to SEQ_FUSED_MAX_H only: `if constexpr` in f).
-template <int HC = 64, class F> bool dispatch_hidden(int H, F&& f) {
-  if constexpr (HC > SEQ_MAX_H) return false;
-  else return H == HC ? f(std::integral_constant<int, HC>()) : dispatch_hidden<HC + 64>(H, f);
-}
 
 int seq_fwd(kbj_ctx* ctx, hipStream_t st, int H, const SeqFwdArgs& a0) {   // a0.counters: zeroed by the caller
   SeqFwdArgs a = a0;
   a.timeout_ticks = ws_of(ctx)->seq_timeout_ticks;
   KbjKernelTimer timer(st, a.X ? (a.ldx == KBJ_LD_ACTOR ? KBJ_KIND_SEQ_FWD_OBS : KBJ_KIND_SEQ_FWD_FUSED) : KBJ_KIND_SEQ_FWD, 2.0 * a.T * a.B * 4.0 * H * (H + (a.X ? (a.kx ? a.kx : H) : 0)));
-  const bool built = dispatch_hidden(H, [&](auto hc) {
-    constexpr int HC = decltype(hc)::value, UW = SEQ_UW;
-    int grid = (HC / (SEQ_UNITS * UW)) * ((a.B + SEQ_ROWS - 1) / SEQ_ROWS);
-    if (ctx->set.seq_drop > 0 && grid > 1) { --ctx->set.seq_drop; --grid; }   // fault injection (KbjSettings::seq_drop)
-    const dim3 block(256 * UW);
-    if constexpr (HC <= SEQ_FUSED_MAX_H) {
-      if (a.X && a.ldx == KBJ_LD_ACTOR) { hipLaunchKernelGGL((lstm_seq_fwd_kernel<HC, UW, true, KBJ_LD_ACTOR>), dim3(grid), block, 0, st, a); return true; }   // gates from the observation rows
-      if (a.X) { hipLaunchKernelGGL((lstm_seq_fwd_kernel<HC, UW, true>), dim3(grid), block, 0, st, a); return true; }   // input projection fused
-    }
-    hipLaunchKernelGGL((lstm_seq_fwd_kernel<HC, UW, false>), dim3(grid), block, 0, st, a);   // (wide layers: the schedule never passes X, kbj_read_settings)
-    return true;
-  });
-  return built ? 0 : kbj_fail(ctx, "seq_fwd: the persistent LSTM kernels are built for hidden sizes 64, 128, ..., 512");
+  int drop = 0;
+  if (ctx->set.seq_drop > 0 && seq_grid(H, a.B) > 1) { --ctx->set.seq_drop; drop = 1; }   // fault injection (KbjSettings::seq_drop)
+  return seq_fwd_launch(st, H, a, drop) ? 0 : kbj_fail(ctx, "seq_fwd: the persistent LSTM kernels are built for hidden sizes 64, 128, ..., 512");
 }
 // row groups of a backward-recurrence launch (deterministic mode: rows of its per-row-group bias partials)
 int seq_bwd_row_groups(int B, bool tiles16) { return tiles16 ? (B + BWD16_ROWS - 1) / BWD16_ROWS : (B + SEQ_ROWS - 1) / SEQ_ROWS; }
@@ -299,21 +274,12 @@ int seq_bwd(kbj_ctx* ctx, hipStream_t st, int H, const SeqBwdArgs& a0, bool tile
   SeqBwdArgs a = a0;
   a.timeout_ticks = ws_of(ctx)->seq_timeout_ticks;
   KbjKernelTimer timer(st, tiles16 ? KBJ_KIND_SEQ_BWD16 : KBJ_KIND_SEQ_BWD, 2.0 * a.T * a.B * 4.0 * H * H);
-  const bool built = dispatch_hidden(H, [&](auto hc) {
-    constexpr int HC = decltype(hc)::value, UW = SEQ_UW;
-    if (tiles16) {
-      if constexpr (HC <= SEQ_FUSED_MAX_H) {
-        int grid = (HC / BWD16_UNITS) * ((a.B + BWD16_ROWS - 1) / BWD16_ROWS);
-        if (ctx->set.seq_drop_bwd > 0 && grid > 1 && HC > BWD16_UNITS) { --ctx->set.seq_drop_bwd; --grid; }   // fault injection (a launch without partners has nobody to time out)
-        hipLaunchKernelGGL((lstm_seq_bwd16_kernel<HC>), dim3(grid), dim3(BWD16_NTH), 0, st, a);
-        return true;
-      } else return false;
-    }
-    const dim3 grid((HC / (SEQ_UNITS * UW)) * ((a.B + SEQ_ROWS - 1) / SEQ_ROWS)), block(256 * UW);
-    if constexpr (HC <= SEQ_FUSED_MAX_H) hipLaunchKernelGGL((lstm_seq_bwd_kernel<HC, UW>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((lstm_seq_bwd_wide_kernel<HC, UW>), grid, block, 0, st, a);
-    return true;
-  });
+  bool built;
+  if (tiles16) {
+    int drop = 0;
+    if (ctx->set.seq_drop_bwd > 0 && seq_bwd16_grid(H, a.B) > 1 && H > BWD16_UNITS && H <= SEQ_FUSED_MAX_H) { --ctx->set.seq_drop_bwd; drop = 1; }   // fault injection (a launch without partners has nobody to time out)
+    built = seq_bwd16_launch(st, H, a, drop);
+  } else built = seq_bwd_launch(st, H, a);
   return built ? 0 : kbj_fail(ctx, "seq_bwd: the persistent LSTM kernels are built for hidden sizes 64, 128, ..., 512 (lstm_seq_bwd16_kernel: up to 256)");
 }
 
@@ -341,20 +307,8 @@ template <int H> hipError_t seq_min_blocks_per_cu(int* out) {
 
 // one LSTM layer step over many rows (kbj_lstm_seq.h lstm_step_kernel): grid = unit groups x row chunks, about one workgroup per CU
 int lstm_step(kbj_ctx* ctx, hipStream_t st, int H, const StepArgs& a) {
-  const bool obs = a.ldx == KBJ_LD_ACTOR && a.ldw == KBJ_LD_ACTOR;
-  KbjKernelTimer timer(st, obs ? KBJ_KIND_LSTM_STEP_OBS : KBJ_KIND_LSTM_STEP, 2.0 * a.M * 4.0 * H * (H + (a.kx ? a.kx : H)));
-  const int nug = H / (SEQ_UNITS * 2), nrg = (a.M + SEQ_ROWS - 1) / SEQ_ROWS;
-  const int nch = std::max(1, std::min(nrg, 256 / nug));
-  dim3 grid(nug * nch), block(512);
-  const bool built = dispatch_hidden(H, [&](auto hc) {
-    constexpr int HC = decltype(hc)::value;
-    if constexpr (HC <= SEQ_FUSED_MAX_H) {
-      if (obs) hipLaunchKernelGGL((lstm_step_kernel<HC, 2, KBJ_LD_ACTOR>), grid, block, 0, st, a);
-      else hipLaunchKernelGGL((lstm_step_kernel<HC, 2>), grid, block, 0, st, a);
-      return true;
-    } else return false;
-  });
-  return built ? 0 : kbj_fail(ctx, "lstm_step: the LSTM step kernels are built for hidden_size 64, 128, 192, 256");
+  KbjKernelTimer timer(st, lstm_step_obs(a) ? KBJ_KIND_LSTM_STEP_OBS : KBJ_KIND_LSTM_STEP, 2.0 * a.M * 4.0 * H * (H + (a.kx ? a.kx : H)));
+  return lstm_step_launch(st, H, a) ? 0 : kbj_fail(ctx, "lstm_step: the LSTM step kernels are built for hidden_size 64, 128, 192, 256");
 }
 
 }  // namespace
