@@ -207,5 +207,24 @@ inline bool seq_bwd16_launch(hipStream_t st, int H, const SeqBwdArgs& a, int dro
     } else return false;
   });
 }
+// Resident workgroups per CU of one recurrence kernel at its launch helper's block size: the ONE occupancy table, read by kbj_create's
+// residency check (kbj_nn.hip) and by tools/lstm_check. hipErrorInvalidValue: that kernel is not built for this hidden size.
+enum SeqKernelKind { SEQ_KIND_FWD_PLAIN, SEQ_KIND_FWD_FUSED, SEQ_KIND_FWD_OBS, SEQ_KIND_BWD32 /* the wide kernel above SEQ_FUSED_MAX_H */, SEQ_KIND_BWD16, SEQ_KIND_COUNT };
+inline hipError_t seq_blocks_per_cu(SeqKernelKind kind, int H, int* n) {
+  hipError_t e = hipErrorInvalidValue;
+  dispatch_hidden(H, [&](auto hc) {
+    constexpr int HC = decltype(hc)::value, TH = 256 * SEQ_UW;
+    auto ask = [&](auto kernel, int threads) { e = hipOccupancyMaxActiveBlocksPerMultiprocessor(n, kernel, threads, 0); };
+    if (kind == SEQ_KIND_FWD_PLAIN) ask(lstm_seq_fwd_kernel<HC, SEQ_UW, false, HC>, TH);
+    if constexpr (HC <= SEQ_FUSED_MAX_H) {
+      if (kind == SEQ_KIND_FWD_FUSED) ask(lstm_seq_fwd_kernel<HC, SEQ_UW, true, HC>, TH);
+      if (kind == SEQ_KIND_FWD_OBS) ask(lstm_seq_fwd_kernel<HC, SEQ_UW, true, KBJ_LD_ACTOR>, TH);
+      if (kind == SEQ_KIND_BWD32) ask(lstm_seq_bwd_kernel<HC, SEQ_UW>, TH);
+      if (kind == SEQ_KIND_BWD16) ask(lstm_seq_bwd16_kernel<HC>, BWD16_NTH);
+    } else if (kind == SEQ_KIND_BWD32) ask(lstm_seq_bwd_wide_kernel<HC, SEQ_UW>, TH);
+    return true;
+  });
+  return e;
+}
 
 }  // namespace kbj

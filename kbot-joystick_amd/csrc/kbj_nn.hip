@@ -284,24 +284,12 @@ int seq_bwd(kbj_ctx* ctx, hipStream_t st, int H, const SeqBwdArgs& a0, bool tile
 }
 
 // resident workgroups per CU of the recurrence kernel that fits worst, over EVERY recurrence kernel the schedule may launch for this
-// hidden size (fused forward with the hidden-layer input, fused forward from the observation rows, plain forward, backward): in the
+// hidden size (seq_blocks_per_cu, kbj_lstm_bwd16.h: all five kinds up to SEQ_FUSED_MAX_H, plain forward and wide backward above): in the
 // gfx950 code object the fused forward is the largest (252 VGPRs / 86 KB of LDS at H = 256 against 176 / 52 KB for the backward)
-template <int H> hipError_t seq_min_blocks_per_cu(int* out) {
-  constexpr int threads = 256 * SEQ_UW;
-  int n[4] = {0, 0, 0, 0};
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n[2], lstm_seq_fwd_kernel<H, SEQ_UW, false, H>, threads, 0);
-  if constexpr (H <= SEQ_FUSED_MAX_H) {
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n[0], lstm_seq_fwd_kernel<H, SEQ_UW, true, H>, threads, 0);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n[1], lstm_seq_fwd_kernel<H, SEQ_UW, true, KBJ_LD_ACTOR>, threads, 0);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n[3], lstm_seq_bwd_kernel<H, SEQ_UW>, threads, 0);
-    int n16 = 0;   // the 16 x 64-tile backward form: same grid size ((B / 16) x (H / 64) = (B / 32) x (H / 32)), same 512 threads
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n16, lstm_seq_bwd16_kernel<H>, BWD16_NTH, 0);
-    n[3] = std::min(n[3], n16);
-  } else {
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n[3], lstm_seq_bwd_wide_kernel<H, SEQ_UW>, threads, 0);
-    n[0] = n[1] = n[2];
-  }
-  *out = std::min(std::min(n[0], n[1]), std::min(n[2], n[3]));
+hipError_t seq_min_blocks_per_cu(int H, int* out) {
+  hipError_t e = seq_blocks_per_cu(SEQ_KIND_FWD_PLAIN, H, out);
+  for (int k = 0, n = 0; k < SEQ_KIND_COUNT && e == hipSuccess; ++k)
+    if (H <= SEQ_FUSED_MAX_H || k == SEQ_KIND_BWD32) { e = seq_blocks_per_cu((SeqKernelKind)k, H, &n); *out = std::min(*out, n); }
   return e;
 }
 
@@ -520,10 +508,8 @@ int nn_residency_check(kbj_ctx* ctx, NnWs* w) {
   if (hipGetDeviceProperties(&prop, ctx->device) != hipSuccess) return kbj_fail(ctx, "hipGetDeviceProperties");
   const int cus = prop.multiProcessorCount;
   int per_cu = 0;
-  hipError_t oe = hipSuccess;
-  if (!dispatch_hidden(H, [&](auto hc) { oe = seq_min_blocks_per_cu<decltype(hc)::value>(&per_cu); return true; }))
-    return kbj_fail(ctx, "kbj_create: hidden_size above 512 (persistent LSTM kernels)");
-  if (oe != hipSuccess || per_cu < 1) return kbj_fail(ctx, "kbj_create: occupancy query of the persistent LSTM kernels failed");
+  if (!dispatch_hidden(H, [](auto) { return true; })) return kbj_fail(ctx, "kbj_create: hidden_size above 512 (persistent LSTM kernels)");
+  if (seq_min_blocks_per_cu(H, &per_cu) != hipSuccess || per_cu < 1) return kbj_fail(ctx, "kbj_create: occupancy query of the persistent LSTM kernels failed");
   const long slots = (long)per_cu * cus;
   w->seq_grid = grid; w->seq_slots = (int)slots;
   char msg[320];

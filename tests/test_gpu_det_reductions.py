@@ -6,35 +6,23 @@ The kernels fetch their partials in batches; the ORDER of the additions is the r
 and a non-zero initial output, and before each launch it proves on the host that a pairwise-order sum of the same input differs from the
 chain, so a kernel that adds in another order cannot pass. `reduce_check --plan` (no device, runs in the CPU suite) does that host-side proof
 alone over the same case table."""
-import os
-import subprocess
-
 import pytest
 
-gpu = pytest.mark.gpu      # per test: the --plan test below needs no device
+from tests import check_tool
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOOLS = os.path.join(ROOT, "tools")
+gpu = pytest.mark.gpu      # per test: the --plan test below needs no device
 
 REDUCE_ROWS = [(1, 1), (16, 256), (32, 1024), (33, 257), (512, 1), (512, 40), (511, 65)]       # (nparts, n)
 REDUCE_DOUBLE = [(1, 1), (32, 2), (512, 1), (513, 3), (7, 64)]                                  # (nblocks, w)
 
 
-def _tool(*args):
-    out = subprocess.run(["make", "-C", TOOLS, "-s", "reduce_check"], capture_output=True, text=True, timeout=600, cwd=ROOT)
-    assert out.returncode == 0, (out.stdout[-500:], out.stderr[-1500:])
-    out = subprocess.run([os.path.join(TOOLS, "reduce_check"), *args], capture_output=True, text=True, timeout=120, cwd=ROOT)
-    print(out.stdout)
-    return out.returncode, out.stdout, out.stderr
-
-
 @pytest.fixture(scope="module")
 def report():
-    return _tool()
+    return check_tool.run("reduce_check", timeout=120)
 
 
 def _cases(so, kernel):
-    return [l for l in so.splitlines() if l.startswith("case ") and l.split()[1] == kernel]
+    return [l for l in check_tool.case_lines(so) if l.split()[1] == kernel]
 
 
 def _check_table(so):
@@ -57,18 +45,14 @@ def _check_table(so):
 def test_plan_every_input_tells_a_pairwise_sum_from_the_chain():
     """No device: the tool builds every case's input and verifies on the host that the pairwise-order sum differs from the sequential one in
     at least one output, i.e. that the GPU test's bit-for-bit demand cannot be met by a kernel that adds in tree order."""
-    rc, so, se = _tool("--plan")
-    assert rc == 0 and "REDUCE CHECK PLAN OK" in so and "FAIL" not in so, (so[-2000:], se[-500:])
+    rc, so, se = check_tool.run("reduce_check", "--plan", timeout=120)
+    check_tool.assert_finished(rc, so, se, "REDUCE CHECK PLAN OK")
     _check_table(so)
 
 
 @gpu
 def test_every_second_stage_is_bit_identical_to_the_sequential_sum(report):
-    rc, so, se = report
-    failing = [l for l in so.splitlines() if "FAIL" in l]
-    assert rc == 0 and "REDUCE CHECK PASSED" in so and not failing, (failing[:40], so[-1500:], se[-500:])
-    count = [l for l in so.splitlines() if l.startswith("cases ")]
-    assert len(count) == 1 and int(count[0].split()[1]) == len([l for l in so.splitlines() if l.startswith("case ")])
+    check_tool.assert_finished(*report, "REDUCE CHECK PASSED")
 
 
 @gpu

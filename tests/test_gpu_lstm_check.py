@@ -7,15 +7,12 @@ step computed from the kernel's own stored inputs, the links between steps (Hout
 partials) bit for bit: nothing compounds over t, the bounds stay near 1e-6 and one wrong row, unit, gate, step or keep flag is O(1).
 `lstm_check --plan` (no device, runs in the CPU suite) proves over the same case table that the gates are not saturated, that the checker
 passes a host fp32 model of every kernel and that it rejects eight mutants of that model wherever a case exercises the mutated feature."""
-import os
-import subprocess
-
 import pytest
 
-gpu = pytest.mark.gpu      # per test: the --plan test below needs no device
+from tests import check_tool
+from tests.check_tool import case_lines as _case_lines
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOOLS = os.path.join(ROOT, "tools")
+gpu = pytest.mark.gpu      # per test: the --plan test below needs no device
 
 KEEPS = ["ones", "zeros", "t0", "tlast", "hashed"]          # every recurrence case with T >= 2; T = 1: ones and zeros (the other three coincide with zeros)
 ALL_H = [64, 128, 192, 256, 320, 384, 448, 512]
@@ -31,26 +28,14 @@ BWD16 = [(h, b, t) for h in FUSED_H for b in (1, 15, 16, 17, 48) for t in (1, 2,
 STEP = [(h, m, obs) for h in FUSED_H for obs in (False, True) for m in (1, 33)] + [(256, 1061, False), (64, 4129, False)]
 
 
-def _tool(*args):
-    out = subprocess.run(["make", "-C", TOOLS, "-s", "lstm_check"], capture_output=True, text=True, timeout=600, cwd=ROOT)
-    assert out.returncode == 0, (out.stdout[-500:], out.stderr[-1500:])
-    out = subprocess.run([os.path.join(TOOLS, "lstm_check"), *args], capture_output=True, text=True, timeout=300, cwd=ROOT)
-    print(out.stdout[-6000:])
-    return out.returncode, out.stdout, out.stderr
-
-
 @pytest.fixture(scope="module")
 def plan():
-    return _tool("--plan")
+    return check_tool.run("lstm_check", "--plan", timeout=300)
 
 
 @pytest.fixture(scope="module")
 def report():
-    return _tool()
-
-
-def _case_lines(so):
-    return [l for l in so.splitlines() if l.startswith("case ")]
+    return check_tool.run("lstm_check", timeout=300)
 
 
 def _expected():
@@ -109,8 +94,8 @@ def _check_table(so):
 def test_plan_gates_alive_model_accepted_every_mutant_rejected(plan):
     """No device. Per case: >= 90 % of the gate pre-activations within |x| <= 3; the checker passes the host fp32 model; every mutant is
     rejected by more than 100 x the bound wherever the case exercises the feature, and says n/a exactly where it does not."""
-    rc, so, se = plan
-    assert rc == 0 and "LSTM CHECK PLAN OK" in so and "FAIL" not in so, (so[-2000:], se[-500:])
+    check_tool.assert_finished(*plan, "LSTM CHECK PLAN OK")
+    so = plan[1]
     _check_table(so)
     lines = _case_lines(so)
     for kernel, desc, fam, t, keep, b, kx_short, part in _expected():
@@ -127,11 +112,8 @@ def test_plan_gates_alive_model_accepted_every_mutant_rejected(plan):
 
 @gpu
 def test_every_recurrence_kernel_matches_the_stepwise_double_reference(report, plan):
-    rc, so, se = report
-    failing = [l for l in so.splitlines() if "FAIL" in l]
-    assert rc == 0 and "LSTM CHECK PASSED" in so and not failing, (failing[:40], so[-1500:], se[-500:])
-    count = [l for l in so.splitlines() if l.startswith("cases ")]
-    assert len(count) == 1 and int(count[0].split()[1]) == len(_case_lines(so)) == len(_case_lines(plan[1]))
+    check_tool.assert_finished(*report, "LSTM CHECK PASSED")
+    assert len(_case_lines(report[1])) == len(_case_lines(plan[1]))
 
 
 @gpu

@@ -11,27 +11,16 @@ driver's `-m gpu` run:
   reference at ragged shapes inside NaN / bit-pattern guard bands - bit for bit on integer operands, within the derived fp32 bound on reals;
   `gemm_check --plan` (no device, runs in the CPU suite) proves that the integer inputs satisfy the bit-exactness precondition.
 """
-import os
-import subprocess
-
 import pytest
 
+from tests import check_tool
+
 gpu = pytest.mark.gpu      # per test: the --plan test below needs no device
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOOLS = os.path.join(ROOT, "tools")
-
-
-def _run(cmd, timeout=600):
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
-    return out.returncode, out.stdout, out.stderr
 
 
 @gpu
 def test_wave_primitives_and_arrow_solve_bit_identical_to_the_emulation():
-    rc, so, se = _run(["make", "-C", os.path.join(TOOLS, "wave_test"), "-s"])
-    assert rc == 0, (so[-500:], se[-1500:])
-    rc, so, se = _run([os.path.join(TOOLS, "wave_test", "wave_test")], timeout=300)
+    rc, so, se = check_tool.run("wave", timeout=300, binary="wave_test/wave_test")
     assert rc == 0 and "WAVE TEST PASSED" in so, (so[-2000:], se[-500:])
     lines = [l for l in so.splitlines() if l.strip()]
     prim = [l for l in lines if l.split()[1:2] == ["ok"]]
@@ -45,9 +34,7 @@ def test_wave_primitives_and_arrow_solve_bit_identical_to_the_emulation():
 
 @gpu
 def test_gemm_bf16x3_operand_range():
-    rc, so, se = _run(["make", "-C", TOOLS, "-s", "gemm_bench"])
-    assert rc == 0, (so[-500:], se[-1500:])
-    rc, so, se = _run([os.path.join(TOOLS, "gemm_bench"), "10"], timeout=600)
+    rc, so, se = check_tool.run("gemm_bench", "10", timeout=600)
     assert rc == 0 and "X3 RANGE TEST PASSED" in so, (so[-3000:], se[-500:])
     rows = [l for l in so.splitlines() if l.lstrip().startswith("A x 2^")]
     assert len(rows) == 24 and all(l.rstrip().endswith("ok") or "bounded loss" in l for l in rows), so
@@ -59,26 +46,12 @@ GEMM_CHECK_FORMS = ("linear_fwd", "rollout_gates", "critic_input_projection", "g
                     "g1a")
 
 
-def _gemm_check_plan():
-    rc, so, se = _run(["make", "-C", TOOLS, "-s", "gemm_check"])
-    assert rc == 0, (so[-500:], se[-1500:])
-    rc, so, se = _run([os.path.join(TOOLS, "gemm_check"), "--plan"], timeout=300)
-    return rc, so, se
-
-
-def _case_lines(so):
-    return [l for l in so.splitlines() if l.startswith("case ")]
-
-
 def test_gemm_check_plan_inputs_satisfy_the_exactness_precondition():
     """No device: the tool enumerates its case table, builds the integer inputs and verifies that sum |a||b| + |bias| + |C0| < 2^24 for every
     output element, i.e. that the reference alone entitles the GPU test to demand bit-identical results."""
-    rc, so, se = _gemm_check_plan()
-    assert rc == 0 and "GEMM CHECK PLAN OK" in so, (so[-2000:], se[-500:])
-    cases = _case_lines(so)
-    count = [l for l in so.splitlines() if l.startswith("cases ")]
-    assert len(count) == 1 and int(count[0].split()[1]) == len(cases) > 0
-    assert not any("FAIL" in l for l in so.splitlines()), [l for l in so.splitlines() if "FAIL" in l][:20]
+    rc, so, se = check_tool.run("gemm_check", "--plan", timeout=300)
+    check_tool.assert_finished(rc, so, se, "GEMM CHECK PLAN OK")
+    cases = check_tool.case_lines(so)
     for form in GEMM_CHECK_FORMS:                                   # every call site of kbj_nn.hip, as issued and with x3 = 1
         mine = [l for l in cases if l.split()[2] == form]
         assert any(" x3=0->" in l for l in mine) and any(" x3=1->" in l for l in mine), form
@@ -89,15 +62,12 @@ def test_gemm_check_plan_inputs_satisfy_the_exactness_precondition():
 
 @gpu
 def test_gemm_check_every_form_against_the_double_reference():
-    rc, so, se = _gemm_check_plan()
-    assert rc == 0, (so[-2000:], se[-500:])
-    planned = int([l for l in so.splitlines() if l.startswith("cases ")][0].split()[1])
-    rc, so, se = _run([os.path.join(TOOLS, "gemm_check")], timeout=300)
-    lines = so.splitlines()
-    failing = [l for l in lines if "FAIL" in l]
-    assert rc == 0 and "GEMM CHECK PASSED" in so, (failing[:40], so[-1500:], se[-500:])
-    cases = _case_lines(so)
+    rc, so, se = check_tool.run("gemm_check", "--plan", timeout=300)
+    check_tool.assert_finished(rc, so, se, "GEMM CHECK PLAN OK")
+    planned = len(check_tool.case_lines(so))
+    rc, so, se = check_tool.run("gemm_check", timeout=300)
+    check_tool.assert_finished(rc, so, se, "GEMM CHECK PASSED")
+    cases = check_tool.case_lines(so)
     assert len(cases) == planned, (len(cases), planned)
     for form in GEMM_CHECK_FORMS:
         assert any(l.split()[2] == form for l in cases), form
-    assert not failing, failing[:40]

@@ -4,14 +4,12 @@
 // Every launch goes through gemm_launch<A_KC, B_KC>(stream, g, force_big), the entry point of the call sites in kbj_nn.hip, so the
 // launcher's tile choice, the x3 eligibility (gemm_x3_form) and the split-K reduce launch are under test with the kernels. No timing.
 //
-// HARNESS (the same for every case)
-//  * Every operand and every output is a window of a larger device array: a guard band in front and behind (8 rows + 256 floats) and, where
-//    the form allows ld > row length, padding behind every row. Operand guard and padding are NaN, so a read outside the logical operand
-//    poisons the result; in a gathered A the stored rows that the index list does not name are NaN too. Output guard and padding hold the
-//    bit pattern 0xDEADBEEF and must be bit-identical after the launch (rows beyond M and the columns between N and ldc included): a changed
-//    guard word is a stray store. The deterministic split-K slab starts as NaN (a reduce that reads a slice nobody wrote shows) and its guard
-//    is checked like an output's. All windows live in one device arena with 4 MB of unused slack at both ends and NaN everywhere at the
-//    start, so that a kernel that strays by a whole tile still reads mapped memory and fails a check instead of faulting.
+// HARNESS (the same for every case; arena, fill values and tally: tools/kbj_check.h, which documents the guard scheme)
+//  * Every operand and every output is a two-dimensional window (Mat) of a larger array from the arena: a guard band in front and behind
+//    (8 rows + 256 floats) and, where the form allows ld > row length, padding behind every row. Operand guard and padding are NaN; in a
+//    gathered A the stored rows that the index list does not name are NaN too. Output guard and padding hold the bit pattern and must be
+//    bit-identical after the launch (rows beyond M and the columns between N and ldc included). The deterministic split-K slab starts as
+//    NaN (a reduce that reads a slice nobody wrote shows) and its guard is checked like an output's.
 //  * beta = 0 launches start from a NaN-filled C (the old value must not enter); beta = 1 and split-K launches start from known values that
 //    the reference includes.
 //  * No form of kbj_gemm.h reads padding by design: the buffer-load fast path is taken only for tiles whose rows and 32 k are all in range,
@@ -52,36 +50,15 @@
 // that gemm_x3_form picks what the comments of kbj_gemm.h promise (promised_x3 below restates them: plain, GEN or silent fallback).
 // The widest launch is linear_bwd_weight2 with the folded layer's 475-column second problem (n1 + 475 columns: the table of call sites
 // asks for that width); everything else stays within 257 x 257 x 476.
-#include <hip/hip_runtime.h>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <cstdint>
-#include <cmath>
-#include <vector>
-#include <string>
 #include <map>
-#include <algorithm>
+#include "kbj_check.h"
 #include "kbj_gemm.h"
 
-thread_local kbj_ctx* kbj_prof_ctx = nullptr;
-thread_local std::string kbj_global_error;
 using namespace kbj;
-
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); fflush(stdout); exit(2); } } while (0)
-
-static inline uint32_t mix(uint32_t x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; }
-static inline uint32_t hash3(uint32_t tag, uint32_t r, uint32_t c) { return mix(mix(mix(tag) + r * 0x9E3779B9u) + c * 0x85EBCA6Bu + 1u); }
-static inline int pick(int row, int salt, int n) { return (int)(mix((uint32_t)row * 31u + (uint32_t)salt * 0x632BE5ABu + 7u) % (uint32_t)n); }
-static inline float bits_f(uint32_t b) { float f; memcpy(&f, &b, 4); return f; }
-static inline uint32_t f_bits(float f) { uint32_t b; memcpy(&b, &f, 4); return b; }
-static const float PATTERN = bits_f(0xDEADBEEFu);
-static const float QNAN = bits_f(0x7FC00000u);
 
 enum Fam { EXACT = 0, PIECE_A = 1, PIECE_B = 2, REAL = 3 };
 static float val_int(uint32_t h, int amp) { return (float)((int)(h % (uint32_t)(2 * amp + 1)) - amp); }
 static float val_piece(uint32_t h) { const int v = 0x10000 | 0x101 | (int)(h & 0xFFFFu); return (h >> 31) ? -(float)v : (float)v; }
-static float val_real(uint32_t h) { return (float)((int)(h >> 8) - (1 << 23)) * (1.0f / (float)(1 << 23)); }
 
 // ---- one stored array: a window [rows][len] with leading dimension ld inside a guarded host image / device allocation ----
 struct Mat {
@@ -98,18 +75,8 @@ struct Mat {
   bool inside(size_t i) const { if (i < lead) return false; const size_t o = i - lead; return o / ld < (size_t)rows && o % ld < (size_t)len; }
 };
 
-struct Arena {
-  static constexpr size_t SLACK = (size_t)4 << 20, CAP = (size_t)64 << 20;
-  char* base = nullptr; size_t used = SLACK;
-  void init() { CK(hipMalloc(reinterpret_cast<void**>(&base), CAP)); CK(hipMemset(base, 0xFF, CAP)); }
-  void reset() { used = SLACK; }
-  void* take(size_t bytes) {
-    used = (used + 255) / 256 * 256;
-    if (used + bytes > CAP - SLACK) { printf("arena too small\n"); exit(2); }
-    void* p = base + used; used += bytes; return p;
-  }
-  void upload(Mat& m) { m.d = reinterpret_cast<float*>(take(m.h.size() * 4)); CK(hipMemcpy(m.d, m.h.data(), m.h.size() * 4, hipMemcpyHostToDevice)); }
-};
+static Arena arena((size_t)64 << 20);
+static void upload(Mat& m) { m.d = reinterpret_cast<float*>(arena.take(m.h.size() * 4)); CK(hipMemcpy(m.d, m.h.data(), m.h.size() * 4, hipMemcpyHostToDevice)); }
 
 // ---- one case ----
 struct Spec {
@@ -217,7 +184,6 @@ static void make_stored(const Spec& s, const Logical& L, Stored& S) {
   if (s.slab) { S.slab.shape(s.sk * M, N, N, 0); S.slab.fill(QNAN); }
 }
 
-static Arena arena;
 static std::vector<float> got;
 
 // copies an output back; false on a changed guard / padding word. The logical window lands in `got` at the Mat's own offsets.
@@ -225,7 +191,7 @@ static bool guards_intact(const Mat& m, bool keep) {
   std::vector<float> tmp; std::vector<float>& g = keep ? got : tmp;
   g.resize(m.h.size());
   CK(hipMemcpy(g.data(), m.d, g.size() * 4, hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < g.size(); ++i) if (!m.inside(i) && f_bits(g[i]) != f_bits(m.h[i])) return false;
+  for (size_t i = 0; i < g.size(); ++i) if (!m.inside(i) && !same_bits(g[i], m.h[i])) return false;
   return true;
 }
 
@@ -242,7 +208,7 @@ static Outcome run_one(const Spec& s, const Logical& L, Stored& S, Fam fam, int 
   Outcome o;
   arena.reset();
   Mat* mats[8] = {&S.A, &S.A2, &S.B, &S.B2, &S.C, &S.C2, &S.bias, &S.slab};
-  for (Mat* m : mats) if (m->used) arena.upload(*m);
+  for (Mat* m : mats) if (m->used) upload(*m);
   if (!S.idx.empty()) { S.idx_d = reinterpret_cast<int*>(arena.take(S.idx.size() * 4)); CK(hipMemcpy(S.idx_d, S.idx.data(), S.idx.size() * 4, hipMemcpyHostToDevice)); }
   GemmArgs g{S.A.dev(), S.B.dev(), S.C.dev(), s.bias ? S.bias.dev() : nullptr, s.M, s.N, s.K, s.lda, s.ldb, s.ldc, s.beta, s.sk, nullptr};
   if (s.k1 > 0) { g.A2 = S.A2.dev(); g.B2 = S.B2.dev(); g.k1 = s.k1; }
@@ -258,9 +224,7 @@ static Outcome run_one(const Spec& s, const Logical& L, Stored& S, Fam fam, int 
   CK(hipDeviceSynchronize());
   const int nA = s.n1 > 0 ? s.n1 : s.N;
   const int sk = s.sk > 1 ? s.sk : 1;
-  const double u = std::ldexp(1.0, -24);
-  const double nr = (*x3form ? 6.0 * s.K + 9.0 : (double)s.K) + sk + 2;
-  const double gam = nr * u / (1.0 - nr * u) + (s.K + 2) * std::ldexp(1.0, -52);
+  const double gam = gamma_n((*x3form ? 6.0 * s.K + 9.0 : (double)s.K) + sk + 2) + (s.K + 2) * std::ldexp(1.0, -52);
   for (int part = 0; part < (s.n1 > 0 ? 2 : 1); ++part) {
     const Mat& C = part ? S.C2 : S.C;
     if (!guards_intact(C, true)) fail(o, "stray store (guard or padding of C changed)");
@@ -282,8 +246,6 @@ static Outcome run_one(const Spec& s, const Logical& L, Stored& S, Fam fam, int 
 struct FormStat { double frac = 0, frac_x3 = 0; int cases = 0, fails = 0; };
 static std::map<std::string, FormStat> stats;
 static std::vector<std::string> form_order;
-static bool plan_mode = false;
-static int case_lines = 0, failures = 0;
 
 static std::string describe(const Spec& s) {
   char b[512];
@@ -321,7 +283,7 @@ static void run_case(Spec s) {
       for (int x3 = 0; x3 < 2; ++x3) { ok[x3] = false; res[x3] += std::string(" ") + fname + "=FAIL(precondition: sum |a||b| + |bias| + |C0| >= 2^24)"; }
       continue;
     }
-    if (plan_mode) continue;
+    if (tally.plan_mode) continue;
     Stored S; make_stored(s, L, S);
     for (int x3 = 0; x3 < 2; ++x3) {
       if ((fam == PIECE_A || fam == PIECE_B) && !x3) continue;
@@ -337,12 +299,12 @@ static void run_case(Spec s) {
   }
   for (int x3 = 0; x3 < 2; ++x3) {
     const int want = x3 ? promised : 0;
-    if (!plan_mode && form_seen[x3] != want) { ok[x3] = false; res[x3] += " x3form=FAIL(gemm_x3_form disagrees with the promise)"; }
+    if (!tally.plan_mode && form_seen[x3] != want) { ok[x3] = false; res[x3] += " x3form=FAIL(gemm_x3_form disagrees with the promise)"; }
     static const char* fn[3] = {"exact-kernel", "x3-plain", "x3-GEN"};
     printf("case %4d %s x3=%d->%s(TM=%d) :%s : %s\n", 2 * s.id + x3, describe(s).c_str(), x3, fn[want], launcher_big(s) ? 2 : 1, res[x3].c_str(),
-           ok[x3] ? (plan_mode ? "planned" : "ok") : "FAIL");
-    ++case_lines; ++fs.cases;
-    if (!ok[x3]) { ++failures; ++fs.fails; }
+           ok[x3] ? (tally.plan_mode ? "planned" : "ok") : "FAIL");
+    tally.count(ok[x3]); ++fs.cases;
+    if (!ok[x3]) ++fs.fails;
   }
 }
 
@@ -427,20 +389,11 @@ static void all_cases(bool elig) {
 }
 
 int main(int argc, char** argv) {
-  plan_mode = argc > 1 && std::string(argv[1]) == "--plan";
-  if (!plan_mode) arena.init();
+  tally.args(argc, argv);
+  if (!tally.plan_mode) arena.init();
   all_cases(false);
   all_cases(true);
-  if (plan_mode) {
-    printf("cases %d\n", case_lines);
-    if (failures) { printf("GEMM CHECK PLAN FAILED: %d inputs break the exactness precondition\n", failures); return 1; }
-    printf("GEMM CHECK PLAN OK\n");
-    return 0;
-  }
-  for (const std::string& f : form_order) { const FormStat& fs = stats[f];
+  if (!tally.plan_mode) for (const std::string& f : form_order) { const FormStat& fs = stats[f];
     printf("worst fraction of the bound  %-24s exact kernel %.3f   x3 kernel %.3f   (%d cases, %d failed)\n", f.c_str(), fs.frac, fs.frac_x3, fs.cases, fs.fails); }
-  printf("cases %d\n", case_lines);
-  if (failures) { printf("GEMM CHECK FAILED: %d of %d cases\n", failures, case_lines); return 1; }
-  printf("GEMM CHECK PASSED\n");
-  return 0;
+  return tally.finish("GEMM");
 }

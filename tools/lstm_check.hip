@@ -54,46 +54,27 @@
 //   rows beyond B contributing zero - reproduced on the host from the stored dG and demanded BIT FOR BIT. The array has exactly
 //   ceil(B / rows) rows between its guards: a grid with a row group too many writes into a guard.
 //
-// HARNESS. Inputs sit between 64 words of NaN, outputs between 64 words of 0xDEADBEEF that must survive, in an arena that is NaN wherever no
-// case data lies; pure outputs start as NaN (an element nobody wrote fails its check). Where kx < KX the columns kx..ldx of X are NaN and the
+// HARNESS (tools/kbj_check.h: the arena, the guarded window, the tally). Every array is a window, inputs between NaN and outputs between
+// the bit pattern; pure outputs start as NaN (an element nobody wrote fails its check). Where kx < KX the columns kx..ldx of X are NaN and the
 // weight columns there hold +-1000: the result must see neither. Counters and the error word are zeroed before each launch. Before a
-// recurrence launch the grid must be resident (hipOccupancyMaxActiveBlocksPerMultiprocessor x CUs) and at most 64 workgroups, else the case
-// FAILs without a launch; the step kernel never waits for another workgroup and runs the library's own grid (up to 256). A set error word or
-// any HIP error ends the run at once.
+// recurrence launch the grid must be resident (seq_blocks_per_cu of kbj_lstm_bwd16.h, the library's own occupancy table, x CUs) and at most
+// 64 workgroups, else the case FAILs without a launch; the step kernel never waits for another workgroup and runs the library's own grid
+// (up to 256). A set error word or any HIP error ends the run at once.
 //
 // --plan (no device). Per case: (1) at least 90 % of the double reference's gate pre-activations have |x| <= 3 (a saturated gate hides a wrong
 // recurrent term); (2) the checker passes a host fp32 model of the kernel (plain loops from the Args comments, expf and a division);
 // (3) the checker rejects every mutant of that model, by more than 100 x the bound in at least one element, in every case that exercises the
 // mutated feature (`exercised` below: a rule on the case's parameters, mirrored by tests/test_gpu_lstm_check.py); other cases say n/a.
-#include <hip/hip_runtime.h>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <cstdint>
-#include <cmath>
-#include <vector>
-#include <string>
-#include <algorithm>
 #include <atomic>
 #include <thread>
+#include "kbj_check.h"
 #include "kbj_lstm_seq.h"
 #include "kbj_lstm_bwd16.h"
 
 using namespace kbj;
 
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); fflush(stdout); exit(2); } } while (0)
-
-static inline uint32_t mix(uint32_t x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; }
-static inline uint32_t hash3(uint32_t tag, uint32_t r, uint32_t c) { return mix(mix(mix(tag) + r * 0x9E3779B9u) + c * 0x85EBCA6Bu + 1u); }
-static inline float bits_f(uint32_t b) { float f; memcpy(&f, &b, 4); return f; }
-static inline uint32_t f_bits(float f) { uint32_t b; memcpy(&b, &f, 4); return b; }
-static const float PATTERN = bits_f(0xDEADBEEFu);
-static const float QNAN = bits_f(0x7FC00000u);
-static float val_real(uint32_t h) { return (float)((int)(h >> 8) - (1 << 23)) * (1.0f / (float)(1 << 23)); }   // uniform(-1, 1) on a 24-bit grid
 static void fill(std::vector<float>& v, size_t n, uint32_t tag, float scale) { v.resize(n); for (size_t i = 0; i < n; ++i) v[i] = scale * val_real(hash3(tag, (uint32_t)(i >> 16), (uint32_t)(i & 0xFFFF))); }
 
-static const double U = std::ldexp(1.0, -24);
-static double gamma_n(int n) { return n * U / (1.0 - n * U); }
 constexpr double C_SIG = 4.0, C_TANH = 9.0, REF_ERR = 1e-9, SECOND_ORDER = 1.01, FLUSH = 1e-35;
 static double sigm(double x) { return 1.0 / (1.0 + std::exp(-x)); }
 
@@ -268,7 +249,7 @@ struct Chk {
       worst[cat] = ratio;
     }
   }
-  void exact(int cat, float got, float want, int t, int r, int gate, int unit) { upd(cat, f_bits(got) == f_bits(want) ? 0.0 : INFINITY, 0.0, t, r, gate, unit); }
+  void exact(int cat, float got, float want, int t, int r, int gate, int unit) { upd(cat, same_bits(got, want) ? 0.0 : INFINITY, 0.0, t, r, gate, unit); }
   double max_ratio() const { double m = 0; for (int i = 0; i < NCAT; ++i) m = std::max(m, worst[i]); return m; }
   void merge(const Chk& o) {
     if (o.max_ratio() > 1.0 && max_ratio() <= 1.0) memcpy(why, o.why, sizeof why);
@@ -365,10 +346,8 @@ static double make_bwd(Bwd& q, int H, int B, int T, int rows, bool part, int kee
   fill(q.db0, (size_t)4 * H, id * 16u + 10, 1.0f);
   return f.alive;
 }
-static float chain_rows(const float* v, int n) { float s = 0; for (int i = 0; i < n; ++i) s += v[i]; return s; }
-static float tree_rows(const float* v, int n) { if (n == 1) return v[0]; const int h = n / 2; return tree_rows(v, h) + tree_rows(v + h, n - h); }
-// per-row-group bias partials from a stored dG, in the documented order (tree = false) or with the rows added pairwise
-static void db_part_of(const Bwd& q, const std::vector<float>& dG, bool tree, std::vector<float>& out) {
+// per-row-group bias partials from a stored dG, in the documented order or with the rows added pairwise
+static void db_part_of(const Bwd& q, const std::vector<float>& dG, bool pairwise, std::vector<float>& out) {
   const int H = q.H, B = q.B, T = q.T, R = q.rows;
   out.assign((size_t)q.nrg() * 4 * H, 0.0f);
   par_for(q.nrg(), [&](int rg) {
@@ -379,7 +358,7 @@ static void db_part_of(const Bwd& q, const std::vector<float>& dG, bool tree, st
         if (r < B) for (int t = T - 1; t >= 0; --t) s += dG[((size_t)t * B + r) * 4 * H + j];
         col[i] = s;
       }
-      out[(size_t)rg * 4 * H + j] = tree ? tree_rows(col.data(), R) : chain_rows(col.data(), R);
+      out[(size_t)rg * 4 * H + j] = pairwise ? tree(col.data(), R, 1) : chain(col.data(), R, 1);
     }
   });
 }
@@ -456,56 +435,13 @@ static Chk check_bwd(const Bwd& q) {
 }
 
 // ---- device side ---------------------------------------------------------------------------------------------------------------------------
-constexpr int GUARD = 64;
-struct Arena {
-  static constexpr size_t SLACK = (size_t)4 << 20, CAP = (size_t)96 << 20;
-  char* base = nullptr; size_t used = SLACK, high = SLACK;
-  void init() { CK(hipMalloc(reinterpret_cast<void**>(&base), CAP)); CK(hipMemset(base, 0xFF, CAP)); }
-  void reset() { if (high > SLACK) CK(hipMemset(base + SLACK, 0xFF, high - SLACK)); used = high = SLACK; }
-  float* take(size_t words) {
-    used = (used + 255) / 256 * 256;
-    if (used + words * 4 > CAP - SLACK) { printf("arena too small\n"); exit(2); }
-    float* p = reinterpret_cast<float*>(base + used); used += words * 4; high = used; return p;
-  }
-};
-static Arena arena;
-struct Win { float* d = nullptr; size_t n = 0; };
-// upload `v` between guards: NaN around an input, 0xDEADBEEF around an output
-static Win put(const std::vector<float>& v, bool output) {
-  std::vector<float> img(v.size() + 2 * GUARD, output ? PATTERN : QNAN);
-  std::copy(v.begin(), v.end(), img.begin() + GUARD);
-  Win w; w.n = v.size(); w.d = arena.take(img.size()) + GUARD;
-  CK(hipMemcpy(w.d - GUARD, img.data(), img.size() * 4, hipMemcpyHostToDevice));
-  return w;
-}
-static bool get(const Win& w, std::vector<float>& v) {   // false: a guard word changed
-  std::vector<float> img(w.n + 2 * GUARD);
-  CK(hipMemcpy(img.data(), w.d - GUARD, img.size() * 4, hipMemcpyDeviceToHost));
-  bool ok = true;
-  for (int i = 0; i < GUARD; ++i) ok = ok && f_bits(img[i]) == 0xDEADBEEFu && f_bits(img[GUARD + w.n + i]) == 0xDEADBEEFu;
-  v.assign(img.begin() + GUARD, img.begin() + GUARD + w.n);
-  return ok;
-}
+static Arena arena((size_t)96 << 20);
 static int n_cus = 0; static unsigned timeout_ticks = 0; static unsigned* sync_words = nullptr;   // [256 counters][error word]
-enum DevKernel { DK_FWD_PLAIN, DK_FWD_FUSED, DK_FWD_OBS, DK_BWD32, DK_BWD16 };
-static int blocks_per_cu(int which, int H) {
-  int n = 0;
-  dispatch_hidden(H, [&](auto hc) {
-    constexpr int HC = decltype(hc)::value, TH = 256 * SEQ_UW;
-    if (which == DK_FWD_PLAIN) CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, lstm_seq_fwd_kernel<HC, SEQ_UW, false, HC>, TH, 0));
-    if constexpr (HC <= SEQ_FUSED_MAX_H) {
-      if (which == DK_FWD_FUSED) CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, lstm_seq_fwd_kernel<HC, SEQ_UW, true, HC>, TH, 0));
-      if (which == DK_FWD_OBS) CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, lstm_seq_fwd_kernel<HC, SEQ_UW, true, KBJ_LD_ACTOR>, TH, 0));
-      if (which == DK_BWD32) CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, lstm_seq_bwd_kernel<HC, SEQ_UW>, TH, 0));
-      if (which == DK_BWD16) CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, lstm_seq_bwd16_kernel<HC>, BWD16_NTH, 0));
-    } else if (which == DK_BWD32) CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, lstm_seq_bwd_wide_kernel<HC, SEQ_UW>, TH, 0));
-    return true;
-  });
-  return n;
-}
-static bool resident(int which, int H, int grid, char* why, size_t nwhy) {
+static bool resident(SeqKernelKind kind, int H, int grid, char* why, size_t nwhy) {
   if (grid > 64) { snprintf(why, nwhy, "grid %d above the tool's 64 workgroups: not launched", grid); return false; }
-  const long slots = (long)blocks_per_cu(which, H) * n_cus;
+  int per_cu = 0;
+  if (seq_blocks_per_cu(kind, H, &per_cu) != hipSuccess) per_cu = 0;   // not built for this hidden size: no slots
+  const long slots = (long)per_cu * n_cus;
   if (grid > slots) { snprintf(why, nwhy, "grid %d not resident (%ld slots): not launched", grid, slots); return false; }
   return true;
 }
@@ -524,38 +460,38 @@ static void finish_launch(const char* kernel, const char* what) {
 // runs the case on the device into p's outputs; false (with why) if it was not launched or a guard changed
 static bool device_fwd(Fwd& p, const char* kernel, const char* what, char* why, size_t nwhy) {
   const int H = p.H, B = p.B, T = p.T;
-  if (!resident(p.form == PLAIN ? DK_FWD_PLAIN : p.form == FUSED ? DK_FWD_FUSED : DK_FWD_OBS, H, seq_grid(H, B), why, nwhy)) return false;
+  if (!resident(p.form == PLAIN ? SEQ_KIND_FWD_PLAIN : p.form == FUSED ? SEQ_KIND_FWD_FUSED : SEQ_KIND_FWD_OBS, H, seq_grid(H, B), why, nwhy)) return false;
   arena.reset();
   std::vector<float> g0 = p.form == PLAIN ? p.Gin : std::vector<float>((size_t)T * B * 4 * H, QNAN), hm((size_t)(T + 1) * p.bh(), QNAN), cm = hm, out((size_t)T * p.bh(), QNAN);
   std::copy(p.H0.begin(), p.H0.end(), hm.begin()); std::copy(p.C0.begin(), p.C0.end(), cm.begin());
-  const Win G = put(g0, true), Hm = put(hm, true), Cm = put(cm, true), Hout = put(out, true), TanhC = put(out, true), Whh = put(p.Whh, false), keep = put(p.keep, false);
+  const Win<float> G = arena.put(g0, true), Hm = arena.put(hm, true), Cm = arena.put(cm, true), Hout = arena.put(out, true), TanhC = arena.put(out, true), Whh = arena.put(p.Whh, false), keep = arena.put(p.keep, false);
   SeqFwdArgs a{};
   a.G = G.d; a.Whh = Whh.d; a.Hm = Hm.d; a.Cm = Cm.d; a.Hout = Hout.d; a.TanhC = TanhC.d; a.keep = keep.d;
   a.counters = sync_words; a.err = sync_words + 256; a.T = T; a.B = B; a.stamps = nullptr; a.timeout_ticks = timeout_ticks;
   if (p.form != PLAIN) {
-    a.X = put(p.X, false).d; a.Wih = put(p.Wih, false).d; a.bias = put(p.bias, false).d;
+    a.X = arena.put(p.X, false).d; a.Wih = arena.put(p.Wih, false).d; a.bias = arena.put(p.bias, false).d;
     if (p.form == OBS) { a.ldx = a.ldw = p.ld; a.kx = p.kx; }
   }
   prepare_launch();
   if (!seq_fwd_launch(0, H, a, 0)) { snprintf(why, nwhy, "no kernel for this hidden size"); return false; }
   finish_launch(kernel, what);
-  bool ok = get(G, p.G); ok = get(Hm, p.Hm) && ok; ok = get(Cm, p.Cm) && ok; ok = get(Hout, p.Hout) && ok; ok = get(TanhC, p.TanhC) && ok;
+  bool ok = arena.get(G, p.G); ok = arena.get(Hm, p.Hm) && ok; ok = arena.get(Cm, p.Cm) && ok; ok = arena.get(Hout, p.Hout) && ok; ok = arena.get(TanhC, p.TanhC) && ok;
   if (!ok) snprintf(why, nwhy, "stray store (guard changed)");
   return ok;
 }
 static bool device_step(Fwd& p, const char* kernel, const char* what, char* why, size_t nwhy) {
   const int H = p.H;
   arena.reset();
-  const Win Hin = put(p.H0, true), C = put(p.C0, true), Hout = put(std::vector<float>(p.bh(), QNAN), true);   // Hin between output guards too: it must come back unchanged
+  const Win<float> Hin = arena.put(p.H0, true), C = arena.put(p.C0, true), Hout = arena.put(std::vector<float>(p.bh(), QNAN), true);   // Hin between output guards too: it must come back unchanged
   StepArgs a{};
-  a.X = put(p.X, false).d; a.ldx = p.ld; a.kx = p.form == OBS ? p.kx : 0;
-  a.Wih = put(p.Wih, false).d; a.ldw = p.ld; a.Whh = put(p.Whh, false).d; a.bias = put(p.bias, false).d;
+  a.X = arena.put(p.X, false).d; a.ldx = p.ld; a.kx = p.form == OBS ? p.kx : 0;
+  a.Wih = arena.put(p.Wih, false).d; a.ldw = p.ld; a.Whh = arena.put(p.Whh, false).d; a.bias = arena.put(p.bias, false).d;
   a.Hin = Hin.d; a.Hout = Hout.d; a.C = C.d; a.M = p.B;
   prepare_launch();
   if (!lstm_step_launch(0, H, a)) { snprintf(why, nwhy, "no kernel for this hidden size"); return false; }
   finish_launch(kernel, what);
   std::vector<float> hin, c;
-  bool ok = get(Hin, hin); ok = get(C, c) && ok; ok = get(Hout, p.Hout) && ok;
+  bool ok = arena.get(Hin, hin); ok = arena.get(C, c) && ok; ok = arena.get(Hout, p.Hout) && ok;
   p.Hm.assign(2 * p.bh(), QNAN); p.Cm = p.Hm;
   std::copy(hin.begin(), hin.end(), p.Hm.begin()); std::copy(c.begin(), c.end(), p.Cm.begin() + p.bh());
   if (!ok) snprintf(why, nwhy, "stray store (guard changed)");
@@ -563,26 +499,24 @@ static bool device_step(Fwd& p, const char* kernel, const char* what, char* why,
 }
 static bool device_bwd(Bwd& q, const char* kernel, const char* what, char* why, size_t nwhy) {
   const int H = q.H, B = q.B, T = q.T; const bool t16 = q.rows == BWD16_ROWS;
-  if (!resident(t16 ? DK_BWD16 : DK_BWD32, H, t16 ? seq_bwd16_grid(H, B) : seq_grid(H, B), why, nwhy)) return false;
+  if (!resident(t16 ? SEQ_KIND_BWD16 : SEQ_KIND_BWD32, H, t16 ? seq_bwd16_grid(H, B) : seq_grid(H, B), why, nwhy)) return false;
   arena.reset();
-  const Win dG = put(std::vector<float>((size_t)T * B * 4 * H, QNAN), true), db = put(q.db0, true), part = put(std::vector<float>((size_t)q.nrg() * 4 * H, QNAN), true);
+  const Win<float> dG = arena.put(std::vector<float>((size_t)T * B * 4 * H, QNAN), true), db = arena.put(q.db0, true), part = arena.put(std::vector<float>((size_t)q.nrg() * 4 * H, QNAN), true);
   SeqBwdArgs a{};
-  a.Gact = put(q.Gact, false).d; a.TanhC = put(q.TanhC, false).d; a.Cm = put(q.Cm, false).d; a.dHabove = put(q.dHa, false).d;
-  a.keep = put(q.keep, false).d; a.Whh = put(q.Whh, false).d; a.dG = dG.d;
+  a.Gact = arena.put(q.Gact, false).d; a.TanhC = arena.put(q.TanhC, false).d; a.Cm = arena.put(q.Cm, false).d; a.dHabove = arena.put(q.dHa, false).d;
+  a.keep = arena.put(q.keep, false).d; a.Whh = arena.put(q.Whh, false).d; a.dG = dG.d;
   a.counters = sync_words; a.err = sync_words + 256; a.T = T; a.B = B;
   a.db = db.d; a.db_part = q.part ? part.d : nullptr; a.timeout_ticks = timeout_ticks; a.stamps = nullptr;
   prepare_launch();
   if (!(t16 ? seq_bwd16_launch(0, H, a, 0) : seq_bwd_launch(0, H, a))) { snprintf(why, nwhy, "no kernel for this hidden size"); return false; }
   finish_launch(kernel, what);
-  bool ok = get(dG, q.dG); ok = get(db, q.db) && ok; ok = get(part, q.db_part) && ok;
-  if (q.part) for (int j = 0; j < 4 * H; ++j) ok = ok && f_bits(q.db[j]) == f_bits(q.db0[j]);   // deterministic mode leaves db to the ordered second stage
+  bool ok = arena.get(dG, q.dG); ok = arena.get(db, q.db) && ok; ok = arena.get(part, q.db_part) && ok;
+  if (q.part) for (int j = 0; j < 4 * H; ++j) ok = ok && same_bits(q.db[j], q.db0[j]);   // deterministic mode leaves db to the ordered second stage
   if (!ok) snprintf(why, nwhy, "stray store (guard or, in deterministic mode, db changed)");
   return ok;
 }
 
 // ---- driver ------------------------------------------------------------------------------------------------------------------------------
-static bool plan_mode = false;
-static int cases = 0, failures = 0;
 static double worst_frac[8][NCAT], worst_free[8], worst_tanh_u = 0;   // per kernel name
 static std::vector<std::string> kernel_names;
 static int kernel_index(const char* k) { for (size_t i = 0; i < kernel_names.size(); ++i) if (kernel_names[i] == k) return (int)i; kernel_names.push_back(k); return (int)kernel_names.size() - 1; }
@@ -598,7 +532,7 @@ static void report_device(const char* kernel, const char* what, bool ran, const 
   if (ran) { for (int c = 0; c < NCAT; ++c) worst_frac[ki][c] = std::max(worst_frac[ki][c], k.worst[c]); worst_tanh_u = std::max(worst_tanh_u, k.tanh_pure_u); }
   char fr[40] = ""; if (free_err >= 0) { snprintf(fr, sizeof fr, " free %.3g", free_err); worst_free[ki] = std::max(worst_free[ki], free_err); }
   printf("case %-10s %-40s : %s%s%s\n", kernel, what, ok ? "ok" : "FAIL ", ok ? fractions(k).c_str() : (ran ? k.why : why), ok ? fr : "");
-  ++cases; if (!ok) ++failures;
+  tally.count(ok);
 }
 // plan mode: alive gates, model accepted, mutants rejected
 template <class P, class Model, class Check>
@@ -620,7 +554,7 @@ static void report_plan(const char* kernel, const char* what, int fam, P& prob, 
     else { ok = false; snprintf(b, sizeof b, " %s=FAIL (passes within %.3g x bound)", MUTN[m], r); line += b; }
   }
   printf("case %-10s %-40s : %s %s\n", kernel, what, ok ? "planned" : "FAIL", line.c_str());
-  ++cases; if (!ok) ++failures;
+  tally.count(ok);
 }
 
 static uint32_t next_id = 1;
@@ -632,7 +566,7 @@ static void fwd_case(int form, int H, int B, int T, int kx, int keep) {
   Fwd p; make_fwd(p, H, B, T, form, kx, keep, next_id++);
   FwdRef ref; ref_fwd(p, ref);
   const bool kx_short = p.kx < p.KX;
-  if (plan_mode) { report_plan(KN[form], what, FAM_FWD, p, ref.alive, model_fwd, check_fwd, T, keep, B, kx_short, false); return; }
+  if (tally.plan_mode) { report_plan(KN[form], what, FAM_FWD, p, ref.alive, model_fwd, check_fwd, T, keep, B, kx_short, false); return; }
   char why[160] = "";
   const bool ran = device_fwd(p, KN[form], what, why, sizeof why);
   report_device(KN[form], what, ran, ran ? check_fwd(p) : Chk(), why, ran ? free_running_error(p, ref) : -1.0);
@@ -645,7 +579,7 @@ static void bwd_case(int rows, int H, int B, int T, bool part, int keep) {
   const char* kernel = rows == BWD16_ROWS ? "bwd16" : (H <= SEQ_FUSED_MAX_H ? "bwd" : "bwd_wide");
   char what[96]; snprintf(what, sizeof what, "H=%d B=%d T=%d bias=%s keep=%s", H, B, T, part ? "part" : "atomic", KEEPN[keep]);
   Bwd q; const double alive = make_bwd(q, H, B, T, rows, part, keep, next_id++);
-  if (plan_mode) { report_plan(kernel, what, FAM_BWD, q, alive, model_bwd, check_bwd, T, keep, B, false, part); return; }
+  if (tally.plan_mode) { report_plan(kernel, what, FAM_BWD, q, alive, model_bwd, check_bwd, T, keep, B, false, part); return; }
   char why[160] = "";
   const bool ran = device_bwd(q, kernel, what, why, sizeof why);
   report_device(kernel, what, ran, ran ? check_bwd(q) : Chk(), why, -1.0);
@@ -663,15 +597,15 @@ static void step_case(int H, int M, bool obs) {
   else snprintf(what, sizeof what, "H=%d M=%d grid=%d", H, M, lstm_step_grid(H, M));
   Fwd p; make_fwd(p, H, M, 1, obs ? OBS : FUSED, obs ? KBJ_NOBS_ACTOR : 0, K_ONES, next_id++);
   FwdRef ref; ref_fwd(p, ref);
-  if (plan_mode) { report_plan(kernel, what, FAM_STEP, p, ref.alive, model_step, check_step, 1, K_ONES, M, obs, false); return; }
+  if (tally.plan_mode) { report_plan(kernel, what, FAM_STEP, p, ref.alive, model_step, check_step, 1, K_ONES, M, obs, false); return; }
   char why[160] = "";
   const bool ran = device_step(p, kernel, what, why, sizeof why);
   report_device(kernel, what, ran, ran ? check_step(p) : Chk(), why, -1.0);
 }
 
 int main(int argc, char** argv) {
-  plan_mode = argc > 1 && std::string(argv[1]) == "--plan";
-  if (!plan_mode) {
+  tally.args(argc, argv);
+  if (!tally.plan_mode) {
     int dev = 0, wall_khz = 0;
     CK(hipGetDevice(&dev));
     CK(hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -698,8 +632,7 @@ int main(int argc, char** argv) {
   // step kernel: one row group per workgroup, then 34 row groups on 32 chunks and 130 on 128 (ragged last group)
   for (int H = 64; H <= SEQ_FUSED_MAX_H; H += 64) for (int obs = 0; obs < 2; ++obs) for (int M : {1, 33}) step_case(H, M, obs != 0);
   step_case(256, 1061, false); step_case(64, 4129, false);
-  printf("cases %d\n", cases);
-  if (!plan_mode) {
+  if (!tally.plan_mode) {
     for (size_t i = 0; i < kernel_names.size(); ++i) {
       printf("worst fraction of the bound, %-10s:", kernel_names[i].c_str());
       for (int c = 0; c < NCAT; ++c) if (worst_frac[i][c] > 0 || c == C_LINK) printf(" %s %.3f", CATN[c], worst_frac[i][c]);
@@ -708,7 +641,5 @@ int main(int argc, char** argv) {
     }
     printf("seq_tanh worst observed error %.2f u (derived C_tanh = %.0f u, C_sig = %.0f u)\n", worst_tanh_u, C_TANH, C_SIG);
   }
-  if (failures) { printf("LSTM CHECK FAILED: %d of %d cases\n", failures, cases); return 1; }
-  printf(plan_mode ? "LSTM CHECK PLAN OK\n" : "LSTM CHECK PASSED\n");
-  return 0;
+  return tally.finish("LSTM");
 }

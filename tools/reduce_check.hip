@@ -14,28 +14,15 @@
 // order - or in any order that a tree and a chain cannot be told apart by - could not pass by accident. The seed of a case is advanced until
 // that holds (at most 64 times, else the case fails); with fewer than three partials a tree IS the chain, those cases say "order n/a".
 //
-// HARNESS. Partials sit in a NaN-filled allocation (a partial read from outside the array, or from a split-K slice that the GEMM would not
-// have written, poisons the sum if it is added), outputs in a window with 64 words of bit pattern 0xDEADBEEF (fp64: twice) on both sides
-// and in the padding between N and ldc, which must be unchanged after the launch.
-#include <hip/hip_runtime.h>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <cstdint>
-#include <cmath>
-#include <vector>
-#include <string>
+// HARNESS (tools/kbj_check.h: the arena, the guarded window, the tally). Partials and split-K slabs are input windows: a partial read from
+// outside the array, or from a split-K slice that the GEMM would not have written, poisons the sum if it is added. Outputs are output
+// windows; the padding between N and ldc holds the bit pattern too and must be unchanged after the launch.
+#include "kbj_check.h"
 #include "kbj_gemm.h"
 #include "kbj_nn_kernels.h"
 
-thread_local kbj_ctx* kbj_prof_ctx = nullptr;
-thread_local std::string kbj_global_error;
 using namespace kbj;
 
-#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); fflush(stdout); exit(2); } } while (0)
-
-static inline uint32_t mix(uint32_t x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; }
-static inline uint32_t hash3(uint32_t tag, uint32_t r, uint32_t c) { return mix(mix(mix(tag) + r * 0x9E3779B9u) + c * 0x85EBCA6Bu + 1u); }
 // sign * 2^e * (1 + fraction), e in [-20, 20]
 static double value(uint32_t tag, uint32_t r, uint32_t c) {
   const uint32_t h = hash3(tag, r, c), h2 = mix(h ^ 0xA5A5A5A5u);
@@ -43,27 +30,12 @@ static double value(uint32_t tag, uint32_t r, uint32_t c) {
   const double m = 1.0 + (double)(h & 0x7FFFFFu) / 8388608.0 + (double)(mix(h2) >> 9) / 70368744177664.0;   // 46 fraction bits (fp32 cases round them)
   return std::ldexp((h >> 31) ? -m : m, e);
 }
-template <class T> static bool same_bits(T a, T b) { return memcmp(&a, &b, sizeof(T)) == 0; }
 
-// the documented order, and the order that must NOT pass for it
-template <class T> static T chain(const T* v, size_t n, size_t stride) { T s = 0; for (size_t i = 0; i < n; ++i) s += v[i * stride]; return s; }
-template <class T> static T tree(const T* v, size_t n, size_t stride) {
-  if (n == 0) return 0;
-  if (n == 1) return v[0];
-  const size_t h = n / 2;
-  return tree(v, h, stride) + tree(v + h * stride, n - h, stride);
-}
-
-static int failures = 0, cases = 0;
-static bool plan_mode = false;
+static Arena arena((size_t)16 << 20);
 static void report(const char* kernel, const std::string& what, bool order_applies, bool ok, const char* why) {
-  printf("case %-22s %-44s %s : %s%s\n", kernel, what.c_str(), order_applies ? "order matters" : "order n/a    ", ok ? (plan_mode ? "planned" : "ok") : "FAIL ", ok ? "" : why);
-  ++cases; if (!ok) ++failures;
+  printf("case %-22s %-44s %s : %s%s\n", kernel, what.c_str(), order_applies ? "order matters" : "order n/a    ", ok ? (tally.plan_mode ? "planned" : "ok") : "FAIL ", ok ? "" : why);
+  tally.count(ok);
 }
-
-constexpr int GUARD = 64;
-template <class T> static T pattern() { uint64_t b = 0xDEADBEEFDEADBEEFull; T t; memcpy(&t, &b, sizeof(T)); return t; }
-template <class T> static T qnan() { return (T)std::nan(""); }
 
 // ---- column-wise second stages: reduce_rows (fp32, n columns) and reduce_double (fp64, w <= 64 columns) --------------------------------------
 template <class T, class Launch>
@@ -85,26 +57,16 @@ static void column_case(const char* kernel, int nparts, int n, uint32_t id, Laun
     if (found) break;
   }
   if (!found) { report(kernel, what, true, false, "no input found whose pairwise sum differs from the chain"); return; }
-  if (plan_mode) { report(kernel, what, order_applies, true, ""); return; }
-  const size_t slack = 4096;   // NaN behind the partials
-  T *part_d, *out_d;
-  CK(hipMalloc(reinterpret_cast<void**>(&part_d), (part.size() + slack) * sizeof(T)));
-  std::vector<T> img(part.size() + slack, qnan<T>());
-  std::copy(part.begin(), part.end(), img.begin());
-  CK(hipMemcpy(part_d, img.data(), img.size() * sizeof(T), hipMemcpyHostToDevice));
-  std::vector<T> oimg(n + 2 * GUARD, pattern<T>());
-  std::copy(out0.begin(), out0.end(), oimg.begin() + GUARD);
-  CK(hipMalloc(reinterpret_cast<void**>(&out_d), oimg.size() * sizeof(T)));
-  CK(hipMemcpy(out_d, oimg.data(), oimg.size() * sizeof(T), hipMemcpyHostToDevice));
-  launch(part_d, nparts, n, out_d + GUARD);
+  if (tally.plan_mode) { report(kernel, what, order_applies, true, ""); return; }
+  arena.reset();
+  const Win<T> part_w = arena.put(part, false), out_w = arena.put(out0, true);
+  launch(part_w.d, nparts, n, out_w.d);
   CK(hipGetLastError());
   CK(hipDeviceSynchronize());
-  std::vector<T> got(oimg.size());
-  CK(hipMemcpy(got.data(), out_d, got.size() * sizeof(T), hipMemcpyDeviceToHost));
-  CK(hipFree(part_d)); CK(hipFree(out_d));
-  bool guards = true, exact = true;
-  for (int i = 0; i < GUARD; ++i) guards = guards && same_bits(got[i], pattern<T>()) && same_bits(got[GUARD + n + i], pattern<T>());
-  for (int c = 0; c < n; ++c) exact = exact && same_bits(got[GUARD + c], ref[c]);
+  std::vector<T> got;
+  const bool guards = arena.get(out_w, got);
+  bool exact = true;
+  for (int c = 0; c < n; ++c) exact = exact && same_bits(got[c], ref[c]);
   report(kernel, what, order_applies, guards && exact, !guards ? "stray store (guard changed)" : "differs from the chain in slice order");
 }
 
@@ -119,7 +81,7 @@ static void splitk_case(int M, int N, int K, int sk, int n1, int ldc, int ldc2, 
   std::vector<float> slab((size_t)sk * MN), c0(MN), ref(MN);
   uint32_t seed = 0x40000000u + id * 64u; bool found = !order_applies;
   for (int attempt = 0; attempt < 64; ++attempt, ++seed) {
-    for (int ks = 0; ks < sk; ++ks) for (size_t i = 0; i < MN; ++i) slab[ks * MN + i] = ks < nks ? (float)value(seed * 2u, ks, (uint32_t)i) : qnan<float>();
+    for (int ks = 0; ks < sk; ++ks) for (size_t i = 0; i < MN; ++i) slab[ks * MN + i] = ks < nks ? (float)value(seed * 2u, ks, (uint32_t)i) : QNAN;
     bool differs = false;
     for (size_t i = 0; i < MN; ++i) {
       c0[i] = (float)value(seed * 2u + 1u, 0, (uint32_t)i);
@@ -131,36 +93,29 @@ static void splitk_case(int M, int N, int K, int sk, int n1, int ldc, int ldc2, 
     if (found) break;
   }
   if (!found) { report("splitk_reduce", what, true, false, "no input found whose pairwise sum differs from the chain"); return; }
-  if (plan_mode) { report("splitk_reduce", what, order_applies, true, ""); return; }
-  // C [M][ldc] (columns < nA), C2 [M][ldc2] (the second problem's nB columns): guards around, pattern in the padding
-  const size_t slack = 4096;
-  std::vector<float> simg(slab.size() + slack, qnan<float>());
-  std::copy(slab.begin(), slab.end(), simg.begin());
-  std::vector<float> cimg((size_t)M * ldc + 2 * GUARD, pattern<float>()), c2img(nB ? (size_t)M * ldc2 + 2 * GUARD : 0, pattern<float>());
+  if (tally.plan_mode) { report("splitk_reduce", what, order_applies, true, ""); return; }
+  // C [M][ldc] (columns < nA), C2 [M][ldc2] (the second problem's nB columns): pattern in the padding
+  std::vector<float> cimg((size_t)M * ldc, PATTERN), c2img((size_t)M * ldc2 * (nB > 0), PATTERN);
   for (int m = 0; m < M; ++m) for (int n = 0; n < N; ++n) {
-    if (n < nA) cimg[GUARD + (size_t)m * ldc + n] = c0[(size_t)m * N + n];
-    else c2img[GUARD + (size_t)m * ldc2 + (n - nA)] = c0[(size_t)m * N + n];
+    if (n < nA) cimg[(size_t)m * ldc + n] = c0[(size_t)m * N + n];
+    else c2img[(size_t)m * ldc2 + (n - nA)] = c0[(size_t)m * N + n];
   }
-  float *slab_d, *c_d, *c2_d = nullptr;
-  CK(hipMalloc(reinterpret_cast<void**>(&slab_d), simg.size() * 4)); CK(hipMemcpy(slab_d, simg.data(), simg.size() * 4, hipMemcpyHostToDevice));
-  CK(hipMalloc(reinterpret_cast<void**>(&c_d), cimg.size() * 4)); CK(hipMemcpy(c_d, cimg.data(), cimg.size() * 4, hipMemcpyHostToDevice));
-  if (nB) { CK(hipMalloc(reinterpret_cast<void**>(&c2_d), c2img.size() * 4)); CK(hipMemcpy(c2_d, c2img.data(), c2img.size() * 4, hipMemcpyHostToDevice)); }
-  GemmArgs g{nullptr, nullptr, c_d + GUARD, nullptr, M, N, K, 0, 0, ldc, 1, sk, nullptr};
-  if (nB) { g.C2 = c2_d + GUARD; g.n1 = n1; g.ldc2 = ldc2; }
-  g.skws = slab_d;
+  arena.reset();
+  const Win<float> slab_w = arena.put(slab, false), c_w = arena.put(cimg, true), c2_w = arena.put(c2img, true);
+  GemmArgs g{nullptr, nullptr, c_w.d, nullptr, M, N, K, 0, 0, ldc, 1, sk, nullptr};
+  if (nB) { g.C2 = c2_w.d; g.n1 = n1; g.ldc2 = ldc2; }
+  g.skws = slab_w.d;
   splitk_reduce_launch(0, g, sk);
   CK(hipGetLastError());
   CK(hipDeviceSynchronize());
-  std::vector<float> got(cimg.size()), got2(c2img.size());
-  CK(hipMemcpy(got.data(), c_d, got.size() * 4, hipMemcpyDeviceToHost));
-  if (nB) CK(hipMemcpy(got2.data(), c2_d, got2.size() * 4, hipMemcpyDeviceToHost));
-  CK(hipFree(slab_d)); CK(hipFree(c_d)); if (c2_d) CK(hipFree(c2_d));
-  bool guards = true, exact = true;
+  std::vector<float> got, got2;
+  bool guards = arena.get(c_w, got), exact = true;
+  guards = arena.get(c2_w, got2) && guards;
   auto scan = [&](const std::vector<float>& gimg, const std::vector<float>& img, int ld, int cols, int col0) {
     for (size_t i = 0; i < gimg.size(); ++i) {
-      const bool in = i >= (size_t)GUARD && i < (size_t)GUARD + (size_t)M * ld && (int)((i - GUARD) % ld) < cols;
-      if (!in) guards = guards && same_bits(gimg[i], img[i]);
-      else { const size_t m = (i - GUARD) / ld, n = (i - GUARD) % ld; exact = exact && same_bits(gimg[i], ref[m * N + col0 + n]); }
+      const size_t m = i / ld, n = i % ld;
+      if ((int)n >= cols) guards = guards && same_bits(gimg[i], img[i]);
+      else exact = exact && same_bits(gimg[i], ref[m * N + col0 + n]);
     }
   };
   scan(got, cimg, ldc, nA, 0);
@@ -169,7 +124,8 @@ static void splitk_case(int M, int N, int K, int sk, int n1, int ldc, int ldc2, 
 }
 
 int main(int argc, char** argv) {
-  plan_mode = argc > 1 && std::string(argv[1]) == "--plan";
+  tally.args(argc, argv);
+  if (!tally.plan_mode) arena.init();
   // reduce_rows: one and several column blocks, ragged widths, one to 512 partial rows (the call sites: 16 / 32 row groups x H or 4H columns,
   // 512 rows x 1 / 40 columns)
   static const int RR[7][2] = {{1, 1}, {16, 256}, {32, 1024}, {33, 257}, {512, 1}, {512, 40}, {511, 65}};
@@ -188,9 +144,5 @@ int main(int argc, char** argv) {
   splitk_case(70, 130, 33, 7, 0, 133, 0, id++);          // per = 32: two written (the last one k), five empty
   splitk_case(70, 130, 96 * 24, 24, 64, 72, 67, id++);   // paired: columns >= n1 = 64 go to C2 with its own, unaligned leading dimension
   splitk_case(128, 256, 96 * 2, 2, 128, 128, 140, id++);
-  printf("cases %d\n", cases);
-  if (failures) { printf("REDUCE CHECK FAILED: %d of %d cases\n", failures, cases); return 1; }
-  if (plan_mode) { printf("REDUCE CHECK PLAN OK\n"); return 0; }
-  printf("REDUCE CHECK PASSED\n");
-  return 0;
+  return tally.finish("REDUCE");
 }
