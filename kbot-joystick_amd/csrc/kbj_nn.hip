@@ -648,23 +648,22 @@ int policy_nets(kbj_ctx* ctx, hipStream_t s, const float* params_d, int net_lo, 
       }
       CellFwdArgs2 ca;
       ca.a[0] = CellFwdArgs{G, cc, h, cc, nullptr, nullptr, nullptr, nullptr, cnt, H};
-      hipLaunchKernelGGL(lstm_cell_fwd_kernel, dim3((cnt * H + 255) / 256, 1), dim3(256), 0, s, ca);
+      lstm_cell_fwd_launch(s, ca, 1);
       x = h;
     }
     if (n == 3) continue;  // the mirrored critic's value is only needed under the gradient; at rollout time only its carry advances
     if (n == 0) {   // output projection + low-pass + sample + log-prob as one launch (the chain env -> actor -> env waits for it)
-      hipLaunchKernelGGL(actor_head_fused_kernel, dim3((cnt + HEAD_ENVS * HEAD_WAVES - 1) / (HEAD_ENVS * HEAD_WAVES)), dim3(64 * HEAD_WAVES), 0, s, x, H,
-                         params_d + o.w_out, params_d + o.b_out, obs, carry->lpf_d + (size_t)n0 * KBJ_NU, w.joint_bias_d, hp, seed, (uint32_t)(c.env_id_offset + n0),
-                         step_index, argmax, cnt, action_d + (size_t)n0 * KBJ_NU, logp_d + n0);
+      actor_head_fused_launch(s, x, H, params_d + o.w_out, params_d + o.b_out, obs, carry->lpf_d + (size_t)n0 * KBJ_NU, w.joint_bias_d, hp, seed,
+                              (uint32_t)(c.env_id_offset + n0), step_index, argmax, cnt, action_d + (size_t)n0 * KBJ_NU, logp_d + n0);
       continue;
     }
     if (n == 1 && o.nout == 1) {
-      hipLaunchKernelGGL(critic_value_fused_kernel, g1((size_t)cnt * 32), dim3(256), 0, s, x, H, params_d + o.w_out, params_d + o.b_out, cnt, value_d + n0);
+      critic_value_fused_launch(s, x, H, params_d + o.w_out, params_d + o.b_out, cnt, value_d + n0);
       continue;
     }
     // n == 2: the mirrored actor only advances its low-pass state (no sample)
     linear_fwd(s, x, H, params_d + o.w_out, H, params_d + o.b_out, Out, 40, cnt, o.nout, H, 0);
-    hipLaunchKernelGGL(actor_head_lpf_kernel, g1((size_t)cnt * KBJ_NU), dim3(256), 0, s, Out, obs, carry->lpf_mirror_d + (size_t)n0 * KBJ_NU, w.joint_bias_d, c.lpf_alpha, cnt, w.net[0].ld_obs);
+    actor_head_lpf_launch(s, Out, obs, carry->lpf_mirror_d + (size_t)n0 * KBJ_NU, w.joint_bias_d, c.lpf_alpha, cnt, w.net[0].ld_obs);
   }
   return 0;
 }
@@ -682,7 +681,7 @@ void carry_reset_nets(kbj_ctx* ctx, hipStream_t s, int net_lo, int net_hi, int n
       cp.p[2 * l] = h_plane(w, hc, k, l, n0, partner);
       cp.p[2 * l + 1] = hc + (size_t)(2 * l + 1) * w.N * w.H + (size_t)n0 * w.H;
     }
-    hipLaunchKernelGGL(carry_reset_kernel, dim3((cnt + 3) / 4), dim3(256), 0, s, cp, cnt, w.H, lpf[k] ? lpf[k] + (size_t)n0 * KBJ_NU : nullptr, done_d + (size_t)n0 * done_stride, done_stride);
+    carry_reset_launch(s, cp, cnt, w.H, lpf[k] ? lpf[k] + (size_t)n0 * KBJ_NU : nullptr, done_d + (size_t)n0 * done_stride, done_stride);
   }
 }
 
@@ -849,7 +848,7 @@ int kbj_init_params(kbj_ctx* ctx, uint32_t seed, float* params_d) {
   int H = w.Hu;
   uint32_t leaf = 0;
   auto fill = [&](size_t off, size_t n, int fan_in) {
-    hipLaunchKernelGGL(init_uniform_kernel, g1(n), dim3(256), 0, ctx->stream, params_d + off, n, 1.0f / std::sqrt((float)fan_in), seed, leaf++);
+    init_uniform_launch(ctx->stream, params_d + off, n, 1.0f / std::sqrt((float)fan_in), seed, leaf++);
   };
   for (int n = 0; n < 2; ++n) {
     const NetOff& o = u.net[n];

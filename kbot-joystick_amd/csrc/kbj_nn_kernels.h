@@ -38,6 +38,10 @@ __global__ void lstm_cell_fwd_kernel(CellFwdArgs2 args) {
   a.c_out[idx] = c;
   if (a.hm_next) { float k = a.keep[m]; a.hm_next[idx] = h * k; a.cm_next[idx] = c * k; a.tanhc[idx] = tc; }
 }
+// one thread per (row, unit); blockIdx.y picks the problem: `count` (1 or 2) problems of ONE size M x H per launch
+inline void lstm_cell_fwd_launch(hipStream_t st, const CellFwdArgs2& a, int count) {
+  hipLaunchKernelGGL(lstm_cell_fwd_kernel, dim3((a.a[0].M * a.a[0].H + 255) / 256, count), dim3(256), 0, st, a);
+}
 
 // ---- threefry (same generator as the env kernels; RNG stream KBJ_RNG_ACTION / KBJ_RNG_INIT) ---------------------
 __device__ __forceinline__ uint32_t nn_rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
@@ -126,6 +130,12 @@ __global__ __launch_bounds__(64 * HEAD_WAVES) void actor_head_fused_kernel(const
     logp[n0 + lane] = lp;
   }
 }
+inline int actor_head_fused_grid(int N) { return (N + HEAD_ENVS * HEAD_WAVES - 1) / (HEAD_ENVS * HEAD_WAVES); }
+inline void actor_head_fused_launch(hipStream_t st, const float* hin, int H, const float* Wout, const float* bout, const float* obs, float* lpf, const float* joint_bias,
+                                    HeadParams hp, uint32_t seed, uint32_t env_off, uint32_t step, int argmax, int N, float* action, float* logp) {
+  hipLaunchKernelGGL(actor_head_fused_kernel, dim3(actor_head_fused_grid(N)), dim3(64 * HEAD_WAVES), 0, st, hin, H, Wout, bout, obs, lpf, joint_bias, hp, seed, env_off, step,
+                     argmax, N, action, logp);
+}
 
 // the rollout's critic head as one launch: value[n] = h[n] . w_out + b_out (one output; 32 lanes per env)
 __global__ __launch_bounds__(256) void critic_value_fused_kernel(const float* __restrict__ hin /*[N][H]*/, int H, const float* __restrict__ wout /*[H]*/,
@@ -139,6 +149,9 @@ __global__ __launch_bounds__(256) void critic_value_fused_kernel(const float* __
     }
   for (int o = 16; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
   if (n < N && j == 0) value[n] = acc + bout[0];
+}
+inline void critic_value_fused_launch(hipStream_t st, const float* hin, int H, const float* wout, const float* bout, int N, float* value) {
+  hipLaunchKernelGGL(critic_value_fused_kernel, dim3((unsigned)(((size_t)N * 32 + 255) / 256)), dim3(256), 0, st, hin, H, wout, bout, N, value);
 }
 
 // value_d[n] = out[n][0]
@@ -157,6 +170,9 @@ __global__ void carry_reset_kernel(CarryPlanes hc, int cnt, int H, float* __rest
   for (int p = 0; p < hc.n; ++p)
     for (int k = lane; k < H; k += 64) hc.p[p][(size_t)row * H + k] = 0.0f;
   if (lpf && lane < KBJ_NU) lpf[(size_t)row * KBJ_NU + lane] = 0.0f;
+}
+inline void carry_reset_launch(hipStream_t st, const CarryPlanes& hc, int cnt, int H, float* lpf, const float* done, int stride) {
+  hipLaunchKernelGGL(carry_reset_kernel, dim3((cnt + 3) / 4), dim3(256), 0, st, hc, cnt, H, lpf, done, stride);   // four wavefronts, four env rows per workgroup
 }
 
 // ---- minibatch gathers ---------------------------------------------------------------------------------------------
@@ -454,6 +470,9 @@ __global__ void actor_head_lpf_kernel(const float* __restrict__ out, const float
   float y0 = lpf[i];
   lpf[i] = y0 + alpha * (mean - y0);
 }
+inline void actor_head_lpf_launch(hipStream_t st, const float* out, const float* obs, float* lpf, const float* joint_bias, float alpha, int N, int ld_obs) {
+  hipLaunchKernelGGL(actor_head_lpf_kernel, dim3((unsigned)(((size_t)N * KBJ_NU + 255) / 256)), dim3(256), 0, st, out, obs, lpf, joint_bias, alpha, N, ld_obs);
+}
 // per sample: action_mirror_loss = mean_j (y_j - mirror_joints(y_m)_j)^2 * sa, value_mirror_loss = (v - v_m)^2 * sc; both are
 // averaged over the minibatch and added to the loss. Writes the direct gradients on y, y_m (dy, dym [R][20]) and adds the
 // value terms to dvalue / writes dvalue_m. macc[5], macc[6] accumulate the two loss sums.
@@ -744,6 +763,9 @@ __global__ void init_uniform_kernel(float* __restrict__ p, size_t n, float bound
   nn_threefry(seed ^ ((uint32_t)KBJ_RNG_INIT * 0x9E3779B9u), leaf, (uint32_t)(i >> 32), (uint32_t)i, b0, b1);
   float u = (float)(b0 >> 8) * (1.0f / 16777216.0f);
   p[i] = fmaf(2 * bound, u, -bound);
+}
+inline void init_uniform_launch(hipStream_t st, float* p, size_t n, float bound, uint32_t seed, uint32_t leaf) {
+  hipLaunchKernelGGL(init_uniform_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p, n, bound, seed, leaf);
 }
 
 }  // namespace kbj

@@ -421,8 +421,72 @@ HPARAM_HEAD_CASES = ["max_std=0.35", "min_std=0.2", "var_scale=1.5", "var_scale=
 HPARAM_SHAPES = [(64, 40, 32, 9), (256, 40, 32, 12)]
 
 
+# ---- the counter generator behind the action and init streams (kbj_model.h KBJ_RNG_ACTION = 5, KBJ_RNG_INIT = 8), vectorised ----
+RNG_ACTION, RNG_INIT = 5, 8
+# tools/head_check: the largest E_Z of its table (max of the derivable 2.16e-6 and 4 x the host fp32 restatement's error over a case's draws);
+# the device's worst |z - z_ref| measured against it is in EXPERIMENTS.md
+Z_BOUND = 3.3e-6
+
+
+def threefry_np(k0, k1, c0, c1):
+    """threefry2x32-20 (Salmon et al., SC'11) over broadcast integer arrays, every word taken mod 2^32: (x0, x1) as uint64 arrays below 2^32.
+    Pinned to oracle.threefry (itself pinned to the Random123 known answers) by tests/test_oracle_physics.py."""
+    M = np.uint64(0xFFFFFFFF)
+    k0, k1, c0, c1 = np.broadcast_arrays(*(np.asarray(v).astype(np.uint64) & M for v in (k0, k1, c0, c1)))
+    ks = (k0, k1, k0 ^ k1 ^ np.uint64(0x1BD11BDA))
+    x0, x1 = (c0 + ks[0]) & M, (c1 + ks[1]) & M
+    rot = (13, 15, 26, 6, 17, 29, 16, 24)
+    for g in range(5):
+        for r in range(4):
+            n = np.uint64(rot[(g & 1) * 4 + r])
+            x0 = (x0 + x1) & M
+            x1 = (((x1 << n) | (x1 >> (np.uint64(32) - n))) & M) ^ x0
+        x0 = (x0 + ks[(g + 1) % 3]) & M
+        x1 = (x1 + ks[(g + 2) % 3] + np.uint64(g + 1)) & M
+    return x0, x1
+
+
+def stream_key(seed, stream):
+    return (int(seed) ^ (stream * 0x9E3779B9)) & 0xFFFFFFFF
+
+
+def z_ref(seed, env, step, joint):
+    """The action stream's Gaussian draw from the exact threefry words, radius and cosine in double: key (seed ^ stream, env), counter
+    (step, joint); u1 = ((b0 >> 8) + 1) / 2^24 and u2 = (b1 >> 8) / 2^24 are exact in fp32, the angle is the fp32 constant's product."""
+    b0, b1 = threefry_np(stream_key(seed, RNG_ACTION), env, step, joint)
+    u1, u2 = ((b0 >> np.uint64(8)) + np.uint64(1)).astype(np.float64) / 2 ** 24, (b1 >> np.uint64(8)).astype(np.float64) / 2 ** 24
+    return np.sqrt(-2.0 * np.log(u1)) * np.cos(float(np.float32(6.283185307179586)) * u2)
+
+
+def init_uniform_ref(seed, leaf, n, fan_in):
+    """init_uniform_kernel bit for bit: element i of leaf `leaf` is fmaf(2 b, u, -b) with b = 1 / sqrtf(fan_in) and u = (b0 >> 8) / 2^24 of
+    threefry(key (seed ^ stream, leaf), counter (i >> 32, i)). b = mb 2^(e - 24) and u = k 2^-24 make the exact value the integer
+    mb (2 k - 2^24) (below 2^49: exact in int64) times 2^(e - 48); the one rounding of the fma is the int64 -> float32 conversion."""
+    b = np.float32(1.0) / np.sqrt(np.float32(fan_in))
+    m, e = np.frexp(b)
+    mb = int(m * 2 ** 24)
+    i = np.arange(n, dtype=np.uint64)
+    b0, _ = threefry_np(stream_key(seed, RNG_INIT), leaf, i >> np.uint64(32), i)
+    k = (b0 >> np.uint64(8)).astype(np.int64)
+    return np.ldexp((mb * (2 * k - 2 ** 24)).astype(np.float32), int(e) - 48)
+
+
+def init_params_ref(H, seed, depth=2, extra_obs=(0, 0)):
+    """kbj_init_params bit for bit as [(leaf name, offset, values)]: the leaves in the order of oracle.nn.param_shapes, numbered from 0, laid
+    out back to back; fan-in = the input projection's width for its weight and bias, the hidden size for every other leaf."""
+    from oracle import nn as ON
+    out, off = [], 0
+    for leaf, (name, shp) in enumerate(ON.param_shapes(H, depth, extra_obs)):
+        nin = (ON.NOBS_ACTOR + extra_obs[0]) if name.startswith("actor") else (ON.NOBS_CRITIC + extra_obs[1])
+        n = int(np.prod(shp))
+        out.append((name, off, init_uniform_ref(seed, leaf, n, nin if ".input_proj." in name else H)))
+        off += n
+    return out
+
+
 def init_like_params(H, seed, depth=2):
-    """A CPU draw from the distribution of kbj_init_params (uniform +-1/sqrt(fan_in) per leaf; not its stream): fp64 flat vector."""
+    """A CPU draw from the distribution of kbj_init_params (uniform +-1/sqrt(fan_in) per leaf; not its stream: init_params_ref above follows
+    the stream): fp64 flat vector."""
     import torch
     from oracle import nn as ON
     g = torch.Generator(device="cpu").manual_seed(seed)

@@ -70,6 +70,96 @@ def test_policy_step_matches_oracle(H, N):                                      
     ctx.close()
 
 
+@pytest.mark.parametrize("head", ["default", "max_std=0.35"])
+@pytest.mark.parametrize("H", [64, 256])
+def test_policy_step_sampled_actions_follow_the_generator(H, head):
+    """Every sampled action against the oracle's mean + std * z_ref, z_ref from the exact threefry words (tests/helpers.z_ref): N = 100 (seven
+    env tiles, the last ragged, two workgroups), env_id_offset = 1000, a small step index and one with the top bit set, the default head and one
+    whose max_std clamp holds a good share of the std entries. Bound e_mu + |z| e_sd + sd e_z: e_mu = e_sd = the 2e-5 the argmax test above
+    holds mean and value to, e_z = the draw bound of tools/head_check (helpers.Z_BOUND)."""
+    from tests import helpers as Hp
+    N, seed = 100, 7
+    m, cfg, ctx, torch, buffers = _setup(N, 32, 4, H, env_id_offset=1000, **(Hp.HPARAM_CASES[head] if head != "default" else {}))
+    from oracle import nn as ON
+    params = torch.zeros(ctx.param_count(), device="cuda:0")
+    ctx.init_params(3, params)
+    g = torch.Generator(device="cpu").manual_seed(1)
+    aobs = torch.zeros(N, L.LD_ACTOR); aobs[:, :65] = torch.randn(N, 65, generator=g)
+    cobs = torch.zeros(N, L.LD_CRITIC); cobs[:, :475] = torch.randn(N, 475, generator=g)
+    hc_a0, hc_c0, lpf0 = torch.randn(2, 2, N, H, generator=g) * 0.5, torch.randn(2, 2, N, H, generator=g) * 0.5, torch.randn(N, 20, generator=g) * 0.3
+    p = ON.unflatten(params.detach().cpu().double(), H)
+    jb = torch.tensor(list(m.joint_bias), dtype=torch.float64)
+    out_a, _ = ON.net_forward(p, "actor", aobs[:, :65].double(), [[hc_a0[l, 0].double(), hc_a0[l, 1].double()] for l in range(2)])
+    mean, std, _ = ON.actor_head(out_a, aobs.double(), lpf0.double(), jb, cfg)
+    if head != "default":
+        share = float((std >= cfg.max_std).double().mean())
+        assert 0.1 <= share <= 0.9, share
+    action, logp, value = torch.zeros(N, 20, device="cuda:0"), torch.zeros(N, device="cuda:0"), torch.zeros(N, device="cuda:0")
+    for step in (5, 0x80000007):
+        carry = buffers.CarryBuffers(N, H, 2, "cuda:0")
+        carry.actor_hc.copy_(hc_a0); carry.critic_hc.copy_(hc_c0); carry.lpf.copy_(lpf0)
+        ctx.policy_step(params, aobs.cuda(), cobs.cuda(), carry.c, seed, step, False, action, logp, value)
+        ctx.synchronize()
+        z = torch.from_numpy(Hp.z_ref(seed, 1000 + np.arange(N)[:, None], step, np.arange(20)[None, :]))
+        err, bound = (action.cpu().double() - (mean + std * z)).abs(), 2e-5 + z.abs() * 2e-5 + std * Hp.Z_BOUND
+        print(f"H={H} {head} step={step}: worst error / bound {float((err / bound).max()):.3f}")
+        assert bool((err <= bound).all()), (step, float((err / bound).max()), int((err / bound).argmax()))
+    ctx.close()
+
+
+@pytest.mark.parametrize("H,D", [(64, 2), (100, 3), (512, 1)])
+def test_init_params_follow_the_init_stream_leaf_by_leaf(H, D):
+    """kbj_init_params bit for bit against the host restatement (tests/helpers.init_params_ref): the leaf numbering, the offsets and the fan-ins
+    of the caller's layout (H = 100 runs padded inside; its parameters are laid out at 100), and no two leaves share their numbers."""
+    from tests import helpers as Hp
+    m, cfg, ctx, torch, buffers = _setup(32, 32, 4, H, depth=D)
+    params = torch.full((ctx.param_count(),), float("nan"), device="cuda:0")
+    ctx.init_params(21, params)
+    ctx.synchronize()
+    pn, leaves = params.cpu().numpy(), Hp.init_params_ref(H, 21, D)
+    assert sum(len(v) for _, _, v in leaves) == pn.size
+    for name, off, want in leaves:
+        got = pn[off:off + len(want)]
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (name, off, int((got != want).sum()))
+    heads = {}
+    for name, off, want in leaves:      # leaves of the same fan-in would coincide in their common prefix if `leaf` did not enter the key
+        k = min(len(want), 64)
+        assert pn[off:off + k].tobytes() not in heads, (name, heads.get(pn[off:off + k].tobytes()))
+        heads[pn[off:off + k].tobytes()] = name
+    ctx.close()
+
+
+def test_rollout_actions_follow_the_generator_at_every_step(monkeypatch):
+    """Sibling of tests/test_gpu_switches.py::test_get_ppo_variables_reproduces_the_rollout (the same task, two rollouts): every stored action
+    of a rollout against the forward pass's own action_mean / action_std and z_ref(seed, env, iteration * T + t, joint) from the exact threefry words (tests/helpers.z_ref). The second rollout runs as iteration 3, so
+    its steps are 60 .. 79: a first_step_index that is dropped, or not advanced by t, fails every element. Bound on (a - mean) / std - z_ref:
+    (e_mu + |z| e_sd + sd e_z) / sd with e_mu = e_sd = 2e-5 (what the policy-step tests hold mean and std to) and e_z = helpers.Z_BOUND."""
+    import os
+    import torch
+    from kbot_joystick_amd.host.task import HumanoidWalkingTask
+    from tests import helpers as Hp
+    from tests.test_gpu_host import _small
+    for k in list(os.environ):
+        if k.startswith("KBJ_") and k != "KBJ_LIB_NAME":
+            monkeypatch.delenv(k)
+    task = HumanoidWalkingTask(_small(num_envs=128, batch_size=64, hidden_size=128, rollout_length_seconds=0.4))
+    T, N = task.T, task.N
+    assert (T, N) == (20, 128)
+    for iteration in (0, 3):              # the second rollout starts from non-trivial carries and contains resets
+        task.iteration = iteration
+        task.rollout()
+        torch.cuda.synchronize()
+        pv = task.get_ppo_variables(task.traj)
+        torch.cuda.synchronize()
+        a, mu, sd = task.traj.action[:T].cpu().double(), pv["action_mean"].cpu().double(), pv["action_std"].cpu().double()
+        steps = iteration * T + np.arange(T)
+        z = torch.from_numpy(Hp.z_ref(task.config.seed, task.kcfg.env_id_offset + np.arange(N)[None, :, None], steps[:, None, None], np.arange(20)[None, None, :]))
+        err, bound = ((a - mu) / sd - z).abs(), (2e-5 + z.abs() * 2e-5 + sd * Hp.Z_BOUND) / sd
+        print(f"iteration {iteration}: worst error / bound {float((err / bound).max()):.3f}")
+        assert bool((err <= bound).all()), (iteration, float((err / bound).max()), int((err / bound).argmax()))
+    task.ctx.close()
+
+
 def _synthetic_traj(torch, buffers, N, T, H, seed=0, mirror=False, depth=2):
     from tests import helpers
     tr = buffers.TrajBuffers(T, N, H, depth, "cuda:0", mirror=mirror)

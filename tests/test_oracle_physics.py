@@ -26,6 +26,40 @@ def test_threefry_known_answers():
     assert O.threefry(0x13198A2E, 0x03707344, 0x243F6A88, 0x85A308D3) == (0xC4923A9C, 0x483DF7A0)
 
 
+def test_vectorised_threefry_and_draws_match_the_oracle_generator():
+    """tests/helpers.threefry_np (the reference of the GPU tests that hold every sampled action and every initial parameter to the generator)
+    against oracle.threefry on a few hundred words, the wrap-around of every word included; z_ref and init_uniform_ref against the scalar
+    restatement of the kernels' formulas from those words."""
+    import math
+    from fractions import Fraction
+    from tests import helpers as Hp
+    assert tuple(int(v) for v in Hp.threefry_np(0x13198A2E, 0x03707344, 0x243F6A88, 0x85A308D3)) == (0xC4923A9C, 0x483DF7A0)
+    rng = np.random.default_rng(5)
+    words = rng.integers(0, 2 ** 32, size=(300, 4), dtype=np.uint64)
+    words[:8] = [[0, 0, 0, 0], [2 ** 32 - 1] * 4, [7, 2 ** 32 - 16, 5, 19], [7, 2 ** 32 - 1, 0x80000007, 0], [1, 2, 3, 4], [4, 3, 2, 1], [0, 1, 0, 1], [1, 0, 1, 0]]
+    x0, x1 = Hp.threefry_np(words[:, 0], words[:, 1], words[:, 2], words[:, 3])
+    for w, a, b in zip(words, x0, x1):
+        assert O.threefry(*(int(v) for v in w)) == (int(a), int(b)), w
+    # a key / counter above 2^32 wraps as the device's uint32 addition does
+    assert [int(v) for v in Hp.threefry_np(5, 0xFFFFFFF0 + 17, 3, 4)] == list(O.threefry(5, 1, 3, 4))
+    seed, env, step = 7, 1000 + np.arange(4)[:, None], 0x80000007
+    z = Hp.z_ref(seed, env, step, np.arange(20)[None, :])
+    for n in range(4):
+        for j in range(20):
+            b0, b1 = O.threefry(Hp.stream_key(seed, Hp.RNG_ACTION), 1000 + n, step, j)
+            want = math.sqrt(-2 * math.log(((b0 >> 8) + 1) / 2 ** 24)) * math.cos(float(np.float32(6.283185307179586)) * ((b1 >> 8) / 2 ** 24))
+            assert z[n, j] == pytest.approx(want, abs=1e-14)
+    for fan_in, leaf in ((65, 0), (475, 9), (100, 3)):
+        got = Hp.init_uniform_ref(11, leaf, 50, fan_in)
+        b = np.float32(1.0) / np.sqrt(np.float32(fan_in))
+        for i in range(50):
+            b0, _ = O.threefry(Hp.stream_key(11, Hp.RNG_INIT), leaf, 0, i)
+            exact = Fraction(float(b)) * (2 * Fraction(b0 >> 8, 2 ** 24) - 1)
+            assert got.dtype == np.float32 and abs(Fraction(float(got[i])) - exact) <= abs(exact) * Fraction(1, 2 ** 24) and abs(float(got[i])) <= float(b)
+            assert float(got[i]) == float(np.float32(float(exact)))       # a Fraction -> double -> float conversion: double rounding would need a 29-bit tie
+    assert not np.array_equal(Hp.init_uniform_ref(11, 0, 50, 65), Hp.init_uniform_ref(11, 1, 50, 65))
+
+
 def test_total_mass(model, model_full):
     # <inertial> sums + the 4.19 g sphere MuJoCo infers for the base body (SURVEY.md A.1)
     assert abs(model.total_mass - 36.339 - 0.00419) < 2e-3
