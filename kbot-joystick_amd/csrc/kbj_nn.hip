@@ -118,53 +118,7 @@ ParamLayout layout_params(const kbj_config& c, int H) {
 template <class C> auto& carry_hc(C& c, int n) { return n == 0 ? c.actor_hc_d : n == 1 ? c.critic_hc_d : n == 2 ? c.actor_mirror_hc_d : c.critic_mirror_hc_d; }
 template <class T> auto& traj_carry0(T& t, int n) { return n == 0 ? t.carry0_actor_hc_d : n == 1 ? t.carry0_critic_hc_d : n == 2 ? t.carry0_actor_mirror_hc_d : t.carry0_critic_mirror_hc_d; }
 
-// Mirror of the packed observation rows as (source index, multiplier, offset) per element (mirror_rows_kernel).
-// Follows the index/sign lists of the reference's mirror_obs functions (train.py:1574-1756); element order = the obs packing
-// of kbj_env_task.h write_obs (kbj_model.h KBJ_NOBS_*).
-// extra_actor / extra_critic user columns behind the reference's are carried over unchanged (identity entries): a user term that is not
-// mirror-invariant has to be mirrored by the user's own mirror-loss code, as in the reference (train.py:1574-1756 names every key).
-void build_mirror_tables(const kbj_model& m, std::vector<MirrorEntry>& ta, std::vector<MirrorEntry>& tc, int extra_actor = 0, int extra_critic = 0) {
-  auto swp = [](int i) { return i < 5 ? i + 5 : (i < 10 ? i - 5 : i); };  // left leg <-> right leg, arms stay (train.py:1574-1582)
-  tc.assign(KBJ_LD_CRITIC, MirrorEntry{0, 0.0f, 0.0f});
-  for (int k = 0; k < KBJ_LD_CRITIC; ++k) tc[k].src = k;
-  auto keep = [&](int k, float sgn) { tc[k] = MirrorEntry{k, sgn, 0.0f}; };
-  for (int i = 0; i < KBJ_NU; ++i) {
-    int s = swp(i);
-    auto rng = [&](int j) { return std::fmax(m.joint_bias[j] - m.joint_lo[j], m.joint_hi[j] - m.joint_bias[j]); };
-    tc[KBJ_OBS_JPOS + i] = MirrorEntry{KBJ_OBS_JPOS + s, -rng(s) / rng(i), (-m.joint_bias[s] - m.joint_bias[i]) / rng(i)};   // normalised joint positions
-    tc[KBJ_OBS_JVEL + i] = MirrorEntry{KBJ_OBS_JVEL + s, -1.0f, 0.0f};                                                      // joint velocities / 10
-    tc[KBJ_OBS_ACTFRC + i] = MirrorEntry{KBJ_OBS_ACTFRC + s, -1.0f, 0.0f};                                                  // actuator force / 4 (critic)
-  }
-  // roll, pitch, unit projected gravity: the reference mirrors the raw vector (g0, -g1, g2) and encodes it again (train.py:1596-1603,
-  // 1338-1349): roll = atan2(g1, -g2) changes sign, pitch and the norm do not
-  keep(KBJ_OBS_PG, -1); keep(KBJ_OBS_PG + 1, 1); keep(KBJ_OBS_PG + 2, 1); keep(KBJ_OBS_PG + 3, -1); keep(KBJ_OBS_PG + 4, 1);
-  keep(KBJ_OBS_GYRO, -1); keep(KBJ_OBS_GYRO + 1, 1); keep(KBJ_OBS_GYRO + 2, -1);   // gyro
-  keep(KBJ_OBS_ZEROCMD, 1);                                                          // zero-command flag (the norm of cmd[0:3] is mirror invariant)
-  const float cs[16] = {1, -1, -1, 1, -1, 1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // vx, vy, wz, height, roll, pitch, 10 arm targets
-  for (int k = 0; k < 16; ++k) keep(KBJ_OBS_CMD + k, cs[k]);
-  ta.assign(tc.begin(), tc.begin() + KBJ_LD_ACTOR);
-  for (int k = KBJ_NOBS_ACTOR; k < KBJ_LD_ACTOR; ++k) ta[k] = MirrorEntry{k, 0.0f, 0.0f};
-  tc[KBJ_OBS_TOUCH] = MirrorEntry{KBJ_OBS_TOUCH + 1, 1, 0}; tc[KBJ_OBS_TOUCH + 1] = MirrorEntry{KBJ_OBS_TOUCH, 1, 0};           // foot touch L <-> R
-  const float fs[3] = {1, -1, 1};
-  for (int k = 0; k < 3; ++k) { tc[KBJ_OBS_FEETPOS + k] = MirrorEntry{KBJ_OBS_FEETPOS + 3 + k, fs[k], 0}; tc[KBJ_OBS_FEETPOS + 3 + k] = MirrorEntry{KBJ_OBS_FEETPOS + k, fs[k], 0}; }   // feet positions
-  keep(KBJ_OBS_BASEPOS, 1); keep(KBJ_OBS_BASEPOS + 1, 1); keep(KBJ_OBS_BASEPOS + 2, 1);                                      // base position
-  keep(KBJ_OBS_BASEQUAT, 1); keep(KBJ_OBS_BASEQUAT + 1, -1); keep(KBJ_OBS_BASEQUAT + 2, -1); keep(KBJ_OBS_BASEQUAT + 3, 1);  // base quaternion
-  const float ci[10] = {1, 1, -1, 1, 1, 1, 1, -1, 1, -1}, cv[6] = {1, -1, 1, -1, 1, -1};
-  for (int b = 0; b < 23; ++b) {
-    for (int k = 0; k < 10; ++k) keep(KBJ_OBS_CINERT + 10 * b + k, ci[k]);      // cinert
-    for (int k = 0; k < 6; ++k) keep(KBJ_OBS_CVEL + 6 * b + k, cv[k]);          // cvel
-  }
-  keep(KBJ_OBS_LINVEL, 1); keep(KBJ_OBS_LINVEL + 1, -1); keep(KBJ_OBS_LINVEL + 2, 1);     // base linear velocity
-  keep(KBJ_OBS_ANGVEL, -1); keep(KBJ_OBS_ANGVEL + 1, 1); keep(KBJ_OBS_ANGVEL + 2, -1);    // base angular velocity
-  keep(KBJ_OBS_HEIGHT, 1);                                                                 // base height
-  for (int k = KBJ_NOBS_CRITIC; k < KBJ_LD_CRITIC; ++k) tc[k] = MirrorEntry{k, 0.0f, 0.0f};
-  auto widen = [](std::vector<MirrorEntry>& t, int nobs, int extra) {
-    t.resize(KBJ_LD_OF(nobs + extra));
-    for (int k = nobs; k < (int)t.size(); ++k) t[k] = MirrorEntry{k, k < nobs + extra ? 1.0f : 0.0f, 0.0f};
-  };
-  if (extra_actor > 0) widen(ta, KBJ_NOBS_ACTOR, extra_actor);
-  if (extra_critic > 0) widen(tc, KBJ_NOBS_CRITIC, extra_critic);
-}
+// build_mirror_tables (the (source index, multiplier, offset) tables of mirror_rows_kernel): kbj_nn_kernels.h, beside the kernel
 
 template <class T> int dalloc(kbj_ctx* ctx, NnWs& w, T** p, size_t count) {
   void* q = nullptr;
@@ -180,7 +134,7 @@ constexpr int g_fold_sk = 8;        // k slices of the small W_ih0^T Z product o
 #define KBJ_SPLITK_WGS 768   // re-swept in round 5 under the four-launches-together schedule: 256 / 384 / 512 / 768 / 1024 -> 6.10 / 6.0 / 5.96 / 5.86 / 5.95 ms per minibatch
 #endif
 constexpr int g_splitk_wgs = KBJ_SPLITK_WGS;   // target number of workgroups of a split-K weight-gradient GEMM (512 ... 1536 measured flat)
-constexpr int DETP_ROWS = 512, DETP_COLS = 4 * 512;   // (columns: one gate row of the widest layer, 4 SEQ_MAX_H)
+constexpr int DETP_COLS = 4 * 512;   // (rows: DETP_ROWS, kbj_nn_kernels.h; columns: one gate row of the widest layer, 4 SEQ_MAX_H)
 
 // lane index of a stream of this context (deterministic-mode workspaces are per lane: launches on different lanes overlap)
 int lane_of(kbj_ctx* ctx, hipStream_t s) { return s == ctx->stream ? 0 : (s == ctx->stream2 ? 1 : (s == ctx->side[0] ? 2 : 3)); }
@@ -203,8 +157,6 @@ float* det_partials(kbj_ctx* ctx, hipStream_t s) {
   NnWs& w = *ws_of(ctx);
   return w.sched.deterministic ? w.detp[lane_of(ctx, s)] : nullptr;
 }
-
-inline dim3 g1(size_t n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
 
 // y = x W^T + b  (x [M][K] lda, W [N][K])
 void linear_fwd(hipStream_t s, const float* x, int lda, const float* W, int ldw, const float* bias, float* y, int ldy, int M, int N, int K, int beta) {
@@ -252,7 +204,7 @@ void linear_bwd_weight2(kbj_ctx* ctx, hipStream_t s, bool x3, const float* dy, i
 // column sums of X [M][N] (ld) added to out[N]: atomics over 512 row slices, or (deterministic) per-slice partials + ordered reduce
 void colsum_acc(kbj_ctx* ctx, hipStream_t s, const float* X, int M, int N, int ld, float* out) {
   float* part = det_partials(ctx, s);
-  hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64, DETP_ROWS), dim3(256), 0, s, X, M, N, ld, out, part);
+  colsum_launch(s, X, M, N, ld, out, part);
   if (part) reduce_rows_launch(s, part, DETP_ROWS, N, out);
 }
 
@@ -580,7 +532,7 @@ const float* fold_actor_weights(kbj_ctx* ctx, hipStream_t s, const float* params
   const NetOff& oa = w.net[0];
   GemmArgs g{params_d + oa.w_ih[0], params_d + oa.w_in, w.Weff, nullptr, 4 * H, oa.nin, H, H, oa.nin, oa.ld_obs, 0, 1, nullptr};
   gemm_launch<true, false>(s, g);
-  hipLaunchKernelGGL(matvec_kernel, dim3((4 * H + 3) / 4), dim3(256), 0, s, params_d + oa.w_ih[0], params_d + oa.b_in, params_d + oa.b[0], 4 * H, H, w.beff);
+  matvec_launch(s, params_d + oa.w_ih[0], params_d + oa.b_in, params_d + oa.b[0], 4 * H, H, w.beff);
   return w.Weff;
 }
 
@@ -593,7 +545,7 @@ void repitch_input_weights(kbj_ctx* ctx, hipStream_t s, const float* params_d, i
   for (int k = k_lo; k < k_hi; ++k) {
     const NetOff& o = w.net[k];
     if (o.nin == o.ld_obs) continue;
-    hipLaunchKernelGGL(repitch_rows_kernel, g1((size_t)w.H * o.ld_obs), dim3(256), 0, s, params_d + o.w_in, w.H, o.nin, o.ld_obs, w.WinP[k]);
+    repitch_rows_launch(s, params_d + o.w_in, w.H, o.nin, o.ld_obs, w.WinP[k]);
   }
 }
 
@@ -618,7 +570,7 @@ int policy_nets(kbj_ctx* ctx, hipStream_t s, const float* params_d, int net_lo, 
     float* G = w.rG[n] + (size_t)n0 * 4 * H;
     float* Out = w.rOut[n] + (size_t)n0 * 40;
     if (n >= 2) {  // mirror branches advance their own carries on the mirrored observations (train.py:1463-1481, 1555-1560)
-      hipLaunchKernelGGL(mirror_rows_kernel, g1((size_t)cnt * o.ld_obs), dim3(256), 0, s, obs, obs_m, (size_t)cnt, o.ld_obs, w.mtab[k]);
+      mirror_rows_launch(s, obs, obs_m, (size_t)cnt, o.ld_obs, w.mtab[k]);
       obs = obs_m;
     }
     const bool fused = fused_any && net_uses_step_kernel(w, n);
@@ -707,7 +659,7 @@ void unpad_params(kbj_ctx* ctx, hipStream_t s, const float* internal, float* use
 void repitch_hc(kbj_ctx* ctx, hipStream_t s, const float* src, float* dst, int ws, int wd) {
   NnWs& w = *ws_of(ctx);
   const size_t rows = (size_t)2 * w.D * w.N;
-  hipLaunchKernelGGL(repitch_pad_kernel, g1(rows * wd), dim3(256), 0, s, src, dst, rows, ws, wd);
+  repitch_pad_launch(s, src, dst, rows, ws, wd);
 }
 // the caller's carry as an H-wide internal one (lpf state is not hidden-size dependent: shared)
 kbj_carry pad_carry(kbj_ctx* ctx, hipStream_t s, const kbj_carry& c) {
@@ -949,12 +901,9 @@ int head_gathers(kbj_ctx* ctx, hipStream_t st, const kbj_traj* tr, const int32_t
   NnWs& w = *ws_of(ctx);
   const int T = tr->T, N = tr->N, H = w.H, B = w.B, R = T * B, D = w.D;
   const int lda = w.net[0].ld_obs;
-  if (lda % 4 == 0 && ((size_t)tr->actor_obs_d & 15) == 0)
-    hipLaunchKernelGGL(gather_rows4_kernel, g1((size_t)R * (lda / 4)), dim3(256), 0, st, reinterpret_cast<const float4*>(tr->actor_obs_d), idx, T, N, B, lda / 4, lda / 4, lda / 4,
-                       reinterpret_cast<float4*>(w.tb[0].obs));
-  else hipLaunchKernelGGL(gather_rows_kernel, g1((size_t)R * lda), dim3(256), 0, st, tr->actor_obs_d, idx, T, N, B, lda, lda, lda, w.tb[0].obs);
+  gather_rows_launch(st, tr->actor_obs_d, idx, T, N, B, lda, lda, w.tb[0].obs, lda);   // (w.tb[0].obs is an allocation of its own: 16-byte aligned)
   GatherSmallArgs gs{tr->action_d, nullptr, nullptr, nullptr, nullptr, tr->aux_d, w.act, w.logp_old, w.val_old, w.adv, w.target, w.keep};
-  hipLaunchKernelGGL(gather_small_kernel, g1((size_t)R), dim3(256), 0, st, gs, idx, T, N, B, KBJ_NU + 4, KBJ_NU + 5);   // keep flags: all the recurrences need of these
+  gather_small_launch(st, gs, idx, T, N, B, KBJ_NU + 4, KBJ_NU + 5);   // keep flags: all the recurrences need of these
   if (w.mirror && (!traj_carry0(*tr, 2) || !traj_carry0(*tr, 3) || !tr->carry0_lpf_mirror_d))
     return kbj_fail(ctx, "PPO pass: the mirror losses are enabled, the trajectory needs the mirror-branch carries");
   GatherCarryArgs gc;
@@ -967,7 +916,7 @@ int head_gathers(kbj_ctx* ctx, hipStream_t st, const kbj_traj* tr, const int32_t
   gc.nlpf = 0;
   gc.src[gc.nplanes] = tr->carry0_lpf_d; gc.dst[gc.nplanes] = w.lpf0; gc.nlpf++;
   if (w.mirror) { gc.src[gc.nplanes + 1] = tr->carry0_lpf_mirror_d; gc.dst[gc.nplanes + 1] = w.lpf0_m; gc.nlpf++; }
-  hipLaunchKernelGGL(gather_carry_kernel, dim3((B * H + 255) / 256, gc.nplanes + gc.nlpf), dim3(256), 0, st, gc, idx, B, H);
+  gather_carry_launch(st, gc, idx, B, H);
   return 0;
 }
 
@@ -1000,14 +949,9 @@ int ppo_forward_nets(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, co
     const NetOff& oa = w.net[0];
     GemmArgs g{params_d + oa.w_ih[0], params_d + oa.w_in, w.Weff, nullptr, 4 * H, oa.nin, H, H, oa.nin, oa.ld_obs, 0, 1, nullptr};
     gemm_launch<true, false>(s, g);
-    hipLaunchKernelGGL(matvec_kernel, dim3((4 * H + 3) / 4), dim3(256), 0, s, params_d + oa.w_ih[0], params_d + oa.b_in, params_d + oa.b[0], 4 * H, H, w.beff);
+    matvec_launch(s, params_d + oa.w_ih[0], params_d + oa.b_in, params_d + oa.b[0], 4 * H, H, w.beff);
   }
-  auto gather = [&](hipStream_t st, const float* src, int wdt, int lds, float* dst, int ldd) {
-    if (wdt % 4 == 0 && lds % 4 == 0 && ldd % 4 == 0 && ((size_t)src & 15) == 0 && ((size_t)dst & 15) == 0)
-      hipLaunchKernelGGL(gather_rows4_kernel, g1((size_t)R * (wdt / 4)), dim3(256), 0, st, reinterpret_cast<const float4*>(src), idx, T, N, B, wdt / 4, lds / 4, ldd / 4,
-                         reinterpret_cast<float4*>(dst));
-    else hipLaunchKernelGGL(gather_rows_kernel, g1((size_t)R * wdt), dim3(256), 0, st, src, idx, T, N, B, wdt, lds, ldd, dst);
-  };
+  auto gather = [&](hipStream_t st, const float* src, int wdt, int lds, float* dst, int ldd) { gather_rows_launch(st, src, idx, T, N, B, wdt, lds, dst, ldd); };
   // The large critic observation block (97 MB per minibatch, 45 us at HBM speed): the forward pass reads it once, through the critic's
   // input projection - which fetches its rows straight from the trajectory through the minibatch's indices (GemmArgs::a_idx) - so the
   // gathered copy, which the backward pass and the mirror branch want, is made on the critic's side lane, off the chain that starts the
@@ -1033,7 +977,7 @@ int ppo_forward_nets(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, co
     // fork from the net lanes after that point, so every later reader and accumulator is ordered behind the clears.
     hipStream_t sm = sc.one_stream ? s : ctx->side[0];
     if (!sc.one_stream) KBJ_HIP(ctx, hipStreamWaitEvent(sm, ctx->ev_fork, 0));
-    hipLaunchKernelGGL(gather_small_kernel, g1((size_t)R * (KBJ_NU + 4)), dim3(256), 0, sm, gs, idx, T, N, B, 0, KBJ_NU + 4);
+    gather_small_launch(sm, gs, idx, T, N, B, 0, KBJ_NU + 4);
     if (grad) {
       KBJ_HIP(ctx, hipMemsetAsync(w.stats, 0, 16 * sizeof(double), sm));
 #ifndef KBJ_NO_TAIL_CLEAN
@@ -1044,8 +988,8 @@ int ppo_forward_nets(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, co
         KBJ_HIP(ctx, hipMemcpyAsync(w.stats, w.ext_adv_sums, 2 * sizeof(double), hipMemcpyDeviceToDevice, sm));
         KBJ_HIP(ctx, hipMemcpyAsync(w.stats + 11, w.ext_adv_sums + 2, sizeof(double), hipMemcpyDeviceToDevice, sm));
       } else {
-        hipLaunchKernelGGL(adv_stats_kernel, dim3(32), dim3(256), 0, sm, w.adv, R, w.stats, sc.deterministic ? w.detd : (double*)nullptr);
-        if (sc.deterministic) reduce_double_launch(sm, w.detd, 32, 2, w.stats);
+        adv_stats_launch(sm, w.adv, R, w.stats, sc.deterministic ? w.detd : (double*)nullptr);
+        if (sc.deterministic) reduce_double_launch(sm, w.detd, ADV_STATS_BLOCKS, 2, w.stats);
       }
       KBJ_HIP(ctx, hipMemsetAsync(grad_d, 0, w.nparams * sizeof(float), sm));
       if (sc.fold_actor)
@@ -1059,7 +1003,7 @@ int ppo_forward_nets(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, co
   KBJ_HIP(ctx, hipEventRecord(ctx->ev_join, ns[0]));
   if (w.mirror)   // mirrored observation rows: actor's on the caller's stream, critic's behind its gather
     for (int k = 0; k < 2; ++k)
-      hipLaunchKernelGGL(mirror_rows_kernel, g1((size_t)R * w.net[k].ld_obs), dim3(256), 0, ns[k], w.tb[k].obs, w.tb[2 + k].obs, (size_t)R, w.net[k].ld_obs, w.mtab[k]);
+      mirror_rows_launch(ns[k], w.tb[k].obs, w.tb[2 + k].obs, (size_t)R, w.net[k].ld_obs, w.mtab[k]);
   // ---- forward through time: actor on the caller's stream, critic on the context's second stream (the recurrences are
   // latency bound, so the two nets overlap) ----
   const int stamp_sel = ctx->set.stamp_sel;   // diagnostics build: 1 + net + 2 * layer picks the stamped forward launch
@@ -1078,7 +1022,7 @@ int ppo_forward_nets(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, co
     // its element-wise load path for this operand (55 instead of ~90 TF for the critic's 12 GFLOP, at the head of the longer chain): a
     // re-pitched copy with the observation rows' stride (zeros behind column nin, as in the observation rows) is made first; the
     // contraction then runs over the padded width
-    if (n < 2) hipLaunchKernelGGL(repitch_rows_kernel, g1((size_t)H * o.ld_obs), dim3(256), 0, ns[n & 1], params_d + o.w_in, H, o.nin, o.ld_obs, w.WinP[n & 1]);
+    if (n < 2) repitch_rows_launch(ns[n & 1], params_d + o.w_in, H, o.nin, o.ld_obs, w.WinP[n & 1]);
     if (n == 1 && gather_late) {
       GemmArgs g{tr->critic_obs_d, w.WinP[1], w.tb[1].X0, params_d + o.b_in, R, H, o.ld_obs, o.ld_obs, o.ld_obs, H, 0, 1, nullptr};
       g.a_idx = idx; g.a_B = B; g.a_N = N;
@@ -1136,12 +1080,12 @@ int ppo_forward_body(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, co
     linear_fwd(ns[n], w.tb[n].Hout[D - 1], H, params_d + o.w_out, H, params_d + o.b_out, w.tb[n].Out, 40, R, o.nout, H, 0);
   }
   HeadParams hp{c.min_std, c.max_std, c.var_scale, c.lpf_alpha, w.net[0].ld_obs};
-  hipLaunchKernelGGL(actor_head_pre_kernel, g1((size_t)R * KBJ_NU), dim3(256), 0, s, w.tb[0].Out, w.tb[0].obs, w.joint_bias_d, hp, R, w.y, w.sd);
-  hipLaunchKernelGGL(actor_head_train_fwd_kernel, g1((size_t)B * KBJ_NU, 64), dim3(64), 0, s, w.keep, w.lpf0, hp, T, B, w.y);
-  hipLaunchKernelGGL(gaussian_logp_kernel, g1(R), dim3(256), 0, s, w.y, w.sd, w.act, R, out->logp_d, out->entropy_d ? out->entropy_d : w.ent);
+  actor_head_pre_launch(s, w.tb[0].Out, w.tb[0].obs, w.joint_bias_d, hp, R, w.y, w.sd);
+  actor_head_train_fwd_launch(s, w.keep, w.lpf0, hp, T, B, w.y);
+  gaussian_logp_launch(s, w.y, w.sd, w.act, R, out->logp_d, out->entropy_d ? out->entropy_d : w.ent);
   if (out->action_std_d) KBJ_HIP(ctx, hipMemcpyAsync(out->action_std_d, w.sd, (size_t)R * KBJ_NU * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (out->action_mean_d) KBJ_HIP(ctx, hipMemcpyAsync(out->action_mean_d, w.y, (size_t)R * KBJ_NU * sizeof(float), hipMemcpyDeviceToDevice, s));
-  hipLaunchKernelGGL(critic_value_kernel, g1(R), dim3(256), 0, ns[1], w.tb[1].Out, 40, R, out->value_d);
+  critic_value_launch(ns[1], w.tb[1].Out, 40, R, out->value_d);
   if (!w.sched.one_stream) {
     KBJ_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
     KBJ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
@@ -1177,36 +1121,26 @@ int ppo_grad_body(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const
   // recurrences meet the critic's GEMM phases instead of the critic's recurrences
   HeadParams hp{c.min_std, c.max_std, c.var_scale, c.lpf_alpha, w.net[0].ld_obs};
   PpoParams pp{c.clip_param, c.value_clip, c.value_loss_coef, c.entropy_coef, c.log_ratio_clip, c.adv_eps};
-  hipLaunchKernelGGL(actor_head_pre_kernel, g1((size_t)R * KBJ_NU), dim3(256), 0, s, w.tb[0].Out, w.tb[0].obs, w.joint_bias_d, hp, R, w.y, w.sd);
-  hipLaunchKernelGGL(actor_head_train_fwd_kernel, g1((size_t)B * KBJ_NU, 64), dim3(64), 0, s, w.keep, w.lpf0, hp, T, B, w.y);
-  hipLaunchKernelGGL(gaussian_logp_kernel, g1(R), dim3(256), 0, s, w.y, w.sd, w.act, R, w.logp, w.ent);
-  hipLaunchKernelGGL(ppo_loss_kernel, g1(R), dim3(256), 0, s, w.logp, w.value, w.ent, w.logp_old, w.val_old, w.adv, w.target, w.stats, pp, R, w.dlogp, w.dvalue,
-                     w.stats + 2, one_stream ? 0 : 1);
+  actor_head_pre_launch(s, w.tb[0].Out, w.tb[0].obs, w.joint_bias_d, hp, R, w.y, w.sd);
+  actor_head_train_fwd_launch(s, w.keep, w.lpf0, hp, T, B, w.y);
+  gaussian_logp_launch(s, w.y, w.sd, w.act, R, w.logp, w.ent);
+  ppo_loss_launch(s, w.logp, w.value, w.ent, w.logp_old, w.val_old, w.adv, w.target, w.stats, pp, R, w.dlogp, w.dvalue, w.stats + 2, one_stream ? 0 : 1);
   if (fused_critic_head) {
     const NetOff& oc = w.net[1];
     TrainBufs& tc = w.tb[1];
-    const dim3 grid(2048), block(256);
-    const bool built = dispatch_hidden(H, [&](auto hc) {
-      hipLaunchKernelGGL((critic_head_kernel<decltype(hc)::value / 64>), grid, block, 0, ns[1], tc.Hout[D - 1], params_d + oc.w_out, params_d + oc.b_out, w.val_old, w.target,
-                         pp, R, w.value, w.dvalue, tc.dOut, tc.dHa, w.stats + 2);
-      return true;
-    });
+    const bool built = critic_head_launch(ns[1], H, tc.Hout[D - 1], params_d + oc.w_out, params_d + oc.b_out, w.val_old, w.target, pp, R, w.value, w.dvalue, tc.dOut, tc.dHa, w.stats + 2);
     if (!built) return kbj_fail(ctx, "kbj_ppo_grad: critic_head_kernel is built for hidden sizes 64, 128, ..., 512");
-    if (one_stream) hipLaunchKernelGGL(ppo_loss_kernel, g1(R), dim3(256), 0, s, w.logp, w.value, w.ent, w.logp_old, w.val_old, w.adv, w.target, w.stats, pp, R, w.dlogp, w.dvalue,
-                                       w.stats + 2, 1);   // (the actor's launch above was a no-op in this diagnostic mode)
+    if (one_stream) ppo_loss_launch(s, w.logp, w.value, w.ent, w.logp_old, w.val_old, w.adv, w.target, w.stats, pp, R, w.dlogp, w.dvalue, w.stats + 2, 1);   // (the actor's launch above was a no-op in this diagnostic mode)
   } else {
-    hipLaunchKernelGGL(critic_value_kernel, g1(R), dim3(256), 0, ns[1], w.tb[1].Out, 40, R, w.value);
-    hipLaunchKernelGGL(ppo_loss_kernel, g1(R), dim3(256), 0, ns[1], w.logp, w.value, w.ent, w.logp_old, w.val_old, w.adv, w.target, w.stats, pp, R, w.dlogp, w.dvalue,
-                       w.stats + 2, one_stream ? 3 : 2);
+    critic_value_launch(ns[1], w.tb[1].Out, 40, R, w.value);
+    ppo_loss_launch(ns[1], w.logp, w.value, w.ent, w.logp_old, w.val_old, w.adv, w.target, w.stats, pp, R, w.dlogp, w.dvalue, w.stats + 2, one_stream ? 3 : 2);
   }
   if (w.mirror) {   // aux losses between each net and its mirror branch (train.py:1463-1481)
-    hipLaunchKernelGGL(actor_head_pre_kernel, g1((size_t)R * KBJ_NU), dim3(256), 0, s, w.tb[2].Out, w.tb[2].obs, w.joint_bias_d, hp, R, w.y_m, w.sd_m);
-    hipLaunchKernelGGL(actor_head_train_fwd_kernel, g1((size_t)B * KBJ_NU, 64), dim3(64), 0, s, w.keep, w.lpf0_m, hp, T, B, w.y_m);
-    hipLaunchKernelGGL(mirror_loss_kernel, g1(R), dim3(256), 0, s, w.y, w.y_m, w.value, w.value_m, c.actor_mirror_loss_scale, c.critic_mirror_loss_scale, R, w.dy, w.dy_m,
-                       w.dvalue, w.dvalue_m, w.stats + 2, one_stream ? 0 : 1);
-    hipLaunchKernelGGL(critic_value_kernel, g1(R), dim3(256), 0, ns[1], w.tb[3].Out, 40, R, w.value_m);
-    hipLaunchKernelGGL(mirror_loss_kernel, g1(R), dim3(256), 0, ns[1], w.y, w.y_m, w.value, w.value_m, c.actor_mirror_loss_scale, c.critic_mirror_loss_scale, R, w.dy, w.dy_m,
-                       w.dvalue, w.dvalue_m, w.stats + 2, one_stream ? 3 : 2);
+    actor_head_pre_launch(s, w.tb[2].Out, w.tb[2].obs, w.joint_bias_d, hp, R, w.y_m, w.sd_m);
+    actor_head_train_fwd_launch(s, w.keep, w.lpf0_m, hp, T, B, w.y_m);
+    mirror_loss_launch(s, w.y, w.y_m, w.value, w.value_m, c.actor_mirror_loss_scale, c.critic_mirror_loss_scale, R, w.dy, w.dy_m, w.dvalue, w.dvalue_m, w.stats + 2, one_stream ? 0 : 1);
+    critic_value_launch(ns[1], w.tb[3].Out, 40, R, w.value_m);
+    mirror_loss_launch(ns[1], w.y, w.y_m, w.value, w.value_m, c.actor_mirror_loss_scale, c.critic_mirror_loss_scale, R, w.dy, w.dy_m, w.dvalue, w.dvalue_m, w.stats + 2, one_stream ? 3 : 2);
   }
   // The metrics line is nobody's input. It used to be a one-thread launch on a side lane right here - where every CU is about to be taken by the
   // backward recurrences (250 registers x 2 wavefronts per SIMD), so in most minibatches it sat dispatched-but-unplaced for ~450 us (2.9 % of the
@@ -1217,13 +1151,12 @@ int ppo_grad_body(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const
   hipEvent_t ev_critic_loss = critic_fork_recorded ? ctx->ev_side[1] : ctx->ev_pool[ctx->ev_next++ & 31];
   if (!one_stream) hipEventRecord(ev_critic_loss, ns[1]);
   // ---- backward ---- (dOut needs no clearing: the actor head writes all 40 columns, the critic's GEMMs read column 0 only)
-  hipLaunchKernelGGL(actor_head_bwd_pre_kernel, g1((size_t)R * KBJ_NU), dim3(256), 0, s, w.tb[0].Out, w.y, w.sd, w.act, w.dlogp,
-                     w.mirror ? w.dy : (const float*)nullptr, -c.entropy_coef / (float)R, hp, R, w.tb[0].dOut);
-  hipLaunchKernelGGL(actor_head_train_bwd_kernel, g1((size_t)B * KBJ_NU, 64), dim3(64), 0, s, w.keep, hp, T, B, w.tb[0].dOut);
+  actor_head_bwd_pre_launch(s, w.tb[0].Out, w.y, w.sd, w.act, w.dlogp, w.mirror ? w.dy : (const float*)nullptr, -c.entropy_coef / (float)R, hp, R, w.tb[0].dOut);
+  actor_head_train_bwd_launch(s, w.keep, hp, T, B, w.tb[0].dOut);
   if (!fused_critic_head) KBJ_HIP(ctx, hipMemcpy2DAsync(w.tb[1].dOut, 40 * sizeof(float), w.dvalue, sizeof(float), sizeof(float), R, hipMemcpyDeviceToDevice, ns[1]));
   if (w.mirror) {   // the mirror actor only sees the aux gradient on its filtered mean (no log-prob, no entropy term)
-    hipLaunchKernelGGL(actor_head_bwd_pre_kernel, g1((size_t)R * KBJ_NU), dim3(256), 0, s, w.tb[2].Out, w.y_m, w.sd_m, w.y_m, w.zeroR, w.dy_m, 0.0f, hp, R, w.tb[2].dOut);
-    hipLaunchKernelGGL(actor_head_train_bwd_kernel, g1((size_t)B * KBJ_NU, 64), dim3(64), 0, s, w.keep, hp, T, B, w.tb[2].dOut);
+    actor_head_bwd_pre_launch(s, w.tb[2].Out, w.y_m, w.sd_m, w.y_m, w.zeroR, w.dy_m, 0.0f, hp, R, w.tb[2].dOut);
+    actor_head_train_bwd_launch(s, w.keep, hp, T, B, w.tb[2].dOut);
     KBJ_HIP(ctx, hipMemcpy2DAsync(w.tb[3].dOut, 40 * sizeof(float), w.dvalue_m, sizeof(float), sizeof(float), R, hipMemcpyDeviceToDevice, ns[1]));
   }
   // The critical path of a net is dOut -> dH -> (recurrence, dX) per layer. Weight/bias gradients hang off it: they go to the
@@ -1252,9 +1185,9 @@ int ppo_grad_body(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const
   auto fold_bias_terms = [&](int k, hipStream_t st) {
     const NetOff& oa = w.net[k];
     float* part = det_partials(ctx, st);
-    hipLaunchKernelGGL(matvec_t_acc_kernel, dim3((H + 63) / 64, 16), dim3(256), 0, st, params_d + oa.w_ih[0], grad_d + oa.b[0], 4 * H, H, grad_d + oa.b_in, part);
-    if (part) reduce_rows_launch(st, part, 16, H, grad_d + oa.b_in);
-    hipLaunchKernelGGL(outer_acc_kernel, g1((size_t)4 * H * H), dim3(256), 0, st, grad_d + oa.w_ih[0], grad_d + oa.b[0], params_d + oa.b_in, 4 * H, H);
+    matvec_t_acc_launch(st, params_d + oa.w_ih[0], grad_d + oa.b[0], 4 * H, H, grad_d + oa.b_in, part);
+    if (part) reduce_rows_launch(st, part, MATVEC_T_SLICES, H, grad_d + oa.b_in);
+    outer_acc_launch(st, grad_d + oa.w_ih[0], grad_d + oa.b[0], params_d + oa.b_in, 4 * H, H);
   };
   bool bias_done[2] = {false, false};
   // WHERE A LAYER'S WEIGHT-GRADIENT PAIR RUNS (round 6: explicit stream order, no pause kernel). The input gradient of layer l is on the
@@ -1366,7 +1299,7 @@ int ppo_grad_body(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const
   // A data-parallel host may start its all-reduce now, under the critic's tail (kbj_stream_wait_actor_grad).
   if (fold_actor && !bias_done[0]) fold_bias_terms(0, ns[0]);
   if (!one_stream) hipStreamWaitEvent(ns[0], ev_critic_loss, 0);   // (fired ~3 ms ago)
-  hipLaunchKernelGGL(ppo_metrics_kernel, dim3(1), dim3(1), 0, ns[0], w.stats + 2, w.stats, pp, R, metrics_d);
+  ppo_metrics_launch(ns[0], w.stats + 2, w.stats, pp, R, metrics_d);
   if (one_stream) {
     if (fold_actor && fold_critic && !bias_done[1]) fold_bias_terms(1, ns[1]);
     hipLaunchKernelGGL(lane_tail_kernel, dim3(2 * MAXD * 4), dim3(SEQ_COUNTER_WORDS), 0, ctx->stream, w.seq_counters, -1, w.seq_err, grad_d, grad_d + w.nactor);
@@ -1486,8 +1419,8 @@ int kbj_adamw_step(kbj_ctx* ctx, float* params_d, float* m_d, float* v_d, const 
   if (!w.sumsq_clean) KBJ_HIP(ctx, hipMemsetAsync(sumsq, 0, sizeof(double), s));
   w.sumsq_clean = false;
   double* part = w.sched.deterministic ? w.detd : nullptr;
-  hipLaunchKernelGGL(sumsq_kernel, dim3(512), dim3(256), 0, s, grad_d, w.user.nparams, grad_scale, sumsq, part);
-  if (part) reduce_double_launch(s, part, 512, 1, sumsq);
+  sumsq_launch(s, grad_d, w.user.nparams, grad_scale, sumsq, part);
+  if (part) reduce_double_launch(s, part, SUMSQ_BLOCKS, 1, sumsq);
   AdamParams ap{c.learning_rate, c.adam_b1, c.adam_b2, c.adam_eps, c.weight_decay, c.max_grad_norm,
                 (float)(1.0 - std::pow((double)c.adam_b1, (double)step)), (float)(1.0 - std::pow((double)c.adam_b2, (double)step)), grad_scale};
   hipLaunchKernelGGL(adamw_kernel, g1(w.user.nparams), dim3(256), 0, s, params_d, m_d, v_d, grad_d, w.user.nparams, sumsq, ap, w.seq_err);

@@ -4,11 +4,17 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
+#include <vector>
 #include "kbj_model.h"
+#include "kbj_lstm_seq.h"   // dispatch_hidden (critic_head_launch)
 
 namespace kbj {
 
 constexpr float kLog2Pi = 1.8378770664093453f;
+// The grid of a one-dimensional launch over n elements. Every kernel below has its launch configuration in a ctx-free *_launch helper beside it:
+// kbj_nn.hip calls the helpers, and so do the stand-alone kernel checks under tools/, so grids and blocks are under test with the kernels.
+inline dim3 g1(size_t n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
 
 // gate non-linearities on the hardware exp/rcp units (same definitions as kbj_lstm_seq.h so rollout and update agree)
 __device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }      // same forms as kbj_lstm_seq.h seq_sigmoid / seq_tanh
@@ -159,6 +165,9 @@ __global__ void critic_value_kernel(const float* __restrict__ out, int ld, int N
   int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n < N) value[n] = out[(size_t)n * ld];
 }
+inline void critic_value_launch(hipStream_t st, const float* out, int ld, int N, float* value) {
+  hipLaunchKernelGGL(critic_value_kernel, g1(N), dim3(256), 0, st, out, ld, N, value);
+}
 
 // carry <- carry * (done == 0) (train.py:1502-1506): 2 x depth [cnt][H] planes (h0, c0, h1, c1, ... - the h planes may live in the
 // rollout's ping-pong scratch), lpf [cnt][20]
@@ -197,12 +206,13 @@ __global__ void gather_rows4_kernel(const float4* __restrict__ src, const int* _
   int b = r % B, t = r / B;
   dst[r * ld_dst4 + k] = src[((size_t)t * N + idx[b]) * ld_src4 + k];
 }
-// keep[t][b] = 1 - (aux[t][idx[b]][DONE] != 0)
-__global__ void gather_keep_kernel(const float* __restrict__ aux, const int* __restrict__ idx, int T, int N, int B, float* __restrict__ keep) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= T * B) return;
-  int b = i % B, t = i / B;
-  keep[i] = aux[((size_t)t * N + idx[b]) * KBJ_AUX_SIZE + KBJ_AUX_DONE] != 0 ? 0.0f : 1.0f;
+// rows of `wdt` floats out of rows `lds` apart into rows `ldd` apart: the 16-byte form where widths, strides and both bases allow it
+inline void gather_rows_launch(hipStream_t st, const float* src, const int* idx, int T, int N, int B, int wdt, int lds, float* dst, int ldd) {
+  const size_t R = (size_t)T * B;
+  if (wdt % 4 == 0 && lds % 4 == 0 && ldd % 4 == 0 && ((size_t)src & 15) == 0 && ((size_t)dst & 15) == 0)
+    hipLaunchKernelGGL(gather_rows4_kernel, g1(R * (wdt / 4)), dim3(256), 0, st, reinterpret_cast<const float4*>(src), idx, T, N, B, wdt / 4, lds / 4, ldd / 4,
+                       reinterpret_cast<float4*>(dst));
+  else hipLaunchKernelGGL(gather_rows_kernel, g1(R * wdt), dim3(256), 0, st, src, idx, T, N, B, wdt, lds, ldd, dst);
 }
 
 // all per-sample scalars of the minibatch in one launch: action (20 columns), old log-prob, old value, advantage, target, keep
@@ -226,6 +236,9 @@ __global__ void gather_small_kernel(GatherSmallArgs a, const int* __restrict__ i
   else if (c == KBJ_NU + 3) { if (a.target) a.target_o[r] = a.target[src]; }
   else a.keep_o[r] = a.aux[src * KBJ_AUX_SIZE + KBJ_AUX_DONE] != 0 ? 0.0f : 1.0f;
 }
+inline void gather_small_launch(hipStream_t st, const GatherSmallArgs& a, const int* idx, int T, int N, int B, int c0, int c1) {
+  hipLaunchKernelGGL(gather_small_kernel, g1((size_t)T * B * (c1 - c0)), dim3(256), 0, st, a, idx, T, N, B, c0, c1);
+}
 // the carries at the start of the trajectory: up to 16 [N][H] planes and 2 [N][20] low-pass states, one launch (blockIdx.y = plane)
 struct GatherCarryArgs { const float* src[8 * KBJ_MAX_DEPTH + 2]; float* dst[8 * KBJ_MAX_DEPTH + 2]; int nplanes, nlpf; };   // 4 nets x depth x (h, c) + 2 low-pass states
 __global__ void gather_carry_kernel(GatherCarryArgs a, const int* __restrict__ idx, int B, int H) {
@@ -235,6 +248,9 @@ __global__ void gather_carry_kernel(GatherCarryArgs a, const int* __restrict__ i
   if (i >= B * w) return;
   int b = i / w, k = i - b * w;
   a.dst[p][i] = a.src[p][(size_t)idx[b] * w + k];
+}
+inline void gather_carry_launch(hipStream_t st, const GatherCarryArgs& a, const int* idx, int B, int H) {
+  hipLaunchKernelGGL(gather_carry_kernel, dim3((B * H + 255) / 256, a.nplanes + a.nlpf), dim3(256), 0, st, a, idx, B, H);
 }
 
 // ---- actor head over a minibatch trajectory: per (b, j) thread scans time (low-pass filter recursion) --------------
@@ -248,6 +264,9 @@ __global__ void actor_head_pre_kernel(const float* __restrict__ out, const float
   int j = (int)(i - r * KBJ_NU);
   y[i] = out[r * 40 + j] + joint_bias[j] + (j >= 10 ? obs[r * hp.ld_obs + KBJ_OBS_CMD + 6 + (j - 10)] : 0.0f);
   sd[i] = fminf((softplusf_(out[r * 40 + KBJ_NU + j]) + hp.min_std) * hp.var_scale, hp.max_std);
+}
+inline void actor_head_pre_launch(hipStream_t st, const float* out, const float* obs, const float* joint_bias, HeadParams hp, int R, float* y, float* sd) {
+  hipLaunchKernelGGL(actor_head_pre_kernel, g1((size_t)R * KBJ_NU), dim3(256), 0, st, out, obs, joint_bias, hp, R, y, sd);
 }
 // stage 2 (one thread per (b, j), serial in t): one-pole low-pass over the means in place, state reset where done
 __global__ void actor_head_train_fwd_kernel(const float* __restrict__ keep, const float* __restrict__ lpf0, HeadParams hp, int T, int B, float* __restrict__ y) {
@@ -274,6 +293,9 @@ __global__ void actor_head_train_fwd_kernel(const float* __restrict__ keep, cons
     }
   }
 }
+inline void actor_head_train_fwd_launch(hipStream_t st, const float* keep, const float* lpf0, HeadParams hp, int T, int B, float* y) {
+  hipLaunchKernelGGL(actor_head_train_fwd_kernel, g1((size_t)B * KBJ_NU, 64), dim3(64), 0, st, keep, lpf0, hp, T, B, y);
+}
 // logp[r] / entropy[r] from y, sd, act (one thread per (t,b))
 __global__ void gaussian_logp_kernel(const float* __restrict__ y, const float* __restrict__ sd, const float* __restrict__ act, int R,
                                      float* __restrict__ logp, float* __restrict__ ent) {
@@ -286,6 +308,9 @@ __global__ void gaussian_logp_kernel(const float* __restrict__ y, const float* _
     en += 0.5f + 0.5f * kLog2Pi + logf(s);
   }
   logp[r] = lp; ent[r] = en;
+}
+inline void gaussian_logp_launch(hipStream_t st, const float* y, const float* sd, const float* act, int R, float* logp, float* ent) {
+  hipLaunchKernelGGL(gaussian_logp_kernel, g1(R), dim3(256), 0, st, y, sd, act, R, logp, ent);
 }
 
 // ---- PPO loss (restated ksim defaults): statistics pass then per-sample gradient coefficients ------------
@@ -302,6 +327,10 @@ __global__ void adv_stats_kernel(const float* __restrict__ adv, int R, double* _
     if (part) { part[2 * blockIdx.x] = s1[0]; part[2 * blockIdx.x + 1] = s2[0]; }
     else { atomicAdd(&stats[0], s1[0]); atomicAdd(&stats[1], s2[0]); }   // stats zeroed by the caller
   }
+}
+constexpr int ADV_STATS_BLOCKS = 32;   // workgroups of adv_stats_kernel = pairs of partials in deterministic mode
+inline void adv_stats_launch(hipStream_t st, const float* adv, int R, double* stats, double* part) {
+  hipLaunchKernelGGL(adv_stats_kernel, dim3(ADV_STATS_BLOCKS), dim3(256), 0, st, adv, R, stats, part);
 }
 // out[j] += sum over blocks b (in order) of part[b * w + j], j < w (w <= 64): the fixed-order second stage of the double-precision sums.
 // ONE workgroup of 256 threads. The order of the additions is what fixes the bits - a chain from zero over b = 0, 1, ..., then out += s - and a
@@ -401,6 +430,10 @@ __global__ void ppo_loss_kernel(const float* __restrict__ logp, const float* __r
   for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) for (int k = 0; k < 5; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + o]; __syncthreads(); }
   if (threadIdx.x == 0) for (int k = 0; k < 5; ++k) if (k == 1 ? (part & 2) : (part & 1)) atomicAdd(&macc[k], red[k][0]);
 }
+inline void ppo_loss_launch(hipStream_t st, const float* logp, const float* value, const float* ent, const float* logp_old, const float* value_old, const float* adv,
+                            const float* target, const double* stats, PpoParams pp, int R, float* dlogp, float* dvalue, double* macc, int part) {
+  hipLaunchKernelGGL(ppo_loss_kernel, g1(R), dim3(256), 0, st, logp, value, ent, logp_old, value_old, adv, target, stats, pp, R, dlogp, dvalue, macc, part);
+}
 // critic head, fused (one output, train.py:993-1004 + the value terms of the PPO loss): value = h w + b -> clipped value loss ->
 // dL/dvalue -> dL/dh = dL/dvalue * w, all in one pass over the top layer's output rows (one wavefront per row, VPL = H / 64 floats per
 // lane). Replaces a [R x H] x [H x 1] GEMM, the value gather, the value half of ppo_loss_kernel, a strided copy and a K = 1 GEMM on
@@ -437,6 +470,15 @@ __global__ void critic_head_kernel(const float* __restrict__ h, const float* __r
   __syncthreads();
   if (threadIdx.x == 0) atomicAdd(&macc[1], red[0] + red[1] + red[2] + red[3]);
 }
+// false: no instantiation for this hidden size (built for 64, 128, ..., 512)
+inline bool critic_head_launch(hipStream_t st, int H, const float* h, const float* w_out, const float* b_out, const float* value_old, const float* target, PpoParams pp, int R,
+                               float* value, float* dvalue, float* dout, float* dh, double* macc) {
+  const dim3 grid(2048), block(256);
+  return dispatch_hidden(H, [&](auto hc) {
+    hipLaunchKernelGGL((critic_head_kernel<decltype(hc)::value / 64>), grid, block, 0, st, h, w_out, b_out, value_old, target, pp, R, value, dvalue, dout, dh, macc);
+    return true;
+  });
+}
 // metrics[10] = loss, policy, value, entropy, clipfrac, kl, adv_mean, adv_std, action_mirror_loss, value_mirror_loss
 __global__ void ppo_metrics_kernel(const double* __restrict__ macc, const double* __restrict__ stats, PpoParams pp, int R, float* __restrict__ metrics) {
   double pol = macc[0] / R, vl = macc[1] / R, en = macc[2] / R, ma = macc[5] / R, mc = macc[6] / R;
@@ -446,6 +488,9 @@ __global__ void ppo_metrics_kernel(const double* __restrict__ macc, const double
   metrics[8] = (float)ma; metrics[9] = (float)mc;
   metrics[1] = (float)pol; metrics[2] = (float)vl; metrics[3] = (float)en; metrics[4] = (float)(macc[3] / R); metrics[5] = (float)(macc[4] / R);
   metrics[6] = (float)mean; metrics[7] = (float)sqrt(var > 0 ? var : 0);
+}
+inline void ppo_metrics_launch(hipStream_t st, const double* macc, const double* stats, PpoParams pp, int R, float* metrics) {
+  hipLaunchKernelGGL(ppo_metrics_kernel, dim3(1), dim3(1), 0, st, macc, stats, pp, R, metrics);
 }
 
 // ---- mirror aux losses (train.py:1463-1481, 1574-1756) ---------------------------------------------------------------
@@ -459,6 +504,56 @@ __global__ void mirror_rows_kernel(const float* __restrict__ in, float* __restri
   int k = (int)(i - r * ld);
   MirrorEntry e = tab[k];
   out[i] = e.mul * in[r * ld + e.src] + e.add;
+}
+// Mirror of the packed observation rows as (source index, multiplier, offset) per element (mirror_rows_kernel).
+// Follows the index/sign lists of the reference's mirror_obs functions (train.py:1574-1756); element order = the obs packing
+// of kbj_env_task.h write_obs (kbj_model.h KBJ_NOBS_*).
+// extra_actor / extra_critic user columns behind the reference's are carried over unchanged (identity entries): a user term that is not
+// mirror-invariant has to be mirrored by the user's own mirror-loss code, as in the reference (train.py:1574-1756 names every key).
+inline void build_mirror_tables(const kbj_model& m, std::vector<MirrorEntry>& ta, std::vector<MirrorEntry>& tc, int extra_actor = 0, int extra_critic = 0) {
+  auto swp = [](int i) { return i < 5 ? i + 5 : (i < 10 ? i - 5 : i); };  // left leg <-> right leg, arms stay (train.py:1574-1582)
+  tc.assign(KBJ_LD_CRITIC, MirrorEntry{0, 0.0f, 0.0f});
+  for (int k = 0; k < KBJ_LD_CRITIC; ++k) tc[k].src = k;
+  auto keep = [&](int k, float sgn) { tc[k] = MirrorEntry{k, sgn, 0.0f}; };
+  for (int i = 0; i < KBJ_NU; ++i) {
+    int s = swp(i);
+    auto rng = [&](int j) { return std::fmax(m.joint_bias[j] - m.joint_lo[j], m.joint_hi[j] - m.joint_bias[j]); };
+    tc[KBJ_OBS_JPOS + i] = MirrorEntry{KBJ_OBS_JPOS + s, -rng(s) / rng(i), (-m.joint_bias[s] - m.joint_bias[i]) / rng(i)};   // normalised joint positions
+    tc[KBJ_OBS_JVEL + i] = MirrorEntry{KBJ_OBS_JVEL + s, -1.0f, 0.0f};                                                      // joint velocities / 10
+    tc[KBJ_OBS_ACTFRC + i] = MirrorEntry{KBJ_OBS_ACTFRC + s, -1.0f, 0.0f};                                                  // actuator force / 4 (critic)
+  }
+  // roll, pitch, unit projected gravity: the reference mirrors the raw vector (g0, -g1, g2) and encodes it again (train.py:1596-1603,
+  // 1338-1349): roll = atan2(g1, -g2) changes sign, pitch and the norm do not
+  keep(KBJ_OBS_PG, -1); keep(KBJ_OBS_PG + 1, 1); keep(KBJ_OBS_PG + 2, 1); keep(KBJ_OBS_PG + 3, -1); keep(KBJ_OBS_PG + 4, 1);
+  keep(KBJ_OBS_GYRO, -1); keep(KBJ_OBS_GYRO + 1, 1); keep(KBJ_OBS_GYRO + 2, -1);   // gyro
+  keep(KBJ_OBS_ZEROCMD, 1);                                                          // zero-command flag (the norm of cmd[0:3] is mirror invariant)
+  const float cs[16] = {1, -1, -1, 1, -1, 1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // vx, vy, wz, height, roll, pitch, 10 arm targets
+  for (int k = 0; k < 16; ++k) keep(KBJ_OBS_CMD + k, cs[k]);
+  ta.assign(tc.begin(), tc.begin() + KBJ_LD_ACTOR);
+  for (int k = KBJ_NOBS_ACTOR; k < KBJ_LD_ACTOR; ++k) ta[k] = MirrorEntry{k, 0.0f, 0.0f};
+  tc[KBJ_OBS_TOUCH] = MirrorEntry{KBJ_OBS_TOUCH + 1, 1, 0}; tc[KBJ_OBS_TOUCH + 1] = MirrorEntry{KBJ_OBS_TOUCH, 1, 0};           // foot touch L <-> R
+  const float fs[3] = {1, -1, 1};
+  for (int k = 0; k < 3; ++k) { tc[KBJ_OBS_FEETPOS + k] = MirrorEntry{KBJ_OBS_FEETPOS + 3 + k, fs[k], 0}; tc[KBJ_OBS_FEETPOS + 3 + k] = MirrorEntry{KBJ_OBS_FEETPOS + k, fs[k], 0}; }   // feet positions
+  keep(KBJ_OBS_BASEPOS, 1); keep(KBJ_OBS_BASEPOS + 1, 1); keep(KBJ_OBS_BASEPOS + 2, 1);                                      // base position
+  keep(KBJ_OBS_BASEQUAT, 1); keep(KBJ_OBS_BASEQUAT + 1, -1); keep(KBJ_OBS_BASEQUAT + 2, -1); keep(KBJ_OBS_BASEQUAT + 3, 1);  // base quaternion
+  const float ci[10] = {1, 1, -1, 1, 1, 1, 1, -1, 1, -1}, cv[6] = {1, -1, 1, -1, 1, -1};
+  for (int b = 0; b < 23; ++b) {
+    for (int k = 0; k < 10; ++k) keep(KBJ_OBS_CINERT + 10 * b + k, ci[k]);      // cinert
+    for (int k = 0; k < 6; ++k) keep(KBJ_OBS_CVEL + 6 * b + k, cv[k]);          // cvel
+  }
+  keep(KBJ_OBS_LINVEL, 1); keep(KBJ_OBS_LINVEL + 1, -1); keep(KBJ_OBS_LINVEL + 2, 1);     // base linear velocity
+  keep(KBJ_OBS_ANGVEL, -1); keep(KBJ_OBS_ANGVEL + 1, 1); keep(KBJ_OBS_ANGVEL + 2, -1);    // base angular velocity
+  keep(KBJ_OBS_HEIGHT, 1);                                                                 // base height
+  for (int k = KBJ_NOBS_CRITIC; k < KBJ_LD_CRITIC; ++k) tc[k] = MirrorEntry{k, 0.0f, 0.0f};
+  auto widen = [](std::vector<MirrorEntry>& t, int nobs, int extra) {
+    t.resize(KBJ_LD_OF(nobs + extra));
+    for (int k = nobs; k < (int)t.size(); ++k) t[k] = MirrorEntry{k, k < nobs + extra ? 1.0f : 0.0f, 0.0f};
+  };
+  if (extra_actor > 0) widen(ta, KBJ_NOBS_ACTOR, extra_actor);
+  if (extra_critic > 0) widen(tc, KBJ_NOBS_CRITIC, extra_critic);
+}
+inline void mirror_rows_launch(hipStream_t st, const float* in, float* out, size_t rows, int ld, const MirrorEntry* tab) {
+  hipLaunchKernelGGL(mirror_rows_kernel, g1(rows * ld), dim3(256), 0, st, in, out, rows, ld, tab);
 }
 // mirror branch of the actor head at rollout time: only the low-pass state advances (no sampling)
 __global__ void actor_head_lpf_kernel(const float* __restrict__ out, const float* __restrict__ obs, float* __restrict__ lpf,
@@ -498,6 +593,10 @@ __global__ void mirror_loss_kernel(const float* __restrict__ y, const float* __r
     atomicAdd(&macc[6], (double)(sc * ev * ev));
   }
 }
+inline void mirror_loss_launch(hipStream_t st, const float* y, const float* ym, const float* v, const float* vm, float sa, float sc, int R, float* dy, float* dym,
+                               float* dvalue, float* dvalue_m, double* macc, int part) {
+  hipLaunchKernelGGL(mirror_loss_kernel, g1(R), dim3(256), 0, st, y, ym, v, vm, sa, sc, R, dy, dym, dvalue, dvalue_m, macc, part);
+}
 
 // actor head backward: per (b, j) thread, reverse scan through the low-pass recursion.
 // dL/dlogp [T][B] and the constant entropy coefficient (+ an optional direct gradient on y) -> dOut [T][B][40]
@@ -517,6 +616,10 @@ __global__ void actor_head_bwd_pre_kernel(const float* __restrict__ out, const f
   float raw = out[r * 40 + KBJ_NU + j];
   float pre = (softplusf_(raw) + hp.min_std) * hp.var_scale;
   dout[r * 40 + KBJ_NU + j] = pre < hp.max_std ? gs * hp.var_scale * sigmoidf_(raw) : 0.0f;
+}
+inline void actor_head_bwd_pre_launch(hipStream_t st, const float* out, const float* y, const float* sd, const float* act, const float* dlogp, const float* dy_extra,
+                                      float dent, HeadParams hp, int R, float* dout) {
+  hipLaunchKernelGGL(actor_head_bwd_pre_kernel, g1((size_t)R * KBJ_NU), dim3(256), 0, st, out, y, sd, act, dlogp, dy_extra, dent, hp, R, dout);
 }
 // stage 2 (one thread per (b, j), reverse scan through the low-pass recursion), in place on dout[.., j]
 __global__ void actor_head_train_bwd_kernel(const float* __restrict__ keep, HeadParams hp, int T, int B, float* __restrict__ dout) {
@@ -543,6 +646,9 @@ __global__ void actor_head_train_bwd_kernel(const float* __restrict__ keep, Head
     }
   }
 }
+inline void actor_head_train_bwd_launch(hipStream_t st, const float* keep, HeadParams hp, int T, int B, float* dout) {
+  hipLaunchKernelGGL(actor_head_train_bwd_kernel, g1((size_t)B * KBJ_NU, 64), dim3(64), 0, st, keep, hp, T, B, dout);
+}
 
 // y[m] = sum_k W[m][k] x[k] + add[m]   (W [M][K] row-major; one thread per row)
 // one wavefront per output row (launch: M / 4 blocks of 256 threads): coalesced reads along k, DPP-free shuffle reduction
@@ -553,6 +659,9 @@ __global__ void matvec_kernel(const float* __restrict__ W, const float* __restri
   for (int k = l; k < K; k += 64) s += W[(size_t)m * K + k] * x[k];
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
   if (l == 0) y[m] = s + (add ? add[m] : 0.0f);
+}
+inline void matvec_launch(hipStream_t st, const float* W, const float* x, const float* add, int M, int K, float* y) {
+  hipLaunchKernelGGL(matvec_kernel, dim3((M + 3) / 4), dim3(256), 0, st, W, x, add, M, K, y);
 }
 // y[n] += sum_k W[k][n] x[k]   (W [K][N] row-major): block = 64 columns x 4 row phases, grid.y slices of k, one atomic per column and
 // block (a single thread per column walking all K rows serially took 270 us on the critical path of every minibatch)
@@ -569,6 +678,10 @@ __global__ void matvec_t_acc_kernel(const float* __restrict__ W, const float* __
     if (part) part[(size_t)blockIdx.y * N + n] = v; else atomicAdd(&y[n], v);
   }
 }
+constexpr int MATVEC_T_SLICES = 16;   // k slices of matvec_t_acc_kernel = partial rows in deterministic mode
+inline void matvec_t_acc_launch(hipStream_t st, const float* W, const float* x, int K, int N, float* y, float* part) {
+  hipLaunchKernelGGL(matvec_t_acc_kernel, dim3((N + 63) / 64, MATVEC_T_SLICES), dim3(256), 0, st, W, x, K, N, y, part);
+}
 
 // dst[r][0:ld_dst] = src[r][0:cols] followed by zeros: a weight matrix whose row length is not a multiple of 4 (the critic's 475-wide
 // input projection) re-pitched to 16-byte aligned rows, so that the GEMM takes its vector-free buffer-load path for it
@@ -578,12 +691,18 @@ __global__ void repitch_rows_kernel(const float* __restrict__ src, int rows, int
   const int r = i / ld_dst, c = i - r * ld_dst;
   dst[i] = c < cols ? src[(size_t)r * cols + c] : 0.0f;
 }
+inline void repitch_rows_launch(hipStream_t st, const float* src, int rows, int cols, int ld_dst, float* dst) {
+  hipLaunchKernelGGL(repitch_rows_kernel, g1((size_t)rows * ld_dst), dim3(256), 0, st, src, rows, cols, ld_dst, dst);
+}
 
 // C[m][n] += u[m] v[n]   (rank-1 update, C [M][N] row-major)
 __global__ void outer_acc_kernel(float* __restrict__ C, const float* __restrict__ u, const float* __restrict__ v, int M, int N) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (size_t)M * N) return;
   C[i] += u[i / N] * v[i % N];
+}
+inline void outer_acc_launch(hipStream_t st, float* C, const float* u, const float* v, int M, int N) {
+  hipLaunchKernelGGL(outer_acc_kernel, g1((size_t)M * N), dim3(256), 0, st, C, u, v, M, N);
 }
 
 // column sums: out[n] (+)= sum_m X[m][n]  (bias gradients); one block per 64 columns, 256 threads = 4 row phases
@@ -642,6 +761,10 @@ __global__ void colsum_kernel(const float* __restrict__ X, int M, int N, int ld,
     if (part) part[(size_t)blockIdx.y * N + c] = v; else atomicAdd(&out[c], v);
   }
 }
+constexpr int DETP_ROWS = 512;   // row slices of colsum_kernel = partial rows in deterministic mode
+inline void colsum_launch(hipStream_t st, const float* X, int M, int N, int ld, float* out, float* part) {
+  hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64, DETP_ROWS), dim3(256), 0, st, X, M, N, ld, out, part);
+}
 
 // ---- GAE (gamma, lambda train.py:1769-1770): one thread per env, reverse scan ------------------------------------------
 __global__ void gae_kernel(const float* __restrict__ value, const float* __restrict__ reward, const float* __restrict__ aux, int T, int N,
@@ -693,6 +816,10 @@ __global__ void sumsq_kernel(const float* __restrict__ g, size_t n, float scale,
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
   if (threadIdx.x == 0) { if (part) part[blockIdx.x] = red[0]; else atomicAdd(out, red[0]); }
+}
+constexpr int SUMSQ_BLOCKS = 512;   // workgroups of sumsq_kernel = partials in deterministic mode
+inline void sumsq_launch(hipStream_t st, const float* g, size_t n, float scale, double* out, double* part) {
+  hipLaunchKernelGGL(sumsq_kernel, dim3(SUMSQ_BLOCKS), dim3(256), 0, st, g, n, scale, out, part);
 }
 struct AdamParams { float lr, b1, b2, eps, wd, max_norm, bc1, bc2, gscale; };
 // Fail-stop: a gradient whose global norm is not finite leaves parameters and moments untouched and raises err[1]; err[0] is the
@@ -753,6 +880,9 @@ __global__ void repitch_pad_kernel(const float* __restrict__ src, float* __restr
   if (i >= rows * wd) return;
   const size_t r = i / wd; const int c = (int)(i % wd);
   dst[i] = c < ws ? src[r * ws + c] : 0.0f;
+}
+inline void repitch_pad_launch(hipStream_t st, const float* src, float* dst, size_t rows, int ws, int wd) {
+  hipLaunchKernelGGL(repitch_pad_kernel, g1(rows * wd), dim3(256), 0, st, src, dst, rows, ws, wd);
 }
 
 // ---- parameter init: U(+-1/sqrt(fan_in)) per leaf (equinox default), threefry stream KBJ_RNG_INIT ------------------------

@@ -1,5 +1,5 @@
 """What the drivers of the stand-alone programs under tools/ share (test_gpu_tools.py, test_gpu_det_reductions.py, test_gpu_lstm_check.py,
-test_gpu_head_check.py):
+test_gpu_head_check.py, test_gpu_update_check.py):
 build the program from source with hipcc on the box that runs it, run it, and the closing checks every kernel check's report has to meet."""
 import os
 import subprocess

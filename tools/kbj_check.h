@@ -1,4 +1,4 @@
-// What the kernel checks under tools/ share (gemm_check, reduce_check, lstm_check, head_check): error exit, hashes and fill values, rounding constants,
+// What the kernel checks under tools/ share (gemm_check, reduce_check, lstm_check, head_check, update_check): error exit, hashes and fill values, rounding constants,
 // the documented-order sums, the guarded device memory and the tally with its closing lines. Each tool is ONE translation unit that
 // includes this header once; value families, bounds, case tables and `case` lines are the tool's own.
 //
