@@ -139,7 +139,11 @@ typedef struct kbj_config {
   int32_t enable_pushes;
   int32_t enable_noise;
   int32_t max_episode_steps; /* 12 s / 0.02 s = 600 */
-  int32_t solver_newton;     /* 1 = Newton direction (default), 0 = Polak-Ribiere CG */
+  int32_t solver_newton;     /* constraint solver of the physics step, both served by their own HIP kernels. 1 (default) = Newton direction with the exact
+                              * Hessian; 0 = Polak-Ribiere CG on the M^-1-preconditioned gradient: search = -Mgrad + max(0, grad.(Mgrad - Mgrad_old) /
+                              * (grad_old.Mgrad_old)) search, the first iteration of a solve steepest descent. Warm start, exit tests and line search
+                              * are shared. At the launch block's iterations=8, ls_iterations=8 (train.py:1777-1778) CG stops at the cap where
+                              * Newton has converged: a different dynamics. Any other value is refused (kbj_check_config) */
   int32_t deterministic;     /* 1 = the PPO update reduces in a fixed order (split-K slabs, per-block partials) instead of with fp32 / fp64 atomics:
                                 two updates from the same state give bit-identical parameters, as the reference's XLA program does; default 0 */
   int32_t extra_obs_actor;   /* floats the host appends to every actor / critic observation row (0..KBJ_MAX_EXTRA_OBS, default 0): the input */

@@ -57,7 +57,8 @@ int kbj_check_config(const kbj_config* cfg, char* why, size_t why_bytes) {
   if (!cfg) return fail("null config");
   if (cfg->num_envs <= 0 || cfg->substeps <= 0 || cfg->rollout_len <= 0) return fail("bad config sizes");
   if (cfg->command_mode < 0 || cfg->command_mode > 2) return fail("command_mode must be 0 (UnifiedCommand sampler), 1 (fixed command) or 2 (the sampler with jax.random's key handling)");
-  if (cfg->solver_newton != 1) return fail("only the Newton solver is implemented on the GPU (solver_newton = 1)");
+  if (cfg->solver_newton != 0 && cfg->solver_newton != 1)
+    return fail("solver_newton must be 1 (Newton direction, the default) or 0 (Polak-Ribiere CG on the M^-1-preconditioned gradient), not " + std::to_string(cfg->solver_newton));
   if (cfg->hidden_size < 1 || cfg->hidden_size > 512 || cfg->depth < 1 || cfg->depth > KBJ_MAX_DEPTH)
     return fail("hidden_size must be in 1..512 (multiples of 64 run unpadded; above 256 on the wide, untuned schedule) and depth in 1..4 (train.py:78-85 defaults 128 / 2, launch 256 / 2)");
   if (cfg->extra_obs_actor < 0 || cfg->extra_obs_actor > KBJ_MAX_EXTRA_OBS || cfg->extra_obs_critic < 0 || cfg->extra_obs_critic > KBJ_MAX_EXTRA_OBS)
@@ -229,6 +230,7 @@ int kbj_profile_end(kbj_ctx* ctx, float* env_step_ms, int* env_step_launches, fl
     else if (k == KBJ_KIND_SEQ_BWD16) snprintf(st.name, sizeof(st.name), "%s<%d>", names[k], hk);
     else if (k == KBJ_KIND_LSTM_STEP || k == KBJ_KIND_LSTM_STEP_OBS)
       snprintf(st.name, sizeof(st.name), "%s<%d, 2, %d>", names[k], hk, k == KBJ_KIND_LSTM_STEP_OBS ? KBJ_LD_ACTOR : hk);
+    else if (k == KBJ_KIND_ENV_STEP) snprintf(st.name, sizeof(st.name), "%s", ctx->cfg_h.solver_newton ? names[k] : "env_step_cg_kernel");
     else snprintf(st.name, sizeof(st.name), "%s", names[k]);
     st.launches = 0; st.total_ms = 0; st.flops = 0;
   }

@@ -12,47 +12,59 @@ namespace {
 
 
 
+// The constraint solver (kbj_config.solver_newton; kbj_env_phys.h phys_solve<CG>) is a compile-time parameter of every kernel that runs a
+// forward pass, and each of them exists twice: the Newton ones keep their names and, instruction for instruction, the code they had before CG
+// was served; the `_cg_` ones sit beside them. The host picks the symbol at launch from the context's config (KBJ_LAUNCH_SOLVER below);
+// nothing branches on the solver inside a kernel. The three reset-type kernels are stamped out of a macro each rather than wrapped around
+// an inlined body: the extra inlining level changes hipcc's register allocation and packing of the Newton form.
+//
 // grid = N workgroups of one wavefront; env state rows are read/written lane-contiguously (coalesced)
-__global__ __launch_bounds__(64) void env_reset_kernel(const kbj_model* __restrict__ m, const kbj_config* __restrict__ c, const float* __restrict__ mc, const PhysConst* __restrict__ pcp, uint32_t seed,
-                                                       float* __restrict__ ep, float* __restrict__ es, float* actor0, float* critic0, float* aux0) {
-  __shared__ KbjShared S;
-  const int env = blockIdx.x;
-  PFOR(k, (int)(sizeof(KbjModelLds) / sizeof(float))) reinterpret_cast<float*>(&S.mc)[k] = mc[k];
-  PFOR(k, (int)(sizeof(PhysConst) / sizeof(float))) reinterpret_cast<float*>(&S.pc)[k] = reinterpret_cast<const float*>(pcp)[k];
-  PFOR(k, KBJ_ES_SIZE) S.es[k] = 0;
-  PFOR(k, 12) S.zrow[k] = 0;
-  KBJ_SYNC();
-  Rng rng{seed, (uint32_t)(c->env_id_offset + env)};
-  const PhysConst& pc = S.pc;
-  task_reset(S, *m, *c, pc, rng);
-  task_write_obs(S, *m, *c, rng, actor0 + (size_t)env * KBJ_LD_OF(KBJ_NOBS_ACTOR + c->extra_obs_actor), critic0 + (size_t)env * KBJ_LD_OF(KBJ_NOBS_CRITIC + c->extra_obs_critic), aux0 + (size_t)env * KBJ_AUX_SIZE);
-  PFOR(k, KBJ_EP_SIZE) ep[(size_t)env * KBJ_EP_SIZE + k] = S.ep[k];
-  PFOR(k, KBJ_ES_SIZE) es[(size_t)env * KBJ_ES_SIZE + k] = S.es[k];
+#define KBJ_ENV_RESET_KERNEL(NAME, CG) \
+__global__ __launch_bounds__(64) void NAME(const kbj_model* __restrict__ m, const kbj_config* __restrict__ c, const float* __restrict__ mc, const PhysConst* __restrict__ pcp, uint32_t seed, \
+                                                       float* __restrict__ ep, float* __restrict__ es, float* actor0, float* critic0, float* aux0) { \
+  __shared__ KbjShared S; \
+  const int env = blockIdx.x; \
+  PFOR(k, (int)(sizeof(KbjModelLds) / sizeof(float))) reinterpret_cast<float*>(&S.mc)[k] = mc[k]; \
+  PFOR(k, (int)(sizeof(PhysConst) / sizeof(float))) reinterpret_cast<float*>(&S.pc)[k] = reinterpret_cast<const float*>(pcp)[k]; \
+  PFOR(k, KBJ_ES_SIZE) S.es[k] = 0; \
+  PFOR(k, 12) S.zrow[k] = 0; \
+  KBJ_SYNC(); \
+  Rng rng{seed, (uint32_t)(c->env_id_offset + env)}; \
+  const PhysConst& pc = S.pc; \
+  task_reset<CG>(S, *m, *c, pc, rng); \
+  task_write_obs(S, *m, *c, rng, actor0 + (size_t)env * KBJ_LD_OF(KBJ_NOBS_ACTOR + c->extra_obs_actor), critic0 + (size_t)env * KBJ_LD_OF(KBJ_NOBS_CRITIC + c->extra_obs_critic), aux0 + (size_t)env * KBJ_AUX_SIZE); \
+  PFOR(k, KBJ_EP_SIZE) ep[(size_t)env * KBJ_EP_SIZE + k] = S.ep[k]; \
+  PFOR(k, KBJ_ES_SIZE) es[(size_t)env * KBJ_ES_SIZE + k] = S.es[k]; \
 }
+KBJ_ENV_RESET_KERNEL(env_reset_kernel, false)
+KBJ_ENV_RESET_KERNEL(env_reset_cg_kernel, true)
 
 // re-initialise the envs whose mask entry is non-zero, exactly as env_step_kernel does for an env its own terminations finish (same
 // task_reset / task_write_obs on the env's state row: the episode counter advances, the randomisers, reset distributions and the first
 // command are drawn from the env's streams) and rewrite their next observation rows; other envs are untouched. For terminations decided
 // OUTSIDE the kernel (user-written Termination terms on the host, train.py:817 protocol).
-__global__ __launch_bounds__(64) void env_reset_where_kernel(const kbj_model* __restrict__ m, const kbj_config* __restrict__ c, const float* __restrict__ mc, const PhysConst* __restrict__ pcp, uint32_t seed,
-                                                             float* __restrict__ ep, float* __restrict__ es, const float* __restrict__ mask, float* actor_next,
-                                                             float* critic_next, float* aux_next) {
-  __shared__ KbjShared S;
-  const int env = blockIdx.x;
-  if (mask[env] == 0.0f) return;     // uniform over the workgroup
-  PFOR(k, (int)(sizeof(KbjModelLds) / sizeof(float))) reinterpret_cast<float*>(&S.mc)[k] = mc[k];
-  PFOR(k, (int)(sizeof(PhysConst) / sizeof(float))) reinterpret_cast<float*>(&S.pc)[k] = reinterpret_cast<const float*>(pcp)[k];
-  PFOR(k, KBJ_EP_SIZE) S.ep[k] = ep[(size_t)env * KBJ_EP_SIZE + k];
-  PFOR(k, KBJ_ES_SIZE) S.es[k] = es[(size_t)env * KBJ_ES_SIZE + k];
-  PFOR(k, 12) S.zrow[k] = 0;
-  KBJ_SYNC();
-  Rng rng{seed, (uint32_t)(c->env_id_offset + env)};
-  const PhysConst& pc = S.pc;
-  task_reset(S, *m, *c, pc, rng);
-  task_write_obs(S, *m, *c, rng, actor_next + (size_t)env * KBJ_LD_OF(KBJ_NOBS_ACTOR + c->extra_obs_actor), critic_next + (size_t)env * KBJ_LD_OF(KBJ_NOBS_CRITIC + c->extra_obs_critic), aux_next + (size_t)env * KBJ_AUX_SIZE);
-  PFOR(k, KBJ_EP_SIZE) ep[(size_t)env * KBJ_EP_SIZE + k] = S.ep[k];
-  PFOR(k, KBJ_ES_SIZE) es[(size_t)env * KBJ_ES_SIZE + k] = S.es[k];
+#define KBJ_ENV_RESET_WHERE_KERNEL(NAME, CG) \
+__global__ __launch_bounds__(64) void NAME(const kbj_model* __restrict__ m, const kbj_config* __restrict__ c, const float* __restrict__ mc, const PhysConst* __restrict__ pcp, uint32_t seed, \
+                                                             float* __restrict__ ep, float* __restrict__ es, const float* __restrict__ mask, float* actor_next, \
+                                                             float* critic_next, float* aux_next) { \
+  __shared__ KbjShared S; \
+  const int env = blockIdx.x; \
+  if (mask[env] == 0.0f) return;     /* uniform over the workgroup */ \
+  PFOR(k, (int)(sizeof(KbjModelLds) / sizeof(float))) reinterpret_cast<float*>(&S.mc)[k] = mc[k]; \
+  PFOR(k, (int)(sizeof(PhysConst) / sizeof(float))) reinterpret_cast<float*>(&S.pc)[k] = reinterpret_cast<const float*>(pcp)[k]; \
+  PFOR(k, KBJ_EP_SIZE) S.ep[k] = ep[(size_t)env * KBJ_EP_SIZE + k]; \
+  PFOR(k, KBJ_ES_SIZE) S.es[k] = es[(size_t)env * KBJ_ES_SIZE + k]; \
+  PFOR(k, 12) S.zrow[k] = 0; \
+  KBJ_SYNC(); \
+  Rng rng{seed, (uint32_t)(c->env_id_offset + env)}; \
+  const PhysConst& pc = S.pc; \
+  task_reset<CG>(S, *m, *c, pc, rng); \
+  task_write_obs(S, *m, *c, rng, actor_next + (size_t)env * KBJ_LD_OF(KBJ_NOBS_ACTOR + c->extra_obs_actor), critic_next + (size_t)env * KBJ_LD_OF(KBJ_NOBS_CRITIC + c->extra_obs_critic), aux_next + (size_t)env * KBJ_AUX_SIZE); \
+  PFOR(k, KBJ_EP_SIZE) ep[(size_t)env * KBJ_EP_SIZE + k] = S.ep[k]; \
+  PFOR(k, KBJ_ES_SIZE) es[(size_t)env * KBJ_ES_SIZE + k] = S.es[k]; \
 }
+KBJ_ENV_RESET_WHERE_KERNEL(env_reset_where_kernel, false)
+KBJ_ENV_RESET_WHERE_KERNEL(env_reset_where_cg_kernel, true)
 
 // user-written Reset terms (train.py:833-844 protocol): the generalised state of every env as device arrays ...
 __global__ __launch_bounds__(256) void env_get_qstate_kernel(int N, const float* __restrict__ es, float* __restrict__ qpos, float* __restrict__ qvel) {
@@ -63,38 +75,41 @@ __global__ __launch_bounds__(256) void env_get_qstate_kernel(int N, const float*
 }
 // ... and back for the masked envs: new positions / velocities, cleared warm start, then what task_reset does behind the state it draws itself -
 // one forward pass (PD on the held action, kinematics, sensors), the lagged projected gravity re-seeded, the next observation rows rewritten
-__global__ __launch_bounds__(64) void env_set_qstate_kernel(const kbj_model* __restrict__ m, const kbj_config* __restrict__ c, const float* __restrict__ mc, const PhysConst* __restrict__ pcp, uint32_t seed,
-                                                            float* __restrict__ ep, float* __restrict__ es, const float* __restrict__ mask, const float* __restrict__ qpos,
-                                                            const float* __restrict__ qvel, float* actor_next, float* critic_next, float* aux_next) {
-  __shared__ KbjShared S;
-  const int env = blockIdx.x;
-  if (mask && mask[env] == 0.0f) return;     // uniform over the workgroup
-  PFOR(k, (int)(sizeof(KbjModelLds) / sizeof(float))) reinterpret_cast<float*>(&S.mc)[k] = mc[k];
-  PFOR(k, (int)(sizeof(PhysConst) / sizeof(float))) reinterpret_cast<float*>(&S.pc)[k] = reinterpret_cast<const float*>(pcp)[k];
-  PFOR(k, KBJ_EP_SIZE) S.ep[k] = ep[(size_t)env * KBJ_EP_SIZE + k];
-  PFOR(k, KBJ_ES_SIZE) S.es[k] = es[(size_t)env * KBJ_ES_SIZE + k];
-  PFOR(k, 12) S.zrow[k] = 0;
-  KBJ_SYNC();
-  PFOR(k, KBJ_NQ) S.es[KBJ_ES_QPOS + k] = qpos[(size_t)env * KBJ_NQ + k];
-  PFOR(k, KBJ_NV) { S.es[KBJ_ES_QVEL + k] = qvel[(size_t)env * KBJ_NV + k]; S.es[KBJ_ES_WARM + k] = 0; }
-  KBJ_SYNC();
-  PFOR(w, 1) {   // a unit base quaternion whatever the term returned
-    float* q = S.es + KBJ_ES_QPOS + 3;
-    const float n = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    if (!(n > 0)) { q[0] = 1; q[1] = q[2] = q[3] = 0; }
-    else if (fabsf(n - 1.0f) > 1e-6f) { q[0] /= n; q[1] /= n; q[2] /= n; q[3] /= n; }     // (a term that leaves the state alone leaves its bits alone)
-    S.pushing = 0;
-  }
-  KBJ_SYNC();
-  Rng rng{seed, (uint32_t)(c->env_id_offset + env)};
-  const PhysConst& pc = S.pc;
-  task_pd(S, S.es + KBJ_ES_ACT_PREV);
-  phys_forward(S, S.mc, pc);
-  PFOR(k, 3) S.es[KBJ_ES_PGLAG + k] = S.pg[k];
-  KBJ_SYNC();
-  task_write_obs(S, *m, *c, rng, actor_next + (size_t)env * KBJ_LD_OF(KBJ_NOBS_ACTOR + c->extra_obs_actor), critic_next + (size_t)env * KBJ_LD_OF(KBJ_NOBS_CRITIC + c->extra_obs_critic), aux_next + (size_t)env * KBJ_AUX_SIZE);
-  PFOR(k, KBJ_ES_SIZE) es[(size_t)env * KBJ_ES_SIZE + k] = S.es[k];
+#define KBJ_ENV_SET_QSTATE_KERNEL(NAME, CG) \
+__global__ __launch_bounds__(64) void NAME(const kbj_model* __restrict__ m, const kbj_config* __restrict__ c, const float* __restrict__ mc, const PhysConst* __restrict__ pcp, uint32_t seed, \
+                                                            float* __restrict__ ep, float* __restrict__ es, const float* __restrict__ mask, const float* __restrict__ qpos, \
+                                                            const float* __restrict__ qvel, float* actor_next, float* critic_next, float* aux_next) { \
+  __shared__ KbjShared S; \
+  const int env = blockIdx.x; \
+  if (mask && mask[env] == 0.0f) return;     /* uniform over the workgroup */ \
+  PFOR(k, (int)(sizeof(KbjModelLds) / sizeof(float))) reinterpret_cast<float*>(&S.mc)[k] = mc[k]; \
+  PFOR(k, (int)(sizeof(PhysConst) / sizeof(float))) reinterpret_cast<float*>(&S.pc)[k] = reinterpret_cast<const float*>(pcp)[k]; \
+  PFOR(k, KBJ_EP_SIZE) S.ep[k] = ep[(size_t)env * KBJ_EP_SIZE + k]; \
+  PFOR(k, KBJ_ES_SIZE) S.es[k] = es[(size_t)env * KBJ_ES_SIZE + k]; \
+  PFOR(k, 12) S.zrow[k] = 0; \
+  KBJ_SYNC(); \
+  PFOR(k, KBJ_NQ) S.es[KBJ_ES_QPOS + k] = qpos[(size_t)env * KBJ_NQ + k]; \
+  PFOR(k, KBJ_NV) { S.es[KBJ_ES_QVEL + k] = qvel[(size_t)env * KBJ_NV + k]; S.es[KBJ_ES_WARM + k] = 0; } \
+  KBJ_SYNC(); \
+  PFOR(w, 1) {   /* a unit base quaternion whatever the term returned */ \
+    float* q = S.es + KBJ_ES_QPOS + 3; \
+    const float n = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]); \
+    if (!(n > 0)) { q[0] = 1; q[1] = q[2] = q[3] = 0; } \
+    else if (fabsf(n - 1.0f) > 1e-6f) { q[0] /= n; q[1] /= n; q[2] /= n; q[3] /= n; }     /* (a term that leaves the state alone leaves its bits alone) */ \
+    S.pushing = 0; \
+  } \
+  KBJ_SYNC(); \
+  Rng rng{seed, (uint32_t)(c->env_id_offset + env)}; \
+  const PhysConst& pc = S.pc; \
+  task_pd(S, S.es + KBJ_ES_ACT_PREV); \
+  phys_forward<CG>(S, S.mc, pc); \
+  PFOR(k, 3) S.es[KBJ_ES_PGLAG + k] = S.pg[k]; \
+  KBJ_SYNC(); \
+  task_write_obs(S, *m, *c, rng, actor_next + (size_t)env * KBJ_LD_OF(KBJ_NOBS_ACTOR + c->extra_obs_actor), critic_next + (size_t)env * KBJ_LD_OF(KBJ_NOBS_CRITIC + c->extra_obs_critic), aux_next + (size_t)env * KBJ_AUX_SIZE); \
+  PFOR(k, KBJ_ES_SIZE) es[(size_t)env * KBJ_ES_SIZE + k] = S.es[k]; \
 }
+KBJ_ENV_SET_QSTATE_KERNEL(env_set_qstate_kernel, false)
+KBJ_ENV_SET_QSTATE_KERNEL(env_set_qstate_cg_kernel, true)
 
 // overwrite the joystick command of the envs whose mask entry is non-zero (mask == nullptr: all envs): the env's state row (the next step's
 // rewards and its command-switch draw start from it) and the command columns of the NEXT observation rows + aux record, zero-command flag
@@ -127,7 +142,7 @@ __global__ __launch_bounds__(256) void env_set_command_kernel(int N, int lda, in
 // REC: the form that also writes the per-step state record (kbj_traj.qstate_d / kbj_env_record_state). The default rollout runs the other
 // one, whose code is exactly the kernel without the feature (two more pointers live through the substep loop cost 2 VGPR / 8 SGPR spills);
 // the two are separate __global__ functions so that the hot kernel keeps its name in every profile.
-template <bool REC>
+template <bool REC, bool CG>
 __device__ __forceinline__ void env_step_body(const kbj_model* __restrict__ m, const kbj_config* __restrict__ c, const float* __restrict__ mc, const PhysConst* __restrict__ pcp, uint32_t seed,
                                               float* __restrict__ ep, float* __restrict__ es, const float* __restrict__ action,
                                               float* aux_t, float* actor_next, float* critic_next, float* aux_next, int env0, float* qstate_t) {
@@ -142,7 +157,7 @@ __device__ __forceinline__ void env_step_body(const kbj_model* __restrict__ m, c
   Rng rng{seed, (uint32_t)(c->env_id_offset + env)};
   const PhysConst& pc = S.pc;
   KBJ_STAMP(18);
-  task_step(S, *m, *c, pc, rng, action + (size_t)env * KBJ_NU, aux_t + (size_t)env * KBJ_AUX_SIZE, actor_next + (size_t)env * KBJ_LD_OF(KBJ_NOBS_ACTOR + c->extra_obs_actor),
+  task_step<CG>(S, *m, *c, pc, rng, action + (size_t)env * KBJ_NU, aux_t + (size_t)env * KBJ_AUX_SIZE, actor_next + (size_t)env * KBJ_LD_OF(KBJ_NOBS_ACTOR + c->extra_obs_actor),
             critic_next + (size_t)env * KBJ_LD_OF(KBJ_NOBS_CRITIC + c->extra_obs_critic), aux_next + (size_t)env * KBJ_AUX_SIZE,
             REC ? qstate_t + (size_t)env * KBJ_QSTATE_SIZE : nullptr);
   if (S.done) PFOR(k, KBJ_EP_SIZE) ep[(size_t)env * KBJ_EP_SIZE + k] = S.ep[k];
@@ -152,13 +167,27 @@ __device__ __forceinline__ void env_step_body(const kbj_model* __restrict__ m, c
 __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(KBJ_ENV_NUM_VGPR))) void env_step_kernel(const kbj_model* __restrict__ m, const kbj_config* __restrict__ c, const float* __restrict__ mc, const PhysConst* __restrict__ pcp, uint32_t seed,
                                                       float* __restrict__ ep, float* __restrict__ es, const float* __restrict__ action,
                                                       float* aux_t, float* actor_next, float* critic_next, float* aux_next, int env0) {
-  env_step_body<false>(m, c, mc, pcp, seed, ep, es, action, aux_t, actor_next, critic_next, aux_next, env0, nullptr);
+  env_step_body<false, false>(m, c, mc, pcp, seed, ep, es, action, aux_t, actor_next, critic_next, aux_next, env0, nullptr);
 }
 __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(KBJ_ENV_NUM_VGPR))) void env_step_record_kernel(const kbj_model* __restrict__ m, const kbj_config* __restrict__ c, const float* __restrict__ mc, const PhysConst* __restrict__ pcp, uint32_t seed,
                                                       float* __restrict__ ep, float* __restrict__ es, const float* __restrict__ action,
                                                       float* aux_t, float* actor_next, float* critic_next, float* aux_next, int env0, float* qstate_t) {
-  env_step_body<true>(m, c, mc, pcp, seed, ep, es, action, aux_t, actor_next, critic_next, aux_next, env0, qstate_t);
+  env_step_body<true, false>(m, c, mc, pcp, seed, ep, es, action, aux_t, actor_next, critic_next, aux_next, env0, qstate_t);
 }
+// the same two with the Polak-Ribiere CG solver (kbj_config.solver_newton = 0): same register cap, same LDS struct, same launch shape
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(KBJ_ENV_NUM_VGPR))) void env_step_cg_kernel(const kbj_model* __restrict__ m, const kbj_config* __restrict__ c, const float* __restrict__ mc, const PhysConst* __restrict__ pcp, uint32_t seed,
+                                                      float* __restrict__ ep, float* __restrict__ es, const float* __restrict__ action,
+                                                      float* aux_t, float* actor_next, float* critic_next, float* aux_next, int env0) {
+  env_step_body<false, true>(m, c, mc, pcp, seed, ep, es, action, aux_t, actor_next, critic_next, aux_next, env0, nullptr);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(KBJ_ENV_NUM_VGPR))) void env_step_record_cg_kernel(const kbj_model* __restrict__ m, const kbj_config* __restrict__ c, const float* __restrict__ mc, const PhysConst* __restrict__ pcp, uint32_t seed,
+                                                      float* __restrict__ ep, float* __restrict__ es, const float* __restrict__ action,
+                                                      float* aux_t, float* actor_next, float* critic_next, float* aux_next, int env0, float* qstate_t) {
+  env_step_body<true, true>(m, c, mc, pcp, seed, ep, es, action, aux_t, actor_next, critic_next, aux_next, env0, qstate_t);
+}
+// the kernel of the context's solver: NAME_kernel (Newton, the default) or NAME_cg_kernel
+#define KBJ_LAUNCH_SOLVER(ctx, NAME, ...) do { \
+    if ((ctx)->cfg_h.solver_newton) hipLaunchKernelGGL(NAME##_kernel, __VA_ARGS__); else hipLaunchKernelGGL(NAME##_cg_kernel, __VA_ARGS__); } while (0)
 
 #ifdef KBJ_ENV_STAMPS
 extern "C" int kbj_debug_env_stamps(unsigned long long* out32, int clear) {   // diagnostics build only (tools/env_stamps.py)
@@ -288,10 +317,10 @@ int kbj_env_step_range(kbj_ctx* ctx, hipStream_t s, int env0, int count, const f
                        float* aux_next_d, float* qstate_t_d) {
   KbjKernelTimer timer(s, KBJ_KIND_ENV_STEP, 0.0);
   if (qstate_t_d)
-    hipLaunchKernelGGL(env_step_record_kernel, dim3(count), dim3(64), 0, s, ctx->model_d, ctx->cfg_d, ctx->mc_d, (const PhysConst*)ctx->pc_d, ctx->seed, ctx->ep_d, ctx->es_d, action_d, aux_t_d,
+    KBJ_LAUNCH_SOLVER(ctx, env_step_record, dim3(count), dim3(64), 0, s, ctx->model_d, ctx->cfg_d, ctx->mc_d, (const PhysConst*)ctx->pc_d, ctx->seed, ctx->ep_d, ctx->es_d, action_d, aux_t_d,
                        actor_next_d, critic_next_d, aux_next_d, env0, qstate_t_d);
   else
-    hipLaunchKernelGGL(env_step_kernel, dim3(count), dim3(64), 0, s, ctx->model_d, ctx->cfg_d, ctx->mc_d, (const PhysConst*)ctx->pc_d, ctx->seed, ctx->ep_d, ctx->es_d, action_d, aux_t_d,
+    KBJ_LAUNCH_SOLVER(ctx, env_step, dim3(count), dim3(64), 0, s, ctx->model_d, ctx->cfg_d, ctx->mc_d, (const PhysConst*)ctx->pc_d, ctx->seed, ctx->ep_d, ctx->es_d, action_d, aux_t_d,
                        actor_next_d, critic_next_d, aux_next_d, env0);
   KBJ_CHECK_LAUNCH(ctx, "env_step_kernel");
   return 0;
@@ -308,7 +337,7 @@ int kbj_env_reset_all(kbj_ctx* ctx, uint32_t seed, float* actor0_d, float* criti
   kbj_nn_drop_prefetch(ctx);
   hipLaunchKernelGGL(init_reward_carry_kernel, dim3((N + 255) / 256), dim3(256), 0, ctx->stream, ctx->rcarry_d, N);
   KBJ_CHECK_LAUNCH(ctx, "init_reward_carry_kernel");
-  hipLaunchKernelGGL(env_reset_kernel, dim3(N), dim3(64), 0, ctx->stream, ctx->model_d, ctx->cfg_d, ctx->mc_d, (const PhysConst*)ctx->pc_d, seed, ctx->ep_d, ctx->es_d, actor0_d,
+  KBJ_LAUNCH_SOLVER(ctx, env_reset, dim3(N), dim3(64), 0, ctx->stream, ctx->model_d, ctx->cfg_d, ctx->mc_d, (const PhysConst*)ctx->pc_d, seed, ctx->ep_d, ctx->es_d, actor0_d,
                      critic0_d, aux0_d);
   KBJ_CHECK_LAUNCH(ctx, "env_reset_kernel");
   return 0;
@@ -335,7 +364,7 @@ int kbj_env_reset_where(kbj_ctx* ctx, const float* mask_d, float* actor_next_d, 
   if (!ctx || !mask_d || !actor_next_d || !critic_next_d || !aux_next_d) return kbj_fail(ctx, "kbj_env_reset_where: null argument");
   KBJ_HIP(ctx, hipSetDevice(ctx->device));
   kbj_nn_drop_prefetch(ctx);
-  hipLaunchKernelGGL(env_reset_where_kernel, dim3(ctx->cfg_h.num_envs), dim3(64), 0, ctx->stream, ctx->model_d, ctx->cfg_d, ctx->mc_d, (const PhysConst*)ctx->pc_d, ctx->seed, ctx->ep_d, ctx->es_d,
+  KBJ_LAUNCH_SOLVER(ctx, env_reset_where, dim3(ctx->cfg_h.num_envs), dim3(64), 0, ctx->stream, ctx->model_d, ctx->cfg_d, ctx->mc_d, (const PhysConst*)ctx->pc_d, ctx->seed, ctx->ep_d, ctx->es_d,
                      mask_d, actor_next_d, critic_next_d, aux_next_d);
   KBJ_CHECK_LAUNCH(ctx, "env_reset_where_kernel");
   return 0;
@@ -365,7 +394,7 @@ int kbj_env_set_qstate(kbj_ctx* ctx, const float* mask_d, const float* qpos_d, c
   if (!ctx || !qpos_d || !qvel_d || !actor_next_d || !critic_next_d || !aux_next_d) return kbj_fail(ctx, "kbj_env_set_qstate: null argument");
   KBJ_HIP(ctx, hipSetDevice(ctx->device));
   kbj_nn_drop_prefetch(ctx);
-  hipLaunchKernelGGL(env_set_qstate_kernel, dim3(ctx->cfg_h.num_envs), dim3(64), 0, ctx->stream, ctx->model_d, ctx->cfg_d, ctx->mc_d, (const PhysConst*)ctx->pc_d, ctx->seed, ctx->ep_d, ctx->es_d,
+  KBJ_LAUNCH_SOLVER(ctx, env_set_qstate, dim3(ctx->cfg_h.num_envs), dim3(64), 0, ctx->stream, ctx->model_d, ctx->cfg_d, ctx->mc_d, (const PhysConst*)ctx->pc_d, ctx->seed, ctx->ep_d, ctx->es_d,
                      mask_d, qpos_d, qvel_d, actor_next_d, critic_next_d, aux_next_d);
   KBJ_CHECK_LAUNCH(ctx, "env_set_qstate_kernel");
   return 0;

@@ -98,6 +98,11 @@ struct PhysConst {  // constants derived from kbj_config and the model: computed
   int iterations, ls_iterations;
   float tamp, tkw;   // terrain z = tamp sin(tkw x) sin(tkw y); tamp = 0: the plane z = 0
   ImpConst fric, lim, con;
+#ifdef KBJ_EMU
+  int cg;            // kbj_config.solver_newton == 0: Polak-Ribiere CG, which the host emulation picks at run time (kbj_env_task.h). The HIP kernels are
+                     // compiled per solver and the host picks the symbol at launch (kbj_env.hip): they never read a selector, and a word here would
+                     // move every LDS offset behind KbjShared::pc - the Newton kernels' code would no longer be the code they had without CG
+#endif
 };
 KBJ_HD PhysConst phys_const(const kbj_config& c, const kbj_model& m) {
   PhysConst pc;
@@ -110,6 +115,9 @@ KBJ_HD PhysConst phys_const(const kbj_config& c, const kbj_model& m) {
   pc.tol2 = (c.solver_tolerance * m.meaninertia * NV) * (c.solver_tolerance * m.meaninertia * NV);
   pc.fric_ratio = (1 - pc.fric.dmin) / pc.fric.dmin;
   pc.cos_max_tilt = cosf(c.max_tilt_rad);
+#ifdef KBJ_EMU
+  pc.cg = c.solver_newton == 0;
+#endif
   return pc;
 }
 // Everything one env needs between phases, 12.4 KB so that 12 single-wavefront workgroups (3 waves per SIMD) share a CU.
@@ -143,6 +151,7 @@ struct KbjShared {
   float qfrc_act[NV], qfrc_smooth[NV], qacc[NV];
 #if defined(KBJ_ARROW_LDS)   // the LDS formulation of the solver keeps its vectors here; the product kernel keeps them in registers
   float qacc_smooth[NV], Ma[NV], grad[NV], search[NV], mv[NV], vec[NV];
+  float grad_old[NV], mgrad_old[NV];   // CG: the previous iteration's grad and M^-1 grad
   float jar[NROW], jv[NROW];
 #endif
   float conpos[NCON][3], condist[NCON], connrm[NCON][3];

@@ -1,4 +1,4 @@
-// kbj_env_phys.h — rigid-body forward dynamics + soft-constraint Newton solve for one env per wavefront.
+// kbj_env_phys.h — rigid-body forward dynamics + soft-constraint solve (Newton, or Polak-Ribiere CG) for one env per wavefront.
 //
 // the "MuJoCo-XLA physics step" (reference: mjx.step under ksim's engine, configured at
 // train.py:1775-1778). Pipeline per substep: kinematics -> tree com / cinert / cdof -> composite inertia ->
@@ -618,8 +618,9 @@ KBJ_DEV void rows_force(KbjShared& S) {
   KBJ_SYNC();
 }
 
-// Newton iterations on the convex constraint cost with an exact (safeguarded Newton) line search
-KBJ_DEV void phys_solve(KbjShared& S, const KbjModelLds& m, const PhysConst& pc) {
+// Newton iterations on the convex constraint cost with an exact (safeguarded Newton) line search. CG (kbj_config.solver_newton = 0): the
+// same loop with the Polak-Ribiere direction on the M^-1-preconditioned gradient instead of the Newton direction - no Hessian.
+template <bool CG> KBJ_DEV void phys_solve(KbjShared& S, const KbjModelLds& m, const PhysConst& pc) {
   float* warm = S.es + KBJ_ES_WARM;
   arrow_solve(S, S.qfrc_smooth, false);
   PFOR(i, NV) S.qacc_smooth[i] = S.vec[i];
@@ -656,9 +657,24 @@ KBJ_DEV void phys_solve(KbjShared& S, const KbjModelLds& m, const PhysConst& pc)
     float gg = wsum(NV, [&](int l) { return S.grad[l] * S.grad[l]; });
     KBJ_STAMP(9);
     if (scale * sqrtf(gg) < pc.tolerance) break;
-    arrow_solve(S, S.mv, true);
+    if constexpr (CG) {
+      arrow_solve(S, S.grad, false);   // Mgrad = M^-1 grad
+      float beta = 0;
+      if (it > 0) {
+        float num, den;
+        wsum2(NV, [&](int l, float& a, float& b) { a = S.grad[l] * (S.vec[l] - S.mgrad_old[l]); b = S.grad_old[l] * S.mgrad_old[l]; }, num, den);
+        beta = den > 1e-30f ? fmaxf(0.0f, num / den) : 0.0f;
+      }
+      KBJ_SYNC();
+      PFOR(i, NV) {
+        S.search[i] = it == 0 ? -S.vec[i] : -S.vec[i] + beta * S.search[i];
+        S.grad_old[i] = S.grad[i]; S.mgrad_old[i] = S.vec[i];
+      }
+    } else {
+      arrow_solve(S, S.mv, true);
+      PFOR(i, NV) S.search[i] = S.vec[i];
+    }
     KBJ_STAMP(10);
-    PFOR(i, NV) S.search[i] = S.vec[i];
     KBJ_SYNC();
     PFOR(i, NV) S.mv[i] = mul_M_row(S, i, S.search);
     PFOR(r, NROW) S.jv[r] = S.D[r] != 0 ? row_dot(S, r, S.search) : 0.0f;
@@ -793,7 +809,9 @@ KBJ_DEV WF arrow_solve_w(const WF (&m)[11], const WF (&h)[11], const WF (&oh)[5]
   return xm;
 }
 
-KBJ_DEV void phys_solve(KbjShared& S, const KbjModelLds& mdl, const PhysConst& pc) {
+// CG (kbj_config.solver_newton = 0): the Polak-Ribiere direction on Mgrad = M^-1 grad (the arrow solve with zero Hessian rows); the search
+// direction and the previous grad / Mgrad are three more values on the lane that owns the dof. h stays zero and none of its upkeep exists.
+template <bool CG> KBJ_DEV void phys_solve(KbjShared& S, const KbjModelLds& mdl, const PhysConst& pc) {
   constexpr unsigned long long CHAIN = wmask_r_below(5), BASE = wmask_r_below(11) & ~CHAIN, OWN = CHAIN | (BASE & 0xFFFFull);
   WF m[11], h[11], jc[11], jt[16], oh[5];
   WF qs, warm, Df, fl, thr, aref_f, actf, Dl, aref_l, lsa, Dc, aref_c;
@@ -867,6 +885,8 @@ KBJ_DEV void phys_solve(KbjShared& S, const KbjModelLds& mdl, const PhysConst& p
   const float tol2 = pc.tol2;
   int iters = 0;
   WF ff, flm, fc, dnow, w_prev;
+  WF se_cg, grad_old, mgrad_old;      // CG only
+  WLANES(l) { WL(se_cg, l) = 0.0f; WL(grad_old, l) = 0.0f; WL(mgrad_old, l) = 0.0f; }
   WLANES(l) WL(w_prev, l) = 0.0f;     // weight (D in the quadratic zone, else 0) with which this lane's pyramid row currently sits in h
   // forces of the rows at the current residuals; dnow = friction-loss + limit rows in their quadratic zone (unit rows: diagonal of H)
   auto rows_force = [&]() {
@@ -884,13 +904,16 @@ KBJ_DEV void phys_solve(KbjShared& S, const KbjModelLds& mdl, const PhysConst& p
     // contact part of the Hessian, incrementally: only rows whose quadratic-zone flag flipped since the last solve change h (all active
     // rows on the first iteration). The weight changes go through LDS (S.force is free until the solve ends), the changed rows are a
     // ballot mask, so an iteration without flips costs nothing here.
-    WF dw;
-    WLANES(l) {
-      const float w_now = WL(jar_c, l) < 0.0f ? WL(Dc, l) : 0.0f;
-      WL(dw, l) = w_now - WL(w_prev, l); WL(w_prev, l) = w_now;
-      if (l < 32) S.force[ROW_CON + l] = WL(dw, l);
+    unsigned long long chg = 0;
+    if constexpr (!CG) {
+      WF dw;
+      WLANES(l) {
+        const float w_now = WL(jar_c, l) < 0.0f ? WL(Dc, l) : 0.0f;
+        WL(dw, l) = w_now - WL(w_prev, l); WL(w_prev, l) = w_now;
+        if (l < 32) S.force[ROW_CON + l] = WL(dw, l);
+      }
+      chg = wballot([&](int l) { return l < 32 && WL(dw, l) != 0.0f; });
     }
-    const unsigned long long chg = wballot([&](int l) { return l < 32 && WL(dw, l) != 0.0f; });
     // gradient: M qacc - qfrc_smooth - J^T force; J^T f broadcasts the leg's sixteen forces over the transposed rows
     WF gcon = wmul_bcast<0>(fc, jt[0]);
     static_for<1, 16>([&](auto K_) { constexpr int k = decltype(K_)::value; wfmac_bcast<k>(gcon, fc, jt[k]); });
@@ -904,7 +927,7 @@ KBJ_DEV void phys_solve(KbjShared& S, const KbjModelLds& mdl, const PhysConst& p
     KBJ_SYNC();
     KBJ_STAMP(9);
     if (gg < tol2) break;
-    {
+    if constexpr (!CG) {
       unsigned rows = (unsigned)(chg & 0xFFFFu) | (unsigned)((chg >> 16) & 0xFFFFu);   // row k of either leg changed
       while (rows) {
         const int k = __builtin_ctz(rows);
@@ -923,9 +946,25 @@ KBJ_DEV void phys_solve(KbjShared& S, const KbjModelLds& mdl, const PhysConst& p
         }
       }
     }
-    WF ngr;
-    WLANES(l) WL(ngr, l) = -WL(gr, l);
-    const WF se = arrow_solve_w(m, h, oh, dnow, ngr);
+    WF se;
+    if constexpr (CG) {
+      // lanes r > 10 of a solve's result hold the right-hand-side marker, not an unknown: zeroed, so that beta cannot grow them
+      const WF mg = wsel0<wmask_r_below(11)>(arrow_solve_w(m, h, oh, zero, gr));
+      float beta = 0;
+      if (it > 0) {
+        WF b1, b2;
+        WLANES(l) { WL(b1, l) = WL(gr, l) * (WL(mg, l) - WL(mgrad_old, l)); WL(b2, l) = WL(grad_old, l) * WL(mgrad_old, l); }
+        float num, den;
+        wsum2(wsel0<OWN>(b1), wsel0<OWN>(b2), num, den);
+        beta = den > 1e-30f ? fmaxf(0.0f, kbj_fdiv(num, den)) : 0.0f;
+      }
+      WLANES(l) { WL(se_cg, l) = fmaf(beta, WL(se_cg, l), -WL(mg, l)); WL(grad_old, l) = WL(gr, l); WL(mgrad_old, l) = WL(mg, l); }
+      se = se_cg;
+    } else {
+      WF ngr;
+      WLANES(l) WL(ngr, l) = -WL(gr, l);
+      se = arrow_solve_w(m, h, oh, dnow, ngr);
+    }
     KBJ_STAMP(10);
     const WF mv = mul_M(se), jv_c = jdot(se);
     KBJ_STAMP(11);
@@ -1024,7 +1063,7 @@ KBJ_DEV void phys_sensors(KbjShared& S, const KbjModelLds& m) {
 
 // full forward pass on the state in S.es with torques S.ctrl and (if S.pushing) wrench S.push
 // `sensors`: gyro / projected gravity / touch only feed the observations, i.e. they are needed after the LAST substep of a control step
-KBJ_DEV void phys_forward(KbjShared& S, const KbjModelLds& m, const PhysConst& pc, bool sensors = true) {
+template <bool CG> KBJ_DEV void phys_forward(KbjShared& S, const KbjModelLds& m, const PhysConst& pc, bool sensors = true) {
   KBJ_STAMP(0);
   phys_kinematics(S, m); KBJ_STAMP(1);
   phys_com(S, m); KBJ_STAMP(2);
@@ -1032,7 +1071,7 @@ KBJ_DEV void phys_forward(KbjShared& S, const KbjModelLds& m, const PhysConst& p
   phys_collide_vel(S, m, pc); KBJ_STAMP(4);
   phys_smooth_forces(S, m); KBJ_STAMP(5);
   phys_make_constraints(S, m, pc); KBJ_STAMP(6);
-  phys_solve(S, m, pc); KBJ_STAMP(15);
+  phys_solve<CG>(S, m, pc); KBJ_STAMP(15);
   if (sensors) phys_sensors(S, m);
   KBJ_STAMP(16);
 }

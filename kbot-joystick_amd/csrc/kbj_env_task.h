@@ -106,7 +106,7 @@ KBJ_DEV void task_pd(KbjShared& S, const float* action) {
 }
 
 // resets (train.py:1146-1153, 833-844) + per-episode re-initialisation, then one forward pass for the first observation
-KBJ_DEV void task_reset(KbjShared& S, const kbj_model& m, const kbj_config& c, const PhysConst& pc, const Rng& rng) {
+template <bool CG> KBJ_DEV void task_reset(KbjShared& S, const kbj_model& m, const kbj_config& c, const PhysConst& pc, const Rng& rng) {
   float* es = S.es;
   PFOR(w, 1) es[KBJ_ES_EPISODE] = u2f(f2u(es[KBJ_ES_EPISODE]) + 1u);
   KBJ_SYNC();
@@ -147,7 +147,7 @@ KBJ_DEV void task_reset(KbjShared& S, const kbj_model& m, const kbj_config& c, c
   }
   KBJ_SYNC();
   task_pd(S, es + KBJ_ES_ACT_PREV);
-  phys_forward(S, S.mc, pc);
+  phys_forward<CG>(S, S.mc, pc);
   PFOR(k, 3) es[KBJ_ES_PGLAG + k] = S.pg[k];
   KBJ_SYNC();
 }
@@ -277,8 +277,9 @@ KBJ_DEV void task_write_obs(KbjShared& S, const kbj_model& m, const kbj_config& 
 // one control step of one env (mirrors ksim's engine + rollout bookkeeping):
 // latency/drop -> push event -> substeps x (PD, forward, integrate) -> termination -> reward inputs ->
 // reset or command switch -> next observation.
-KBJ_DEV void task_step(KbjShared& S, const kbj_model& m, const kbj_config& c, const PhysConst& pc, const Rng& rng, const float* action,
-                       float* aux_t, float* actor_next, float* critic_next, float* aux_next, float* qstate = nullptr) {
+// CG: the constraint solver of every forward pass (kbj_env_phys.h phys_solve), a compile-time choice so that neither form carries the other.
+template <bool CG> KBJ_DEV void task_step(KbjShared& S, const kbj_model& m, const kbj_config& c, const PhysConst& pc, const Rng& rng, const float* action,
+                                          float* aux_t, float* actor_next, float* critic_next, float* aux_next, float* qstate = nullptr) {
   float* es = S.es;
   uint32_t st = f2u(es[KBJ_ES_STEP]);
   bool drop = rng_u01(rng, KBJ_RNG_DROP, st, 0) < c.drop_action_prob;
@@ -305,7 +306,7 @@ KBJ_DEV void task_step(KbjShared& S, const kbj_model& m, const kbj_config& c, co
   for (int s = 0; s < c.substeps; ++s) {
     if (qstate && s == c.substeps - 1) PFOR(k, KBJ_NQ) qstate[KBJ_QSTATE_QPOS_KIN + k] = es[KBJ_ES_QPOS + k];   // what the last forward pass's kinematics run on
     task_pd(S, s >= lat ? S.act_eff : es + KBJ_ES_ACT_PREV);
-    phys_forward(S, S.mc, pc, s == c.substeps - 1);
+    phys_forward<CG>(S, S.mc, pc, s == c.substeps - 1);
     phys_integrate(S, pc);
     KBJ_STAMP(17);
   }
@@ -333,7 +334,7 @@ KBJ_DEV void task_step(KbjShared& S, const kbj_model& m, const kbj_config& c, co
     aux_t[KBJ_AUX_DONE + 1] = 0;
   }
   KBJ_SYNC();
-  if (S.done) task_reset(S, m, c, pc, rng);
+  if (S.done) task_reset<CG>(S, m, c, pc, rng);
   else {
     PFOR(w, 1) {  // UnifiedCommand.__call__ (train.py:768-785)
       if (c.command_mode == 0 && rng_u01(rng, KBJ_RNG_COMMAND, st + 1, 0) < c.switch_prob) task_sample_command(m, c, rng, st + 1, 0, es + KBJ_ES_CMD);
@@ -346,5 +347,17 @@ KBJ_DEV void task_step(KbjShared& S, const kbj_model& m, const kbj_config& c, co
   }
   task_write_obs(S, m, c, rng, actor_next, critic_next, aux_next);
 }
+
+#ifdef KBJ_EMU
+// the host emulation picks the solver at run time, from the constants phys_const() derived from the config
+static inline void task_reset(KbjShared& S, const kbj_model& m, const kbj_config& c, const PhysConst& pc, const Rng& rng) {
+  if (pc.cg) task_reset<true>(S, m, c, pc, rng); else task_reset<false>(S, m, c, pc, rng);
+}
+static inline void task_step(KbjShared& S, const kbj_model& m, const kbj_config& c, const PhysConst& pc, const Rng& rng, const float* action,
+                             float* aux_t, float* actor_next, float* critic_next, float* aux_next, float* qstate = nullptr) {
+  if (pc.cg) task_step<true>(S, m, c, pc, rng, action, aux_t, actor_next, critic_next, aux_next, qstate);
+  else task_step<false>(S, m, c, pc, rng, action, aux_t, actor_next, critic_next, aux_next, qstate);
+}
+#endif
 
 }  // namespace kbj

@@ -96,6 +96,11 @@ class HumanoidWalkingTaskConfig:
     # from V_{T-1}. KBJ_GAE_TRUNCATION / KBJ_GAE_TAIL in the environment override the defaults (A/B runs with tools/ab_bench.py).
     bootstrap_on_truncation: bool = dataclasses.field(default_factory=lambda: os.environ.get("KBJ_GAE_TRUNCATION", "0") not in ("0", ""))
     bootstrap_tail_value: bool = dataclasses.field(default_factory=lambda: os.environ.get("KBJ_GAE_TAIL", "0") not in ("0", ""))
+    # constraint solver of the physics step (kbj_config.solver_newton): "newton" (the default: the kernel this build is tuned and measured with) or
+    # "cg", Polak-Ribiere CG on the M^-1-preconditioned gradient - SURVEY B.1 records it as ksim's default, and at the launch block's
+    # iterations=8, ls_iterations=8 (train.py:1777-1778) it is a different dynamics, not a cosmetic switch (DESIGN.md section 3 "Solver").
+    # KBJ_SOLVER in the environment overrides the default (A/B runs with tools/ab_bench.py).
+    solver: str = dataclasses.field(default_factory=lambda: os.environ.get("KBJ_SOLVER", "") or "newton")
     # keep qpos / qvel of every env-step (kbj_traj.qstate_d, 262 MB at 8192 x 100): the Python reward terms (extra_rewards) then see a
     # ksim-shaped `host.trajectory.Trajectory` - trajectory.qpos / .qvel / .xpos / .xquat / .obs[...] / .command["unified_command"] as the
     # reference's reward classes read them (train.py:138-506) - instead of the narrower TrajectoryView of the aux record
@@ -143,7 +148,8 @@ class HumanoidWalkingTaskConfig:
                              "or use a non-zero adam_weight_decay (the adamw branch, train.py:1076-1077)")
         T = int(round(self.rollout_length_seconds / self.ctrl_dt))
         kw = dict(num_envs=num_envs_local, env_id_offset=env_id_offset, rollout_len=T, substeps=int(round(self.ctrl_dt / self.dt)),
-                  solver_iterations=self.iterations, ls_iterations=self.ls_iterations, hidden_size=self.hidden_size, depth=self.depth,
+                  solver_iterations=self.iterations, ls_iterations=self.ls_iterations, solver_newton=int(self.solver == "newton"),
+                  hidden_size=self.hidden_size, depth=self.depth,
                   batch_size=self.batch_size, num_passes=self.num_passes, dt=self.dt, ctrl_dt=self.ctrl_dt,
                   latency_lo=self.action_latency_range[0], latency_hi=self.action_latency_range[1],
                   drop_action_prob=self.drop_action_prob, var_scale=self.var_scale, entropy_coef=self.entropy_coef, gamma=self.gamma,
@@ -154,6 +160,8 @@ class HumanoidWalkingTaskConfig:
                   gae_bootstrap_truncation=int(bool(self.bootstrap_on_truncation)), gae_tail_value=int(bool(self.bootstrap_tail_value)))
         if not (0 <= self.extra_actor_obs <= L.MAX_EXTRA_OBS and 0 <= self.extra_critic_obs <= L.MAX_EXTRA_OBS):
             raise ValueError(f"extra_actor_obs / extra_critic_obs must be in 0..{L.MAX_EXTRA_OBS}")
+        if self.solver not in ("newton", "cg"):
+            raise ValueError(f"unknown solver {self.solver!r} (newton | cg)")
         if self.allreduce not in ("per_step", "per_pass"):
             raise ValueError(f"unknown allreduce mode {self.allreduce!r} (per_step | per_pass)")
         if self.terrain not in ("flat", "sine"):

@@ -1,4 +1,4 @@
-"""Micro-benchmark of kbj_env_step alone. usage: bench_env.py N [key=value ...] (kbj_config overrides)"""
+"""Micro-benchmark of kbj_env_step alone. usage: bench_env.py N [--solver newton|cg] [key=value ...] (kbj_config overrides)"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -6,7 +6,12 @@ from kbot_joystick_amd.spec import compiler, layout as L
 from kbot_joystick_amd.host import binding as B
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 8192
 kw = {}
-for a in sys.argv[2:]:
+args = sys.argv[2:]
+if "--solver" in args:      # the constraint solver (kbj_config.solver_newton): "newton" (default) or "cg"
+    i = args.index("--solver"); name = args[i + 1]; del args[i:i + 2]
+    if name not in ("newton", "cg"): sys.exit(f"unknown solver {name!r} (newton | cg)")
+    kw["solver_newton"] = int(name == "newton")
+for a in args:
     k, v = a.split("="); kw[k] = float(v) if "." in v or "e" in v else int(v)
 m = compiler.load_model("kbot-headless"); cfg = L.default_config(num_envs=N, batch_size=min(512, N), **kw)
 ctx = B.Context(m, cfg, 0, torch.cuda.current_stream().cuda_stream)
