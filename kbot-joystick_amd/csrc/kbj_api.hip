@@ -147,7 +147,7 @@ int kbj_create(kbj_ctx** out, const void* model_blob, size_t model_bytes, const 
     KBJ_TRY(hipEventCreateWithFlags(&ctx->ev_side[n], hipEventDisableTiming));
   }
   for (int n = 0; n < 2; ++n) KBJ_TRY(hipEventCreateWithFlags(&ctx->ev_dx[n], hipEventDisableTiming));
-  for (int k = 0; k < 32; ++k) KBJ_TRY(hipEventCreateWithFlags(&ctx->ev_pool[k], hipEventDisableTiming));
+  KBJ_TRY(hipEventCreateWithFlags(&ctx->ev_critic_loss, hipEventDisableTiming));
   KBJ_TRY(hipEventCreateWithFlags(&ctx->ev_actor_grad, hipEventDisableTiming));
   KBJ_TRY(hipEventCreateWithFlags(&ctx->ev_small, hipEventDisableTiming));
   KBJ_TRY(hipEventCreateWithFlags(&ctx->ev_prefetch, hipEventDisableTiming));
@@ -174,7 +174,7 @@ int kbj_destroy(kbj_ctx* ctx) {
   if (ctx->epst_part_d) hipFree(ctx->epst_part_d);
   if (ctx->ev0) hipEventDestroy(ctx->ev0);
   if (ctx->ev1) hipEventDestroy(ctx->ev1);
-  for (int k = 0; k < 32; ++k) if (ctx->ev_pool[k]) hipEventDestroy(ctx->ev_pool[k]);
+  if (ctx->ev_critic_loss) hipEventDestroy(ctx->ev_critic_loss);
   if (ctx->ev_actor_grad) hipEventDestroy(ctx->ev_actor_grad);
   if (ctx->ev_small) hipEventDestroy(ctx->ev_small);
   if (ctx->ev_prefetch) hipEventDestroy(ctx->ev_prefetch);

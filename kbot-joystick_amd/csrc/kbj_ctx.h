@@ -67,12 +67,11 @@ struct kbj_ctx {
   hipStream_t side[2] = {nullptr, nullptr};   // per-net side lanes for weight-gradient GEMMs
   hipEvent_t ev_dx[2] = {nullptr, nullptr};   // per net lane: the lane's recurrence launches of a layer (the upper layer's weight-gradient pair on the side lane starts behind their END)
   hipEvent_t ev_side[2] = {nullptr, nullptr};
-  hipEvent_t ev_obs = nullptr;                // the critic's gathered observation rows are in place (side lane, ppo_forward_nets)
+  hipEvent_t ev_obs = nullptr;                // the critic's gathered observation rows are in place (side lane, kbj_nn.hip Update::input_projections)
   hipEvent_t ev_prefetch = nullptr;           // kbj_ppo_prefetch: the next minibatch's head gathers are done
-  hipEvent_t ev_small = nullptr;              // the minibatch's small gathers / clears on the actor's side lane are done (ppo_forward_nets)
+  hipEvent_t ev_small = nullptr;              // the minibatch's small gathers / clears on the actor's side lane are done (kbj_nn.hip Update::gathers)
   hipEvent_t ev_actor_grad = nullptr;         // recorded by kbj_ppo_grad once the ACTOR's slice of the gradient is final (kbj_stream_wait_actor_grad)
-  hipEvent_t ev_pool[32] = {};                // lane-alignment events of kbj_ppo_grad
-  int ev_next = 0;
+  hipEvent_t ev_critic_loss = nullptr;        // kbj_ppo_grad without the fused critic head: the critic lane's loss half is queued (UpdatePlan::ev_critic_loss)
   kbj_model model_h;
   kbj_config cfg_h;
   KbjSettings set;              // the environment's say about this context (kbj_read_settings, once, in kbj_create); the fault-injection counters count down here

@@ -538,7 +538,7 @@ const float* fold_actor_weights(kbj_ctx* ctx, hipStream_t s, const float* params
 
 // Rollout-time input projections read W_in [H][nin] with nin = 65 / 475 floats per row: no 16-byte alignment, which puts the GEMM on its element-wise
 // load path for that operand (the critic's 8192 x 256 x 475 product ran at 27 TFLOP/s, with four times the load instructions - beside an env kernel
-// that is bound by vector issue). As in the update (ppo_forward_nets): a re-pitched copy with the observation rows' stride, zeros behind column nin,
+// that is bound by vector issue). As in the update (Update::input_projections): a re-pitched copy with the observation rows' stride, zeros behind column nin,
 // made once per rollout / policy step; the contraction then runs over the padded width (the rows' padding columns hold zeros: host/buffers.py).
 void repitch_input_weights(kbj_ctx* ctx, hipStream_t s, const float* params_d, int k_lo = 0, int k_hi = 2) {
   NnWs& w = *ws_of(ctx);
@@ -920,63 +920,148 @@ int head_gathers(kbj_ctx* ctx, hipStream_t st, const kbj_traj* tr, const int32_t
   return 0;
 }
 
-// ---- the first half of a PPO minibatch pass, shared by kbj_ppo_grad and kbj_ppo_forward -----------------------------------------------
-// gathers the minibatch (observations, actions, keep flags, start-of-trajectory carries; with `grad` also the old log-probs / values,
-// advantages and targets), prepares the folded actor weights, and runs both nets forward through time: afterwards w.tb[n].Hout[D-1]
-// holds the top layer's outputs and the BPTT stash is in place. Lanes: actor-type nets on ns[0] (the caller's stream), critic-type nets
-// on ns[1]; on return the two lanes are still forked (the caller joins them).
-int ppo_forward_nets(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const int32_t* idx, const float* adv_d, const float* target_d, float* grad_d,
-                     bool grad, hipStream_t ns[2]) {
-  NnWs& w = *ws_of(ctx);
-  const Sched& sc = w.sched;
-  const int T = tr->T, N = tr->N, H = w.H, B = w.B, R = T * B, D = w.D;
-  // lanes: ns[0] = actor-type nets, ns[1] = critic-type nets; one of them is the caller's stream (Sched::critic_on_caller), the other the context's second
-  ns[0] = (sc.one_stream || !sc.critic_on_caller) ? ctx->stream : ctx->stream2;
-  ns[1] = (sc.one_stream || sc.critic_on_caller) ? ctx->stream : ctx->stream2;
-  hipStream_t s = ns[0];   // "s" below = the actor's lane
-  // hand-off counters of all eight (sixteen with the mirror branches) recurrence launches of this call: one clear, ahead of both lanes
-  // (kbj_ppo_grad leaves them cleared: each lane clears its nets' blocks behind its last recurrence, off the head of the next minibatch's chain)
-  if (!w.counters_clean) KBJ_HIP(ctx, hipMemsetAsync(w.seq_counters, 0, SEQ_COUNTER_TOTAL * sizeof(unsigned), ctx->stream));
-  w.counters_clean = false;
-  KBJ_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-  KBJ_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-  // (first on the actor's lane, ahead of the gathers: the two small launches depend on the parameters only, and behind the gathers they
-  // queue for CU slots behind the 800 workgroups of the critic's input projection - 87 us on the actor's chain instead of ~25)
-  if (sc.fold_actor) {
-    // The actor's input projection (65 -> H, no activation) feeds only layer 0's input GEMM, so gates_0 = obs (W_ih0 W_in)^T +
-    // (W_ih0 b_in + b_0): a 65-deep contraction instead of 65 -> H -> 4H (6.8 instead of 28.5 GFLOP per minibatch forward, and
-    // 6.8 instead of 55 GFLOP backward). Same function, different rounding order (inside the parity tolerances).
-    const NetOff& oa = w.net[0];
-    GemmArgs g{params_d + oa.w_ih[0], params_d + oa.w_in, w.Weff, nullptr, 4 * H, oa.nin, H, H, oa.nin, oa.ld_obs, 0, 1, nullptr};
-    gemm_launch<true, false>(s, g);
-    matvec_launch(s, params_d + oa.w_ih[0], params_d + oa.b_in, params_d + oa.b[0], 4 * H, H, w.beff);
-  }
-  auto gather = [&](hipStream_t st, const float* src, int wdt, int lds, float* dst, int ldd) { gather_rows_launch(st, src, idx, T, N, B, wdt, lds, dst, ldd); };
+// ---- the PPO update (kbj_ppo_grad, kbj_ppo_forward, kbj_ppo_prefetch): ONE plan per call, named lane hops, one function per phase --------
+// A minibatch pass gathers the minibatch (observations, actions, keep flags, start-of-trajectory carries; for the gradient also the old
+// log-probs / values, advantages and targets), prepares the folded actor weights, runs the nets forward through time (afterwards
+// w.tb[n].Hout[D-1] holds the top layer's outputs and the BPTT stash is in place), and - kbj_ppo_grad - the heads, losses and the way back.
+// WHERE every launch goes is decided once, in update_plan(); the phases below read the plan and never re-derive a decision.
+
+// net n of the call (0 actor, 1 critic, 2 / 3 their mirror branches: same weights, queued behind nets 0, 1 on the same lanes)
+//   lane          the net's chain: actor-type nets on one lane, critic-type nets on the other; one of the two is the caller's stream, the other the context's second
+//   side          the net's side lane: work that hangs off the chain (weight-gradient GEMMs, bias sums); on one stream it IS the lane
+//   type          n & 1: the parameter / offset set (NnWs::net) and the per-type side lanes and events
+//   folded0       layer 0 goes backwards through Z = dG0^T obs, without dX0 (Sched::fold_actor; critic-type nets: and Sched::fold_critic)
+//   fwd_folded0   forwards as well: gates_0 = obs Weff^T + beff, no input projection (actor-type nets; the critic's fold is a backward formulation only)
+//   tail_on_lane  the net's layer-0 weight-gradient work, and the pair of the layer above it, run on the net's OWN lane (update_plan says why)
+struct NetPlan { hipStream_t lane, side; int type; bool folded0, fwd_folded0, tail_on_lane; };
+// the call
+//   two_lanes             !Sched::one_stream
+//   gather_late           the critic's gathered observation copy is made on its side lane, under the recurrences
+//   fused_critic_head     critic head, value loss and head backward as ONE kernel on the critic's lane
+//   fuse_ih, fuse_obs     forward input products inside the persistent recurrences
+//   critic_fork_recorded  the critic lane's record behind its loss doubles as the fork of its side lane
+//   ev_critic_loss        what the metrics launch at the end of the actor's lane waits for
+struct UpdatePlan {
+  NetPlan net[4];
+  int nnets;
+  bool two_lanes, gather_late, fused_critic_head, fuse_ih, fuse_obs, critic_fork_recorded;
+  hipEvent_t ev_critic_loss;
+};
+
+UpdatePlan update_plan(kbj_ctx* ctx) {
+  const NnWs& w = *ws_of(ctx); const Sched& sc = w.sched;
+  UpdatePlan p{};
+  p.nnets = w.nnets; p.two_lanes = !sc.one_stream;
   // The large critic observation block (97 MB per minibatch, 45 us at HBM speed): the forward pass reads it once, through the critic's
   // input projection - which fetches its rows straight from the trajectory through the minibatch's indices (GemmArgs::a_idx) - so the
   // gathered copy, which the backward pass and the mirror branch want, is made on the critic's side lane, off the chain that starts the
   // critic's first recurrence. (One stream, mirror branches or an unfolded actor: gathered in front of the projection as before.)
-  const bool gather_late = !sc.one_stream && !w.mirror && sc.fold_actor;
-  if (!gather_late) gather(ns[1], tr->critic_obs_d, w.net[1].ld_obs, w.net[1].ld_obs, w.tb[1].obs, w.net[1].ld_obs);
-  // What the FIRST recurrences read besides the parameters - the actor's observation rows, the keep flags, the start carries - depends on
-  // the trajectory and the indices only. kbj_ppo_prefetch has queued these gathers behind the end of the previous kbj_ppo_grad, on a
-  // side lane, where they run under the optimizer step and the folded-weight preparation instead of between them and the first recurrence.
-  GatherSmallArgs gs{tr->action_d, grad ? tr->logp_d : nullptr, grad ? tr->value_d : nullptr, adv_d, target_d, tr->aux_d, w.act, w.logp_old, w.val_old, w.adv, w.target, w.keep};
-  // A pending hint is ALWAYS waited for, matching or not: its gathers write the same workspace rows (observation copy, keep flags, start
-  // carries) from a side lane, so a call with other arguments must order its own gathers behind them before it overwrites them.
-  const bool pending = w.prefetched_idx != nullptr;
-  const bool prefetched = pending && w.prefetched_idx == idx && w.prefetched_traj == tr && !sc.one_stream;
-  w.prefetched_idx = nullptr; w.prefetched_traj = nullptr;
-  if (pending) KBJ_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_prefetch, 0));
-  if (!prefetched && head_gathers(ctx, s, tr, idx)) return -1;
-  {
+  p.gather_late = p.two_lanes && !w.mirror && sc.fold_actor;
+  // Without the mirror branches the critic's one-output head, the value half of the loss and the head's backward are ONE kernel on the
+  // critic's lane (critic_head_kernel: ~30 us instead of two degenerate GEMMs and three small kernels, ~220 us, on the longer chain).
+  p.fused_critic_head = sc.fused_critic_head && !w.mirror && w.net[1].nout == 1;
+  // forward: the K = H input projections (x W_ih^T + b) run inside the persistent recurrence, their MFMAs placed around the flag poll and
+  // the h-tile fetch where the matrix pipe idles (kbj_lstm_seq.h FUSE): a fused launch takes 1.11 instead of 0.88 ms, the 0.41-0.48 ms
+  // GEMM in front of it and its 210 MB round trip of G disappear: ppo_grad 7.72 -> 7.47 ms. Sched::fuse_ih = false: separate GEMMs.
+  p.fuse_ih = sc.fuse_ih;
+  // the folded actor layer 0 the same way (observation row x Weff inside the recurrence, 17 k-steps): Sched::fuse_obs = false keeps the GEMM
+  p.fuse_obs = sc.fuse_obs && w.net[0].ld_obs == KBJ_LD_ACTOR;
+  // The metrics line is nobody's input. It used to be a one-thread launch on a side lane behind the losses - where every CU is about to be taken by the
+  // backward recurrences (250 registers x 2 wavefronts per SIMD), so in most minibatches it sat dispatched-but-unplaced for ~450 us (2.9 % of the
+  // summed kernel time in a rocprofv3 summary, and the side lane's next launch queued behind it): the same "waiting for a wave slot" artefact as the
+  // pause kernel of rounds 4-5. It now runs at the END of the actor's lane (lane_tails), behind an event recorded on the critic's lane after its loss half.
+  // The critic lane's record doubles as the fork of its side lane when nothing is launched on that lane in between - the fused head: one packet.
+  // The event is then ev_side[1], which the join of the critic's side lane RE-RECORDS at the end of the call (projection_grads_and_joins): the
+  // actor lane's wait in lane_tails is for the end of the critic's side lane - which it has just waited for when the critic's bias terms ran
+  // on its own lane - not for the loss. Harmless (later in the same chain) and redundant there; the packet stays until a measured change
+  // removes it. Without the fused head (or on one stream, where nothing waits) it is an event of its own: the wait is for the loss half,
+  // which fired ~3 ms before.
+  p.critic_fork_recorded = p.two_lanes && p.fused_critic_head;
+  p.ev_critic_loss = p.critic_fork_recorded ? ctx->ev_side[1] : ctx->ev_critic_loss;
+  const int caller_type = sc.critic_on_caller ? 1 : 0;   // the net type whose lane is the caller's stream (Sched::critic_on_caller, kbj_ctx.h)
+  for (int n = 0; n < p.nnets; ++n) {
+    NetPlan& q = p.net[n]; q.type = n & 1;
+    q.lane = p.two_lanes && q.type != caller_type ? ctx->stream2 : ctx->stream;
+    q.side = p.two_lanes ? ctx->side[q.type] : q.lane;
+    q.folded0 = sc.fold_actor && (q.type == 0 || sc.fold_critic);
+    q.fwd_folded0 = q.folded0 && q.type == 0;
+    // The last thing a lane does - layer 0 of its net - needs no side lane: nothing is left on the net's lane for the weight
+    // gradients to run beside, and a cross-lane hop costs 15-20 us each way (fork + join) in the minibatch's tail. (Not with mirror
+    // branches: two nets per lane then read-modify-write the same dW_ih0 through their small products, which only the shared side
+    // lane orders.)
+    q.tail_on_lane = !w.mirror && q.folded0;
+  }
+  return p;
+}
+
+// Lane hops. Every ordering between two lanes of the update is one of these: an event recorded on one stream, waited for on another - one
+// packet each (a cross-queue wait costs the waiting queue ~7 us, 10-25 us when it has to stall: round 6), so a helper issues exactly the
+// calls its name says and a call site that reuses a record (UpdatePlan::critic_fork_recorded; ev_obs, which implies ev_small) says so.
+int ev_record(kbj_ctx* ctx, hipEvent_t ev, hipStream_t on) { KBJ_HIP(ctx, hipEventRecord(ev, on)); return 0; }
+int ev_wait(kbj_ctx* ctx, hipStream_t st, hipEvent_t ev) { KBJ_HIP(ctx, hipStreamWaitEvent(st, ev, 0)); return 0; }
+int hop(kbj_ctx* ctx, hipStream_t from, hipStream_t to, hipEvent_t ev) { return ev_record(ctx, ev, from) || ev_wait(ctx, to, ev) ? -1 : 0; }
+// the net's side lane starts behind what its lane has queued so far (one stream: stream order is the order)
+int fork_side(kbj_ctx* ctx, const UpdatePlan& p, const NetPlan& q) { return p.two_lanes ? hop(ctx, q.lane, q.side, ctx->ev_side[q.type]) : 0; }
+
+// One call of the update: the caller's arguments (adv, target, grad: kbj_ppo_grad only; grad == nullptr is the forward-only pass), the
+// minibatch's dimensions (R = T * B rows), the constants of the actor's head and of the loss, the plan - and the phases, in the order
+// ppo_forward_body / ppo_grad_body call them. Each returns 0 or what kbj_fail returned.
+struct Update {
+  kbj_ctx* ctx; const float* params; const kbj_traj* tr; const int32_t* idx; const float *adv, *target; float* grad;   // what a body below passes in; the rest follows from it
+  NnWs& w = *ws_of(ctx); const Sched& sc = w.sched; const kbj_config& c = ctx->cfg_h; const UpdatePlan p = update_plan(ctx);
+  const int T = tr->T, N = tr->N, H = w.H, B = w.B, R = T * B, D = w.D;
+  const HeadParams hp{c.min_std, c.max_std, c.var_scale, c.lpf_alpha, w.net[0].ld_obs};
+  const PpoParams pp{c.clip_param, c.value_clip, c.value_loss_coef, c.entropy_coef, c.log_ratio_clip, c.adv_eps};
+  bool bias_done[2] = {false, false};   // the layer-0 bias terms of net type k have run on the net's own lane (backward_layer); if not, lane_tails runs them
+
+  // phase: lane setup and counter clear
+  int lanes_begin() {
+    // hand-off counters of all eight (sixteen with the mirror branches) recurrence launches of this call: one clear, ahead of both lanes
+    // (kbj_ppo_grad leaves them cleared: each lane clears its nets' blocks behind its last recurrence, off the head of the next minibatch's chain)
+    if (!w.counters_clean) KBJ_HIP(ctx, hipMemsetAsync(w.seq_counters, 0, SEQ_COUNTER_TOTAL * sizeof(unsigned), ctx->stream));
+    w.counters_clean = false;
+    return hop(ctx, ctx->stream, ctx->stream2, ctx->ev_fork);
+  }
+
+  // phase: folded-weight preparation
+  // (first on the actor's lane, ahead of the gathers: the two small launches depend on the parameters only, and behind the gathers they
+  // queue for CU slots behind the 800 workgroups of the critic's input projection - 87 us on the actor's chain instead of ~25)
+  int folded_weights() {
+    if (!p.net[0].fwd_folded0) return 0;
+    // The actor's input projection (65 -> H, no activation) feeds only layer 0's input GEMM, so gates_0 = obs (W_ih0 W_in)^T +
+    // (W_ih0 b_in + b_0): a 65-deep contraction instead of 65 -> H -> 4H (6.8 instead of 28.5 GFLOP per minibatch forward, and
+    // 6.8 instead of 55 GFLOP backward). Same function, different rounding order (inside the parity tolerances).
+    const NetOff& oa = w.net[0];
+    GemmArgs g{params + oa.w_ih[0], params + oa.w_in, w.Weff, nullptr, 4 * H, oa.nin, H, H, oa.nin, oa.ld_obs, 0, 1, nullptr};
+    gemm_launch<true, false>(p.net[0].lane, g);
+    matvec_launch(p.net[0].lane, params + oa.w_ih[0], params + oa.b_in, params + oa.b[0], 4 * H, H, w.beff);
+    return 0;
+  }
+
+  // the critic's observation rows of the minibatch, gathered (early on its lane, or late on its side lane: UpdatePlan::gather_late)
+  void gather_critic_obs(hipStream_t st, int ld) { gather_rows_launch(st, tr->critic_obs_d, idx, T, N, B, ld, ld, w.tb[1].obs, ld); }
+
+  // phase: gathers - the head gathers on the actor's lane (unless prefetched), the small ones and the clears on its side lane, the critic's
+  // observations on its lane unless they are gathered late (input_projections), the mirrored observation rows
+  int gathers() {
+    const hipStream_t s = p.net[0].lane, sm = p.net[0].side;
+    if (!p.gather_late) gather_critic_obs(p.net[1].lane, w.net[1].ld_obs);
+    // What the FIRST recurrences read besides the parameters - the actor's observation rows, the keep flags, the start carries - depends on
+    // the trajectory and the indices only. kbj_ppo_prefetch has queued these gathers behind the end of the previous kbj_ppo_grad, on a
+    // side lane, where they run under the optimizer step and the folded-weight preparation instead of between them and the first recurrence.
+    // A pending hint is ALWAYS waited for, matching or not: its gathers write the same workspace rows (observation copy, keep flags, start
+    // carries) from a side lane, so a call with other arguments must order its own gathers behind them before it overwrites them.
+    const bool pending = w.prefetched_idx != nullptr;
+    const bool prefetched = pending && w.prefetched_idx == idx && w.prefetched_traj == tr && p.two_lanes;
+    w.prefetched_idx = nullptr; w.prefetched_traj = nullptr;
+    if ((pending && ev_wait(ctx, s, ctx->ev_prefetch)) || (!prefetched && head_gathers(ctx, s, tr, idx))) return -1;
     // Nothing on the forward path needs the rest: actions, old log-probs / values, advantages, targets, the advantage statistics and the
     // cleared accumulators (gradient, folded layer-0 products) are wanted at the loss, two recurrences later. They run on the actor's
     // side lane, idle until the backward pass, instead of in front of the first recurrence (where they were ~170 us of a 6 ms
     // minibatch with the matrix cores idle); both net lanes wait for them behind their last forward recurrence, and the side lanes
     // fork from the net lanes after that point, so every later reader and accumulator is ordered behind the clears.
-    hipStream_t sm = sc.one_stream ? s : ctx->side[0];
-    if (!sc.one_stream) KBJ_HIP(ctx, hipStreamWaitEvent(sm, ctx->ev_fork, 0));
+    if (p.two_lanes && ev_wait(ctx, sm, ctx->ev_fork)) return -1;
+    GatherSmallArgs gs{tr->action_d, grad ? tr->logp_d : nullptr, grad ? tr->value_d : nullptr, adv, target, tr->aux_d, w.act, w.logp_old, w.val_old, w.adv, w.target, w.keep};
     gather_small_launch(sm, gs, idx, T, N, B, 0, KBJ_NU + 4);
     if (grad) {
       KBJ_HIP(ctx, hipMemsetAsync(w.stats, 0, 16 * sizeof(double), sm));
@@ -991,205 +1076,151 @@ int ppo_forward_nets(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, co
         adv_stats_launch(sm, w.adv, R, w.stats, sc.deterministic ? w.detd : (double*)nullptr);
         if (sc.deterministic) reduce_double_launch(sm, w.detd, ADV_STATS_BLOCKS, 2, w.stats);
       }
-      KBJ_HIP(ctx, hipMemsetAsync(grad_d, 0, w.nparams * sizeof(float), sm));
-      if (sc.fold_actor)
-        for (int n = 0; n < w.nnets; ++n)
-          if ((n & 1) == 0 || sc.fold_critic) KBJ_HIP(ctx, hipMemsetAsync(w.Zeff[n], 0, (size_t)4 * H * w.net[n & 1].ld_obs * sizeof(float), sm));
+      KBJ_HIP(ctx, hipMemsetAsync(grad, 0, w.nparams * sizeof(float), sm));
+      for (int n = 0; n < p.nnets; ++n)
+        if (p.net[n].folded0) KBJ_HIP(ctx, hipMemsetAsync(w.Zeff[n], 0, (size_t)4 * H * w.net[p.net[n].type].ld_obs * sizeof(float), sm));
     }
-    if (!sc.one_stream) KBJ_HIP(ctx, hipEventRecord(ctx->ev_small, sm));
+    // ev_join: the critic's lane needs keep / carries (gathered above on the actor's lane) before its first recurrence - not before its input
+    // projection, which only reads its own gather: the wait sits behind the projections (input_projections)
+    if ((p.two_lanes && ev_record(ctx, ctx->ev_small, sm)) || ev_record(ctx, ctx->ev_join, s)) return -1;
+    if (w.mirror)   // mirrored observation rows: actor's on its lane, critic's behind its gather
+      for (int k = 0; k < 2; ++k)
+        mirror_rows_launch(p.net[k].lane, w.tb[k].obs, w.tb[2 + k].obs, (size_t)R, w.net[k].ld_obs, w.mtab[k]);
+    return 0;
   }
-  // the critic's lane needs keep / carries (gathered above on the actor's lane) before its first recurrence - not before its input
-  // projection, which only reads its own gather: the wait sits in front of the recurrences below
-  KBJ_HIP(ctx, hipEventRecord(ctx->ev_join, ns[0]));
-  if (w.mirror)   // mirrored observation rows: actor's on the caller's stream, critic's behind its gather
-    for (int k = 0; k < 2; ++k)
-      mirror_rows_launch(ns[k], w.tb[k].obs, w.tb[2 + k].obs, (size_t)R, w.net[k].ld_obs, w.mtab[k]);
-  // ---- forward through time: actor on the caller's stream, critic on the context's second stream (the recurrences are
-  // latency bound, so the two nets overlap) ----
-  const int stamp_sel = ctx->set.stamp_sel;   // diagnostics build: 1 + net + 2 * layer picks the stamped forward launch
-  const int stamp_net = (stamp_sel - 1) & 1, stamp_layer = ((stamp_sel - 1) >> 1) & 1;
-  // forward: the K = H input projections (x W_ih^T + b) run inside the persistent recurrence, their MFMAs placed around the flag poll and
-  // the h-tile fetch where the matrix pipe idles (kbj_lstm_seq.h FUSE): a fused launch takes 1.11 instead of 0.88 ms, the 0.41-0.48 ms
-  // GEMM in front of it and its 210 MB round trip of G disappear: ppo_grad 7.72 -> 7.47 ms. Sched::fuse_ih = false: separate GEMMs.
-  const bool fuse_ih = sc.fuse_ih;
-  // the folded actor layer 0 the same way (observation row x Weff inside the recurrence, 17 k-steps): Sched::fuse_obs = false keeps the GEMM
-  const bool fuse_obs = sc.fuse_obs && w.net[0].ld_obs == KBJ_LD_ACTOR;
-  // Launch order is layer-major over the nets (nets 2, 3 = mirror branches, same weights, queued behind nets 0, 1 on the same two streams).
-  for (int n = 0; n < w.nnets; ++n) {
-    const NetOff& o = w.net[n & 1];
-    if (sc.fold_actor && (n & 1) == 0) continue;   // actor-type nets: layer-0 gates come straight from the observations
-    // X0 = obs W_in^T + b_in. The stored rows of W_in are nin (65 / 475) floats long - no 16-byte alignment, which would put the GEMM on
-    // its element-wise load path for this operand (55 instead of ~90 TF for the critic's 12 GFLOP, at the head of the longer chain): a
-    // re-pitched copy with the observation rows' stride (zeros behind column nin, as in the observation rows) is made first; the
-    // contraction then runs over the padded width
-    if (n < 2) repitch_rows_launch(ns[n & 1], params_d + o.w_in, H, o.nin, o.ld_obs, w.WinP[n & 1]);
-    if (n == 1 && gather_late) {
-      GemmArgs g{tr->critic_obs_d, w.WinP[1], w.tb[1].X0, params_d + o.b_in, R, H, o.ld_obs, o.ld_obs, o.ld_obs, H, 0, 1, nullptr};
-      g.a_idx = idx; g.a_B = B; g.a_N = N;
-      g.x3 = sc.gemm_x3 ? 1 : 0;
-      gemm_launch<true, true>(ns[1], g, sc.gemm_x3 ? -1 : 2);   // 64 x 128 tiles (kbj_gemm.h: 800 tiles of 128 x 128 are 1.56 rounds paid as 2)
-      // the copy under the recurrences, on the critic's side lane. It starts behind the ACTOR lane's head (ev_join: the folded-weight preparation
-      // and, without a prefetch hint, the head gathers - about when the projection ends; beside it the two would share HBM: 175 instead of 144 us
-      // for the GEMM) and behind the side-lane gathers (ev_small), so that ev_obs implies both and the critic's lane - the chain a minibatch
-      // waits for - carries ONE event wait in front of its loss instead of a record and two waits (each costs the queue ~7 us, round 6)
-      KBJ_HIP(ctx, hipStreamWaitEvent(ctx->side[1], ctx->ev_join, 0));
-      KBJ_HIP(ctx, hipStreamWaitEvent(ctx->side[1], ctx->ev_small, 0));
-      if (grad) gather(ctx->side[1], tr->critic_obs_d, w.net[1].ld_obs, w.net[1].ld_obs, w.tb[1].obs, w.net[1].ld_obs);   // the forward-only pass never reads the copy
-      KBJ_HIP(ctx, hipEventRecord(ctx->ev_obs, ctx->side[1]));
-      continue;
-    }
-    linear_fwd(ns[n & 1], w.tb[n].obs, o.ld_obs, w.WinP[n & 1], o.ld_obs, params_d + o.b_in, w.tb[n].X0, H, R, H, o.ld_obs, 0);
-  }
-  if (!sc.one_stream) KBJ_HIP(ctx, hipStreamWaitEvent(ns[1], ctx->ev_join, 0));   // keep / carries gathered on the actor's lane
-  for (int l = 0; l < D; ++l) {
-    for (int n = 0; n < w.nnets; ++n) {
-      const NetOff& o = w.net[n & 1];
-      TrainBufs& t = w.tb[n];
-      if (sc.fold_actor && (n & 1) == 0 && l == 0) { if (!fuse_obs) linear_fwd(ns[0], t.obs, o.ld_obs, w.Weff, o.ld_obs, w.beff, t.G[0], 4 * H, R, 4 * H, o.nin, 0); }
-      else if (!fuse_ih) linear_fwd(ns[n & 1], l == 0 ? t.X0 : t.Hout[l - 1], H, params_d + o.w_ih[l], H, params_d + o.b[l], t.G[l], 4 * H, R, 4 * H, H, 0);
-    }
-    for (int n = 0; n < w.nnets; ++n) {
-      const NetOff& o = w.net[n & 1];
-      TrainBufs& t = w.tb[n];
-      SeqFwdArgs fa{t.G[l], params_d + o.w_hh[l], t.Hm[l], t.Cm[l], t.Hout[l], t.TanhC[l], w.keep, w.seq_counters + SEQ_COUNTER_WORDS * (4 * l + n), w.seq_err, T, B, (n == stamp_net && l == stamp_layer) ? w.seq_stamps : nullptr};
-      if (sc.fold_actor && (n & 1) == 0 && l == 0) {
-        if (fuse_obs) { fa.X = t.obs; fa.ldx = o.ld_obs; fa.Wih = w.Weff; fa.ldw = o.ld_obs; fa.bias = w.beff; fa.kx = o.nin; }   // gates_0 = obs Weff^T + beff inside the recurrence
-      } else if (fuse_ih) {   // K = H input projections ride inside the recurrence (kbj_lstm_seq.h FUSE)
-        fa.X = l == 0 ? t.X0 : t.Hout[l - 1]; fa.Wih = params_d + o.w_ih[l]; fa.bias = params_d + o.b[l];
+
+  // phase: input projections X0 = obs W_in^T + b_in of the nets that have one forwards (launch order: net-major here, layer-major over the nets below)
+  int input_projections() {
+    for (int n = 0; n < p.nnets; ++n) {
+      const NetPlan& q = p.net[n]; const NetOff& o = w.net[q.type];
+      if (q.fwd_folded0) continue;   // layer-0 gates come straight from the observations
+      // The stored rows of W_in are nin (65 / 475) floats long - no 16-byte alignment, which would put the GEMM on
+      // its element-wise load path for this operand (55 instead of ~90 TF for the critic's 12 GFLOP, at the head of the longer chain): a
+      // re-pitched copy with the observation rows' stride (zeros behind column nin, as in the observation rows) is made first; the
+      // contraction then runs over the padded width
+      if (n < 2) repitch_rows_launch(q.lane, params + o.w_in, H, o.nin, o.ld_obs, w.WinP[q.type]);
+      if (n == 1 && p.gather_late) {
+        GemmArgs g{tr->critic_obs_d, w.WinP[1], w.tb[1].X0, params + o.b_in, R, H, o.ld_obs, o.ld_obs, o.ld_obs, H, 0, 1, nullptr};
+        g.a_idx = idx; g.a_B = B; g.a_N = N; g.x3 = sc.gemm_x3 ? 1 : 0;
+        gemm_launch<true, true>(q.lane, g, sc.gemm_x3 ? -1 : 2);   // 64 x 128 tiles (kbj_gemm.h: 800 tiles of 128 x 128 are 1.56 rounds paid as 2)
+        // the copy under the recurrences, on the critic's side lane. It starts behind the ACTOR lane's head (ev_join: the folded-weight preparation
+        // and, without a prefetch hint, the head gathers - about when the projection ends; beside it the two would share HBM: 175 instead of 144 us
+        // for the GEMM) and behind the side-lane gathers (ev_small), so that ev_obs implies both and the critic's lane - the chain a minibatch
+        // waits for - carries ONE event wait in front of its loss instead of a record and two waits (each costs the queue ~7 us, round 6)
+        if (ev_wait(ctx, q.side, ctx->ev_join) || ev_wait(ctx, q.side, ctx->ev_small)) return -1;
+        if (grad) gather_critic_obs(q.side, o.ld_obs);   // the forward-only pass never reads the copy
+        if (ev_record(ctx, ctx->ev_obs, q.side)) return -1;
+        continue;
       }
-      if (seq_fwd(ctx, ns[n & 1], H, fa)) return -1;
+      linear_fwd(q.lane, w.tb[n].obs, o.ld_obs, w.WinP[q.type], o.ld_obs, params + o.b_in, w.tb[n].X0, H, R, H, o.ld_obs, 0);
     }
+    if (p.two_lanes && ev_wait(ctx, p.net[1].lane, ctx->ev_join)) return -1;   // keep / carries gathered on the actor's lane
+    return 0;
   }
-  if (!sc.one_stream) {
-    KBJ_HIP(ctx, hipStreamWaitEvent(ns[0], ctx->ev_small, 0));   // the side-lane gathers / clears above
-    // the critic's lane: its gathered rows (read by its backward pass) - an event that implies ev_small (above) - or ev_small itself
-    KBJ_HIP(ctx, hipStreamWaitEvent(ns[1], gather_late ? ctx->ev_obs : ctx->ev_small, 0));
-  }
-  return 0;
-}
 
-int ppo_forward_body(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const int32_t* env_idx_d, kbj_ppo_vars* out) {
-  NnWs& w = *ws_of(ctx);
-  const kbj_config& c = ctx->cfg_h;
-  const int T = tr->T, H = w.H, B = w.B, R = T * B, D = w.D;
-  hipStream_t ns[2];
-  if (ppo_forward_nets(ctx, params_d, tr, env_idx_d, nullptr, nullptr, nullptr, false, ns)) return -1;
-  hipStream_t s = ns[0];   // the actor's lane
-  for (int n = 0; n < 2; ++n) {
-    const NetOff& o = w.net[n];
-    linear_fwd(ns[n], w.tb[n].Hout[D - 1], H, params_d + o.w_out, H, params_d + o.b_out, w.tb[n].Out, 40, R, o.nout, H, 0);
+  // phase: forward through time, each net on its lane (the recurrences are latency bound, so the two lanes overlap); layer-major over the nets.
+  // On return the two lanes are still forked (lane_tails / ppo_forward_body join them).
+  int forward_recurrences() {
+    const int stamp_sel = ctx->set.stamp_sel;   // diagnostics build: 1 + net + 2 * layer picks the stamped forward launch
+    const int stamp_net = (stamp_sel - 1) & 1, stamp_layer = ((stamp_sel - 1) >> 1) & 1;
+    for (int l = 0; l < D; ++l) {
+      for (int n = 0; n < p.nnets; ++n) {
+        const NetPlan& q = p.net[n]; const NetOff& o = w.net[q.type]; TrainBufs& t = w.tb[n];
+        if (q.fwd_folded0 && l == 0) { if (!p.fuse_obs) linear_fwd(q.lane, t.obs, o.ld_obs, w.Weff, o.ld_obs, w.beff, t.G[0], 4 * H, R, 4 * H, o.nin, 0); }
+        else if (!p.fuse_ih) linear_fwd(q.lane, l == 0 ? t.X0 : t.Hout[l - 1], H, params + o.w_ih[l], H, params + o.b[l], t.G[l], 4 * H, R, 4 * H, H, 0);
+      }
+      for (int n = 0; n < p.nnets; ++n) {
+        const NetPlan& q = p.net[n]; const NetOff& o = w.net[q.type]; TrainBufs& t = w.tb[n];
+        SeqFwdArgs fa{t.G[l], params + o.w_hh[l], t.Hm[l], t.Cm[l], t.Hout[l], t.TanhC[l], w.keep, w.seq_counters + SEQ_COUNTER_WORDS * (4 * l + n), w.seq_err, T, B, (n == stamp_net && l == stamp_layer) ? w.seq_stamps : nullptr};
+        if (q.fwd_folded0 && l == 0) {
+          if (p.fuse_obs) { fa.X = t.obs; fa.ldx = o.ld_obs; fa.Wih = w.Weff; fa.ldw = o.ld_obs; fa.bias = w.beff; fa.kx = o.nin; }   // gates_0 = obs Weff^T + beff inside the recurrence
+        } else if (p.fuse_ih) {   // K = H input projections ride inside the recurrence (kbj_lstm_seq.h FUSE)
+          fa.X = l == 0 ? t.X0 : t.Hout[l - 1]; fa.Wih = params + o.w_ih[l]; fa.bias = params + o.b[l];
+        }
+        if (seq_fwd(ctx, q.lane, H, fa)) return -1;
+      }
+    }
+    // both lanes wait for the side-lane gathers / clears (gathers): the actor's for ev_small, the critic's for its gathered rows (read by its
+    // backward pass) - an event that implies ev_small - or ev_small itself
+    return p.two_lanes && (ev_wait(ctx, p.net[0].lane, ctx->ev_small) || ev_wait(ctx, p.net[1].lane, p.gather_late ? ctx->ev_obs : ctx->ev_small)) ? -1 : 0;
   }
-  HeadParams hp{c.min_std, c.max_std, c.var_scale, c.lpf_alpha, w.net[0].ld_obs};
-  actor_head_pre_launch(s, w.tb[0].Out, w.tb[0].obs, w.joint_bias_d, hp, R, w.y, w.sd);
-  actor_head_train_fwd_launch(s, w.keep, w.lpf0, hp, T, B, w.y);
-  gaussian_logp_launch(s, w.y, w.sd, w.act, R, out->logp_d, out->entropy_d ? out->entropy_d : w.ent);
-  if (out->action_std_d) KBJ_HIP(ctx, hipMemcpyAsync(out->action_std_d, w.sd, (size_t)R * KBJ_NU * sizeof(float), hipMemcpyDeviceToDevice, s));
-  if (out->action_mean_d) KBJ_HIP(ctx, hipMemcpyAsync(out->action_mean_d, w.y, (size_t)R * KBJ_NU * sizeof(float), hipMemcpyDeviceToDevice, s));
-  critic_value_launch(ns[1], w.tb[1].Out, 40, R, out->value_d);
-  if (!w.sched.one_stream) {
-    KBJ_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
-    KBJ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-  }
-  hipLaunchKernelGGL(poison_vars_kernel, dim3(1), dim3(1), 0, ctx->stream, w.seq_err, out->logp_d, out->value_d);   // a recurrence timed out: no silent garbage
-  KBJ_CHECK_LAUNCH(ctx, "kbj_ppo_forward");
-  if (w.sched.debug_sync) return kbj_synchronize(ctx);
-  return 0;
-}
 
-int ppo_grad_body(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const int32_t* env_idx_d, const float* adv_d, const float* target_d,
-                  float* grad_d, float* metrics_d) {
-  NnWs& w = *ws_of(ctx);
-  const kbj_config& c = ctx->cfg_h;
-  const Sched& sc = w.sched;
-  const int T = tr->T, H = w.H, B = w.B, R = T * B, D = w.D;
-  KbjTimed timed(ctx, true);
-  const bool one_stream = sc.one_stream, fold_actor = sc.fold_actor, fold_critic = sc.fold_critic;
-  hipStream_t ns[2];
-  if (ppo_forward_nets(ctx, params_d, tr, env_idx_d, adv_d, target_d, grad_d, true, ns)) return -1;
-  hipStream_t s = ns[0];   // "s" = the actor's lane (the caller's stream or the context's second one, Sched::critic_on_caller)
-  const int bstamp_sel = ctx->set.bstamp_sel;   // diagnostics build only
-  // Without the mirror branches the critic's one-output head, the value half of the loss and the head's backward are ONE kernel on the
-  // critic's lane (critic_head_kernel: ~30 us instead of two degenerate GEMMs and three small kernels, ~220 us, on the longer chain).
-  const bool fused_critic_head = sc.fused_critic_head && !w.mirror && w.net[1].nout == 1;
-  for (int n = 0; n < w.nnets; ++n) {
-    const NetOff& o = w.net[n & 1];
-    if (n == 1 && fused_critic_head) continue;
-    linear_fwd(ns[n & 1], w.tb[n].Hout[D - 1], H, params_d + o.w_out, H, params_d + o.b_out, w.tb[n].Out, 40, R, o.nout, H, 0);
+  // phase: heads forward - the output projections of the first `nets` nets (not the critic's when the fused head computes it with the loss),
+  // then the actor's head: pre-activation, low-pass scan over time, log-probabilities and entropy. The critic's value is the caller's next launch.
+  void heads_forward(int nets, float* logp, float* ent) {
+    const hipStream_t s = p.net[0].lane;
+    for (int n = 0; n < nets; ++n) {
+      const NetOff& o = w.net[p.net[n].type];
+      if (!(n == 1 && grad && p.fused_critic_head)) linear_fwd(p.net[n].lane, w.tb[n].Hout[D - 1], H, params + o.w_out, H, params + o.b_out, w.tb[n].Out, 40, R, o.nout, H, 0);
+    }
+    actor_head_pre_launch(s, w.tb[0].Out, w.tb[0].obs, w.joint_bias_d, hp, R, w.y, w.sd);
+    actor_head_train_fwd_launch(s, w.keep, w.lpf0, hp, T, B, w.y);
+    gaussian_logp_launch(s, w.y, w.sd, w.act, R, logp, ent);
   }
-  // heads and losses: the policy terms need the actor only, the value terms the critic only (the mirror terms likewise), so each lane
+
+  // phase: losses. The policy terms need the actor only, the value terms the critic only (the mirror terms likewise), so each lane
   // computes its own and the two chains stay independent through the whole call: the shorter actor chain runs ahead, and its
   // recurrences meet the critic's GEMM phases instead of the critic's recurrences
-  HeadParams hp{c.min_std, c.max_std, c.var_scale, c.lpf_alpha, w.net[0].ld_obs};
-  PpoParams pp{c.clip_param, c.value_clip, c.value_loss_coef, c.entropy_coef, c.log_ratio_clip, c.adv_eps};
-  actor_head_pre_launch(s, w.tb[0].Out, w.tb[0].obs, w.joint_bias_d, hp, R, w.y, w.sd);
-  actor_head_train_fwd_launch(s, w.keep, w.lpf0, hp, T, B, w.y);
-  gaussian_logp_launch(s, w.y, w.sd, w.act, R, w.logp, w.ent);
-  ppo_loss_launch(s, w.logp, w.value, w.ent, w.logp_old, w.val_old, w.adv, w.target, w.stats, pp, R, w.dlogp, w.dvalue, w.stats + 2, one_stream ? 0 : 1);
-  if (fused_critic_head) {
-    const NetOff& oc = w.net[1];
-    TrainBufs& tc = w.tb[1];
-    const bool built = critic_head_launch(ns[1], H, tc.Hout[D - 1], params_d + oc.w_out, params_d + oc.b_out, w.val_old, w.target, pp, R, w.value, w.dvalue, tc.dOut, tc.dHa, w.stats + 2);
-    if (!built) return kbj_fail(ctx, "kbj_ppo_grad: critic_head_kernel is built for hidden sizes 64, 128, ..., 512");
-    if (one_stream) ppo_loss_launch(s, w.logp, w.value, w.ent, w.logp_old, w.val_old, w.adv, w.target, w.stats, pp, R, w.dlogp, w.dvalue, w.stats + 2, 1);   // (the actor's launch above was a no-op in this diagnostic mode)
-  } else {
-    critic_value_launch(ns[1], w.tb[1].Out, 40, R, w.value);
-    ppo_loss_launch(ns[1], w.logp, w.value, w.ent, w.logp_old, w.val_old, w.adv, w.target, w.stats, pp, R, w.dlogp, w.dvalue, w.stats + 2, one_stream ? 3 : 2);
+  int losses() {
+    const hipStream_t s = p.net[0].lane, sv = p.net[1].lane;   // the actor's lane, the critic's
+    ppo_loss_launch(s, w.logp, w.value, w.ent, w.logp_old, w.val_old, w.adv, w.target, w.stats, pp, R, w.dlogp, w.dvalue, w.stats + 2, p.two_lanes ? 1 : 0);
+    if (p.fused_critic_head) {
+      const NetOff& oc = w.net[1]; TrainBufs& tc = w.tb[1];
+      const bool built = critic_head_launch(sv, H, tc.Hout[D - 1], params + oc.w_out, params + oc.b_out, w.val_old, w.target, pp, R, w.value, w.dvalue, tc.dOut, tc.dHa, w.stats + 2);
+      if (!built) return kbj_fail(ctx, "kbj_ppo_grad: critic_head_kernel is built for hidden sizes 64, 128, ..., 512");
+      if (!p.two_lanes) ppo_loss_launch(s, w.logp, w.value, w.ent, w.logp_old, w.val_old, w.adv, w.target, w.stats, pp, R, w.dlogp, w.dvalue, w.stats + 2, 1);   // (the actor's launch above was a no-op in this diagnostic mode)
+    } else {
+      critic_value_launch(sv, w.tb[1].Out, 40, R, w.value);
+      ppo_loss_launch(sv, w.logp, w.value, w.ent, w.logp_old, w.val_old, w.adv, w.target, w.stats, pp, R, w.dlogp, w.dvalue, w.stats + 2, p.two_lanes ? 2 : 3);
+    }
+    if (w.mirror) {   // aux losses between each net and its mirror branch (train.py:1463-1481)
+      actor_head_pre_launch(s, w.tb[2].Out, w.tb[2].obs, w.joint_bias_d, hp, R, w.y_m, w.sd_m);
+      actor_head_train_fwd_launch(s, w.keep, w.lpf0_m, hp, T, B, w.y_m);
+      mirror_loss_launch(s, w.y, w.y_m, w.value, w.value_m, c.actor_mirror_loss_scale, c.critic_mirror_loss_scale, R, w.dy, w.dy_m, w.dvalue, w.dvalue_m, w.stats + 2, p.two_lanes ? 1 : 0);
+      critic_value_launch(sv, w.tb[3].Out, 40, R, w.value_m);
+      mirror_loss_launch(sv, w.y, w.y_m, w.value, w.value_m, c.actor_mirror_loss_scale, c.critic_mirror_loss_scale, R, w.dy, w.dy_m, w.dvalue, w.dvalue_m, w.stats + 2, p.two_lanes ? 2 : 3);
+    }
+    return p.two_lanes ? ev_record(ctx, p.ev_critic_loss, sv) : 0;   // for the metrics launch (UpdatePlan::ev_critic_loss)
   }
-  if (w.mirror) {   // aux losses between each net and its mirror branch (train.py:1463-1481)
-    actor_head_pre_launch(s, w.tb[2].Out, w.tb[2].obs, w.joint_bias_d, hp, R, w.y_m, w.sd_m);
-    actor_head_train_fwd_launch(s, w.keep, w.lpf0_m, hp, T, B, w.y_m);
-    mirror_loss_launch(s, w.y, w.y_m, w.value, w.value_m, c.actor_mirror_loss_scale, c.critic_mirror_loss_scale, R, w.dy, w.dy_m, w.dvalue, w.dvalue_m, w.stats + 2, one_stream ? 0 : 1);
-    critic_value_launch(ns[1], w.tb[3].Out, 40, R, w.value_m);
-    mirror_loss_launch(ns[1], w.y, w.y_m, w.value, w.value_m, c.actor_mirror_loss_scale, c.critic_mirror_loss_scale, R, w.dy, w.dy_m, w.dvalue, w.dvalue_m, w.stats + 2, one_stream ? 3 : 2);
+
+  // The two dH buffers of a net alternate down the layers: dh_of(t, l) is what layer l's backward recurrence reads (l = D - 1: the head's
+  // input gradient), dh_of(t, l - 1) where its input gradient goes (l = 0: dX0, the input projection's)
+  float* dh_of(const TrainBufs& t, int l) const { return (D - 1 - l) % 2 == 0 ? t.dHa : t.dHb; }
+
+  // phase: head backward and output-projection gradients (dOut needs no clearing: the actor head writes all 40 columns, the critic's GEMMs read column 0 only)
+  int heads_backward() {
+    const hipStream_t s = p.net[0].lane;
+    actor_head_bwd_pre_launch(s, w.tb[0].Out, w.y, w.sd, w.act, w.dlogp, w.mirror ? w.dy : (const float*)nullptr, -c.entropy_coef / (float)R, hp, R, w.tb[0].dOut);
+    actor_head_train_bwd_launch(s, w.keep, hp, T, B, w.tb[0].dOut);
+    if (!p.fused_critic_head) KBJ_HIP(ctx, hipMemcpy2DAsync(w.tb[1].dOut, 40 * sizeof(float), w.dvalue, sizeof(float), sizeof(float), R, hipMemcpyDeviceToDevice, p.net[1].lane));
+    if (w.mirror) {   // the mirror actor only sees the aux gradient on its filtered mean (no log-prob, no entropy term)
+      actor_head_bwd_pre_launch(s, w.tb[2].Out, w.y_m, w.sd_m, w.y_m, w.zeroR, w.dy_m, 0.0f, hp, R, w.tb[2].dOut);
+      actor_head_train_bwd_launch(s, w.keep, hp, T, B, w.tb[2].dOut);
+      KBJ_HIP(ctx, hipMemcpy2DAsync(w.tb[3].dOut, 40 * sizeof(float), w.dvalue_m, sizeof(float), sizeof(float), R, hipMemcpyDeviceToDevice, p.net[1].lane));
+    }
+    // The critical path of a net is dOut -> dH -> (recurrence, dX) per layer. Weight/bias gradients hang off it: they go to the
+    // net's side lane so the throughput-bound split-K GEMMs run beside the dX GEMMs in the GEMM phases.
+    for (int n = 0; n < p.nnets; ++n) {
+      const NetPlan& q = p.net[n]; const NetOff& o = w.net[q.type]; TrainBufs& t = w.tb[n];
+      if (!(n == 1 && p.fused_critic_head)) linear_bwd_input(q.lane, sc.gemm_x3, t.dOut, 40, params + o.w_out, H, t.dHa, H, R, H, o.nout, 0);
+      if (n == 1 && p.critic_fork_recorded) { if (ev_wait(ctx, q.side, ctx->ev_side[1])) return -1; }   // recorded behind the loss (losses): one packet
+      else if (fork_side(ctx, p, q)) return -1;
+      linear_bwd_weight(ctx, q.side, sc.gemm_x3, t.dOut, 40, t.Hout[D - 1], H, grad + o.w_out, H, o.nout, H, R);
+      colsum_acc(ctx, q.side, t.dOut, R, o.nout, 40, grad + o.b_out);
+    }
+    return 0;
   }
-  // The metrics line is nobody's input. It used to be a one-thread launch on a side lane right here - where every CU is about to be taken by the
-  // backward recurrences (250 registers x 2 wavefronts per SIMD), so in most minibatches it sat dispatched-but-unplaced for ~450 us (2.9 % of the
-  // summed kernel time in a rocprofv3 summary, and the side lane's next launch queued behind it): the same "waiting for a wave slot" artefact as the
-  // pause kernel of rounds 4-5. It now runs at the END of the actor's lane (below), behind an event of the critic's loss half.
-  // (the critic lane's record doubles as the fork of its side lane below when nothing is launched on it in between - the fused head: one packet)
-  const bool critic_fork_recorded = !one_stream && fused_critic_head;
-  hipEvent_t ev_critic_loss = critic_fork_recorded ? ctx->ev_side[1] : ctx->ev_pool[ctx->ev_next++ & 31];
-  if (!one_stream) hipEventRecord(ev_critic_loss, ns[1]);
-  // ---- backward ---- (dOut needs no clearing: the actor head writes all 40 columns, the critic's GEMMs read column 0 only)
-  actor_head_bwd_pre_launch(s, w.tb[0].Out, w.y, w.sd, w.act, w.dlogp, w.mirror ? w.dy : (const float*)nullptr, -c.entropy_coef / (float)R, hp, R, w.tb[0].dOut);
-  actor_head_train_bwd_launch(s, w.keep, hp, T, B, w.tb[0].dOut);
-  if (!fused_critic_head) KBJ_HIP(ctx, hipMemcpy2DAsync(w.tb[1].dOut, 40 * sizeof(float), w.dvalue, sizeof(float), sizeof(float), R, hipMemcpyDeviceToDevice, ns[1]));
-  if (w.mirror) {   // the mirror actor only sees the aux gradient on its filtered mean (no log-prob, no entropy term)
-    actor_head_bwd_pre_launch(s, w.tb[2].Out, w.y_m, w.sd_m, w.y_m, w.zeroR, w.dy_m, 0.0f, hp, R, w.tb[2].dOut);
-    actor_head_train_bwd_launch(s, w.keep, hp, T, B, w.tb[2].dOut);
-    KBJ_HIP(ctx, hipMemcpy2DAsync(w.tb[3].dOut, 40 * sizeof(float), w.dvalue_m, sizeof(float), sizeof(float), R, hipMemcpyDeviceToDevice, ns[1]));
-  }
-  // The critical path of a net is dOut -> dH -> (recurrence, dX) per layer. Weight/bias gradients hang off it: they go to the
-  // net's side stream so the throughput-bound split-K GEMMs run beside the dX GEMMs in the GEMM phases.
-  auto side_of = [&](int n) { return one_stream ? ns[n & 1] : ctx->side[n & 1]; };
-  auto fork_side = [&](int n) { if (!one_stream) { hipEventRecord(ctx->ev_side[n & 1], ns[n & 1]); hipStreamWaitEvent(ctx->side[n & 1], ctx->ev_side[n & 1], 0); } };
-  float *dh_above[4], *dx_out[4];
-  for (int n = 0; n < w.nnets; ++n) {
-    const NetOff& o = w.net[n & 1];
-    TrainBufs& t = w.tb[n];
-    if (!(n == 1 && fused_critic_head)) linear_bwd_input(ns[n & 1], sc.gemm_x3, t.dOut, 40, params_d + o.w_out, H, t.dHa, H, R, H, o.nout, 0);
-    if (n == 1 && critic_fork_recorded) hipStreamWaitEvent(ctx->side[1], ctx->ev_side[1], 0);   // recorded with the metrics fork above
-    else fork_side(n);
-    linear_bwd_weight(ctx, side_of(n), sc.gemm_x3, t.dOut, 40, t.Hout[D - 1], H, grad_d + o.w_out, H, o.nout, H, R);
-    colsum_acc(ctx, side_of(n), t.dOut, R, o.nout, 40, grad_d + o.b_out);
-    dh_above[n] = t.dHa; dx_out[n] = t.dHb;
-  }
-  // INVARIANT of the schedule: no kernel waits for another LAUNCH. The only inter-workgroup waits are those of the persistent recurrences,
-  // inside one launch whose grid is resident by construction (kbj_nn_create). Everything else is ordered by stream events, so any
-  // serialisation of kernels (rocprofv3 --pmc, AMD_SERIALIZE_KERNEL=3) runs the same schedule to the same results. (Round 3 / 4 carried
-  // chunk-gated variants - a one-wavefront gate kernel polling a recurrence's progress in front of the GEMMs that consume it, KBJ_BWD_CHUNKS /
-  // KBJ_DW_GATE: measured flat to 0.3 %, and dispatched alone under a serialising profiler the gate spins to its bound. They are gone,
-  // DESIGN.md section 10.)
-  // the bias terms of layer 0 (db_0 is complete with the net's layer-0 recurrence; the read-modify-write of dW_ih0 must follow the folded product into it, on the same lane): db_in = W_ih0^T db_0, dW_ih0 += db_0 b_in^T
-  // (X0 = obs W_in^T + b_in)
-  auto fold_bias_terms = [&](int k, hipStream_t st) {
+
+  // the bias terms of layer 0 of a folded net type k (db_0 is complete with the net's layer-0 recurrence; the read-modify-write of dW_ih0 must follow the
+  // folded product into it, on the same lane): db_in = W_ih0^T db_0, dW_ih0 += db_0 b_in^T   (X0 = obs W_in^T + b_in)
+  void fold_bias_terms(int k, hipStream_t st) {
     const NetOff& oa = w.net[k];
     float* part = det_partials(ctx, st);
-    matvec_t_acc_launch(st, params_d + oa.w_ih[0], grad_d + oa.b[0], 4 * H, H, grad_d + oa.b_in, part);
-    if (part) reduce_rows_launch(st, part, MATVEC_T_SLICES, H, grad_d + oa.b_in);
-    outer_acc_launch(st, grad_d + oa.w_ih[0], grad_d + oa.b[0], params_d + oa.b_in, 4 * H, H);
-  };
-  bool bias_done[2] = {false, false};
+    matvec_t_acc_launch(st, params + oa.w_ih[0], grad + oa.b[0], 4 * H, H, grad + oa.b_in, part);
+    if (part) reduce_rows_launch(st, part, MATVEC_T_SLICES, H, grad + oa.b_in);
+    outer_acc_launch(st, grad + oa.w_ih[0], grad + oa.b[0], params + oa.b_in, 4 * H, H);
+  }
+
   // WHERE A LAYER'S WEIGHT-GRADIENT PAIR RUNS (round 6: explicit stream order, no pause kernel). The input gradient of layer l is on the
   // net's critical chain (the recurrence of layer l - 1 reads it) and the recurrences take whole CUs (250 registers x 2 wavefronts per SIMD):
   // a weight-gradient GEMM that is eligible at the same moment as a recurrence races it for the CUs, and a recurrence advances at the pace of
@@ -1199,126 +1230,154 @@ int ppo_grad_body(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const
   // launch. Rounds 4-5 reached the same order through a 30 us sleep kernel that in practice waited for a wave slot until the recurrences
   // retired (KBJ_DW_DELAY_US, seq_delay_kernel: deleted) - an accident of occupancy, not an order. No launch's start depends on another
   // launch's occupancy any more.
-  struct PendingDW { int n, l; };
-  std::vector<PendingDW> pending_dw;
-  auto launch_dw_pair = [&](hipStream_t st, int n, int l) {
-    const NetOff& o = w.net[n & 1];
-    TrainBufs& t = w.tb[n];
-    linear_bwd_weight2(ctx, st, sc.gemm_x3, t.dGl[l], 4 * H, t.Hm[l], l == 0 ? t.X0 : t.Hout[l - 1], H, grad_d + o.w_hh[l], grad_d + o.w_ih[l], H, 4 * H, H, R);
-  };
-  for (int l = D - 1; l >= 0; --l) {
-    for (int n = 0; n < w.nnets; ++n) {
-      const NetOff& o = w.net[n & 1];
-      TrainBufs& t = w.tb[n];
-      SeqBwdArgs ba{t.G[l], t.TanhC[l], t.Cm[l], dh_above[n], w.keep, params_d + o.w_hh[l], t.dGl[l], w.seq_counters + SEQ_COUNTER_WORDS * (4 * (D + l) + n), w.seq_err, T, B, grad_d + o.b[l]};
-      ba.db_part = det_partials(ctx, ns[n & 1]);   // deterministic mode: per-row-group bias sums, added in order below
-      if (w.seq_bstamps && bstamp_sel == 1 + n + 2 * l) ba.stamps = w.seq_bstamps;
-      const bool tiles16 = sc.bwd16;
-      if (seq_bwd(ctx, ns[n & 1], H, ba, tiles16)) return -1;
-      if (ba.db_part) reduce_rows_launch(ns[n & 1], ba.db_part, seq_bwd_row_groups(B, tiles16), 4 * H, grad_d + o.b[l]);
+  void dw_pair(hipStream_t st, int n, int l) {
+    const NetOff& o = w.net[p.net[n].type]; TrainBufs& t = w.tb[n];
+    linear_bwd_weight2(ctx, st, sc.gemm_x3, t.dGl[l], 4 * H, t.Hm[l], l == 0 ? t.X0 : t.Hout[l - 1], H, grad + o.w_hh[l], grad + o.w_ih[l], H, 4 * H, H, R);
+  }
+  // the pair of layer l + 1 of net n, in pass l of the layer loop: ONE decision per net, asked at the two places of the pass where the pair
+  // may be issued - right behind the pass's recurrence launches (at_tail = false) and last in the net's layer-0 work (at_tail = true)
+  int dw_pair_above(int n, int l, bool at_tail) {
+    const NetPlan& q = p.net[n];
+    const bool on_tail = p.two_lanes && q.tail_on_lane && l == 0;   // last on the net's own lane (two lanes in the tail instead of four: measured equal)
+    if (l + 1 >= D || on_tail != at_tail) return 0;
+    if (!p.two_lanes || on_tail) { dw_pair(q.lane, n, l + 1); return 0; }   // (one lane: stream order is the order)
+    if (hop(ctx, q.lane, q.side, ctx->ev_dx[q.type])) return -1;   // the side lane, behind the recurrence launch(es) of this pass on the net's lane
+    dw_pair(q.side, n, l + 1);
+    return 0;
+  }
+
+  // phase: one backward layer pass - the recurrences of layer l of every net, the weight-gradient pairs of layer l + 1, then per net the
+  // input gradient (the next pass's dH) or, at a folded layer 0, the folded products
+  // INVARIANT of the schedule: no kernel waits for another LAUNCH. The only inter-workgroup waits are those of the persistent recurrences,
+  // inside one launch whose grid is resident by construction (kbj_nn_create). Everything else is ordered by stream events, so any
+  // serialisation of kernels (rocprofv3 --pmc, AMD_SERIALIZE_KERNEL=3) runs the same schedule to the same results. (Round 3 / 4 carried
+  // chunk-gated variants - a one-wavefront gate kernel polling a recurrence's progress in front of the GEMMs that consume it, KBJ_BWD_CHUNKS /
+  // KBJ_DW_GATE: measured flat to 0.3 %, and dispatched alone under a serialising profiler the gate spins to its bound. They are gone,
+  // DESIGN.md section 10.)
+  int backward_layer(int l) {
+    for (int n = 0; n < p.nnets; ++n) {
+      const NetPlan& q = p.net[n]; const NetOff& o = w.net[q.type]; TrainBufs& t = w.tb[n];
+      SeqBwdArgs ba{t.G[l], t.TanhC[l], t.Cm[l], dh_of(t, l), w.keep, params + o.w_hh[l], t.dGl[l], w.seq_counters + SEQ_COUNTER_WORDS * (4 * (D + l) + n), w.seq_err, T, B, grad + o.b[l]};
+      ba.db_part = det_partials(ctx, q.lane);   // deterministic mode: per-row-group bias sums, added in order below
+      if (w.seq_bstamps && ctx->set.bstamp_sel == 1 + n + 2 * l) ba.stamps = w.seq_bstamps;   // diagnostics build only
+      if (seq_bwd(ctx, q.lane, H, ba, sc.bwd16)) return -1;
+      if (ba.db_part) reduce_rows_launch(q.lane, ba.db_part, seq_bwd_row_groups(B, sc.bwd16), 4 * H, grad + o.b[l]);
     }
     // the layer above's weight gradients, behind THIS layer's recurrence of the same net
-    const bool tail_on_own_lane = l == 0 && !w.mirror && fold_actor;   // (the own_lane case below: the pair follows the net's layer-0 work on its lane)
-    for (const PendingDW& p : pending_dw) {
-      if (one_stream) { launch_dw_pair(ns[p.n & 1], p.n, p.l); continue; }   // one lane: stream order is the order
-      if (tail_on_own_lane && ((p.n & 1) == 0 || fold_critic)) continue;      // issued in the net loop below
-      hipStream_t ws = side_of(p.n);
-      hipEventRecord(ctx->ev_dx[p.n & 1], ns[p.n & 1]);   // behind the recurrence launch(es) above on that lane
-      hipStreamWaitEvent(ws, ctx->ev_dx[p.n & 1], 0);
-      launch_dw_pair(ws, p.n, p.l);
-    }
-    for (int n = 0; n < w.nnets; ++n) {
-      const NetOff& o = w.net[n & 1];
-      TrainBufs& t = w.tb[n];
-      hipStream_t s = ns[n & 1], ws = side_of(n);
-      const bool folded = fold_actor && l == 0 && ((n & 1) == 0 || fold_critic);
-      // The last thing a lane does - layer 0 of its net - needs no side lane: nothing is left on the net's lane for the weight
-      // gradients to run beside, and a cross-lane hop costs 15-20 us each way (fork + join) in the minibatch's tail. (Not with mirror
-      // branches: two nets per lane then read-modify-write the same dW_ih0 through their small products, which only the shared side
-      // lane orders.)
-      const bool own_lane = l == 0 && !w.mirror && folded;
-      if (folded) {
-        if (own_lane) ws = s;
-        else fork_side(n);     // the side lane starts behind the whole recurrence
-        // layer 0 backwards through the (activation-free) input projection without dX0: dW_hh0 += dG0^T Hm and Z = dG0^T obs in
-        // one launch; two small products then carry Z back to the stored parameters
-        float* Z = w.Zeff[n];
-        const int ts = H % 128 == 0 ? 128 : 64;   // the column split (n1 = H) must fall on a tile boundary
-        int sk = std::max(2, std::min(g_splitk_wgs / ((4 * H / ts) * (H / ts + (o.nin + ts - 1) / ts)), (R + 255) / 256));
-        GemmArgs g{t.dGl[0], t.Hm[0], grad_d + o.w_hh[0], nullptr, 4 * H, H + o.nin, R, 4 * H, H, H, 1, sk, nullptr};
-        g.B2 = t.obs; g.C2 = Z; g.n1 = H; g.ldb2 = o.ld_obs; g.ldc2 = o.ld_obs;
-        g.skws = sk_workspace(ctx, ws, (size_t)sk * 4 * H * (H + o.nin));
-        g.x3 = sc.gemm_x3;
-        gemm_launch<false, false>(ws, g, ts == 128 ? 1 : 0);
-        // dW_in += W_ih0^T Z, dW_ih0 += Z W_in^T (the bias terms follow from db_0 at the end)
-        // (a 4H-deep contraction on a handful of output tiles: split over k so that it is a short kernel, not a 130 us tail on 32 workgroups)
-        GemmArgs g1a{params_d + o.w_ih[0], Z, grad_d + o.w_in, nullptr, H, o.nin, 4 * H, H, o.ld_obs, o.nin, 1, g_fold_sk, nullptr};
-        g1a.skws = sk_workspace(ctx, ws, (size_t)g_fold_sk * H * o.nin);   // (same lane, stream-ordered behind the launch above: the slab is free again)
-        gemm_launch<false, false>(ws, g1a);
-        GemmArgs g2a{Z, params_d + o.w_in, grad_d + o.w_ih[0], nullptr, 4 * H, H, o.nin, o.ld_obs, o.nin, H, 1, 1, nullptr};
-        gemm_launch<true, true>(ws, g2a);
-        // (365.3 / 364.5 / 363.6 -> 364.8 / 363.8 / 362.9 ms per iteration: the critic's pair no longer waits for the last low-priority GEMM)
-        if (own_lane && n < 2) { fold_bias_terms(n, ws); bias_done[n] = true; }   // right here, on the net's own lane: not behind the side lane's join at the end
-        if (own_lane && !one_stream)   // the upper layers' pairs of this net: last on its own lane (two lanes in the tail instead of four: measured equal)
-          for (const PendingDW& p : pending_dw) if (p.n == n && p.l > l) launch_dw_pair(s, p.n, p.l);
+    for (int n = 0; n < p.nnets; ++n)
+      if (dw_pair_above(n, l, false)) return -1;
+    for (int n = 0; n < p.nnets; ++n) {
+      const NetPlan& q = p.net[n]; const NetOff& o = w.net[q.type]; TrainBufs& t = w.tb[n];
+      if (!(q.folded0 && l == 0)) {
+        // the input gradient as ONE product on the net's own lane, behind the recurrence (it is the next layer's input)
+        linear_bwd_input(q.lane, sc.gemm_x3, t.dGl[l], 4 * H, params + o.w_ih[l], H, dh_of(t, l - 1), H, R, H, 4 * H, 0, H <= 256 ? 2 : -1);
+        // the weight gradients: in the next pass, behind layer l - 1's recurrence (dw_pair_above); layer 0's start behind the input gradient
+        if (l == 0 && fork_side(ctx, p, q)) return -1;
+        if (l == 0) dw_pair(q.side, n, 0);
         continue;
       }
-      // the input gradient as ONE product on the net's own lane, behind the recurrence (it is the next layer's input)
-      linear_bwd_input(s, sc.gemm_x3, t.dGl[l], 4 * H, params_d + o.w_ih[l], H, dx_out[n], H, R, H, 4 * H, 0, H <= 256 ? 2 : -1);
-      if (l > 0) pending_dw.push_back(PendingDW{n, l});   // issued in the next pass of the layer loop, behind layer l - 1's recurrence
-      else {
-        fork_side(n);   // the weight gradients start behind the input gradient
-        launch_dw_pair(ws, n, l);
-      }
-      std::swap(dh_above[n], dx_out[n]);
+      const hipStream_t ws = q.tail_on_lane ? q.lane : q.side;   // (NetPlan::tail_on_lane)
+      if (!q.tail_on_lane && fork_side(ctx, p, q)) return -1;     // the side lane starts behind the whole recurrence
+      // layer 0 backwards through the (activation-free) input projection without dX0: dW_hh0 += dG0^T Hm and Z = dG0^T obs in
+      // one launch; two small products then carry Z back to the stored parameters
+      float* Z = w.Zeff[n];
+      const int ts = H % 128 == 0 ? 128 : 64;   // the column split (n1 = H) must fall on a tile boundary
+      int sk = std::max(2, std::min(g_splitk_wgs / ((4 * H / ts) * (H / ts + (o.nin + ts - 1) / ts)), (R + 255) / 256));
+      GemmArgs g{t.dGl[0], t.Hm[0], grad + o.w_hh[0], nullptr, 4 * H, H + o.nin, R, 4 * H, H, H, 1, sk, nullptr};
+      g.B2 = t.obs; g.C2 = Z; g.n1 = H; g.ldb2 = o.ld_obs; g.ldc2 = o.ld_obs;
+      g.skws = sk_workspace(ctx, ws, (size_t)sk * 4 * H * (H + o.nin));
+      g.x3 = sc.gemm_x3;
+      gemm_launch<false, false>(ws, g, ts == 128 ? 1 : 0);
+      // dW_in += W_ih0^T Z, dW_ih0 += Z W_in^T (the bias terms follow from db_0 at the end)
+      // (a 4H-deep contraction on a handful of output tiles: split over k so that it is a short kernel, not a 130 us tail on 32 workgroups)
+      GemmArgs g1a{params + o.w_ih[0], Z, grad + o.w_in, nullptr, H, o.nin, 4 * H, H, o.ld_obs, o.nin, 1, g_fold_sk, nullptr};
+      g1a.skws = sk_workspace(ctx, ws, (size_t)g_fold_sk * H * o.nin);   // (same lane, stream-ordered behind the launch above: the slab is free again)
+      gemm_launch<false, false>(ws, g1a);
+      GemmArgs g2a{Z, params + o.w_in, grad + o.w_ih[0], nullptr, 4 * H, H, o.nin, o.ld_obs, o.nin, H, 1, 1, nullptr};
+      gemm_launch<true, true>(ws, g2a);
+      // (365.3 / 364.5 / 363.6 -> 364.8 / 363.8 / 362.9 ms per iteration: the critic's pair no longer waits for the last low-priority GEMM)
+      if (q.tail_on_lane && n < 2) { fold_bias_terms(n, ws); bias_done[n] = true; }   // right here, on the net's own lane: not behind the side lane's join at the end
+      if (dw_pair_above(n, l, true)) return -1;
     }
-    // what was pending when this pass began has been issued; what this pass pushed stays for the next
-    pending_dw.erase(std::remove_if(pending_dw.begin(), pending_dw.end(), [&](const PendingDW& p) { return p.l > l; }), pending_dw.end());
+    return 0;
   }
-  for (int n = 0; n < w.nnets; ++n) {
-    const NetOff& o = w.net[n & 1];
-    TrainBufs& t = w.tb[n];
-    hipStream_t s = ns[n & 1];
-    if (!(fold_actor && ((n & 1) == 0 || fold_critic))) {   // input projection (dh_above now holds dX0)
-      linear_bwd_weight(ctx, s, sc.gemm_x3, dh_above[n], H, t.obs, o.ld_obs, grad_d + o.w_in, o.nin, H, o.nin, R);
-      colsum_acc(ctx, s, dh_above[n], R, H, H, grad_d + o.b_in);
-    }
-    if (!one_stream) {
+
+  // phase: input-projection gradients of the nets that are not folded, and the joins of the side lanes
+  int projection_grads_and_joins() {
+    for (int n = 0; n < p.nnets; ++n) {
+      const NetPlan& q = p.net[n]; const NetOff& o = w.net[q.type]; TrainBufs& t = w.tb[n];
+      if (!q.folded0) {   // input projection (dX0: where layer 0's input gradient went)
+        linear_bwd_weight(ctx, q.lane, sc.gemm_x3, dh_of(t, -1), H, t.obs, o.ld_obs, grad + o.w_in, o.nin, H, o.nin, R);
+        colsum_acc(ctx, q.lane, dh_of(t, -1), R, H, H, grad + o.b_in);
+      }
+      if (!p.two_lanes) continue;
       // join of the net's side lane (output-projection gradients, bias sums). The critic's side lane joins the ACTOR's lane when nothing on the
       // critic's own lane reads what it wrote any more (bias terms done): the actor's lane is joined into the caller's stream below, so the
       // critic's chain - on the caller's stream by default - ends with ONE event wait, for an event that fired long before
-      hipStream_t joiner = ((n & 1) == 1 && sc.critic_on_caller && bias_done[1]) ? ns[0] : s;
-      hipEventRecord(ctx->ev_side[n & 1], ctx->side[n & 1]); hipStreamWaitEvent(joiner, ctx->ev_side[n & 1], 0);
+      const bool to_actor = q.type == 1 && q.lane == ctx->stream && bias_done[1];
+      if (hop(ctx, q.side, to_actor ? p.net[0].lane : q.lane, ctx->ev_side[q.type])) return -1;
     }
+    return 0;
   }
+
+  // phase: lane tails.
   // Each lane ends with ONE small kernel behind its last gradient GEMM: it clears the hand-off counter blocks of the lane's nets (every recurrence
   // of the call has run: the next kbj_ppo_grad / kbj_ppo_forward starts without a clear on its chain) and poisons the lane's slice of the gradient
   // when a recurrence timed out (a truncated gradient: every data-parallel rank must skip the optimizer step; one NaN marker per slice is
   // enough, the norm covers the whole vector).
   // The actor's slice grad[0, nactor) is final here, ~0.4 ms before the critic's (shorter chain: folded layer 0, no 475-wide projection).
   // A data-parallel host may start its all-reduce now, under the critic's tail (kbj_stream_wait_actor_grad).
-  if (fold_actor && !bias_done[0]) fold_bias_terms(0, ns[0]);
-  if (!one_stream) hipStreamWaitEvent(ns[0], ev_critic_loss, 0);   // (fired ~3 ms ago)
-  ppo_metrics_launch(ns[0], w.stats + 2, w.stats, pp, R, metrics_d);
-  if (one_stream) {
-    if (fold_actor && fold_critic && !bias_done[1]) fold_bias_terms(1, ns[1]);
-    hipLaunchKernelGGL(lane_tail_kernel, dim3(2 * MAXD * 4), dim3(SEQ_COUNTER_WORDS), 0, ctx->stream, w.seq_counters, -1, w.seq_err, grad_d, grad_d + w.nactor);
-    KBJ_HIP(ctx, hipEventRecord(ctx->ev_actor_grad, ctx->stream));
-  } else {
-    hipLaunchKernelGGL(lane_tail_kernel, dim3(2 * MAXD * 4), dim3(SEQ_COUNTER_WORDS), 0, ns[0], w.seq_counters, 0, w.seq_err, grad_d, (float*)nullptr);
-    KBJ_HIP(ctx, hipEventRecord(ctx->ev_actor_grad, ns[0]));
-    if (fold_actor && fold_critic && !bias_done[1]) fold_bias_terms(1, ns[1]);   // on the critic's own lane (its side lane has joined it above), beside the actor's
-    hipLaunchKernelGGL(lane_tail_kernel, dim3(2 * MAXD * 4), dim3(SEQ_COUNTER_WORDS), 0, ns[1], w.seq_counters, 1, w.seq_err, grad_d + w.nactor, (float*)nullptr);
+  int lane_tails(float* metrics_d) {
+    const hipStream_t sa = p.net[0].lane, sv = p.net[1].lane;   // the actor's lane, the critic's
+    if (p.net[0].folded0 && !bias_done[0]) fold_bias_terms(0, sa);
+    if (p.two_lanes && ev_wait(ctx, sa, p.ev_critic_loss)) return -1;   // (UpdatePlan::ev_critic_loss says what this waits for in each case)
+    ppo_metrics_launch(sa, w.stats + 2, w.stats, pp, R, metrics_d);
+    if (!p.two_lanes) {
+      if (p.net[1].folded0 && !bias_done[1]) fold_bias_terms(1, sv);
+      hipLaunchKernelGGL(lane_tail_kernel, dim3(2 * MAXD * 4), dim3(SEQ_COUNTER_WORDS), 0, ctx->stream, w.seq_counters, -1, w.seq_err, grad, grad + w.nactor);
+      return ev_record(ctx, ctx->ev_actor_grad, ctx->stream);
+    }
+    hipLaunchKernelGGL(lane_tail_kernel, dim3(2 * MAXD * 4), dim3(SEQ_COUNTER_WORDS), 0, sa, w.seq_counters, 0, w.seq_err, grad, (float*)nullptr);
+    if (ev_record(ctx, ctx->ev_actor_grad, sa)) return -1;
+    if (p.net[1].folded0 && !bias_done[1]) fold_bias_terms(1, sv);   // on the critic's own lane (its side lane has joined it above), beside the actor's
+    hipLaunchKernelGGL(lane_tail_kernel, dim3(2 * MAXD * 4), dim3(SEQ_COUNTER_WORDS), 0, sv, w.seq_counters, 1, w.seq_err, grad + w.nactor, (float*)nullptr);
     // join: the lane that is NOT the caller's stream into the caller's stream. With the critic on the caller's stream (default) the wait is for an
     // event that was recorded long ago - the actor's lane finishes first - so the tail of a minibatch crosses no queue either.
-    KBJ_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
-    KBJ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+    return hop(ctx, ctx->stream2, ctx->stream, ctx->ev_join);
   }
+};
+
+int ppo_forward_body(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const int32_t* env_idx_d, kbj_ppo_vars* out) {
+  Update u{ctx, params_d, tr, env_idx_d, nullptr, nullptr, nullptr};
+  NnWs& w = u.w;
+  const hipStream_t s = u.p.net[0].lane;   // the actor's lane
+  if (u.lanes_begin() || u.folded_weights() || u.gathers() || u.input_projections() || u.forward_recurrences()) return -1;
+  u.heads_forward(2, out->logp_d, out->entropy_d ? out->entropy_d : w.ent);
+  if (out->action_std_d) KBJ_HIP(ctx, hipMemcpyAsync(out->action_std_d, w.sd, (size_t)u.R * KBJ_NU * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (out->action_mean_d) KBJ_HIP(ctx, hipMemcpyAsync(out->action_mean_d, w.y, (size_t)u.R * KBJ_NU * sizeof(float), hipMemcpyDeviceToDevice, s));
+  critic_value_launch(u.p.net[1].lane, w.tb[1].Out, 40, u.R, out->value_d);
+  if (u.p.two_lanes && hop(ctx, ctx->stream2, ctx->stream, ctx->ev_join)) return -1;
+  hipLaunchKernelGGL(poison_vars_kernel, dim3(1), dim3(1), 0, ctx->stream, w.seq_err, out->logp_d, out->value_d);   // a recurrence timed out: no silent garbage
+  KBJ_CHECK_LAUNCH(ctx, "kbj_ppo_forward");
+  if (u.sc.debug_sync) return kbj_synchronize(ctx);
+  return 0;
+}
+
+int ppo_grad_body(kbj_ctx* ctx, const float* params_d, const kbj_traj* tr, const int32_t* env_idx_d, const float* adv_d, const float* target_d,
+                  float* grad_d, float* metrics_d) {
+  KbjTimed timed(ctx, true);
+  Update u{ctx, params_d, tr, env_idx_d, adv_d, target_d, grad_d};
+  if (u.lanes_begin() || u.folded_weights() || u.gathers() || u.input_projections() || u.forward_recurrences()) return -1;
+  u.heads_forward(u.p.nnets, u.w.logp, u.w.ent);
+  if (u.losses() || u.heads_backward()) return -1;
+  for (int l = u.D - 1; l >= 0; --l)
+    if (u.backward_layer(l)) return -1;
+  if (u.projection_grads_and_joins() || u.lane_tails(metrics_d)) return -1;
 #ifndef KBJ_NO_TAIL_CLEAN   // A/B
-  w.counters_clean = true;
+  u.w.counters_clean = true;
 #endif
   KBJ_CHECK_LAUNCH(ctx, "kbj_ppo_grad");
-  if (sc.debug_sync) return kbj_synchronize(ctx);   // KBJ_DEBUG=1: surface a hand-off timeout at the call that caused it
+  if (u.sc.debug_sync) return kbj_synchronize(ctx);   // KBJ_DEBUG=1: surface a hand-off timeout at the call that caused it
   return 0;
 }
 
@@ -1364,10 +1423,8 @@ int kbj_ppo_prefetch(kbj_ctx* ctx, const kbj_traj* traj, const int32_t* env_idx_
   if (traj->T != w.T || traj->N != w.N) return kbj_fail(ctx, "kbj_ppo_prefetch: trajectory shape does not match the context");
   if (w.sched.one_stream || w.padded()) return 0;      // nothing to overlap with on one lane; padded sizes re-pitch the carries per call: served without the hint
   hipStream_t lane = ctx->side[1];
-  KBJ_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));      // behind everything queued so far (the previous minibatch's last reader of these buffers)
-  KBJ_HIP(ctx, hipStreamWaitEvent(lane, ctx->ev_fork, 0));
-  if (head_gathers(ctx, lane, traj, env_idx_d)) return -1;
-  KBJ_HIP(ctx, hipEventRecord(ctx->ev_prefetch, lane));
+  if (hop(ctx, ctx->stream, lane, ctx->ev_fork)) return -1;      // behind everything queued so far (the previous minibatch's last reader of these buffers)
+  if (head_gathers(ctx, lane, traj, env_idx_d) || ev_record(ctx, ctx->ev_prefetch, lane)) return -1;
   w.prefetched_idx = env_idx_d; w.prefetched_traj = traj;
   KBJ_CHECK_LAUNCH(ctx, "kbj_ppo_prefetch");
   return 0;

@@ -47,7 +47,7 @@ def _ctx(monkeypatch, env, N, B, T, H, **kw):
     return m, cfg, ctx
 
 
-def _problem(torch, m, cfg, ctx, N, B, T, H, seed=0):
+def _problem(torch, m, cfg, ctx, N, B, T, H, seed=0, depth=2):
     """A synthetic minibatch problem (as tests/test_gpu_nn.py) + the autograd gradient of the oracle."""
     from kbot_joystick_amd.host import buffers
     from oracle import nn as ON
@@ -55,7 +55,7 @@ def _problem(torch, m, cfg, ctx, N, B, T, H, seed=0):
     P = ctx.param_count()
     params = torch.zeros(P, device="cuda:0")
     ctx.init_params(11, params)
-    tr = _synthetic_traj(torch, buffers, N, T, H, seed=seed)
+    tr = _synthetic_traj(torch, buffers, N, T, H, seed=seed, depth=depth)
     jb = torch.tensor(list(m.joint_bias), dtype=torch.float64)
     p64 = params.detach().cpu().double()
     g = torch.Generator(device="cpu").manual_seed(5)
@@ -63,9 +63,9 @@ def _problem(torch, m, cfg, ctx, N, B, T, H, seed=0):
     ao, co = tr.actor_obs[:T].cpu().double(), tr.critic_obs[:T].cpu().double()
     act, done = tr.action.cpu().double(), tr.done.cpu().double()
     with torch.no_grad():
-        ca = [[tr.carry0_actor_hc[l, k].cpu().double() for k in range(2)] for l in range(2)]
-        cc = [[tr.carry0_critic_hc[l, k].cpu().double() for k in range(2)] for l in range(2)]
-        lp, v, en, *_ = ON.ppo_variables(ON.unflatten(p64, H), cfg, jb, ao, co, act, done, ca, cc, tr.carry0_lpf.cpu().double())
+        ca = [[tr.carry0_actor_hc[l, k].cpu().double() for k in range(2)] for l in range(depth)]
+        cc = [[tr.carry0_critic_hc[l, k].cpu().double() for k in range(2)] for l in range(depth)]
+        lp, v, en, *_ = ON.ppo_variables(ON.unflatten(p64, H, depth), cfg, jb, ao, co, act, done, ca, cc, tr.carry0_lpf.cpu().double(), depth)
     tr.logp.copy_((lp + 0.3 * torch.randn(T, N, generator=g).double()).float())
     tr.value.copy_((v + 0.3 * torch.randn(T, N, generator=g).double()).float())
     ctx.gae(tr.c, tr.adv, tr.target)
@@ -73,15 +73,15 @@ def _problem(torch, m, cfg, ctx, N, B, T, H, seed=0):
     return params, tr, idx, (lp, v, en), (jb, p64, ao, co, act, done)
 
 
-def _autograd(torch, cfg, tr, idx, H, aux):
+def _autograd(torch, cfg, tr, idx, H, aux, depth=2):
     from oracle import nn as ON
     jb, p64, ao, co, act, done = aux
     adv_o, tgt_o = ON.gae(tr.value.cpu().double(), tr.reward.cpu().double(), done, cfg.gamma, cfg.lam)
     pf = p64.clone().requires_grad_(True)
     ii = idx.long()
-    ca = [[tr.carry0_actor_hc[l, k].cpu().double()[ii] for k in range(2)] for l in range(2)]
-    cc = [[tr.carry0_critic_hc[l, k].cpu().double()[ii] for k in range(2)] for l in range(2)]
-    lp, v, en, *_ = ON.ppo_variables(ON.unflatten(pf, H), cfg, jb, ao[:, ii], co[:, ii], act[:, ii], done[:, ii], ca, cc, tr.carry0_lpf.cpu().double()[ii])
+    ca = [[tr.carry0_actor_hc[l, k].cpu().double()[ii] for k in range(2)] for l in range(depth)]
+    cc = [[tr.carry0_critic_hc[l, k].cpu().double()[ii] for k in range(2)] for l in range(depth)]
+    lp, v, en, *_ = ON.ppo_variables(ON.unflatten(pf, H, depth), cfg, jb, ao[:, ii], co[:, ii], act[:, ii], done[:, ii], ca, cc, tr.carry0_lpf.cpu().double()[ii], depth)
     loss, _ = ON.ppo_loss(cfg, lp, v, en, tr.logp.cpu().double()[:, ii], tr.value.cpu().double()[:, ii], adv_o[:, ii], tgt_o[:, ii])
     loss.backward()
     return pf.grad, float(loss.detach())
@@ -108,6 +108,35 @@ def test_switch_gradient_matches_autograd(monkeypatch, name, H, N, B, T):
         assert (a - b).abs().max() / (b.abs().max() + 1e-12) < 2e-3, (name, leaf)
         off += n
     assert (gg - go).norm() / go.norm() < 1e-4
+    ctx.close()
+
+
+@pytest.mark.parametrize("name", [k for k in SWITCHES if k != "KBJ_ROLLOUT_STEP=0"])
+@pytest.mark.parametrize("depth", [1, 3])
+def test_switch_gradient_matches_autograd_at_other_depths(monkeypatch, name, depth):
+    """Where the update's launches go depends on switch x depth, and the test above runs depth 2 only. Depth 1: the top layer is layer 0, so no
+    weight-gradient pair ever waits for a lower layer's recurrence. Depth 3: the pair of layer 2 goes to the side lane behind layer 1's
+    recurrence while the pair of layer 1 ends the net's own lane (or follows on the side lane, by switch). Same problem, reference and
+    tolerances as the test above, at its smallest shape."""
+    import torch
+    from oracle import nn as ON
+    H, N, B, T = 64, 12, 8, 7
+    m, cfg, ctx = _ctx(monkeypatch, SWITCHES[name], N, B, T, H, depth=depth)
+    params, tr, idx, _, aux = _problem(torch, m, cfg, ctx, N, B, T, H, depth=depth)
+    P = ctx.param_count()
+    grad, metrics = torch.zeros(P, device="cuda:0"), torch.zeros(10, device="cuda:0")
+    ctx.ppo_grad(params, tr.c, idx.cuda(), B, tr.adv, tr.target, grad, metrics)
+    ctx.synchronize()
+    go, loss = _autograd(torch, cfg, tr, idx, H, aux, depth=depth)
+    gg = grad.cpu().double()
+    assert abs(float(metrics[0]) - loss) < 2e-4 * (1 + abs(loss))
+    off = 0
+    for leaf, shp in ON.param_shapes(H, depth):
+        n = int(np.prod(shp))
+        a, b = gg[off:off + n], go[off:off + n]
+        assert (a - b).abs().max() / (b.abs().max() + 1e-12) < 2e-3, (name, depth, leaf)
+        off += n
+    assert off == P and (gg - go).norm() / go.norm() < 1e-4
     ctx.close()
 
 
