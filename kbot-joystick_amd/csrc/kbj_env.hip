@@ -312,16 +312,17 @@ __global__ void init_reward_carry_kernel(float* carry, int N) {
 
 void kbj_nn_drop_prefetch(kbj_ctx* ctx);   // kbj_nn.hip: a pending next-minibatch hint dies with the trajectory contents it was made from
 
-// one control step of the envs [env0, env0 + count) on stream s; row pointers are those of env 0
-int kbj_env_step_range(kbj_ctx* ctx, hipStream_t s, int env0, int count, const float* action_d, float* aux_t_d, float* actor_next_d, float* critic_next_d,
-                       float* aux_next_d, float* qstate_t_d) {
+// one control step of all envs on stream s (the kernels' first-env parameter: 0)
+int kbj_env_step_all(kbj_ctx* ctx, hipStream_t s, const float* action_d, float* aux_t_d, float* actor_next_d, float* critic_next_d, float* aux_next_d,
+                     float* qstate_t_d) {
   KbjKernelTimer timer(s, KBJ_KIND_ENV_STEP, 0.0);
+  const int N = ctx->cfg_h.num_envs;
   if (qstate_t_d)
-    KBJ_LAUNCH_SOLVER(ctx, env_step_record, dim3(count), dim3(64), 0, s, ctx->model_d, ctx->cfg_d, ctx->mc_d, (const PhysConst*)ctx->pc_d, ctx->seed, ctx->ep_d, ctx->es_d, action_d, aux_t_d,
-                       actor_next_d, critic_next_d, aux_next_d, env0, qstate_t_d);
+    KBJ_LAUNCH_SOLVER(ctx, env_step_record, dim3(N), dim3(64), 0, s, ctx->model_d, ctx->cfg_d, ctx->mc_d, (const PhysConst*)ctx->pc_d, ctx->seed, ctx->ep_d, ctx->es_d, action_d, aux_t_d,
+                       actor_next_d, critic_next_d, aux_next_d, 0, qstate_t_d);
   else
-    KBJ_LAUNCH_SOLVER(ctx, env_step, dim3(count), dim3(64), 0, s, ctx->model_d, ctx->cfg_d, ctx->mc_d, (const PhysConst*)ctx->pc_d, ctx->seed, ctx->ep_d, ctx->es_d, action_d, aux_t_d,
-                       actor_next_d, critic_next_d, aux_next_d, env0);
+    KBJ_LAUNCH_SOLVER(ctx, env_step, dim3(N), dim3(64), 0, s, ctx->model_d, ctx->cfg_d, ctx->mc_d, (const PhysConst*)ctx->pc_d, ctx->seed, ctx->ep_d, ctx->es_d, action_d, aux_t_d,
+                       actor_next_d, critic_next_d, aux_next_d, 0);
   KBJ_CHECK_LAUNCH(ctx, "env_step_kernel");
   return 0;
 }
@@ -351,7 +352,7 @@ int kbj_env_step(kbj_ctx* ctx, const float* action_d, float* aux_t_d, float* act
   if (!action_d || !aux_t_d || !actor_next_d || !critic_next_d || !aux_next_d) return kbj_fail(ctx, "kbj_env_step: null pointer");
   KBJ_HIP(ctx, hipSetDevice(ctx->device));
   kbj_nn_drop_prefetch(ctx);
-  return kbj_env_step_range(ctx, ctx->stream, 0, ctx->cfg_h.num_envs, action_d, aux_t_d, actor_next_d, critic_next_d, aux_next_d, q);
+  return kbj_env_step_all(ctx, ctx->stream, action_d, aux_t_d, actor_next_d, critic_next_d, aux_next_d, q);
 }
 
 int kbj_env_record_state(kbj_ctx* ctx, float* qstate_t_d) {

@@ -117,6 +117,11 @@ ParamLayout layout_params(const kbj_config& c, int H) {
 // the carries of net n (0 actor, 1 critic, 2 / 3 their mirror branches) in a kbj_carry, the start carries in a kbj_traj
 template <class C> auto& carry_hc(C& c, int n) { return n == 0 ? c.actor_hc_d : n == 1 ? c.critic_hc_d : n == 2 ? c.actor_mirror_hc_d : c.critic_mirror_hc_d; }
 template <class T> auto& traj_carry0(T& t, int n) { return n == 0 ? t.carry0_actor_hc_d : n == 1 ? t.carry0_critic_hc_d : n == 2 ? t.carry0_actor_mirror_hc_d : t.carry0_critic_mirror_hc_d; }
+// the mirror losses are on and this carry / this trajectory (null: not part of the call) lacks one of the mirror-branch arrays
+bool mirror_arrays_missing(bool mirror, const kbj_carry* c, const kbj_traj* t) {
+  return mirror && ((c && (!c->actor_mirror_hc_d || !c->critic_mirror_hc_d || !c->lpf_mirror_d)) ||
+                    (t && (!t->carry0_actor_mirror_hc_d || !t->carry0_critic_mirror_hc_d || !t->carry0_lpf_mirror_d)));
+}
 
 // build_mirror_tables (the (source index, multiplier, offset) tables of mirror_rows_kernel): kbj_nn_kernels.h, beside the kernel
 
@@ -501,150 +506,17 @@ void kbj_nn_destroy(kbj_ctx* ctx) {
 }
 
 
-int kbj_env_step_range(kbj_ctx* ctx, hipStream_t s, int env0, int count, const float* action_d, float* aux_t_d, float* actor_next_d, float* critic_next_d,
-                       float* aux_next_d, float* qstate_t_d);   // kbj_env.hip
+int kbj_env_step_all(kbj_ctx* ctx, hipStream_t s, const float* action_d, float* aux_t_d, float* actor_next_d, float* critic_next_d, float* aux_next_d,
+                     float* qstate_t_d);   // kbj_env.hip
 
 namespace {
 
-// One control step of the nets [net_lo, net_hi) (0 actor, 1 critic, 2/3 their mirror branches) for the env rows [n0, n0 + cnt) on
-// stream s. All pointers are those of env row 0.
-// Rollout-time layer steps run in lstm_step_kernel (fused [x | h] product + cell). Its output h cannot alias its input, so every h
-// plane of the carry has a ping-pong partner in the workspace: a call with parity 0 reads the caller's planes and writes the partners,
-// parity 1 the other way round. kbj_rollout alternates per control step; the caller's arrays hold the state again when it returns.
-// KBJ_ROLLOUT_STEP=0 (Sched::rollout_step): the previous form, one GEMM over [x | h] plus a cell kernel per layer, in place.
-// Only the actor proper (net 0) sits on the rollout's critical chain (env -> actor -> env). The critic and the mirror branches run on side
-// lanes under the env kernel, where the only free resources are those of its last, partial round of wavefronts (8192 envs = 2.67 rounds
-// of 12 per CU: 168 VGPRs per SIMD and ~58 KB of LDS per CU for the last third of the kernel): a 64x64-tile GEMM workgroup (4 waves x 84
-// VGPRs, 37 KB) fits there, a layer-step workgroup (8 waves x 220 VGPRs) does not and would run into the next actor chain instead. So the
-// side-lane nets keep the GEMM + cell form on small tiles (414 vs 418 ms per iteration).
-bool net_uses_step_kernel(const NnWs& w, int n) { return w.sched.rollout_step && n == 0; }
-float* h_plane(NnWs& w, float* hc, int n, int l, int n0, bool partner) {
-  if (!net_uses_step_kernel(w, n)) partner = false;
-  return (partner ? w.rH[n][l] : hc + (size_t)(2 * l) * w.N * w.H) + (size_t)n0 * w.H;
-}
-
-// The actor's input projection (65 -> H, no activation) feeds only layer 0's input product, so gates_0 = obs (W_ih0 W_in)^T +
-// (W_ih0 b_in + b_0), as in kbj_ppo_grad: prepares w.Weff / w.beff for these parameters and returns w.Weff (null: not folded)
-const float* fold_actor_weights(kbj_ctx* ctx, hipStream_t s, const float* params_d) {
-  NnWs& w = *ws_of(ctx);
-  const int H = w.H;
-  if (!w.sched.rollout_step || w.net[0].ld_obs != KBJ_LD_ACTOR || !w.sched.fold_actor) return nullptr;
-  const NetOff& oa = w.net[0];
-  GemmArgs g{params_d + oa.w_ih[0], params_d + oa.w_in, w.Weff, nullptr, 4 * H, oa.nin, H, H, oa.nin, oa.ld_obs, 0, 1, nullptr};
-  gemm_launch<true, false>(s, g);
-  matvec_launch(s, params_d + oa.w_ih[0], params_d + oa.b_in, params_d + oa.b[0], 4 * H, H, w.beff);
-  return w.Weff;
-}
-
-// Rollout-time input projections read W_in [H][nin] with nin = 65 / 475 floats per row: no 16-byte alignment, which puts the GEMM on its element-wise
-// load path for that operand (the critic's 8192 x 256 x 475 product ran at 27 TFLOP/s, with four times the load instructions - beside an env kernel
-// that is bound by vector issue). As in the update (Update::input_projections): a re-pitched copy with the observation rows' stride, zeros behind column nin,
-// made once per rollout / policy step; the contraction then runs over the padded width (the rows' padding columns hold zeros: host/buffers.py).
-void repitch_input_weights(kbj_ctx* ctx, hipStream_t s, const float* params_d, int k_lo = 0, int k_hi = 2) {
-  NnWs& w = *ws_of(ctx);
-  for (int k = k_lo; k < k_hi; ++k) {
-    const NetOff& o = w.net[k];
-    if (o.nin == o.ld_obs) continue;
-    repitch_rows_launch(s, params_d + o.w_in, w.H, o.nin, o.ld_obs, w.WinP[k]);
-  }
-}
-
-// weff: the folded actor input weights (W_ih0 W_in, bias in w.beff) when the caller has prepared them for these parameters, else null
-// (the caller has also run repitch_input_weights for these parameters)
-int policy_nets(kbj_ctx* ctx, hipStream_t s, const float* params_d, int net_lo, int net_hi, int n0, int cnt, const float* actor_obs_d, const float* critic_obs_d,
-                kbj_carry* carry, uint32_t seed, uint32_t step_index, int argmax, float* action_d, float* logp_d, float* value_d, int parity, const float* weff) {
-  NnWs& w = *ws_of(ctx);
-  const kbj_config& c = ctx->cfg_h;
-  const int N = w.N, H = w.H;
-  const bool fused_any = w.sched.rollout_step;
-  const float* obs_base[2] = {actor_obs_d, critic_obs_d};
-  HeadParams hp{c.min_std, c.max_std, c.var_scale, c.lpf_alpha, w.net[0].ld_obs};
-  for (int n = net_lo; n < net_hi; ++n) {
-    const int k = n & 1;
-    float* const hc = carry_hc(*carry, n);
-    const NetOff& o = w.net[k];
-    const float* obs = obs_base[k] + (size_t)n0 * o.ld_obs;
-    float* obs_m = n >= 2 ? w.rObsM[k] + (size_t)n0 * o.ld_obs : nullptr;
-    // scratch rows are private to (net, env row): lanes and side lanes never share them
-    float* X = w.rX[n] + (size_t)n0 * H;
-    float* G = w.rG[n] + (size_t)n0 * 4 * H;
-    float* Out = w.rOut[n] + (size_t)n0 * 40;
-    if (n >= 2) {  // mirror branches advance their own carries on the mirrored observations (train.py:1463-1481, 1555-1560)
-      mirror_rows_launch(s, obs, obs_m, (size_t)cnt, o.ld_obs, w.mtab[k]);
-      obs = obs_m;
-    }
-    const bool fused = fused_any && net_uses_step_kernel(w, n);
-    const bool folded = fused && weff && k == 0 && o.ld_obs == KBJ_LD_ACTOR;   // actor-type net: layer-0 gates straight from the observation row
-    if (!folded) {
-      if (o.nin != o.ld_obs) linear_fwd(s, obs, o.ld_obs, w.WinP[k], o.ld_obs, params_d + o.b_in, X, H, cnt, H, o.ld_obs, 0);   // aligned copy of W_in (repitch_input_weights)
-      else linear_fwd(s, obs, o.ld_obs, params_d + o.w_in, o.nin, params_d + o.b_in, X, H, cnt, H, o.nin, 0);
-    }
-    const float* x = X;
-    for (int l = 0; l < w.D; ++l) {
-      float* cc = hc + (size_t)(2 * l + 1) * N * H + (size_t)n0 * H;
-      if (fused) {
-        const float* h_in = h_plane(w, hc, n, l, n0, parity != 0);
-        float* h_out = h_plane(w, hc, n, l, n0, parity == 0);
-        StepArgs sa{x, H, 0, params_d + o.w_ih[l], H, params_d + o.w_hh[l], params_d + o.b[l], h_in, h_out, cc, cnt};
-        if (l == 0 && folded) { sa.X = obs; sa.ldx = o.ld_obs; sa.kx = o.nin; sa.Wih = weff; sa.ldw = o.ld_obs; sa.bias = w.beff; }
-        if (lstm_step(ctx, s, H, sa)) return -1;
-        x = h_out;
-        continue;
-      }
-      float* h = hc + (size_t)(2 * l) * N * H + (size_t)n0 * H;
-      {  // gates = [x | h] [W_ih | W_hh]^T + b as ONE launch over the concatenated contraction (no read-modify-write of G)
-        GemmArgs g{x, params_d + o.w_ih[l], G, params_d + o.b[l], cnt, 4 * H, 2 * H, H, H, 4 * H, 0, 1, nullptr};
-        g.A2 = h; g.B2 = params_d + o.w_hh[l]; g.k1 = H;
-        g.x3 = w.sched.gemm_x3 ? 1 : 0;
-        gemm_launch<true, true>(s, g, (n > 0 && w.sched.rollout_step) ? 0 : -1);   // side-lane nets: 64x64 tiles (see net_uses_step_kernel)
-      }
-      CellFwdArgs2 ca;
-      ca.a[0] = CellFwdArgs{G, cc, h, cc, nullptr, nullptr, nullptr, nullptr, cnt, H};
-      lstm_cell_fwd_launch(s, ca, 1);
-      x = h;
-    }
-    if (n == 3) continue;  // the mirrored critic's value is only needed under the gradient; at rollout time only its carry advances
-    if (n == 0) {   // output projection + low-pass + sample + log-prob as one launch (the chain env -> actor -> env waits for it)
-      actor_head_fused_launch(s, x, H, params_d + o.w_out, params_d + o.b_out, obs, carry->lpf_d + (size_t)n0 * KBJ_NU, w.joint_bias_d, hp, seed,
-                              (uint32_t)(c.env_id_offset + n0), step_index, argmax, cnt, action_d + (size_t)n0 * KBJ_NU, logp_d + n0);
-      continue;
-    }
-    if (n == 1 && o.nout == 1) {
-      critic_value_fused_launch(s, x, H, params_d + o.w_out, params_d + o.b_out, cnt, value_d + n0);
-      continue;
-    }
-    // n == 2: the mirrored actor only advances its low-pass state (no sample)
-    linear_fwd(s, x, H, params_d + o.w_out, H, params_d + o.b_out, Out, 40, cnt, o.nout, H, 0);
-    actor_head_lpf_launch(s, Out, obs, carry->lpf_mirror_d + (size_t)n0 * KBJ_NU, w.joint_bias_d, c.lpf_alpha, cnt, w.net[0].ld_obs);
-  }
-  return 0;
-}
-
-// carry <- 0 where done, for the nets [net_lo, net_hi) and env rows [n0, n0 + cnt); parity as policy_nets: which copy of the h planes is live
-void carry_reset_nets(kbj_ctx* ctx, hipStream_t s, int net_lo, int net_hi, int n0, int cnt, kbj_carry* carry, const float* done_d, int done_stride, int parity) {
-  NnWs& w = *ws_of(ctx);
-  float* lpf[4] = {carry->lpf_d, nullptr, carry->lpf_mirror_d, nullptr};
-  const bool partner = parity != 0 && w.sched.rollout_step;
-  for (int k = net_lo; k < net_hi; ++k) {
-    float* const hc = carry_hc(*carry, k);
-    CarryPlanes cp;
-    cp.n = 2 * w.D;
-    for (int l = 0; l < w.D; ++l) {
-      cp.p[2 * l] = h_plane(w, hc, k, l, n0, partner);
-      cp.p[2 * l + 1] = hc + (size_t)(2 * l + 1) * w.N * w.H + (size_t)n0 * w.H;
-    }
-    carry_reset_launch(s, cp, cnt, w.H, lpf[k] ? lpf[k] + (size_t)n0 * KBJ_NU : nullptr, done_d + (size_t)n0 * done_stride, done_stride);
-  }
-}
-
-// the h planes of nets [net_lo, net_hi) back from their ping-pong partners into the caller's arrays
-int carry_h_home(kbj_ctx* ctx, hipStream_t s, int net_lo, int net_hi, kbj_carry* carry) {
-  NnWs& w = *ws_of(ctx);
-  for (int k = net_lo; k < net_hi; ++k)
-    for (int l = 0; l < w.D && net_uses_step_kernel(w, k); ++l)
-      KBJ_HIP(ctx, hipMemcpyAsync(carry_hc(*carry, k) + (size_t)(2 * l) * w.N * w.H, w.rH[k][l], (size_t)w.N * w.H * sizeof(float), hipMemcpyDeviceToDevice, s));
-  return 0;
-}
+// Lane hops. Every ordering between two lanes, of the rollout and of the update, is one of these: an event recorded on one stream, waited for
+// on another - one packet each (a cross-queue wait costs the waiting queue ~7 us, 10-25 us when it has to stall: round 6), so a helper issues
+// exactly the calls its name says and a call site that reuses a record (UpdatePlan::critic_fork_recorded; ev_obs, which implies ev_small) says so.
+int ev_record(kbj_ctx* ctx, hipEvent_t ev, hipStream_t on) { KBJ_HIP(ctx, hipEventRecord(ev, on)); return 0; }
+int ev_wait(kbj_ctx* ctx, hipStream_t st, hipEvent_t ev) { KBJ_HIP(ctx, hipStreamWaitEvent(st, ev, 0)); return 0; }
+int hop(kbj_ctx* ctx, hipStream_t from, hipStream_t to, hipEvent_t ev) { return ev_record(ctx, ev, from) || ev_wait(ctx, to, ev) ? -1 : 0; }
 
 // ---- free hidden_size: conversions at the ABI boundary of a padded context (NnWs::Hu != NnWs::H) ----
 void pad_params(kbj_ctx* ctx, hipStream_t s, const float* user, float* internal) {
@@ -683,97 +555,266 @@ kbj_traj pad_traj_carry0(kbj_ctx* ctx, hipStream_t s, const kbj_traj& tr) {
   return p;
 }
 
-// The critic's value of ONE observation row [N][ld_critic] from a COPY of its carries (kbj_critic_value; the tail pass of kbj_rollout for
-// kbj_config.gae_tail_value): critic_hc_d [D][2][N][hc_width] goes into w.tail_hc (re-pitched when the caller's hidden_size is not the kernels'),
-// then the critic leg of policy_nets steps the copy - the launches kbj_policy_step makes for net 1 (side-lane GEMM tiles, gate GEMM + cell kernel in
-// place, fused value head), so the value is bit-identical to the one a policy step writes from the same carries and row. The critic never runs on
-// the layer-step kernel (net_uses_step_kernel), so no ping-pong partner plane is involved; its scratch rows w.rX[1] / w.rG[1] belong to policy_nets
-// alone (the update and kbj_ppo_prefetch work in w.tb[] and the gather buffers). The caller has run repitch_input_weights for params_d on a
-// stream ordered in front of s. Nets 0, 2 and 3 do not run: no other carry, no low-pass state moves.
-int critic_tail(kbj_ctx* ctx, hipStream_t s, const float* params_d, const float* critic_obs_d, const float* critic_hc_d, int hc_width, float* value_d) {
-  NnWs& w = *ws_of(ctx);   // (w.tail_hc: allocated at kbj_create exactly when gae_tail_value is set; both callers have checked)
-  if (hc_width == w.H) KBJ_HIP(ctx, hipMemcpyAsync(w.tail_hc, critic_hc_d, (size_t)2 * w.D * w.N * w.H * sizeof(float), hipMemcpyDeviceToDevice, s));
-  else repitch_hc(ctx, s, critic_hc_d, w.tail_hc, hc_width, w.H);
-  kbj_carry sc = {};
-  sc.critic_hc_d = w.tail_hc;
-  return policy_nets(ctx, s, params_d, 1, 2, 0, w.N, nullptr, critic_obs_d, &sc, 0, 0, 0, nullptr, nullptr, value_d, 0, nullptr);
+// ---- the rollout (kbj_rollout, kbj_policy_step, kbj_critic_value, kbj_carry_reset): ONE plan per call, one function per phase ----
+// A control step runs every net of the context once on one observation row: mirrored rows (mirror branches), input projection, the LSTM
+// layers, the head. WHICH kernels a net runs, and on which lane, is decided once per entry-point call, in rollout_plan(); the phases of
+// Rollout read the plan and never re-derive a decision.
+
+// net n of the call (0 actor, 1 critic, 2 / 3 their mirror branches: the same weights on mirrored observation rows, with carries of their own)
+//   lane          the stream the net's launches go to
+//   type          n & 1: the parameter / offset set (NnWs::net), the mirror table
+//   step_kernel   its layers run in lstm_step_kernel (fused [x | h] product + cell) on ping-pong h planes; false: one GEMM over [x | h] plus a
+//                 cell kernel per layer, in place
+//   folded0       layer-0 gates straight from the observation row through Weff / beff, no input projection (fold_actor_weights has prepared them)
+//   tile          the tile selector its gate GEMMs pass to gemm_launch: -1 the launcher's choice, 0 = 64 x 64
+//   head          what follows the top layer
+//   mirrored      its observation rows are mirrored first (train.py:1463-1481, 1555-1560)
+//   hc, lpf       its carries [D][2][N][H] and low-pass state [N][KBJ_NU] (null: the net has none) in the call's kbj_carry
+//   X, G, Out, obs_m, rH   its scratch rows and its h planes' partners: private to the net, lanes never share them
+enum HeadKind {
+  HEAD_SAMPLE,   // output projection + low-pass + sample + log-prob as one launch (the chain env -> actor -> env waits for it)
+  HEAD_VALUE,    // output projection to the value, one launch
+  HEAD_LPF,      // the mirrored actor only advances its low-pass state (no sample)
+  HEAD_NONE      // the mirrored critic's value is only needed under the gradient; at rollout time only its carry advances
+};
+struct RolloutNet { hipStream_t lane; int type; bool step_kernel, folded0, mirrored; int tile; HeadKind head; float *hc, *lpf, *X, *G, *Out, *obs_m, **rH; };
+// the call
+//   serial   every net on the caller's stream: kbj_policy_step, kbj_critic_value, kbj_carry_reset; kbj_rollout under KBJ_ROLLOUT_PIPELINE=0
+//   side     the lane of the critic and the mirror branches (serial: the caller's stream)
+struct RolloutPlan { RolloutNet net[4]; int nnets; bool serial; hipStream_t side; };
+
+RolloutPlan rollout_plan(kbj_ctx* ctx, const kbj_carry& carry, bool serial) {
+  NnWs& w = *ws_of(ctx); const Sched& sc = w.sched;
+  RolloutPlan p{};
+  p.nnets = w.nnets; p.serial = serial;
+  // The actor -> env step -> carry reset chain runs on the caller's stream; the critic (and the mirror branches), which the env never waits
+  // for, on a side lane: its small kernels and GEMMs slip into the env kernel's ramp-up / tail (-8.5 ms per iteration against the serial
+  // order). (A two-lane software pipeline over env halves existed until round 4: with 12 env wavefronts per CU no GEMM workgroup can be
+  // co-resident, the lanes only alternated - gone.)
+  p.side = serial ? ctx->stream : ctx->side[0];
+  const HeadKind heads[4] = {HEAD_SAMPLE, HEAD_VALUE, HEAD_LPF, HEAD_NONE};
+  float* const lpf[4] = {carry.lpf_d, nullptr, carry.lpf_mirror_d, nullptr};
+  for (int n = 0; n < p.nnets; ++n) {
+    RolloutNet& q = p.net[n]; q.type = n & 1;
+    q.lane = n == 0 ? ctx->stream : p.side;
+    // Rollout-time layer steps run in lstm_step_kernel (fused [x | h] product + cell). Its output h cannot alias its input, so every h
+    // plane of the carry has a ping-pong partner in the workspace: a step with parity 0 reads the caller's planes and writes the partners,
+    // parity 1 the other way round. kbj_rollout alternates per control step; the caller's arrays hold the state again when it returns.
+    // KBJ_ROLLOUT_STEP=0 (Sched::rollout_step): the previous form, one GEMM over [x | h] plus a cell kernel per layer, in place.
+    // Only the actor proper (net 0) sits on the rollout's critical chain (env -> actor -> env). The critic and the mirror branches run on side
+    // lanes under the env kernel, where the only free resources are those of its last, partial round of wavefronts (8192 envs = 2.67 rounds
+    // of 12 per CU: 168 VGPRs per SIMD and ~58 KB of LDS per CU for the last third of the kernel): a 64x64-tile GEMM workgroup (4 waves x 84
+    // VGPRs, 37 KB) fits there, a layer-step workgroup (8 waves x 220 VGPRs) does not and would run into the next actor chain instead. So the
+    // side-lane nets keep the GEMM + cell form on small tiles (414 vs 418 ms per iteration).
+    q.step_kernel = sc.rollout_step && n == 0;
+    q.tile = sc.rollout_step && n > 0 ? 0 : -1;
+    // The actor's input projection (65 -> H, no activation) feeds only layer 0's input product, so gates_0 = obs (W_ih0 W_in)^T +
+    // (W_ih0 b_in + b_0), as in kbj_ppo_grad (inside the layer-step kernel only: the GEMM + cell form keeps the projection)
+    q.folded0 = q.step_kernel && sc.fold_actor && w.net[0].ld_obs == KBJ_LD_ACTOR;
+    q.head = heads[n]; q.mirrored = n >= 2;
+    q.hc = carry_hc(carry, n); q.lpf = lpf[n];
+    q.X = w.rX[n]; q.G = w.rG[n]; q.Out = w.rOut[n]; q.obs_m = q.mirrored ? w.rObsM[q.type] : nullptr; q.rH = w.rH[n];
+  }
+  return p;
 }
 
+// the rows of one control step: what the nets read and write at step t, what the env step writes for step t + 1
+struct StepRows {
+  const float *actor_obs, *critic_obs; float *aux, *action, *logp, *value, *actor_next, *critic_next, *aux_next, *qstate;
+  uint32_t step_index; int argmax, parity;   // parity: which copy of the step-kernel nets' h planes is live (0: the caller's arrays)
+};
+
+// One call of the rollout half: the parameters (H wide), the plan, the seed - and the phases. Each returns 0 or what kbj_fail returned.
+struct Rollout {
+  kbj_ctx* ctx; const float* params; const RolloutPlan p; uint32_t seed;
+  NnWs& w = *ws_of(ctx); const kbj_config& c = ctx->cfg_h; const int N = w.N, H = w.H;
+  const HeadParams hp{c.min_std, c.max_std, c.var_scale, c.lpf_alpha, w.net[0].ld_obs};
+
+  float* c_plane(const RolloutNet& q, int l) { return q.hc + (size_t)(2 * l + 1) * N * H; }
+  float* h_plane(const RolloutNet& q, int l, bool partner) { return partner ? q.rH[l] : q.hc + (size_t)(2 * l) * N * H; }
+
+  // phase: the folded actor weights w.Weff / w.beff for these parameters (RolloutNet::folded0)
+  void fold_actor_weights(hipStream_t s) {
+    if (!p.net[0].folded0) return;
+    const NetOff& oa = w.net[0];
+    GemmArgs g{params + oa.w_ih[0], params + oa.w_in, w.Weff, nullptr, 4 * H, oa.nin, H, H, oa.nin, oa.ld_obs, 0, 1, nullptr};
+    gemm_launch<true, false>(s, g);
+    matvec_launch(s, params + oa.w_ih[0], params + oa.b_in, params + oa.b[0], 4 * H, H, w.beff);
+  }
+
+  // phase: re-pitched input weights of the net types [k_lo, k_hi)
+  // Rollout-time input projections read W_in [H][nin] with nin = 65 / 475 floats per row: no 16-byte alignment, which puts the GEMM on its element-wise
+  // load path for that operand (the critic's 8192 x 256 x 475 product ran at 27 TFLOP/s, with four times the load instructions - beside an env kernel
+  // that is bound by vector issue). As in the update (Update::input_projections): a re-pitched copy with the observation rows' stride, zeros behind column nin,
+  // made once per rollout / policy step; the contraction then runs over the padded width (the rows' padding columns hold zeros: host/buffers.py).
+  void repitch_input_weights(hipStream_t s, int k_lo = 0, int k_hi = 2) {
+    for (int k = k_lo; k < k_hi; ++k) {
+      const NetOff& o = w.net[k];
+      if (o.nin != o.ld_obs) repitch_rows_launch(s, params + o.w_in, H, o.nin, o.ld_obs, w.WinP[k]);
+    }
+  }
+
+  // phase: the net's observation rows, mirrored first for the mirror branches
+  const float* observation_rows(const RolloutNet& q, const StepRows& v) {
+    const float* obs = q.type == 0 ? v.actor_obs : v.critic_obs;
+    if (!q.mirrored) return obs;
+    mirror_rows_launch(q.lane, obs, q.obs_m, (size_t)N, w.net[q.type].ld_obs, w.mtab[q.type]);
+    return q.obs_m;
+  }
+
+  // phase: input projection X = obs W_in^T + b_in through the aligned copy of W_in (repitch_input_weights), or the stored one where it is aligned
+  void input_projection(const RolloutNet& q, const float* obs) {
+    const NetOff& o = w.net[q.type];
+    if (o.nin != o.ld_obs) linear_fwd(q.lane, obs, o.ld_obs, w.WinP[q.type], o.ld_obs, params + o.b_in, q.X, H, N, H, o.ld_obs, 0);
+    else linear_fwd(q.lane, obs, o.ld_obs, params + o.w_in, o.nin, params + o.b_in, q.X, H, N, H, o.nin, 0);
+  }
+
+  // phase: the layers on lstm_step_kernel, from one copy of the h planes into the other; returns the top layer's output (null: failed)
+  const float* layers_step_kernel(const RolloutNet& q, const float* obs, int parity) {
+    const NetOff& o = w.net[q.type];
+    const float* x = q.X;
+    for (int l = 0; l < w.D; ++l) {
+      float* h_out = h_plane(q, l, parity == 0);
+      StepArgs sa{x, H, 0, params + o.w_ih[l], H, params + o.w_hh[l], params + o.b[l], h_plane(q, l, parity != 0), h_out, c_plane(q, l), N};
+      if (l == 0 && q.folded0) { sa.X = obs; sa.ldx = o.ld_obs; sa.kx = o.nin; sa.Wih = w.Weff; sa.ldw = o.ld_obs; sa.bias = w.beff; }
+      if (lstm_step(ctx, q.lane, H, sa)) return nullptr;
+      x = h_out;
+    }
+    return x;
+  }
+
+  // phase: the layers as gate GEMM + cell kernel, in place in the carry; returns the top layer's output
+  const float* layers_gemm_cell(const RolloutNet& q) {
+    const NetOff& o = w.net[q.type];
+    const float* x = q.X;
+    for (int l = 0; l < w.D; ++l) {
+      float *h = h_plane(q, l, false), *cc = c_plane(q, l);
+      // gates = [x | h] [W_ih | W_hh]^T + b as ONE launch over the concatenated contraction (no read-modify-write of G)
+      GemmArgs g{x, params + o.w_ih[l], q.G, params + o.b[l], N, 4 * H, 2 * H, H, H, 4 * H, 0, 1, nullptr};
+      g.A2 = h; g.B2 = params + o.w_hh[l]; g.k1 = H;
+      g.x3 = w.sched.gemm_x3 ? 1 : 0;
+      gemm_launch<true, true>(q.lane, g, q.tile);
+      CellFwdArgs2 ca;
+      ca.a[0] = CellFwdArgs{q.G, cc, h, cc, nullptr, nullptr, nullptr, nullptr, N, H};
+      lstm_cell_fwd_launch(q.lane, ca, 1);
+      x = h;
+    }
+    return x;
+  }
+
+  // phase: the head on the top layer's output x (RolloutNet::head)
+  void head(const RolloutNet& q, const float* x, const float* obs, const StepRows& v) {
+    const NetOff& o = w.net[q.type];
+    if (q.head == HEAD_SAMPLE)
+      actor_head_fused_launch(q.lane, x, H, params + o.w_out, params + o.b_out, obs, q.lpf, w.joint_bias_d, hp, seed, (uint32_t)c.env_id_offset, v.step_index, v.argmax, N,
+                              v.action, v.logp);
+    else if (q.head == HEAD_VALUE) critic_value_fused_launch(q.lane, x, H, params + o.w_out, params + o.b_out, N, v.value);
+    else if (q.head == HEAD_LPF) {
+      linear_fwd(q.lane, x, H, params + o.w_out, H, params + o.b_out, q.Out, 40, N, o.nout, H, 0);
+      actor_head_lpf_launch(q.lane, q.Out, obs, q.lpf, w.joint_bias_d, c.lpf_alpha, N, w.net[0].ld_obs);
+    }
+  }
+
+  // one control step of net q on its lane: the phases above in order
+  int net_step(const RolloutNet& q, const StepRows& v) {
+    const float* obs = observation_rows(q, v);
+    if (!q.folded0) input_projection(q, obs);
+    const float* x = q.step_kernel ? layers_step_kernel(q, obs, v.parity) : layers_gemm_cell(q);
+    if (!x) return -1;
+    head(q, x, obs, v);
+    return 0;
+  }
+
+  // carry <- 0 where done, on the net's lane; parity as StepRows: which copy of the h planes is live
+  void carry_reset(const RolloutNet& q, const float* done_d, int done_stride, int parity) {
+    CarryPlanes cp;
+    cp.n = 2 * w.D;
+    for (int l = 0; l < w.D; ++l) { cp.p[2 * l] = h_plane(q, l, q.step_kernel && parity != 0); cp.p[2 * l + 1] = c_plane(q, l); }
+    carry_reset_launch(q.lane, cp, N, H, q.lpf, done_d, done_stride);
+  }
+
+  // the h planes of the step-kernel nets back from their ping-pong partners into the caller's arrays, on the caller's stream
+  int planes_home() {
+    for (int n = 0; n < p.nnets; ++n)
+      for (int l = 0; l < w.D && p.net[n].step_kernel; ++l)
+        KBJ_HIP(ctx, hipMemcpyAsync(h_plane(p.net[n], l, false), h_plane(p.net[n], l, true), (size_t)N * H * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    return 0;
+  }
+
+  // The critic's value of ONE observation row [N][ld_critic] from a COPY of its carries (kbj_critic_value; the tail pass of kbj_rollout for
+  // kbj_config.gae_tail_value): critic_hc_d [D][2][N][hc_width] goes into w.tail_hc (re-pitched when the caller's hidden_size is not the kernels'),
+  // then the critic's phases step the copy on the critic's lane: net_step of the plan's net 1 with another carry base, so the value is
+  // bit-identical to the one a policy step writes from the same carries and row. The critic never runs on the layer-step kernel
+  // (rollout_plan), so no ping-pong partner plane is involved; its scratch rows belong to the rollout phases alone (the update and
+  // kbj_ppo_prefetch work in w.tb[] and the gather buffers). The caller has run repitch_input_weights for these parameters on a stream
+  // ordered in front of that lane. Nets 0, 2 and 3 do not run: no other carry, no low-pass state moves.
+  int critic_tail(const float* critic_obs_d, const float* critic_hc_d, int hc_width, float* value_d) {
+    RolloutNet q = p.net[1];   // (w.tail_hc: allocated at kbj_create exactly when gae_tail_value is set; both callers have checked)
+    q.hc = w.tail_hc;
+    if (hc_width == H) KBJ_HIP(ctx, hipMemcpyAsync(w.tail_hc, critic_hc_d, (size_t)2 * w.D * N * H * sizeof(float), hipMemcpyDeviceToDevice, q.lane));
+    else repitch_hc(ctx, q.lane, critic_hc_d, w.tail_hc, hc_width, H);
+    StepRows v{};
+    v.critic_obs = critic_obs_d; v.value = value_d;
+    return net_step(q, v);
+  }
+};
+
 // ---- the H-wide bodies of the entry points below (arguments validated; a padded context passes its internal copies) ----
+// all nets' phases on the caller's stream, then the planes brought home (the new h sits in the partners)
 int policy_step_body(kbj_ctx* ctx, const float* params_d, const float* actor_obs_d, const float* critic_obs_d, kbj_carry* carry, uint32_t seed,
                      uint32_t step_index, int argmax, float* action_d, float* logp_d, float* value_d) {
-  NnWs& w = *ws_of(ctx);
   kbj_nn_drop_prefetch(ctx);   // action / logp / value may be trajectory rows
   KbjTimed timed(ctx, true);
-  repitch_input_weights(ctx, ctx->stream, params_d);
-  if (policy_nets(ctx, ctx->stream, params_d, 0, w.nnets, 0, w.N, actor_obs_d, critic_obs_d, carry, seed, step_index, argmax, action_d, logp_d, value_d, 0,
-                  fold_actor_weights(ctx, ctx->stream, params_d))) return -1;
-  if (w.sched.rollout_step && carry_h_home(ctx, ctx->stream, 0, w.nnets, carry)) return -1;   // the new h sits in the partners: bring it home
+  Rollout r{ctx, params_d, rollout_plan(ctx, *carry, true), seed};
+  r.repitch_input_weights(ctx->stream);
+  r.fold_actor_weights(ctx->stream);   // per call, so that step-wise calls stay bit-identical to the rollout
+  const StepRows v{actor_obs_d, critic_obs_d, nullptr, action_d, logp_d, value_d, nullptr, nullptr, nullptr, nullptr, step_index, argmax, 0};
+  for (int n = 0; n < r.p.nnets; ++n) if (r.net_step(r.p.net[n], v)) return -1;
+  if (r.planes_home()) return -1;
   KBJ_CHECK_LAUNCH(ctx, "kbj_policy_step");
   return 0;
 }
 
+// snapshot, fork, per step: actor / others / env / resets / hop, tail value, join, home copy, rewards
 int rollout_body(kbj_ctx* ctx, const float* params_d, kbj_carry* carry, uint32_t seed, uint32_t first_step_index, kbj_traj* tr) {
   NnWs& w = *ws_of(ctx);
-  const int N = w.N, H = w.H, T = tr->T;
+  const size_t N = w.N, T = tr->T, la = w.net[0].ld_obs, lc = w.net[1].ld_obs, lx = KBJ_AUX_SIZE;
   hipStream_t s = ctx->stream;
   kbj_nn_drop_prefetch(ctx);
-  size_t la = w.net[0].ld_obs, lc = w.net[1].ld_obs, lx = KBJ_AUX_SIZE;
   // observation row T of the previous rollout is row 0 of this one
-  KBJ_HIP(ctx, hipMemcpyAsync(tr->actor_obs_d, tr->actor_obs_d + (size_t)T * N * la, N * la * sizeof(float), hipMemcpyDeviceToDevice, s));
-  KBJ_HIP(ctx, hipMemcpyAsync(tr->critic_obs_d, tr->critic_obs_d + (size_t)T * N * lc, N * lc * sizeof(float), hipMemcpyDeviceToDevice, s));
-  KBJ_HIP(ctx, hipMemcpyAsync(tr->aux_d, tr->aux_d + (size_t)T * N * lx, N * lx * sizeof(float), hipMemcpyDeviceToDevice, s));
-  size_t hcb = (size_t)2 * w.D * N * H * sizeof(float);
-  KBJ_HIP(ctx, hipMemcpyAsync(tr->carry0_actor_hc_d, carry->actor_hc_d, hcb, hipMemcpyDeviceToDevice, s));
-  KBJ_HIP(ctx, hipMemcpyAsync(tr->carry0_critic_hc_d, carry->critic_hc_d, hcb, hipMemcpyDeviceToDevice, s));
-  KBJ_HIP(ctx, hipMemcpyAsync(tr->carry0_lpf_d, carry->lpf_d, (size_t)N * KBJ_NU * sizeof(float), hipMemcpyDeviceToDevice, s));
-  if (w.mirror) {
-    if (!tr->carry0_actor_mirror_hc_d || !tr->carry0_critic_mirror_hc_d || !tr->carry0_lpf_mirror_d || !carry->actor_mirror_hc_d || !carry->critic_mirror_hc_d || !carry->lpf_mirror_d)
-      return kbj_fail(ctx, "kbj_rollout: the mirror losses are enabled, carry and trajectory need the mirror-branch arrays");
-    KBJ_HIP(ctx, hipMemcpyAsync(tr->carry0_actor_mirror_hc_d, carry->actor_mirror_hc_d, hcb, hipMemcpyDeviceToDevice, s));
-    KBJ_HIP(ctx, hipMemcpyAsync(tr->carry0_critic_mirror_hc_d, carry->critic_mirror_hc_d, hcb, hipMemcpyDeviceToDevice, s));
-    KBJ_HIP(ctx, hipMemcpyAsync(tr->carry0_lpf_mirror_d, carry->lpf_mirror_d, (size_t)N * KBJ_NU * sizeof(float), hipMemcpyDeviceToDevice, s));
+  const struct { float* a; size_t ld; } rows[3] = {{tr->actor_obs_d, la}, {tr->critic_obs_d, lc}, {tr->aux_d, lx}};
+  for (const auto& r : rows) KBJ_HIP(ctx, hipMemcpyAsync(r.a, r.a + T * N * r.ld, N * r.ld * sizeof(float), hipMemcpyDeviceToDevice, s));
+  // the start-carry snapshot: per pair of nets (actor, critic; their mirror branches) the two carries, then the pair's low-pass state
+  for (int n = 0; n < w.nnets; n += 2) {
+    for (int k = n; k < n + 2; ++k)
+      KBJ_HIP(ctx, hipMemcpyAsync(traj_carry0(*tr, k), carry_hc(*carry, k), 2 * w.D * N * w.H * sizeof(float), hipMemcpyDeviceToDevice, s));
+    KBJ_HIP(ctx, hipMemcpyAsync(n ? tr->carry0_lpf_mirror_d : tr->carry0_lpf_d, n ? carry->lpf_mirror_d : carry->lpf_d, N * KBJ_NU * sizeof(float), hipMemcpyDeviceToDevice, s));
   }
-  // The actor -> env step -> carry reset chain runs on the caller's stream; the critic (and the mirror branches), which the env never waits
-  // for, on a side lane: its small kernels and GEMMs slip into the env kernel's ramp-up / tail (-8.5 ms per iteration against the serial
-  // order). KBJ_ROLLOUT_PIPELINE=0 (read per call, diagnostics): strictly serial on the caller's stream. (A two-lane software pipeline over
-  // env halves existed until round 4: with 12 env wavefronts per CU no GEMM workgroup can be co-resident, the lanes only alternated - gone.)
-  const char* pipe_env = getenv("KBJ_ROLLOUT_PIPELINE");
-  const bool serial = pipe_env && atoi(pipe_env) == 0;
-  hipStream_t cs = serial ? s : ctx->side[0];                 // critic + mirror branches
-  const float* weff = fold_actor_weights(ctx, s, params_d);   // once: the parameters are fixed for the whole rollout
-  repitch_input_weights(ctx, s, params_d);                    // (ahead of the fork: the side lane's critic reads the copy)
-  if (!serial) {
-    KBJ_HIP(ctx, hipEventRecord(ctx->ev_fork, s));
-    KBJ_HIP(ctx, hipStreamWaitEvent(cs, ctx->ev_fork, 0));
-  }
-  for (int t = 0; t < T; ++t) {
-    const float* ao = tr->actor_obs_d + (size_t)t * N * la;
-    const float* co = tr->critic_obs_d + (size_t)t * N * lc;
-    float* aux_t = tr->aux_d + (size_t)t * N * lx;
-    float* act = tr->action_d + (size_t)t * N * KBJ_NU;
-    if (policy_nets(ctx, s, params_d, 0, 1, 0, N, ao, co, carry, seed, first_step_index + (uint32_t)t, ctx->rollout_argmax, act, tr->logp_d + (size_t)t * N, tr->value_d + (size_t)t * N, t & 1, weff)) return -1;
-    if (policy_nets(ctx, cs, params_d, 1, w.nnets, 0, N, ao, co, carry, seed, first_step_index + (uint32_t)t, 0, act, tr->logp_d + (size_t)t * N, tr->value_d + (size_t)t * N, t & 1, weff)) return -1;
-    int rc = kbj_env_step_range(ctx, s, 0, N, act, aux_t, tr->actor_obs_d + (size_t)(t + 1) * N * la, tr->critic_obs_d + (size_t)(t + 1) * N * lc,
-                                tr->aux_d + (size_t)(t + 1) * N * lx, tr->qstate_d ? tr->qstate_d + (size_t)t * N * KBJ_QSTATE_SIZE : nullptr);
+  const char* pipe_env = getenv("KBJ_ROLLOUT_PIPELINE");   // =0 (read per call, diagnostics): strictly serial on the caller's stream
+  Rollout r{ctx, params_d, rollout_plan(ctx, *carry, pipe_env && atoi(pipe_env) == 0), seed};
+  const RolloutPlan& p = r.p;
+  r.fold_actor_weights(s);      // once: the parameters are fixed for the whole rollout
+  r.repitch_input_weights(s);   // (ahead of the fork: the side lane's critic reads the copy)
+  if (!p.serial && hop(ctx, s, p.side, ctx->ev_fork)) return -1;
+  for (size_t t = 0; t < T; ++t) {
+    const StepRows v{tr->actor_obs_d + t * N * la, tr->critic_obs_d + t * N * lc, tr->aux_d + t * N * lx, tr->action_d + t * N * KBJ_NU, tr->logp_d + t * N, tr->value_d + t * N,
+                     tr->actor_obs_d + (t + 1) * N * la, tr->critic_obs_d + (t + 1) * N * lc, tr->aux_d + (t + 1) * N * lx,
+                     tr->qstate_d ? tr->qstate_d + t * N * KBJ_QSTATE_SIZE : nullptr, first_step_index + (uint32_t)t, ctx->rollout_argmax, (int)(t & 1)};
+    const float* done = v.aux + KBJ_AUX_DONE;
+    for (int n = 0; n < p.nnets; ++n) if (r.net_step(p.net[n], v)) return -1;   // the actor on the caller's stream, the others on the side lane
+    const int rc = kbj_env_step_all(ctx, s, v.action, v.aux, v.actor_next, v.critic_next, v.aux_next, v.qstate);
     if (rc) return rc;
-    carry_reset_nets(ctx, s, 0, 1, 0, N, carry, aux_t + KBJ_AUX_DONE, KBJ_AUX_SIZE, (t + 1) & 1);   // the planes step t + 1 reads
-    if (!serial) {   // the side lane needs this step's done flags and the next critic observation
-      KBJ_HIP(ctx, hipEventRecord(ctx->ev_side[0], s));
-      KBJ_HIP(ctx, hipStreamWaitEvent(cs, ctx->ev_side[0], 0));
-    }
-    carry_reset_nets(ctx, cs, 1, w.nnets, 0, N, carry, aux_t + KBJ_AUX_DONE, KBJ_AUX_SIZE, (t + 1) & 1);
+    r.carry_reset(p.net[0], done, KBJ_AUX_SIZE, (v.parity + 1) & 1);   // the planes step t + 1 reads
+    if (!p.serial && hop(ctx, s, p.side, ctx->ev_side[0])) return -1;   // the side lane needs this step's done flags and the next critic observation
+    for (int n = 1; n < p.nnets; ++n) r.carry_reset(p.net[n], done, KBJ_AUX_SIZE, (v.parity + 1) & 1);
   }
   // kbj_config.gae_tail_value: V(s_T) for kbj_gae - the critic once more, on observation row T with a copy of the carries the last reset left, on the
   // critic's lane in front of the join (under the tail of the last env step's successors: the actor's carry copy-back and kbj_rewards)
-  if (ctx->cfg_h.gae_tail_value && tr->value_tail_d && critic_tail(ctx, cs, params_d, tr->critic_obs_d + (size_t)T * N * lc, carry->critic_hc_d, H, tr->value_tail_d)) return -1;
+  if (ctx->cfg_h.gae_tail_value && tr->value_tail_d && r.critic_tail(tr->critic_obs_d + T * N * lc, carry->critic_hc_d, w.H, tr->value_tail_d)) return -1;
   KBJ_CHECK_LAUNCH(ctx, "kbj_rollout");
-  if (!serial) {   // join the side lane back into the caller's stream
-    KBJ_HIP(ctx, hipEventRecord(ctx->ev_side[0], cs));
-    KBJ_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_side[0], 0));
-  }
-  if (w.sched.rollout_step && (T & 1) && carry_h_home(ctx, s, 0, w.nnets, carry)) return -1;   // an odd number of steps leaves the live h planes in the partners
-  return kbj_rewards(ctx, tr->aux_d, T, tr->reward_d, tr->reward_comps_d);
+  if (!p.serial && hop(ctx, p.side, s, ctx->ev_side[0])) return -1;   // join the side lane back into the caller's stream
+  if ((T & 1) && r.planes_home()) return -1;   // an odd number of steps leaves the live h planes in the partners
+  return kbj_rewards(ctx, tr->aux_d, (int)T, tr->reward_d, tr->reward_comps_d);
 }
 
 }  // namespace
@@ -817,8 +858,7 @@ int kbj_policy_step(kbj_ctx* ctx, const float* params_d, const float* actor_obs_
   if (!ctx || !params_d || !actor_obs_d || !critic_obs_d || !carry || !action_d || !logp_d || !value_d) return kbj_fail(ctx, "kbj_policy_step: null argument");
   KBJ_HIP(ctx, hipSetDevice(ctx->device));
   NnWs& w = *ws_of(ctx);
-  if (w.mirror && (!carry->actor_mirror_hc_d || !carry->critic_mirror_hc_d || !carry->lpf_mirror_d))
-    return kbj_fail(ctx, "kbj_policy_step: the mirror losses are enabled, the carry needs the mirror-branch arrays");
+  if (mirror_arrays_missing(w.mirror, carry, nullptr)) return kbj_fail(ctx, "kbj_policy_step: the mirror losses are enabled, the carry needs the mirror-branch arrays");
   if (!w.padded()) return policy_step_body(ctx, params_d, actor_obs_d, critic_obs_d, carry, seed, step_index, argmax, action_d, logp_d, value_d);
   pad_params(ctx, ctx->stream, params_d, w.pparams);
   kbj_carry pc = pad_carry(ctx, ctx->stream, *carry);
@@ -831,9 +871,10 @@ int kbj_carry_reset(kbj_ctx* ctx, kbj_carry* carry, const float* done_d, int don
   if (!ctx || !carry || !done_d) return kbj_fail(ctx, "kbj_carry_reset: null argument");
   KBJ_HIP(ctx, hipSetDevice(ctx->device));
   NnWs& w = *ws_of(ctx);
-  if (w.mirror && (!carry->actor_mirror_hc_d || !carry->critic_mirror_hc_d || !carry->lpf_mirror_d)) return kbj_fail(ctx, "kbj_carry_reset: mirror-branch carry arrays are NULL");
-  kbj_carry pc = w.padded() ? pad_carry(ctx, ctx->stream, *carry) : *carry;
-  carry_reset_nets(ctx, ctx->stream, 0, w.nnets, 0, w.N, &pc, done_d, done_stride, 0);   // (the body: H wide)
+  if (mirror_arrays_missing(w.mirror, carry, nullptr)) return kbj_fail(ctx, "kbj_carry_reset: the mirror losses are enabled, the carry needs the mirror-branch arrays");
+  const kbj_carry pc = w.padded() ? pad_carry(ctx, ctx->stream, *carry) : *carry;
+  Rollout r{ctx, nullptr, rollout_plan(ctx, pc, true), 0};   // (the body: H wide, the caller's planes live)
+  for (int n = 0; n < r.p.nnets; ++n) r.carry_reset(r.p.net[n], done_d, done_stride, 0);
   if (w.padded()) unpad_carry(ctx, ctx->stream, *carry);
   KBJ_CHECK_LAUNCH(ctx, "carry_reset_kernel");
   return 0;
@@ -847,8 +888,9 @@ int kbj_critic_value(kbj_ctx* ctx, const float* params_d, const float* critic_ob
   kbj_nn_drop_prefetch(ctx);   // value_d may be a trajectory array
   const float* p = params_d;
   if (w.padded()) { pad_params(ctx, ctx->stream, params_d, w.pparams); p = w.pparams; }   // (of the carries only the critic's is read: critic_tail re-pitches it into its copy)
-  repitch_input_weights(ctx, ctx->stream, p, 1, 2);
-  if (critic_tail(ctx, ctx->stream, p, critic_obs_d, carry->critic_hc_d, w.Hu, value_d)) return -1;
+  Rollout r{ctx, p, rollout_plan(ctx, *carry, true), 0};
+  r.repitch_input_weights(ctx->stream, 1, 2);
+  if (r.critic_tail(critic_obs_d, carry->critic_hc_d, w.Hu, value_d)) return -1;
   KBJ_CHECK_LAUNCH(ctx, "kbj_critic_value");
   return 0;
 }
@@ -858,6 +900,7 @@ int kbj_rollout(kbj_ctx* ctx, const float* params_d, kbj_carry* carry, uint32_t 
   KBJ_HIP(ctx, hipSetDevice(ctx->device));
   NnWs& w = *ws_of(ctx);
   if (tr->N != w.N || tr->T <= 0) return kbj_fail(ctx, "kbj_rollout: trajectory shape does not match the context");
+  if (mirror_arrays_missing(w.mirror, carry, tr)) return kbj_fail(ctx, "kbj_rollout: the mirror losses are enabled, carry and trajectory need the mirror-branch arrays");
   if (!w.padded()) return rollout_body(ctx, params_d, carry, seed, first_step_index, tr);
   // the H-wide schedule on internal copies; the caller's start-carry snapshot is taken here, at its own width
   const size_t ub = (size_t)2 * w.D * w.N * w.Hu * sizeof(float);
@@ -904,8 +947,7 @@ int head_gathers(kbj_ctx* ctx, hipStream_t st, const kbj_traj* tr, const int32_t
   gather_rows_launch(st, tr->actor_obs_d, idx, T, N, B, lda, lda, w.tb[0].obs, lda);   // (w.tb[0].obs is an allocation of its own: 16-byte aligned)
   GatherSmallArgs gs{tr->action_d, nullptr, nullptr, nullptr, nullptr, tr->aux_d, w.act, w.logp_old, w.val_old, w.adv, w.target, w.keep};
   gather_small_launch(st, gs, idx, T, N, B, KBJ_NU + 4, KBJ_NU + 5);   // keep flags: all the recurrences need of these
-  if (w.mirror && (!traj_carry0(*tr, 2) || !traj_carry0(*tr, 3) || !tr->carry0_lpf_mirror_d))
-    return kbj_fail(ctx, "PPO pass: the mirror losses are enabled, the trajectory needs the mirror-branch carries");
+  if (mirror_arrays_missing(w.mirror, nullptr, tr)) return kbj_fail(ctx, "PPO pass: the mirror losses are enabled, the trajectory needs the mirror-branch carries");
   GatherCarryArgs gc;
   gc.nplanes = 0;
   for (int n = 0; n < w.nnets; ++n)
@@ -994,13 +1036,7 @@ UpdatePlan update_plan(kbj_ctx* ctx) {
   return p;
 }
 
-// Lane hops. Every ordering between two lanes of the update is one of these: an event recorded on one stream, waited for on another - one
-// packet each (a cross-queue wait costs the waiting queue ~7 us, 10-25 us when it has to stall: round 6), so a helper issues exactly the
-// calls its name says and a call site that reuses a record (UpdatePlan::critic_fork_recorded; ev_obs, which implies ev_small) says so.
-int ev_record(kbj_ctx* ctx, hipEvent_t ev, hipStream_t on) { KBJ_HIP(ctx, hipEventRecord(ev, on)); return 0; }
-int ev_wait(kbj_ctx* ctx, hipStream_t st, hipEvent_t ev) { KBJ_HIP(ctx, hipStreamWaitEvent(st, ev, 0)); return 0; }
-int hop(kbj_ctx* ctx, hipStream_t from, hipStream_t to, hipEvent_t ev) { return ev_record(ctx, ev, from) || ev_wait(ctx, to, ev) ? -1 : 0; }
-// the net's side lane starts behind what its lane has queued so far (one stream: stream order is the order)
+// the net's side lane starts behind what its lane has queued so far (one stream: stream order is the order); ev_record / ev_wait / hop: above the rollout
 int fork_side(kbj_ctx* ctx, const UpdatePlan& p, const NetPlan& q) { return p.two_lanes ? hop(ctx, q.lane, q.side, ctx->ev_side[q.type]) : 0; }
 
 // One call of the update: the caller's arguments (adv, target, grad: kbj_ppo_grad only; grad == nullptr is the forward-only pass), the

@@ -139,8 +139,7 @@ def test_training_with_mirror_losses_runs():
     task.ctx.close()
 
 
-@pytest.mark.parametrize("mirror,T", [(False, 6), (True, 6), (False, 5)])
-def test_pipelined_rollout_equals_stepwise_calls(mirror, T):
+def _rollout_three_ways(mirror, T, N=512, H=64, D=2):
     """kbj_rollout runs the actor -> env chain on the caller's stream with the critic (and the mirror branches) on a side lane; the trajectory
     must be bit-identical to the strictly serial order (KBJ_ROLLOUT_PIPELINE=0) and to driving kbj_policy_step / kbj_env_step /
     kbj_carry_reset one full-batch call at a time. The rollout alternates the h planes of
@@ -149,10 +148,9 @@ def test_pipelined_rollout_equals_stepwise_calls(mirror, T):
     import torch
     from kbot_joystick_amd.host import binding as Bd, buffers
     from kbot_joystick_amd.spec import compiler, layout as L
-    N, H = 512, 64
     kw = dict(actor_mirror_loss_scale=1.0, critic_mirror_loss_scale=0.01) if mirror else {}
     m = compiler.load_model("kbot-headless")
-    cfg = L.default_config(num_envs=N, batch_size=64, rollout_len=T, hidden_size=H, **kw)
+    cfg = L.default_config(num_envs=N, batch_size=64, rollout_len=T, hidden_size=H, depth=D, **kw)
     import os
     out = []
     for mode in ("serial", "side lane (default)", "stepwise"):
@@ -162,8 +160,8 @@ def test_pipelined_rollout_equals_stepwise_calls(mirror, T):
         ctx = Bd.Context(m, cfg, 0, torch.cuda.current_stream().cuda_stream)
         params = torch.zeros(ctx.param_count(), device="cuda:0")
         ctx.init_params(9, params)
-        carry = buffers.CarryBuffers(N, H, 2, "cuda:0", mirror=mirror)
-        tr = buffers.TrajBuffers(T, N, H, 2, "cuda:0", mirror=mirror)
+        carry = buffers.CarryBuffers(N, H, D, "cuda:0", mirror=mirror)
+        tr = buffers.TrajBuffers(T, N, H, D, "cuda:0", mirror=mirror)
         ctx.env_reset_all(3, tr.actor_obs[T], tr.critic_obs[T], tr.aux[T])
         for it in range(2):           # two rollouts: the second starts from carried state and row T -> row 0
             if mode != "stepwise":
@@ -185,6 +183,23 @@ def test_pipelined_rollout_equals_stepwise_calls(mirror, T):
     os.environ.pop("KBJ_ROLLOUT_PIPELINE", None)
     for a, b, d in zip(*out):
         assert torch.equal(a, d) and torch.equal(b, d)
+
+
+@pytest.mark.parametrize("mirror,T", [(False, 6), (True, 6), (False, 5)])
+def test_pipelined_rollout_equals_stepwise_calls(mirror, T):
+    _rollout_three_ways(mirror, T)
+
+
+@pytest.mark.parametrize("switch,H,D,mirror,T", [
+    ("KBJ_ROLLOUT_STEP", 64, 2, False, 5),   # gate GEMM + cell kernel in place: no partner planes, an odd T must copy nothing home
+    (None, 100, 2, True, 5),                 # padded hidden size: the step-wise calls pad and unpad the carries every call, the rollout once
+    (None, 64, 1, False, 5),
+    (None, 64, 3, True, 6)])
+def test_pipelined_rollout_equals_stepwise_calls_other_forms(monkeypatch, switch, H, D, mirror, T):
+    """The same three-way comparison where the host code takes its other paths, at N = 100 (one ragged last row group of the layer-step kernel)."""
+    if switch:
+        monkeypatch.setenv(switch, "0")      # read once per context, at kbj_create
+    _rollout_three_ways(mirror, T, N=100, H=H, D=D)
 
 
 def test_reward_components_and_actor_export(tmp_path):
