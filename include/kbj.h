@@ -150,6 +150,34 @@ int kbj_carry_reset(kbj_ctx* ctx, kbj_carry* carry, const float* done_d, int don
  * kbj_traj.value_tail_d, BEFORE the update changes the parameters. */
 int kbj_critic_value(kbj_ctx* ctx, const float* params_d, const float* critic_obs_d, const kbj_carry* carry, float* value_d);
 
+/* ---- deployment, convert.py ------------------------------------------------------------------ */
+/* replaces: the two functions convert.py exports for the robot (convert.py:74-119), served from the parameter vector itself. The deployed
+ * function takes RAW sensor values and one FLAT carry per row, not the packed 68-float rows and plane carries of kbj_policy_step; it runs the
+ * actor alone (no critic, no std head, no sampling: the action is dist.mode(), convert.py:119) as ONE launch, one workgroup per row
+ * (csrc/kbj_deploy.h). N is the batch of THIS call, any positive number, independent of kbj_config.num_envs; the design range is N <= 64
+ * (kbj_policy_step stays the throughput path). Flat carry of one row = ravel_pytree(Carry(actor_carry [depth][2][H], lpf_params))
+ * (convert.py:46, 74-78): for each layer h [H] then c [H], then the 20 low-pass floats. */
+typedef struct kbj_deploy_inputs {      /* convert.py:85-91, device arrays, N rows each */
+  const float* joint_angles_d;          /* [N][20] rad, joint order of spec/constants.JOINT_NAMES */
+  const float* joint_angular_velocities_d; /* [N][20] */
+  const float* projected_gravity_d;     /* [N][3]  */
+  const float* gyroscope_d;             /* [N][3]  */
+  const float* command_d;               /* [N][16] order of COMMAND_NAMES */
+} kbj_deploy_inputs;
+/* replaces: metadata carry_size (convert.py:71): depth * 2 * hidden_size + 20 floats per row; host only, < 0 on a null argument */
+int kbj_deploy_carry_size(const kbj_config* cfg);
+/* replaces: init_fn (convert.py:74-82): the initial flat carry, zeros, carry_d [N][carry_size]; asynchronous on the context's stream */
+int kbj_deploy_init(kbj_ctx* ctx, int N, float* carry_d);
+/* replaces: step_fn (convert.py:84-119) for N rows: pack the 65-float observation from the raw inputs (convert.py:93-105; normalize_joint_pos /
+ * normalize_joint_vel / encode_projected_gravity, train.py:1329-1349, with the arithmetic of the env kernel's observation rows), Actor.forward
+ * (train.py:913-941) without the std head, action_d [N][20] = the low-pass filtered mean, carry_out_d = the new flat carry, whose last 20
+ * floats are the action bit for bit. actor_params_d: the first kbj_actor_param_count(cfg) floats of a parameter vector in the layout above,
+ * at the context's hidden_size (a full params_d is accepted; nothing is padded or copied). carry_out_d == carry_in_d is allowed (a workgroup
+ * reads its whole row before it writes). A row's result is bitwise independent of N and of the row's position. Nothing is allocated per
+ * call; asynchronous on the context's stream. A context with extra_obs_actor > 0 is refused: the contract has 65 inputs. */
+int kbj_deploy_step(kbj_ctx* ctx, const float* actor_params_d, const kbj_deploy_inputs* in, int N,
+                    const float* carry_in_d, float* carry_out_d, float* action_d /*[N][20]*/);
+
 /* ---- rollout, §3.2 ------------------------------------------------------------------------- */
 typedef struct kbj_traj {
   int32_t T, N;

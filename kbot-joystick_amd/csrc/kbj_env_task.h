@@ -4,6 +4,7 @@
 // ksim-fork pieces are the ones frozen in DESIGN.md "Spec decisions".
 #pragma once
 #include "kbj_env_phys.h"
+#include "kbj_obs_encode.h"   // encode_pg (shared with the deployed actor step, kbj_deploy.h)
 
 namespace kbj {
 
@@ -196,12 +197,6 @@ KBJ_DEV float task_com_distance(const KbjShared& S) {
   if (fabsf(area) < 1e-12f) { float n = (float)(cnt > 1 ? cnt : 1); cx = mx / n; cy = my / n; }
   else { cx = sx / (6 * area); cy = sy / (6 * area); }
   return sqrtf((cx - S.com2[0]) * (cx - S.com2[0]) + (cy - S.com2[1]) * (cy - S.com2[1]));
-}
-
-KBJ_DEV void encode_pg(const float* g, float* o) {  // train.py:1338-1349
-  float n = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
-  o[0] = atan2f(g[1], -g[2]); o[1] = atan2f(-g[0], sqrtf(g[1] * g[1] + g[2] * g[2]));
-  o[2] = g[0] / n; o[3] = g[1] / n; o[4] = g[2] / n;
 }
 
 // observation packing (train.py:1329-1433) from the derived data of the last forward pass; rows live in HBM

@@ -12,6 +12,7 @@
 #include "kbj_nn_kernels.h"
 #include "kbj_lstm_seq.h"
 #include "kbj_lstm_bwd16.h"
+#include "kbj_deploy.h"
 
 using namespace kbj;
 
@@ -892,6 +893,40 @@ int kbj_critic_value(kbj_ctx* ctx, const float* params_d, const float* critic_ob
   r.repitch_input_weights(ctx->stream, 1, 2);
   if (r.critic_tail(critic_obs_d, carry->critic_hc_d, w.Hu, value_d)) return -1;
   KBJ_CHECK_LAUNCH(ctx, "kbj_critic_value");
+  return 0;
+}
+
+// ---- deployment (convert.py init_fn / step_fn): kbj_deploy.h ----
+int kbj_deploy_carry_size(const kbj_config* cfg) {
+  if (!cfg) return kbj_fail(nullptr, "kbj_deploy_carry_size: null argument");
+  return cfg->depth * 2 * cfg->hidden_size + KBJ_NU;
+}
+
+int kbj_deploy_init(kbj_ctx* ctx, int N, float* carry_d) {
+  if (!ctx || !carry_d) return kbj_fail(ctx, "kbj_deploy_init: null argument");
+  if (N <= 0) return kbj_fail(ctx, "kbj_deploy_init: N must be positive");
+  KBJ_HIP(ctx, hipSetDevice(ctx->device));
+  KBJ_HIP(ctx, hipMemsetAsync(carry_d, 0, (size_t)N * kbj_deploy_carry_size(&ctx->cfg_h) * sizeof(float), ctx->stream));
+  return 0;
+}
+
+int kbj_deploy_step(kbj_ctx* ctx, const float* actor_params_d, const kbj_deploy_inputs* in, int N, const float* carry_in_d, float* carry_out_d, float* action_d) {
+  if (!ctx || !actor_params_d || !in || !in->joint_angles_d || !in->joint_angular_velocities_d || !in->projected_gravity_d || !in->gyroscope_d || !in->command_d ||
+      !carry_in_d || !carry_out_d || !action_d)
+    return kbj_fail(ctx, "kbj_deploy_step: null argument");
+  if (N <= 0) return kbj_fail(ctx, "kbj_deploy_step: N must be positive");
+  if (ctx->cfg_h.extra_obs_actor > 0)
+    return kbj_fail(ctx, "kbj_deploy_step: the context has extra_obs_actor > 0; the deployed contract (convert.py:85-105) has the reference's 65 inputs and no place for user columns");
+  KBJ_HIP(ctx, hipSetDevice(ctx->device));
+  const NnWs& w = *ws_of(ctx);
+  const NetOff& o = w.user.net[0];        // the caller's layout, at its own hidden_size
+  DeployArgs a{};
+  a.params = actor_params_d; a.in = *in; a.carry_in = carry_in_d; a.carry_out = carry_out_d; a.action = action_d;
+  a.model = ctx->model_d; a.alpha = ctx->cfg_h.lpf_alpha; a.H = w.Hu; a.D = w.D;
+  a.w_in = o.w_in; a.b_in = o.b_in; a.w_out = o.w_out; a.b_out = o.b_out;
+  for (int l = 0; l < w.D; ++l) { a.w_ih[l] = o.w_ih[l]; a.w_hh[l] = o.w_hh[l]; a.b[l] = o.b[l]; }
+  actor_deploy_step_launch(ctx->stream, a, N);
+  KBJ_CHECK_LAUNCH(ctx, "actor_deploy_step_kernel");
   return 0;
 }
 

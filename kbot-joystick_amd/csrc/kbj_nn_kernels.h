@@ -25,6 +25,14 @@ __device__ __forceinline__ float softplusf_(float x) { return x > 20.0f ? x : lo
 // G [M][4H] pre-activations (bias included) -> overwritten with the gate activations (i,f,g,o);
 // c_prev [M][H]; writes h_out, c_out (may alias c_prev) and, when given, the masked copies consumed by the next
 // time step (h*keep, c*keep with keep[m] = 1 - done) and tanh(c) for the backward pass.
+// one unit of the cell from its four pre-activations (gate order i, f, g, o) and its previous cell state: the gate activations, the new
+// cell state and its tanh; h = o * tc. The one definition of the cell's arithmetic outside the MFMA recurrences: lstm_cell_fwd_kernel
+// below and the deployed actor step (kbj_deploy.h) both call it.
+__device__ __forceinline__ void lstm_cell_point(float pi, float pf, float pg, float po, float c_prev, float& i, float& f, float& gg, float& o, float& c, float& tc) {
+  i = sigmoidf_(pi); f = sigmoidf_(pf); gg = tanhf_(pg); o = sigmoidf_(po);
+  c = f * c_prev + i * gg;
+  tc = tanhf_(c);
+}
 struct CellFwdArgs {
   float* G; const float* c_prev; float* h_out; float* c_out; float* hm_next; float* cm_next; float* tanhc; const float* keep;
   int M, H;
@@ -36,9 +44,9 @@ __global__ void lstm_cell_fwd_kernel(CellFwdArgs2 args) {
   if (idx >= a.M * a.H) return;
   int m = idx / a.H, u = idx - m * a.H;
   float* g = a.G + (size_t)m * 4 * a.H;
-  float i = sigmoidf_(g[u]), f = sigmoidf_(g[a.H + u]), gg = tanhf_(g[2 * a.H + u]), o = sigmoidf_(g[3 * a.H + u]);
-  float c = f * a.c_prev[idx] + i * gg;
-  float tc = tanhf_(c), h = o * tc;
+  float i, f, gg, o, c, tc;
+  lstm_cell_point(g[u], g[a.H + u], g[2 * a.H + u], g[3 * a.H + u], a.c_prev[idx], i, f, gg, o, c, tc);
+  float h = o * tc;
   g[u] = i; g[a.H + u] = f; g[2 * a.H + u] = gg; g[3 * a.H + u] = o;
   a.h_out[idx] = h;
   a.c_out[idx] = c;

@@ -38,6 +38,12 @@ class PpoVars(C.Structure):
     _fields_ = [("logp_d", C.c_void_p), ("value_d", C.c_void_p), ("entropy_d", C.c_void_p), ("action_std_d", C.c_void_p), ("action_mean_d", C.c_void_p)]
 
 
+class DeployInputs(C.Structure):
+    """kbj_deploy_inputs: the raw sensor arrays of convert.py's step_fn (spec/constants.STEP_FN_INPUTS without the carry), N rows each."""
+    _fields_ = [("joint_angles_d", C.c_void_p), ("joint_angular_velocities_d", C.c_void_p), ("projected_gravity_d", C.c_void_p),
+                ("gyroscope_d", C.c_void_p), ("command_d", C.c_void_p)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("launches", C.c_int32), ("total_ms", C.c_float), ("flops", C.c_double)]
 
@@ -77,6 +83,9 @@ SIGNATURES = {
     "kbj_policy_step": (_i, [_vp, _vp, _vp, _vp, C.POINTER(Carry), _u32, _u32, _i, _vp, _vp, _vp]),
     "kbj_carry_reset": (_i, [_vp, C.POINTER(Carry), _vp, _i]),
     "kbj_critic_value": (_i, [_vp, _vp, _vp, C.POINTER(Carry), _vp]),
+    "kbj_deploy_carry_size": (_i, [_cfgp]),
+    "kbj_deploy_init": (_i, [_vp, _i, _vp]),
+    "kbj_deploy_step": (_i, [_vp, _vp, C.POINTER(DeployInputs), _i, _vp, _vp, _vp]),
     "kbj_rollout": (_i, [_vp, _vp, C.POINTER(Carry), _u32, _u32, C.POINTER(Traj)]),
     "kbj_set_rollout_argmax": (_i, [_vp, _i]),
     "kbj_recurrence_residency": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
@@ -264,6 +273,19 @@ class Context:
         """kbj_critic_value: the critic's value [N] of ONE observation row [N, ld_critic] from the critic carries in `carry`; no carry advances.
         Needs a context with kbj_config.gae_tail_value = 1."""
         self.call("kbj_critic_value", _ptr(params), _ptr(critic_obs), C.byref(carry), _ptr(value))
+
+    def deploy_carry_size(self) -> int:
+        """kbj_deploy_carry_size: floats of one row's flat carry (depth * 2 * hidden_size + 20, convert.py:71)."""
+        return int(self.lib.kbj_deploy_carry_size(C.byref(self.config)))
+
+    def deploy_init(self, n: int, carry):
+        """kbj_deploy_init (convert.py init_fn): zeros into carry [n, carry_size]."""
+        self.call("kbj_deploy_init", int(n), _ptr(carry))
+
+    def deploy_step(self, actor_params, joint_angles, joint_angular_velocities, projected_gravity, gyroscope, command, n: int, carry_in, carry_out, action):
+        """kbj_deploy_step (convert.py step_fn) for n rows: raw sensors + flat carry -> action [n, 20] + new flat carry (carry_out may be carry_in)."""
+        inp = DeployInputs(_ptr(joint_angles), _ptr(joint_angular_velocities), _ptr(projected_gravity), _ptr(gyroscope), _ptr(command))
+        self.call("kbj_deploy_step", _ptr(actor_params), C.byref(inp), int(n), _ptr(carry_in), _ptr(carry_out), _ptr(action))
 
     def rollout(self, params, carry: Carry, seed, first_step_index, traj: Traj):
         self.call("kbj_rollout", _ptr(params), C.byref(carry), seed, first_step_index, C.byref(traj))

@@ -967,6 +967,14 @@ class HumanoidWalkingTask:
         export.export_actor(path, self.params.cpu().numpy(), self.H, c.depth, c.ctrl_dt, self.config.cutoff_frequency, c.min_std, c.max_std,
                             c.var_scale, list(self.model_blob.joint_bias), extra_obs=self.extra_obs)
 
+    def deployed_actor(self, path: Optional[str] = None):
+        """convert.py's init_fn / step_fn on the GPU (host/deploy.py DeployedActor: raw sensors + one flat carry per row -> action): of an
+        `export_actor` archive at `path`, or - without a path - of this task's live parameters."""
+        from . import deploy
+        if path is not None:
+            return deploy.DeployedActor.from_archive(path, self.device, robot=self.config.robot)
+        return deploy.DeployedActor.from_params(self)
+
     def reward_components(self):
         """Mean of every unscaled reward term over the last rollout (train.py:1224-1256 order, spec/constants.REWARD_NAMES);
         needs `log_reward_components=True` in the config (kbj_rollout then also writes the [T][N][12] terms)."""
