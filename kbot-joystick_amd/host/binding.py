@@ -167,20 +167,20 @@ class Context:
     """RAII wrapper of kbj_ctx."""
 
     def __init__(self, model: L.Model, config: L.Config, device: int = 0, stream: int | None = None, lib: C.CDLL | None = None):
+        self._h = _vp()                    # first: close() / __del__ read it whatever fails below
         self.lib = lib if lib is not None else load_library()
         if self.lib.kbj_sizeof_model() != C.sizeof(L.Model) or self.lib.kbj_sizeof_config() != C.sizeof(L.Config):
             raise KbjError("struct layout mismatch between spec/layout.py and libkbj.so")
         if self.lib.kbj_sizeof_traj() != C.sizeof(Traj) or self.lib.kbj_sizeof_carry() != C.sizeof(Carry):
             raise KbjError("struct layout mismatch between host/binding.py (Traj / Carry) and libkbj.so")
         self.model, self.config = model, config
-        self._h = _vp()
         blob = C.string_at(C.addressof(model), C.sizeof(model))
         rc = self.lib.kbj_create(C.byref(self._h), blob, len(blob), C.byref(config), device, stream)
         if rc != 0:
             raise KbjError(self.lib.kbj_last_error(None).decode())
 
     def close(self):
-        if getattr(self, "_h", None) and self._h.value:
+        if self._h.value:
             self.lib.kbj_destroy(self._h)
             self._h = _vp()
 

@@ -169,3 +169,28 @@ def load_ckpt(path: str, part: str = "all", hidden_size: Optional[int] = None, d
 def has_member(path: str, name: str) -> bool:
     with tarfile.open(path, "r:gz") as tar:
         return any(m.name == name for m in tar.getmembers())
+
+
+class ModelView:
+    """What convert.py:39-46 takes out of a checkpoint: `model.actor` with the leaves Actor.forward uses (train.py:847-941), as
+    numpy arrays under their equinox names, plus the carry layout convert.py:71-78 flattens."""
+
+    class _Net:
+        def __init__(self, leaves: dict, prefix: str, depth: int):
+            g = lambda k: leaves[f"{prefix}.{k}"]
+            self.input_proj = _Leaf(weight=g("input_proj.weight"), bias=g("input_proj.bias"))
+            self.rnns = tuple(_Leaf(weight_ih=g(f"rnns.{l}.weight_ih"), weight_hh=g(f"rnns.{l}.weight_hh"), bias=g(f"rnns.{l}.bias")) for l in range(depth))
+            self.output_proj = _Leaf(weight=g("output_proj.weight"), bias=g("output_proj.bias"))
+
+    def __init__(self, flat, hidden_size: int, depth: int = 2, extra_obs=(0, 0)):
+        self.hidden_size, self.depth = hidden_size, depth
+        leaves = dict(split_leaves(flat, hidden_size, depth, extra_obs))
+        self.leaves = leaves
+        self.actor = ModelView._Net(leaves, "actor", depth)
+        self.critic = ModelView._Net(leaves, "critic", depth)
+        self.carry_size = depth * 2 * hidden_size + L.NU     # convert.py:71: flat (depth, 2, H) LSTM carry + 20 low-pass floats
+
+
+class _Leaf:
+    def __init__(self, **kw):
+        self.__dict__.update(kw)

@@ -9,11 +9,12 @@ hot path (viewer, TensorBoard, CLI parsing) is out of scope.
 from __future__ import annotations
 
 import dataclasses
-import math
 import os
+import sys
+import threading
 import time
-from dataclasses import dataclass
-from typing import Optional
+import warnings
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -24,220 +25,21 @@ from . import ckpt as ckpt_io
 from . import dist as dist_util
 from . import wiring
 from .buffers import CarryBuffers, TrajBuffers
-
-
-@dataclass
-class HumanoidWalkingTaskConfig:
-    """Same field names and defaults as the reference config (train.py:73-122 + ksim.PPOConfig fields used in
-    train.py:1761-1791). Defaults are the dataclass defaults of the reference, NOT the launch overrides."""
-    # model (train.py:78-93)
-    hidden_size: int = 128
-    depth: int = 2
-    var_scale: float = 0.5
-    cutoff_frequency: float = 10.0
-    # optimizer (train.py:95-114)
-    learning_rate: float = 5e-4
-    adam_weight_decay: float = 1e-5
-    use_lr_decay: bool = False
-    lr_decay_steps: int = 19_200_000
-    lr_final_multiplier: float = 0.01
-    actor_mirror_loss_scale: float = 1.0
-    critic_mirror_loss_scale: float = 0.01
-    # ksim.PPOConfig fields set by the launch block (train.py:1763-1781)
-    num_envs: int = 4096
-    batch_size: int = 512
-    num_passes: int = 3
-    rollout_length_seconds: float = 2.0
-    entropy_coef: float = 0.004
-    gamma: float = 0.94
-    lam: float = 0.94
-    dt: float = 0.004
-    ctrl_dt: float = 0.02
-    iterations: int = 8
-    ls_iterations: int = 8
-    action_latency_range: tuple = (0.003, 0.01)
-    drop_action_prob: float = 0.05
-    save_every_n_seconds: Optional[float] = 60
-    valid_every_n_steps: Optional[int] = 100      # train.py:1789: deterministic (argmax) validation rollout every n iterations
-    valid_every_n_seconds: Optional[float] = None # train.py:1790
-    render_length_seconds: float = 10.0           # train.py:1785: length of a validation / view rollout
-    max_values_per_plot: int = 50                 # train.py:1783 (plot thinning of the reference's logger; kept for name compatibility)
-    render_track_body_id: int = 0                 # train.py:1784: the body the view's camera follows (0, the world, = the base)
-    run_mode: str = "train"                       # README.md:66-70 `run_mode=view`: launch() plays the checkpointed policy instead of training (host/view.py)
-    # the editable part of get_rewards() / get_commands() (train.py:1206-1256): overrides by reward name
-    reward_scales: Optional[dict] = None          # e.g. {"feet_airtime": 2.0, "torque": 0.0}
-    reward_params: Optional[dict] = None          # e.g. {"base_height": {"standard_height": 0.85}}
-    command_ranges: Optional[dict] = None         # e.g. {"vx_range": (-0.5, 1.5)}; keys as UnifiedCommand's (train.py:1211-1217)
-    # the editable part of get_terminations() (train.py:1258-1269): {"bad_z": {"unhealthy_z": 0.4}, "not_upright": {"max_radians": 0.785},
-    # "episode_length": {"max_length_sec": 12}}; a threshold of -inf / +inf switches the built-in term off (a Python term may replace it)
-    termination_params: Optional[dict] = None
-    # build-specific
-    robot: str = "kbot"                # train.py:1080 loads robot/kbot; BASELINE configs use kbot-headless
-    seed: int = 0
-    fixed_command: Optional[tuple] = None   # BASELINE configs[1]: flat-ground fixed joystick velocity command
-    # a25: the in-tree samplers (UnifiedCommand train.py:725-752, 782-785; PlaneXYPositionReset train.py:834-836) derive their draws from the key
-    # they are called with exactly as jax.random does (split = threefry over a counter, uniform = mantissa fill, bernoulli, randint:
-    # kbj_config.command_mode = 2). The key each call RECEIVES is still this build's own (ksim's split tree is un-vendored), and no JAX is in the
-    # image to produce fixtures: pinned by jax.random's public known answers only, UNVERIFIED against a live JAX. Off by default.
-    jax_random_keys: bool = False
-    terrain: str = "flat"                   # "flat" | "sine" (train.py:1081 loads the "sine" scene; BASELINE configs[4])
-    terrain_amplitude: float = 0.05         # metres; the surface definition is this build's own (DESIGN.md section 3)
-    terrain_wavelength: float = 2.0
-    log_reward_components: bool = False     # keep the 12 unscaled reward terms of every rollout for logging (39 MB at 8192 x 100)
-    # episode accounting on the device (kbj_episode_stats): episodic return, true episode length, termination causes and - with
-    # log_reward_components - the per-episode sum of every reward term, carried per env across rollouts and through checkpoints;
-    # read with task.episode_stats(), merged into scalars() / validate(). Off (the default; KBJ_EPISODE_STATS in the environment overrides
-    # it, for A/B runs with tools/ab_bench.py): nothing is allocated, launched or logged.
-    episode_stats: bool = dataclasses.field(default_factory=lambda: os.environ.get("KBJ_EPISODE_STATS", "0") not in ("0", ""))
-    # GAE boundary conventions (include/kbj.h kbj_gae; DESIGN.md section 0). Both off by default - this build's choice: every termination ends the
-    # return, V_T := V_{T-1} - and selectable, because SURVEY B.2 believes ksim bootstraps through the episode-length "success" termination:
-    # bootstrap_on_truncation: at DONE = +1 (time-out, or a user term's +1) delta = r + gamma V(s_t) - V(s_t) instead of r - V(s_t);
-    # bootstrap_tail_value: the last row bootstraps from the critic's value of observation row T (one more critic step per rollout) instead of
-    # from V_{T-1}. KBJ_GAE_TRUNCATION / KBJ_GAE_TAIL in the environment override the defaults (A/B runs with tools/ab_bench.py).
-    bootstrap_on_truncation: bool = dataclasses.field(default_factory=lambda: os.environ.get("KBJ_GAE_TRUNCATION", "0") not in ("0", ""))
-    bootstrap_tail_value: bool = dataclasses.field(default_factory=lambda: os.environ.get("KBJ_GAE_TAIL", "0") not in ("0", ""))
-    # constraint solver of the physics step (kbj_config.solver_newton): "newton" (the default: the kernel this build is tuned and measured with) or
-    # "cg", Polak-Ribiere CG on the M^-1-preconditioned gradient - SURVEY B.1 records it as ksim's default, and at the launch block's
-    # iterations=8, ls_iterations=8 (train.py:1777-1778) it is a different dynamics, not a cosmetic switch (DESIGN.md section 3 "Solver").
-    # KBJ_SOLVER in the environment overrides the default (A/B runs with tools/ab_bench.py).
-    solver: str = dataclasses.field(default_factory=lambda: os.environ.get("KBJ_SOLVER", "") or "newton")
-    # keep qpos / qvel of every env-step (kbj_traj.qstate_d, 262 MB at 8192 x 100): the Python reward terms (extra_rewards) then see a
-    # ksim-shaped `host.trajectory.Trajectory` - trajectory.qpos / .qvel / .xpos / .xquat / .obs[...] / .command["unified_command"] as the
-    # reference's reward classes read them (train.py:138-506) - instead of the narrower TrajectoryView of the aux record
-    record_state: bool = False
-    # data-parallel exchange (SURVEY.md section 8e): "per_step" = all-reduce the gradient before every optimizer step (the
-    # single-GPU-equivalent default); "per_pass" = north_star's "once per update" variant: accumulate the minibatch gradients of
-    # a pass locally, ONE all-reduce and ONE optimizer step per pass (fewer, larger steps - a different algorithm). KBJ_ALLREDUCE
-    # in the environment overrides the default.
-    allreduce: str = dataclasses.field(default_factory=lambda: os.environ.get("KBJ_ALLREDUCE", "per_step"))
-    # per_step exchange only: all-reduce the actor's gradient slice on a second stream under the critic's tail of kbj_ppo_grad
-    # (kbj_stream_wait_actor_grad), the critic's slice behind the call. Same result; pays only where the exchange is visible (N > 1)
-    overlap_allreduce: bool = dataclasses.field(default_factory=lambda: os.environ.get("KBJ_OVERLAP_ALLREDUCE", "0") not in ("0", ""))
-    # bit-reproducible update: fixed-order reductions instead of fp32 / fp64 atomics in the gradient (kbj_config.deterministic); the
-    # reference's XLA program is deterministic by default, here it costs a few percent (DESIGN.md) and is off unless asked for
-    deterministic: bool = dataclasses.field(default_factory=lambda: os.environ.get("KBJ_DETERMINISTIC", "0") not in ("0", ""))
-    # NOT the default, never the headline: the update's large backward GEMMs through the exact three-way bf16 operand split (kbj_config.gemm_bf16x3,
-    # DESIGN.md section 10b): fp32 in, fp32 accumulate, fp32 out, every product exact up to 2^-23; faster and measured more accurate than the fp32 MFMA chain
-    gemm_bf16x3: bool = dataclasses.field(default_factory=lambda: os.environ.get("KBJ_GEMM_X3", "0") not in ("0", ""))
-    # user observations INTO the network rows (SURVEY.md section 8 f3; the reference's user appends terms to the lists run_actor / run_critic
-    # concatenate, train.py:1351-1433): that many floats are appended behind the reference's 65 / 475 columns of every observation row, the input
-    # projections and the parameter vector grow accordingly (kbj_config.extra_obs_*). Which terms fill them: HumanoidWalkingTask(
-    # extra_observations={name: (term, "actor" | "critic" | "both")}); the widths must add up. 0..64 each.
-    extra_actor_obs: int = 0
-    extra_critic_obs: int = 0
-    # data-parallel variant (SURVEY.md section 8e): normalise a minibatch's advantages with the mean / variance of the GLOBAL minibatch (all
-    # ranks' minibatches of that step: three scalars all-reduced per step) instead of each rank's own. With it the averaged gradient equals the
-    # single-process gradient over the union of the ranks' minibatches. Off by default (what ksim does across devices is not visible).
-    global_advantage_stats: bool = dataclasses.field(default_factory=lambda: os.environ.get("KBJ_GLOBAL_ADV_STATS", "0") not in ("0", ""))
-    # use_lr_decay with adam_weight_decay == 0 is train.py:1074-1075 AS WRITTEN: optax.chain(scale_by_adam(), scale_by_schedule(cosine)) has
-    # no sign flip, i.e. gradient ASCENT. Served only with this explicit opt-in (recorded in the checkpoint's config member); without it
-    # that combination is an error.
-    reproduce_reference_lr_sign: bool = False
-
-    def to_kbj(self, num_envs_local: int, env_id_offset: int = 0) -> L.Config:
-        if self.batch_size <= 0 or num_envs_local % self.batch_size != 0:
-            raise ValueError(f"batch_size {self.batch_size} must divide the per-GPU num_envs {num_envs_local}")
-        # use_lr_decay with adam_weight_decay == 0 is train.py:1074-1075: optax.chain(scale_by_adam(), scale_by_schedule(cosine_schedule)).
-        # AS WRITTEN that chain has no sign flip (optax.adam ends in scale_by_learning_rate = scale(-lr); scale_by_schedule does not), so
-        # the parameters move ALONG the Adam direction: p += lr_t * m / (sqrt(v) + eps). It is served as written - kbj_adamw_step with
-        # weight_decay 0 and the learning rate -cosine_decay_lr (update()) - behind reproduce_reference_lr_sign only; every rank says so at
-        # construction and update() warns once, because it is gradient ascent.
-        if self.use_lr_decay and self.adam_weight_decay == 0.0 and not self.reproduce_reference_lr_sign:
-            raise ValueError("use_lr_decay with adam_weight_decay == 0 is train.py:1074-1075: optax.chain(scale_by_adam, scale_by_schedule) "
-                             "has no sign flip, so the update ASCENDS the loss. Set reproduce_reference_lr_sign=True to run it as written, "
-                             "or use a non-zero adam_weight_decay (the adamw branch, train.py:1076-1077)")
-        T = int(round(self.rollout_length_seconds / self.ctrl_dt))
-        kw = dict(num_envs=num_envs_local, env_id_offset=env_id_offset, rollout_len=T, substeps=int(round(self.ctrl_dt / self.dt)),
-                  solver_iterations=self.iterations, ls_iterations=self.ls_iterations, solver_newton=int(self.solver == "newton"),
-                  hidden_size=self.hidden_size, depth=self.depth,
-                  batch_size=self.batch_size, num_passes=self.num_passes, dt=self.dt, ctrl_dt=self.ctrl_dt,
-                  latency_lo=self.action_latency_range[0], latency_hi=self.action_latency_range[1],
-                  drop_action_prob=self.drop_action_prob, var_scale=self.var_scale, entropy_coef=self.entropy_coef, gamma=self.gamma,
-                  lam=self.lam, learning_rate=self.learning_rate, weight_decay=self.adam_weight_decay, switch_prob=self.ctrl_dt / 5,
-                  actor_mirror_loss_scale=self.actor_mirror_loss_scale, critic_mirror_loss_scale=self.critic_mirror_loss_scale,
-                  lpf_alpha=self.ctrl_dt / (self.ctrl_dt + 1.0 / (2.0 * math.pi * self.cutoff_frequency)), deterministic=int(bool(self.deterministic)),
-                  extra_obs_actor=int(self.extra_actor_obs), extra_obs_critic=int(self.extra_critic_obs), gemm_bf16x3=int(bool(self.gemm_bf16x3)),
-                  gae_bootstrap_truncation=int(bool(self.bootstrap_on_truncation)), gae_tail_value=int(bool(self.bootstrap_tail_value)))
-        if not (0 <= self.extra_actor_obs <= L.MAX_EXTRA_OBS and 0 <= self.extra_critic_obs <= L.MAX_EXTRA_OBS):
-            raise ValueError(f"extra_actor_obs / extra_critic_obs must be in 0..{L.MAX_EXTRA_OBS}")
-        if self.solver not in ("newton", "cg"):
-            raise ValueError(f"unknown solver {self.solver!r} (newton | cg)")
-        if self.allreduce not in ("per_step", "per_pass"):
-            raise ValueError(f"unknown allreduce mode {self.allreduce!r} (per_step | per_pass)")
-        if self.terrain not in ("flat", "sine"):
-            raise ValueError(f"unknown terrain {self.terrain!r} (flat | sine)")
-        if self.terrain == "sine":
-            kw.update(terrain_amp=self.terrain_amplitude, terrain_wavelength=self.terrain_wavelength)
-        if self.jax_random_keys:
-            kw.update(command_mode=2)           # (a fixed command below overrides the sampler, not the reset's key handling... which command_mode 1 switches off too)
-        if self.fixed_command is not None:
-            if self.jax_random_keys:
-                raise ValueError("jax_random_keys selects the UnifiedCommand SAMPLER with jax.random's key handling; it cannot be combined with fixed_command")
-            cmd = list(self.fixed_command) + [0.0] * (L.NCMD - len(self.fixed_command))
-            kw.update(command_mode=1, fixed_command=cmd)
-        for k, (lo, hi) in (self.command_ranges or {}).items():
-            if k not in ("vx_range", "vy_range", "wz_range", "bh_range", "rx_range", "ry_range"):
-                raise KeyError(f"unknown command range {k!r}")
-            kw[k[:2] + "_lo"], kw[k[:2] + "_hi"] = float(lo), float(hi)
-        for name, kv in (self.termination_params or {}).items():
-            for k, v in kv.items():
-                v = float(v)
-                if (name, k) == ("bad_z", "unhealthy_z"):
-                    kw["unhealthy_z"] = max(v, -3.0e38)
-                elif (name, k) == ("not_upright", "max_radians"):
-                    kw["max_tilt_rad"] = min(v, math.pi)
-                elif (name, k) == ("episode_length", "max_length_sec"):
-                    kw["max_episode_steps"] = int(min(round(v / self.ctrl_dt), 2 ** 30))     # round like T and substeps: 2.3 / 0.02 is 115, not 114
-                else:
-                    raise KeyError(f"unknown termination parameter {name}.{k} (bad_z.unhealthy_z | not_upright.max_radians | episode_length.max_length_sec)")
-        kcfg = L.default_config(**kw)
-        wiring.apply_reward_overrides(kcfg, self.reward_scales, self.reward_params)
-        return kcfg
-
-
-def cosine_decay_lr(config: HumanoidWalkingTaskConfig, count: int) -> float:
-    """optax.cosine_decay_schedule(init_value, decay_steps, alpha) at optimizer-update count `count` (train.py:1068-1072)."""
-    frac = min(max(count, 0), config.lr_decay_steps) / config.lr_decay_steps
-    cosine = 0.5 * (1.0 + math.cos(math.pi * frac))
-    return config.learning_rate * ((1.0 - config.lr_final_multiplier) * cosine + config.lr_final_multiplier)
-
-
-def episode_stats_scalars(vec, ctrl_dt: float, prefix: str = "episode/", terms: bool = False) -> dict:
-    """One KBJ_EPST vector (kbj_model.h; layout.EPST) as logger scalars. Means over the finished episodes are omitted when there are none
-    (and the time to failure when none of them failed): a mean of nothing is not a number worth plotting."""
-    E = L.EPST
-    n = float(vec[E["EPISODES"]])
-    out = {prefix + "count": n}
-    if n <= 0:
-        return out
-    mean = float(vec[E["RETURN_SUM"]]) / n
-    out[prefix + "return_mean"] = mean
-    out[prefix + "return_std"] = math.sqrt(max(float(vec[E["RETURN_SUMSQ"]]) / n - mean * mean, 0.0))
-    out[prefix + "return_min"], out[prefix + "return_max"] = float(vec[E["RETURN_MIN"]]), float(vec[E["RETURN_MAX"]])
-    out[prefix + "length_s_mean"] = float(vec[E["LENGTH_SUM"]]) / n * ctrl_dt
-    out[prefix + "length_s_max"] = float(vec[E["LENGTH_MAX"]]) * ctrl_dt
-    fails = float(vec[E["FAIL_HEIGHT"]] + vec[E["FAIL_OTHER"]])
-    if fails > 0:
-        out[prefix + "time_to_failure_s_mean"] = float(vec[E["FAIL_LENGTH_SUM"]]) / fails * ctrl_dt
-    for key, slot in (("frac_fail_height", "FAIL_HEIGHT"), ("frac_fail_other", "FAIL_OTHER"), ("frac_truncated", "TRUNCATED")):
-        out[prefix + key] = float(vec[E[slot]]) / n
-    if terms:
-        for k, name in enumerate(constants.REWARD_NAMES):
-            out[f"{prefix}reward/{name}"] = float(vec[E["TERM_SUM"] + k]) / n
-    return out
-
-
-def launch_config(**overrides) -> HumanoidWalkingTaskConfig:
-    """The reference's launch block (train.py:1761-1791)."""
-    kw = dict(num_envs=4096, batch_size=512, num_passes=3, rollout_length_seconds=2.0, entropy_coef=0.004, learning_rate=5e-4, gamma=0.94,
-              lam=0.94, actor_mirror_loss_scale=0.0, critic_mirror_loss_scale=0.0, hidden_size=256, dt=0.004, ctrl_dt=0.02, iterations=8,
-              ls_iterations=8, action_latency_range=(0.003, 0.01), drop_action_prob=0.05, render_track_body_id=0, render_length_seconds=10,
-              max_values_per_plot=50, save_every_n_seconds=60, valid_every_n_steps=100, valid_every_n_seconds=None)
-    kw.update(overrides)
-    return HumanoidWalkingTaskConfig(**kw)
+from .ckpt import ModelView
+from .config import HumanoidWalkingTaskConfig, cosine_decay_lr, launch_config      # launch_config: re-exported with the rest
+from .episode import EpisodeStats, episode_stats_scalars, fresh_episode_stats
+from .user_terms import UserTerms
 
 
 _NO_PREFETCH = os.environ.get("KBJ_NO_PREFETCH", "0") not in ("0", "")     # A/B switch: kbj_ppo_prefetch is a pure scheduling hint
+
+
+class _Validation(NamedTuple):
+    """The cached context and buffers of validate() / view(), for its (num_envs, T)."""
+    key: tuple
+    ctx: B.Context
+    carry: CarryBuffers
+    traj: TrajBuffers
 
 
 class HumanoidWalkingTask:
@@ -269,26 +71,18 @@ class HumanoidWalkingTask:
         With any of these the rollout runs step by step from the host (policy step, env step, user terms, carry reset: the same calls
         kbj_rollout fuses, bit-identical when no user term fires) instead of as one kbj_rollout call."""
         self.extra_rewards = dict(extra_rewards or {})
-        self.extra_terminations = dict(extra_terminations or {})
-        # an observation term may be given as (term, into) with into in {"actor", "critic", "both"}: its output is then ALSO written into the
-        # networks' input rows, behind the reference's columns (config.extra_actor_obs / extra_critic_obs floats, in dictionary order)
-        self.extra_observations, self.extra_obs_into = {}, {}
-        for name, term in (extra_observations or {}).items():
-            into = None
-            if isinstance(term, tuple):
-                term, into = term
-            into = into if into is not None else getattr(term, "into", None)
-            if into not in (None, "actor", "critic", "both"):
-                raise ValueError(f"observation {name!r}: into must be 'actor', 'critic', 'both' or None, not {into!r}")
-            self.extra_observations[name], self.extra_obs_into[name] = term, into
-        self._obs_started = False
-        self.command_term = command
-        self._command_started = False
-        self.extra_resets = list(extra_resets or [])
-        self._resets_started = False
-        self.extra_obs_buffers: dict = {}
+        self.terms = UserTerms(extra_terminations, extra_observations, command, extra_resets)     # host/user_terms.py
+        self.extra_obs_buffers = self.terms.obs_buffers
         self._extra_carries: dict = {}
         self.extra_reward_means: dict = {}
+        # state that comes into being later: update()'s permutation staging and exchange stream, validate()'s cache, the checkpoint writer
+        self._perm_pinned = self._perm_dev = self._perm_event = None
+        self._comm_stream = None
+        self._adv_sums = None                  # the last global advantage sums: alive until kbj_set_advantage_sums' consumer has run
+        self._warned_ascent = False
+        self._valid: Optional[_Validation] = None
+        self._save_thread = self._save_error = None
+        self.loop_stats: Optional[dict] = None  # launch()'s account of its loop
         if not torch.cuda.is_available():
             raise B.KbjError("HumanoidWalkingTask needs a HIP device (no CPU fallback)")
         self.config = config
@@ -296,7 +90,7 @@ class HumanoidWalkingTask:
         if config.run_mode not in ("train", "view"):
             raise ValueError(f"run_mode must be 'train' or 'view' (README.md:66-70), not {config.run_mode!r}")
         if config.use_lr_decay and config.adam_weight_decay == 0.0 and config.reproduce_reference_lr_sign:
-            import sys                       # every rank, at construction: a single warnings.warn is easy to lose in a multi-rank log
+            # every rank, at construction: a single warnings.warn is easy to lose in a multi-rank log
             print(f"[kbj rank {rank}] reproduce_reference_lr_sign: optax.chain(scale_by_adam, scale_by_schedule) as written in "
                   "train.py:1074-1075 has no sign flip - this run ASCENDS the loss", file=sys.stderr, flush=True)
         self.device = device or torch.device("cuda", torch.cuda.current_device())
@@ -319,23 +113,16 @@ class HumanoidWalkingTask:
         self.carry = self.get_initial_model_carry()
         self.nobs_actor, self.nobs_critic, self.ld_actor, self.ld_critic = L.obs_widths(self.kcfg)
         self.extra_obs = (int(self.kcfg.extra_obs_actor), int(self.kcfg.extra_obs_critic))
-        if any(self.extra_obs) and not any(v for v in self.extra_obs_into.values()):
+        if any(self.extra_obs) and not any(v for v in self.terms.obs_into.values()):
             raise ValueError("config.extra_actor_obs / extra_critic_obs reserve network inputs, but no observation term is routed into them "
                              "(extra_observations={name: (term, 'actor' | 'critic' | 'both')})")
+        self.terms.bind(config.seed, rank, self.device, self.model_blob, self.nobs_actor, self.nobs_critic)
         self.traj = TrajBuffers(self.T, self.N, self.H, self.kcfg.depth, self.device, mirror=self.mirror, reward_comps=config.log_reward_components,
                                 ld_actor=self.ld_actor, ld_critic=self.ld_critic, record_state=config.record_state)
-        # episode accounting (config.episode_stats): per-env accumulator rows next to the env state, one call's result, and on the host the
-        # last rollout's vector and the totals since creation / resume. The result comes back through a pinned buffer behind the kernel
-        # (no sync in the loop); it is folded into the totals when the next rollout starts or when somebody asks.
-        self.ep_acc = self.ep_stats = None
-        if config.episode_stats:
-            self.ep_acc = torch.zeros(self.N, L.EACC["SIZE"], device=self.device)
-            self.ep_stats = torch.zeros(L.EPST["SIZE"], dtype=torch.float64, device=self.device)
-            self._ep_host = torch.zeros(L.EPST["SIZE"], dtype=torch.float64).pin_memory()
-            self._ep_event = torch.cuda.Event()
-            self._ep_pending = False
-            self._ep_last = dist_util.empty_episode_stats()
-            self._ep_total = dist_util.empty_episode_stats()
+        # episode accounting (config.episode_stats; host/episode.py): `ep_acc`, the per-env accumulator rows next to the env state, and
+        # `ep_stats`, one call's result, are the object's own tensors; ep_acc is None means off
+        self.episodes = EpisodeStats(self.N, self.device) if config.episode_stats else None
+        self.ep_acc, self.ep_stats = (self.episodes.acc, self.episodes.stats) if self.episodes is not None else (None, None)
         self.opt_step = 0
         self.iteration = 0
         self._perm_gen = torch.Generator(device="cpu")
@@ -366,35 +153,23 @@ class HumanoidWalkingTask:
     # ---- the hot path ----
     def rollout(self):
         """T control steps of all envs, trajectory + rewards on the device."""
-        if self.extra_terminations or self.extra_observations or self.command_term is not None or self.extra_resets:
+        if self.terms:
             self._rollout_stepwise()
         else:
             self.ctx.rollout(self.params, self.carry.c, self.config.seed, self.iteration * self.T, self.traj.c)
         if self.extra_rewards:
             from .traj_view import apply_extra_rewards
             self.extra_reward_means = apply_extra_rewards(self.extra_rewards, self._extra_carries, self.trajectory(), self.traj.reward)
-        if self.ep_acc is not None:               # behind the user rewards, so that they count; user terminations are in the DONE column already
-            self._fold_episode_stats()
-            self.ctx.episode_stats(self.traj.c, self.ep_acc, self.ep_stats)
-            self._ep_host.copy_(self.ep_stats, non_blocking=True)
-            self._ep_event.record()
-            self._ep_pending = True
-
-    def _fold_episode_stats(self):
-        """The last kbj_episode_stats result, once its copy has landed, becomes `_ep_last` and joins the totals."""
-        if self._ep_pending:
-            self._ep_event.synchronize()
-            self._ep_last = self._ep_host.numpy().copy()
-            self._ep_total = dist_util.combine_episode_stats([self._ep_total, self._ep_last])
-            self._ep_pending = False
+        if self.episodes is not None:             # behind the user rewards, so that they count; user terminations are in the DONE column already
+            self.episodes.after_rollout(self.ctx, self.traj.c)
 
     def episode_stats_vectors(self):
         """(last, total): this rank's raw KBJ_EPST vectors (float64 numpy, layout.EPST) behind episode_stats() - the episodes that finished in
         the last rollout and all since creation / resume."""
         if self.ep_acc is None:
             raise B.KbjError("episode_stats_vectors() needs HumanoidWalkingTaskConfig.episode_stats=True")
-        self._fold_episode_stats()
-        return self._ep_last.copy(), self._ep_total.copy()
+        last, total = self.episodes.vectors()
+        return last.copy(), total.copy()
 
     def episode_stats(self) -> dict:
         """Episode metrics (needs `episode_stats=True` in the config): `episode/...` over the episodes that finished in the LAST rollout,
@@ -403,8 +178,7 @@ class HumanoidWalkingTask:
         reward term. In a multi-rank job the vectors are reduced over the ranks (dist.reduce_episode_stats): every rank must call it."""
         if self.ep_acc is None:
             raise B.KbjError("episode_stats() needs HumanoidWalkingTaskConfig.episode_stats=True")
-        self._fold_episode_stats()
-        last, total = self._ep_last, self._ep_total
+        last, total = self.episodes.vectors()
         if self.world_size > 1 or dist_util.FORCE_COLLECTIVE:
             both = dist_util.reduce_episode_stats(torch.from_numpy(np.stack([last, total])).to(self.device), self.world_size).cpu().numpy()
             last, total = both[0], both[1]
@@ -427,126 +201,22 @@ class HumanoidWalkingTask:
         view.extra_observations = extra
         return view
 
-    def _apply_command(self, ctx, tr, row: int, view, fresh, step_index: int, all_fresh: bool = False):
-        """The user's Command term for observation row `row` of `tr` (train.py:724, 768): `initial_command` for the envs whose episode
-        starts there (`fresh` [N] bool), `__call__(prev_command, ...)` for the others, written by kbj_env_set_command. `all_fresh`: the
-        caller KNOWS every env starts an episode (rows written by a reset of all envs); otherwise both are evaluated and selected on the
-        device - asking `fresh.all()` would drain the queue once per control step."""
-        term, n = self.command_term, tr.aux[row].shape[0]
-        g = torch.Generator(device=self.device)
-        g.manual_seed((self.config.seed * 2654435761 + step_index * 40503 + self.rank) & 0x7FFFFFFFFFFFFFFF)
-        prev = tr.aux[row][:, L.AUX["CMD"]:L.AUX["CMD"] + L.NCMD].clone()
-        new = term.initial_command(view, 1.0, g).reshape(n, L.NCMD).to(torch.float32)
-        if not all_fresh:
-            new = torch.where(fresh[:, None], new, term(prev, view, 1.0, g).reshape(n, L.NCMD).to(torch.float32))
-        ctx.env_set_command(None, new.contiguous(), tr.actor_obs[row], tr.critic_obs[row], tr.aux[row])
-
-    def _apply_resets(self, ctx, tr, row: int, fresh, step_index: int):
-        """The user's Reset terms (train.py:833-844) for observation row `row` of `tr`: evaluated on every env's (qpos, qvel), kept for the envs
-        whose episode starts there (`fresh` [N] bool, None = all), written back - with the rows of the next observation - by kbj_env_set_qstate."""
-        from .traj_view import ResetData
-        n = tr.aux[row].shape[0]
-        qpos, qvel = torch.empty(n, L.NQ, device=self.device), torch.empty(n, L.NV, device=self.device)
-        ctx.env_get_qstate(qpos, qvel)
-        g = torch.Generator(device=self.device)
-        g.manual_seed((self.config.seed * 2246822519 + step_index * 3266489917 + self.rank) & 0x7FFFFFFFFFFFFFFF)
-        data = ResetData(qpos, qvel)
-        for term in self.extra_resets:
-            data = term(data, 1.0, g)
-            # a Reset term returns the data it was given with fields replaced (train.py:833-844): same shapes, finite numbers. Checked here, by name,
-            # on the host (this is the step-wise path of user terms, not the fused rollout): the kernel would carry a NaN into the observation
-            # rows without a word, and a broadcastable wrong shape would only surface as a reshape error further down.
-            for field, width in (("qpos", L.NQ), ("qvel", L.NV)):
-                v = getattr(data, field, None)
-                if not torch.is_tensor(v) or tuple(v.shape) != (n, width):
-                    raise B.KbjError(f"Reset term {type(term).__name__} returned {field} of shape {tuple(v.shape) if torch.is_tensor(v) else type(v).__name__}, "
-                                     f"expected ({n}, {width})")
-                if not bool(torch.isfinite(v).all()):
-                    raise B.KbjError(f"Reset term {type(term).__name__} returned non-finite values in {field}")
-        new_q = data.qpos.to(torch.float32).contiguous()
-        new_v = data.qvel.to(torch.float32).contiguous()
-        self._reset_keep = (new_q, new_v)          # alive until the kernel has run (stream-ordered)
-        mask = None if fresh is None else fresh.to(torch.float32)
-        ctx.env_set_qstate(mask, new_q, new_v, tr.actor_obs[row], tr.critic_obs[row], tr.aux[row])
-
-    def _observe_into_rows(self, tr, row: int, view) -> dict:
-        """Evaluate the user's Observation terms (train.py:635, 682, 706 protocol) on `view` and write those routed into the networks behind the
-        reference's columns of observation row `row` (actor: from column 65, critic: from 475, dictionary order). Returns {name: [N, d]}."""
-        off = {"actor": L.NOBS_ACTOR, "critic": L.NOBS_CRITIC}
-        rows = {"actor": tr.actor_obs[row], "critic": tr.critic_obs[row]}
-        lim = {"actor": self.nobs_actor, "critic": self.nobs_critic}
-        out = {}
-        for name, term in self.extra_observations.items():
-            v = term.observe(view, 1.0, None) if hasattr(term, "observe") else term(view)
-            v = v.reshape(view.N, -1).to(torch.float32)
-            out[name] = v
-            into = self.extra_obs_into.get(name)
-            for net in (("actor", "critic") if into == "both" else (into,) if into else ()):
-                if off[net] + v.shape[1] > lim[net]:
-                    raise B.KbjError(f"observation {name!r} ({v.shape[1]} floats) does not fit the {net} row: config.extra_{net}_obs reserves "
-                                     f"{lim[net] - (L.NOBS_ACTOR if net == 'actor' else L.NOBS_CRITIC)} floats")
-                rows[net][:, off[net]:off[net] + v.shape[1]] = v
-                off[net] += v.shape[1]
-        for net in ("actor", "critic"):
-            if any(i in (net, "both") for i in self.extra_obs_into.values()) and off[net] != lim[net]:
-                raise B.KbjError(f"the observation terms routed into the {net} fill {off[net] - (L.NOBS_ACTOR if net == 'actor' else L.NOBS_CRITIC)} "
-                                 f"floats, config.extra_{net}_obs says {lim[net] - (L.NOBS_ACTOR if net == 'actor' else L.NOBS_CRITIC)}")
-        return out
-
     def _rollout_stepwise(self):
-        """kbj_rollout's steps as separate ABI calls with the user's Termination / Observation terms between the env step and the carry
-        reset (train.py:817, 635 protocols on host/traj_view.StepView)."""
-        from .traj_view import StepView, combine_terminations
-        T, tr, c = self.T, self.traj, self.ctx
-        done_col = 4 * L.AUX["DONE"]
+        """kbj_rollout's steps as separate ABI calls with the user's terms between the env step and the carry reset (host/user_terms.py)."""
+        T, tr, c, terms = self.T, self.traj, self.ctx, self.terms
         tr.actor_obs[0].copy_(tr.actor_obs[T]); tr.critic_obs[0].copy_(tr.critic_obs[T]); tr.aux[0].copy_(tr.aux[T])   # row T of the last rollout is row 0 of this one
         tr.carry0_actor_hc.copy_(self.carry.actor_hc); tr.carry0_critic_hc.copy_(self.carry.critic_hc); tr.carry0_lpf.copy_(self.carry.lpf)
         if self.mirror:
             tr.carry0_actor_mirror_hc.copy_(self.carry.actor_mirror_hc); tr.carry0_critic_mirror_hc.copy_(self.carry.critic_mirror_hc)
             tr.carry0_lpf_mirror.copy_(self.carry.lpf_mirror)
-        first = self.iteration * T
-
-        def observe(row: int, view):
-            vals = self._observe_into_rows(tr, row, view)
-            for name, v in vals.items():
-                if name not in self.extra_obs_buffers:
-                    self.extra_obs_buffers[name] = torch.zeros(T + 1, self.N, v.shape[1], device=self.device)
-                self.extra_obs_buffers[name][row].copy_(v)
-
-        def update_command(row: int, view, fresh, all_fresh: bool = False):
-            self._apply_command(c, tr, row, view, fresh, first + row, all_fresh)
-
-        if self.extra_resets and not self._resets_started:                     # the state env_reset_all drew: every env starts an episode
-            self._apply_resets(c, tr, 0, None, first)
-            self._resets_started = True
-        if self.command_term is not None and not self._command_started:      # the rows env_reset_all wrote: every env starts an episode
-            view0 = StepView(tr.aux[0], tr.actor_obs[0], tr.critic_obs[0], tr.aux[0], self.model_blob)
-            update_command(0, view0, torch.ones(self.N, dtype=torch.bool, device=self.device), all_fresh=True)
-            self._command_started = True
-        for name, buf in self.extra_obs_buffers.items():
+        first = self.iteration * T              # the terms' step index is iteration * T + row
+        for buf in self.extra_obs_buffers.values():
             buf[0].copy_(buf[T])
-        if self.extra_observations and not self._obs_started:                 # the rows env_reset_all wrote carry zeros in the user columns
-            observe(0, StepView(tr.aux[0], tr.actor_obs[0], tr.critic_obs[0], tr.aux[0], self.model_blob))
-            self._obs_started = True
-        for t in range(T):
-            c.policy_step(self.params, tr.actor_obs[t], tr.critic_obs[t], self.carry.c, self.config.seed, first + t, False, tr.action[t], tr.logp[t], tr.value[t])
-            c.env_step(tr.action[t], tr.aux[t], tr.actor_obs[t + 1], tr.critic_obs[t + 1], tr.aux[t + 1], tr.qstate[t] if tr.qstate is not None else None)
-            qs_t = tr.qstate[t] if tr.qstate is not None else None
-            view = StepView(tr.aux[t], tr.actor_obs[t + 1], tr.critic_obs[t + 1], tr.aux[t + 1], self.model_blob, qs_t)
-            if self.extra_terminations:
-                user = combine_terminations(self.extra_terminations, view)
-                fire = (user != 0) & (tr.aux[t][:, L.AUX["DONE"]] == 0)          # the kernel's own terminations already reset their envs
-                c.env_reset_where(fire.to(torch.float32), tr.actor_obs[t + 1], tr.critic_obs[t + 1], tr.aux[t + 1])
-                tr.aux[t][:, L.AUX["DONE"]] = torch.where(fire, user, tr.aux[t][:, L.AUX["DONE"]])
-                view = StepView(tr.aux[t], tr.actor_obs[t + 1], tr.critic_obs[t + 1], tr.aux[t + 1], self.model_blob, qs_t)
-            if self.extra_resets:                                   # the envs this step finished carry their fresh episode's state: the user's Reset terms on top
-                self._apply_resets(c, tr, t + 1, tr.aux[t][:, L.AUX["DONE"]] != 0, first + t + 1)
-                view = StepView(tr.aux[t], tr.actor_obs[t + 1], tr.critic_obs[t + 1], tr.aux[t + 1], self.model_blob, qs_t)
-            if self.command_term is not None:
-                update_command(t + 1, view, tr.aux[t][:, L.AUX["DONE"]] != 0)
-            if self.extra_observations:
-                observe(t + 1, view)
-            c.carry_reset(self.carry.c, tr.aux[t].data_ptr() + done_col, L.AUX["SIZE"])
+        if not terms.started:                   # the state and the rows env_reset_all wrote: every env starts an episode, the user columns are zero
+            terms.run_hooks(c, tr, 0, first, [terms.apply_resets, terms.apply_command, terms.observe])
+            terms.started = True
+        terms.run_steps(c, tr, self.carry, self.params, T, seed=self.config.seed, first_step=first, argmax=False, first_index=first,
+                        hooks=[terms.apply_terminations, terms.apply_resets, terms.apply_command, terms.observe])
         if self.kcfg.gae_tail_value:          # V(s_T) for GAE, as kbj_rollout computes it: row T, the carries the last reset left, the rollout's parameters
             c.critic_value(self.params, tr.critic_obs[T], self.carry.c, tr.value_tail)
         c.rewards(tr.aux, T, tr.reward, tr.comps)
@@ -557,7 +227,7 @@ class HumanoidWalkingTask:
         # stream-ordered copies BEFORE anything of the update is enqueued - a pageable `.to(device)` per pass blocks the host until the
         # queued work has drained and leaves the GPU idle (~0.3 ms) while the next minibatch is being enqueued
         npass = self.kcfg.num_passes
-        if getattr(self, "_perm_pinned", None) is None or self._perm_pinned.shape != (npass, self.N):
+        if self._perm_pinned is None or self._perm_pinned.shape != (npass, self.N):
             self._perm_pinned = torch.empty(npass, self.N, dtype=torch.int32).pin_memory()
             self._perm_dev = torch.empty(npass, self.N, dtype=torch.int32, device=self.device)
             self._perm_event = torch.cuda.Event()
@@ -591,7 +261,7 @@ class HumanoidWalkingTask:
                         continue
                 g = self.grad_acc if per_pass else self.grad
                 if self.config.overlap_allreduce and not per_pass:
-                    if getattr(self, "_comm_stream", None) is None:
+                    if self._comm_stream is None:
                         self._comm_stream = torch.cuda.Stream(device=self.device)
                     scale = dist_util.allreduce_grad_overlapped_(self.ctx, g, self.ctx.actor_param_count(), self.world_size, self._comm_stream)
                 else:
@@ -601,8 +271,7 @@ class HumanoidWalkingTask:
                 if self.config.use_lr_decay:
                     lr = cosine_decay_lr(self.config, self.opt_step)
                     if self.config.adam_weight_decay == 0.0:      # train.py:1074-1075 as written: no sign flip behind scale_by_adam
-                        if not getattr(self, "_warned_ascent", False):
-                            import warnings
+                        if not self._warned_ascent:
                             warnings.warn("use_lr_decay with adam_weight_decay == 0 reproduces train.py:1074-1075 as written: "
                                           "optax.chain(scale_by_adam, scale_by_schedule) has no sign flip, the update ASCENDS the loss")
                             self._warned_ascent = True
@@ -707,11 +376,9 @@ class HumanoidWalkingTask:
         if self.mirror:
             extras.update(actor_mirror_hc=self.carry.actor_mirror_hc.cpu().numpy(), critic_mirror_hc=self.carry.critic_mirror_hc.cpu().numpy(),
                           lpf_mirror=self.carry.lpf_mirror.cpu().numpy())
-        if self.ep_acc is not None:      # episodes in flight and the totals so far (the last rollout's own vector is not state)
-            self._fold_episode_stats()
-            extras.update(ep_acc=self.ep_acc.cpu().numpy(), ep_total=self._ep_total.copy())
+        if self.episodes is not None:
+            extras.update(self.episodes.checkpoint_state())
         # carries of Python StatefulReward terms (extra_rewards): tensors (or tuples / lists of tensors) per term name
-        import numpy as np
         for name, carry in self._extra_carries.items():
             leaves = list(carry) if isinstance(carry, (tuple, list)) else [carry]
             for i, leaf in enumerate(leaves):
@@ -728,7 +395,6 @@ class HumanoidWalkingTask:
         if not background:
             ckpt_io.save_ckpt(*args, **kw)
             return
-        import threading
 
         def write():
             try:
@@ -741,11 +407,10 @@ class HumanoidWalkingTask:
 
     def wait_for_checkpoint(self):
         """Join a background save_checkpoint(); re-raises what the writer raised."""
-        th = getattr(self, "_save_thread", None)
-        if th is not None:
-            th.join()
+        if self._save_thread is not None:
+            self._save_thread.join()
             self._save_thread = None
-            err, self._save_error = getattr(self, "_save_error", None), None
+            err, self._save_error = self._save_error, None
             if err is not None:
                 raise err
 
@@ -765,25 +430,14 @@ class HumanoidWalkingTask:
             self.opt_m.zero_(); self.opt_v.zero_()
             self.opt_step = 0
             if ckpt_io.has_member(path, "opt_state_0"):
-                import warnings
                 warnings.warn(f"{path}: opt_state_0 is present but does not map onto (count, mu, nu) of this model - "
                               "resuming with FRESH Adam moments and optimizer step 0 (parameters were loaded)")
         self.iteration = int(st.get("num_steps", 0))
-        self._obs_started = self.iteration > 0          # a resumed run's row 0 already carries the user observation columns
-        self._command_started = self.iteration > 0      # a resumed run's row 0 already carries the user command term's commands
-        self._resets_started = self.iteration > 0       # ... and its env rows the user Reset terms' state
+        # a resumed run's row 0 already carries the user observation columns and the user command term's commands, its env rows the user Reset terms' state
+        self.terms.started = self.iteration > 0
         x = z["extras"]
-        if self.ep_acc is not None:
-            # episode accounting: the members when the saved run kept them (same env count), else from zero - episodes already running
-            # are then counted from here on (an old checkpoint, a run saved with the switch off, a model-only file)
-            self._ep_pending = False
-            self._ep_last = dist_util.empty_episode_stats()
-            if "ep_acc" in x and "ep_total" in x and tuple(x["ep_acc"].shape) == tuple(self.ep_acc.shape) and x["ep_total"].shape == (L.EPST["SIZE"],):
-                self.ep_acc.copy_(torch.from_numpy(np.ascontiguousarray(x["ep_acc"], np.float32)))
-                self._ep_total = np.array(x["ep_total"], np.float64)
-            else:
-                self.ep_acc.zero_()
-                self._ep_total = dist_util.empty_episode_stats()
+        if self.episodes is not None:
+            self.episodes.load_checkpoint_state(x)
         if "es" not in x:
             return            # a model-only checkpoint (e.g. written by the reference): parameters and optimizer only
         if x["es"].shape[0] != self.N:
@@ -837,35 +491,28 @@ class HumanoidWalkingTask:
         `_capture(ctx, frame)` (view()): called after the reset (frame 0) and after every control step."""
         seconds = self.config.render_length_seconds if seconds is None else seconds
         T = max(1, int(round(seconds / self.config.ctrl_dt)))
-        key = (num_envs, T)
-        if getattr(self, "_valid", None) is None or self._valid[0] != key:
+        key, terms = (num_envs, T), self.terms
+        if self._valid is None or self._valid.key != key:
             vcfg = self.config.to_kbj(num_envs) if num_envs % self.config.batch_size == 0 else dataclasses.replace(self.config, batch_size=num_envs).to_kbj(num_envs)
             vcfg.rollout_len = T
             vcfg.gae_bootstrap_truncation = vcfg.gae_tail_value = 0      # validation never runs GAE: no tail pass, no carry copy
-            if self.command_term is not None:
+            if terms.command_term is not None:
                 vcfg.command_mode = 1
             vctx = B.Context(self.model_blob, vcfg, self.device.index or 0, torch.cuda.current_stream().cuda_stream)
-            self._valid = (key, vctx, CarryBuffers(num_envs, self.H, self.kcfg.depth, self.device, mirror=self.mirror),
-                           TrajBuffers(T, num_envs, self.H, self.kcfg.depth, self.device, mirror=self.mirror, reward_comps=True,
-                                       ld_actor=self.ld_actor, ld_critic=self.ld_critic))
+            self._valid = _Validation(key, vctx, CarryBuffers(num_envs, self.H, self.kcfg.depth, self.device, mirror=self.mirror),
+                                      TrajBuffers(T, num_envs, self.H, self.kcfg.depth, self.device, mirror=self.mirror, reward_comps=True,
+                                                  ld_actor=self.ld_actor, ld_critic=self.ld_critic))
         _, vctx, carry, tr = self._valid
         seed = self.config.seed + seed_offset
         carry.zero_()
         vctx.env_reset_all(seed, tr.actor_obs[0], tr.critic_obs[0], tr.aux[0])
-        if self.extra_resets:                   # the user's Reset terms shape the validation episodes as they shape the training ones
-            self._apply_resets(vctx, tr, 0, None, seed_offset)
-        if self.command_term is not None:       # the user's Command term drives the validation envs as it drives the training ones
-            from .traj_view import StepView
-            self._apply_command(vctx, tr, 0, StepView(tr.aux[0], tr.actor_obs[0], tr.critic_obs[0], tr.aux[0], self.model_blob),
-                                torch.ones(num_envs, dtype=torch.bool, device=self.device), seed_offset, all_fresh=True)
-        feeds = any(self.extra_obs)            # user observation terms that are network inputs drive the validation policy too
-        if feeds:
-            from .traj_view import StepView
-            self._observe_into_rows(tr, 0, StepView(tr.aux[0], tr.actor_obs[0], tr.critic_obs[0], tr.aux[0], self.model_blob))
+        # the user's Reset and Command terms shape and drive the validation episodes as they do the training ones; of the Observation terms
+        # only those that are network inputs matter here (they drive the validation policy too). The terms' step index is seed_offset + row.
+        feeds = any(self.extra_obs)
+        terms.run_hooks(vctx, tr, 0, seed_offset, [terms.apply_resets, terms.apply_command] + ([terms.observe_rows] if feeds else []))
         if _capture is not None:
             _capture(vctx, 0)
-        fused = _capture is None and not feeds and self.command_term is None and not self.extra_resets and not _stepwise
-        if fused:
+        if _capture is None and not feeds and terms.command_term is None and not terms.resets and not _stepwise:
             # no user term and nothing to capture between the steps: ONE kbj_rollout call in argmax mode (the same kernels, bit-identical to the
             # step-by-step loop below, ~3 x fewer host calls: 0.05 instead of 0.15 s for 64 envs x 500 steps). kbj_rollout takes its first
             # observation from row T (the previous rollout's last), so the reset rows move there first.
@@ -875,25 +522,17 @@ class HumanoidWalkingTask:
                 vctx.rollout(self.params, carry.c, seed, 0, tr.c)
             finally:
                 vctx.set_rollout_argmax(False)      # the cached context samples again whatever happened (the flag is context state, not a call argument)
-        for t in range(0 if not fused else T, T):
-            vctx.policy_step(self.params, tr.actor_obs[t], tr.critic_obs[t], carry.c, seed, t, True, tr.action[t], tr.logp[t], tr.value[t])
-            vctx.env_step(tr.action[t], tr.aux[t], tr.actor_obs[t + 1], tr.critic_obs[t + 1], tr.aux[t + 1])
-            if self.extra_resets:
-                self._apply_resets(vctx, tr, t + 1, tr.aux[t][:, L.AUX["DONE"]] != 0, seed_offset + t + 1)
-            if feeds:
-                self._observe_into_rows(tr, t + 1, StepView(tr.aux[t], tr.actor_obs[t + 1], tr.critic_obs[t + 1], tr.aux[t + 1], self.model_blob))
-            if self.command_term is not None:
-                self._apply_command(vctx, tr, t + 1, StepView(tr.aux[t], tr.actor_obs[t + 1], tr.critic_obs[t + 1], tr.aux[t + 1], self.model_blob),
-                                    tr.aux[t][:, L.AUX["DONE"]] != 0, seed_offset + t + 1)
-            vctx.carry_reset(carry.c, tr.aux[t].data_ptr() + 4 * L.AUX["DONE"], L.AUX["SIZE"])
+        else:
+            # NOT training's order (terminations, resets, command, observations): here the observations come BEFORE the command, so an Observation
+            # term that reads the command columns of the row being written sees the previous command where training shows it the new one.
+            # Kept as it is; unifying the two is a behaviour change of its own.
+            hooks = [terms.apply_resets] + ([terms.observe_rows] if feeds else []) + [terms.apply_command]
             if _capture is not None:
-                _capture(vctx, t + 1)
-        if not fused:
+                hooks.append(lambda s: _capture(vctx, s.row))
+            terms.run_steps(vctx, tr, carry, self.params, T, seed=seed, first_step=0, argmax=True, first_index=seed_offset, hooks=hooks)
             vctx.rewards(tr.aux, T, tr.reward, tr.comps)
-        if self.ep_acc is not None:     # the same kernel on the validation trajectory: every validation starts its episodes afresh
-            vacc = torch.zeros(num_envs, L.EACC["SIZE"], device=self.device)
-            vstats = torch.zeros(L.EPST["SIZE"], dtype=torch.float64, device=self.device)
-            vctx.episode_stats(tr.c, vacc, vstats)
+        if self.episodes is not None:   # the same kernel on the validation trajectory: every validation starts its episodes afresh
+            vstats = fresh_episode_stats(vctx, tr.c, num_envs, self.device)
         vctx.synchronize()
         done = tr.done
         fails, succ = float((done < 0).sum()), float((done > 0).sum())
@@ -901,7 +540,7 @@ class HumanoidWalkingTask:
                "valid/episode_length_s": float(T * num_envs / max(1.0, fails + succ + num_envs) * self.config.ctrl_dt), "valid/value_mean": float(tr.value.mean())}
         for name, v in zip(constants.REWARD_NAMES, tr.comps.mean(dim=(0, 1)).cpu().tolist()):
             out[f"valid/reward/{name}"] = v
-        if self.ep_acc is not None:
+        if self.episodes is not None:
             out.update(episode_stats_scalars(vstats.cpu().numpy(), self.config.ctrl_dt, "valid/episode/", terms=True))
         return out
 
@@ -909,9 +548,8 @@ class HumanoidWalkingTask:
         """Drop the cached validation / view context (its env rows, workspace and lanes). validate() builds it again on demand. Measured on
         MI355X (tools/validate_cliff.py, 8192 envs): keeping it costs the training iterations nothing (365.2 ms before the first validation,
         366.1 / 365.3 / 364.8 ms after a validation, a second one and a view), re-creating it costs 0.15 s per validation - so it stays cached."""
-        v = getattr(self, "_valid", None)
-        if v is not None:
-            v[1].close()
+        if self._valid is not None:
+            self._valid.ctx.close()
             self._valid = None
 
     def close(self):
@@ -933,7 +571,7 @@ class HumanoidWalkingTask:
             if frame == 0:
                 eps.append(ep.copy())
         stats = self.validate(num_envs, seconds, seed_offset, _capture=capture)
-        tr = self._valid[3]
+        tr = self._valid.traj
         T = len(frames) - 1
         rec = Recording(self.model_blob, np.stack(frames), eps[0], tr.aux[:T + 1, :, L.AUX["CMD"]:L.AUX["CMD"] + 16].cpu().numpy(), tr.reward[:T].cpu().numpy(),
                         tr.done[:T].cpu().numpy(), self.config.ctrl_dt, self.config.render_track_body_id,
@@ -1052,28 +690,3 @@ class HumanoidWalkingTask:
             logger.close()
         task.loop_stats = stats
         return task
-
-
-class ModelView:
-    """What convert.py:39-46 takes out of a checkpoint: `model.actor` with the leaves Actor.forward uses (train.py:847-941), as
-    numpy arrays under their equinox names, plus the carry layout convert.py:71-78 flattens."""
-
-    class _Net:
-        def __init__(self, leaves: dict, prefix: str, depth: int):
-            g = lambda k: leaves[f"{prefix}.{k}"]
-            self.input_proj = _Leaf(weight=g("input_proj.weight"), bias=g("input_proj.bias"))
-            self.rnns = tuple(_Leaf(weight_ih=g(f"rnns.{l}.weight_ih"), weight_hh=g(f"rnns.{l}.weight_hh"), bias=g(f"rnns.{l}.bias")) for l in range(depth))
-            self.output_proj = _Leaf(weight=g("output_proj.weight"), bias=g("output_proj.bias"))
-
-    def __init__(self, flat, hidden_size: int, depth: int = 2, extra_obs=(0, 0)):
-        self.hidden_size, self.depth = hidden_size, depth
-        leaves = dict(ckpt_io.split_leaves(flat, hidden_size, depth, extra_obs))
-        self.leaves = leaves
-        self.actor = ModelView._Net(leaves, "actor", depth)
-        self.critic = ModelView._Net(leaves, "critic", depth)
-        self.carry_size = depth * 2 * hidden_size + L.NU     # convert.py:71: flat (depth, 2, H) LSTM carry + 20 low-pass floats
-
-
-class _Leaf:
-    def __init__(self, **kw):
-        self.__dict__.update(kw)

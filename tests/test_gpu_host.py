@@ -914,6 +914,109 @@ def test_python_reset_terms():
         t.close()
 
 
+def _recording_terms(log, into=None):
+    """One neutral user term of each kind as HumanoidWalkingTask keywords; every call appends (kind, the seed of the generator it got, or None)."""
+    import torch
+
+    def termination(state, curriculum_level):
+        log.append(("termination", None))
+        return torch.zeros(state.N, device="cuda")
+
+    def reset(data, curriculum_level, rng):
+        log.append(("reset", rng.initial_seed()))
+        return data
+
+    class Command:
+        def initial_command(self, state, curriculum_level, rng):
+            log.append(("initial_command", rng.initial_seed()))
+            return torch.zeros(state.N, L.NCMD, device="cuda")
+
+        def __call__(self, prev_command, state, curriculum_level, rng):
+            log.append(("command", rng.initial_seed()))
+            return prev_command
+
+    class Observation:
+        def observe(self, state, curriculum_level, rng):
+            log.append(("observation", None if rng is None else rng.initial_seed()))
+            return torch.zeros(state.N, 1, device="cuda")
+
+    return dict(extra_terminations={"never": termination}, extra_resets=[reset], command=Command(),
+                extra_observations={"zero": (Observation(), into)})
+
+
+_SEED, _T = 4, 3          # _small()'s seed (rank 0), and T of rollout_length_seconds = 0.06
+
+
+def _command_seed(step_index):
+    return (_SEED * 2654435761 + step_index * 40503 + 0) & 0x7FFFFFFFFFFFFFFF
+
+
+def _reset_seed(step_index):
+    return (_SEED * 2246822519 + step_index * 3266489917 + 0) & 0x7FFFFFFFFFFFFFFF
+
+
+def test_user_term_order_and_generator_seeds_in_training():
+    """The step-wise rollout calls the user terms as terminations -> resets -> command -> observations after every control step, resets ->
+    command -> observations on row 0 of the FIRST rollout only, and seeds the generators of step `iteration * T + row` as written above."""
+    from kbot_joystick_amd.host.task import HumanoidWalkingTask
+    log = []
+    task = HumanoidWalkingTask(_small(rollout_length_seconds=0.06), **_recording_terms(log))
+    assert task.T == _T and log == []
+    task.rollout(); task.iteration += 1; task.rollout()
+    task.ctx.synchronize()
+
+    def step(k):
+        return [("termination", None), ("reset", _reset_seed(k)), ("initial_command", _command_seed(k)), ("command", _command_seed(k)), ("observation", None)]
+    expect = [("reset", _reset_seed(0)), ("initial_command", _command_seed(0)), ("observation", None)]
+    for iteration in range(2):                      # the second rollout has no prologue calls
+        for row in range(1, _T + 1):
+            expect += step(iteration * _T + row)
+    assert log == expect
+    task.close()
+
+
+def test_user_term_order_and_generator_seeds_in_validation():
+    """validate() calls the user terms as resets -> observations -> command (NOT training's order), the same on row 0 of every call, never
+    the termination terms, and an observation term only when it feeds the networks; generators are seeded for step `seed_offset + row`."""
+    from kbot_joystick_amd.host.task import HumanoidWalkingTask
+    log, off = [], 7919
+    task = HumanoidWalkingTask(_small(rollout_length_seconds=0.06, extra_actor_obs=1, extra_critic_obs=1), **_recording_terms(log, "both"))
+    for _ in range(2):                              # the row-0 prologue runs on every call
+        del log[:]
+        task.validate(num_envs=32, seconds=0.06)
+        expect = [("reset", _reset_seed(off)), ("initial_command", _command_seed(off)), ("observation", None)]
+        for row in range(1, _T + 1):
+            k = off + row
+            expect += [("reset", _reset_seed(k)), ("observation", None), ("initial_command", _command_seed(k)), ("command", _command_seed(k))]
+        assert log == expect
+    task.close()
+    unrouted = HumanoidWalkingTask(_small(rollout_length_seconds=0.06), **_recording_terms(log))
+    del log[:]
+    unrouted.validate(num_envs=32, seconds=0.06)
+    kinds = [kind for kind, _ in log]
+    assert kinds == ["reset", "initial_command"] + ["reset", "initial_command", "command"] * _T
+    unrouted.close()
+
+
+def test_stepwise_rollout_with_a_silent_term_equals_the_fused_one():
+    """A task whose only user term is a termination that never fires runs the step-wise loop; its trajectory and env rows are the fused
+    kbj_rollout's bit for bit, and the step-wise validation returns what the fused one returns."""
+    import torch
+    from kbot_joystick_amd.host.task import HumanoidWalkingTask
+    stock = HumanoidWalkingTask(_small(rollout_length_seconds=0.06))
+    user = HumanoidWalkingTask(_small(rollout_length_seconds=0.06), extra_terminations={"never": lambda state, level: torch.zeros(state.N, device="cuda")})
+    for it in range(2):
+        stock.rollout(); user.rollout()
+        torch.cuda.synchronize()
+        for name in ("aux", "actor_obs", "critic_obs", "action", "logp", "value", "reward"):
+            assert torch.equal(getattr(stock.traj, name), getattr(user.traj, name)), (it, name)
+        stock.iteration += 1; user.iteration += 1
+    es, eu = stock.ctx.env_get_state()[1], user.ctx.env_get_state()[1]
+    assert np.array_equal(es.view(np.uint32), eu.view(np.uint32))
+    assert user.validate(num_envs=32, seconds=0.2, _stepwise=True) == user.validate(num_envs=32, seconds=0.2)
+    stock.close(); user.close()
+
+
 def test_example_with_all_six_user_term_protocols_runs():
     """examples/custom_terms.py: a reward (per env on the ksim-shaped Trajectory), a termination (per env on physics_data names), a reset, an observation routed
     into the critic, and a command term, all written in the reference's protocols, train together."""

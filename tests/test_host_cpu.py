@@ -406,3 +406,41 @@ def test_reference_reward_classes_on_a_ksim_shaped_trajectory_match_the_oracle(m
     with pytest.raises(ValueError, match="record_state"):
         TJ.Trajectory(types.SimpleNamespace(aux=torch.zeros(2, 1, A["SIZE"]), qstate=None, action=torch.zeros(1, 1, 20), actor_obs=torch.zeros(2, 1, L.LD_ACTOR),
                                             critic_obs=torch.zeros(2, 1, L.LD_CRITIC)), 1, m)
+
+
+def test_host_state_is_declared_not_discovered():
+    """Every attribute of a host object is assigned in its __init__: nothing in host/ asks itself whether it has one."""
+    host = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "kbot-joystick_amd", "host")
+    files = sorted(glob.glob(os.path.join(host, "*.py")))
+    assert len(files) > 10
+    for path in files:
+        with open(path) as f:
+            assert 'getattr(self, "_' not in f.read(), path
+
+
+_ENV_FLAGS = {"episode_stats": "KBJ_EPISODE_STATS", "bootstrap_on_truncation": "KBJ_GAE_TRUNCATION", "bootstrap_tail_value": "KBJ_GAE_TAIL",
+              "overlap_allreduce": "KBJ_OVERLAP_ALLREDUCE", "deterministic": "KBJ_DETERMINISTIC", "gemm_bf16x3": "KBJ_GEMM_X3",
+              "global_advantage_stats": "KBJ_GLOBAL_ADV_STATS"}
+_ENV_STRINGS = {"solver": ("KBJ_SOLVER", "newton", "cg"), "allreduce": ("KBJ_ALLREDUCE", "per_step", "per_pass")}
+
+
+def test_config_defaults_follow_the_environment(monkeypatch):
+    """The config fields with an environment override: unset, "" and "0" give the off default, "1" switches a flag on, KBJ_SOLVER / KBJ_ALLREDUCE
+    carry their value; the environment is read when a config object is created, and an explicit argument wins."""
+    from kbot_joystick_amd.host.task import HumanoidWalkingTaskConfig, launch_config
+    names = list(_ENV_FLAGS.values()) + [v[0] for v in _ENV_STRINGS.values()]
+    for off in (None, "", "0"):
+        for name in names:
+            monkeypatch.delenv(name, raising=False) if off is None else monkeypatch.setenv(name, off)
+        for cfg in (HumanoidWalkingTaskConfig(), launch_config()):
+            assert all(getattr(cfg, field) is False for field in _ENV_FLAGS), off
+            assert all(getattr(cfg, field) == default for field, (_, default, _) in _ENV_STRINGS.items()), off
+    for field, name in _ENV_FLAGS.items():
+        monkeypatch.setenv(name, "1")
+        assert getattr(HumanoidWalkingTaskConfig(), field) is True and getattr(HumanoidWalkingTaskConfig(**{field: False}), field) is False
+        assert [f for f in _ENV_FLAGS if getattr(HumanoidWalkingTaskConfig(), f)] == [field]       # ... and nobody else's
+        monkeypatch.setenv(name, "0")
+    for field, (name, default, other) in _ENV_STRINGS.items():
+        monkeypatch.setenv(name, other)
+        assert getattr(HumanoidWalkingTaskConfig(), field) == other and getattr(HumanoidWalkingTaskConfig(**{field: default}), field) == default
+        monkeypatch.setenv(name, "")
