@@ -60,6 +60,15 @@ int kbj_env_reset_all(kbj_ctx* ctx, uint32_t seed, float* actor0_d, float* criti
  * (train.py:1091-1105, 1134-1144, 1155-1222, 1258-1269, 1775-1781).
  * action_d [N][20]; aux_t_d [N][72] row of this step (completed); *_next_d rows of step t+1. */
 int kbj_env_step(kbj_ctx* ctx, const float* action_d, float* aux_t_d, float* actor_next_d, float* critic_next_d, float* aux_next_d);
+/* kbj_env_step plus the TERMINAL critic rows (kbj_config.gae_terminal_value; the reference's PPO stack bootstraps a time-out from the value of the
+ * observation the episode ended in, which an env that resets in place never shows in row t+1): for every env whose episode ends in this step
+ * (aux_t DONE != 0), row n of critic_term_d [N][ld_critic] receives the critic's observation of the state as it was BEFORE the reset - the
+ * columns, expressions and derived data of a critic_next row (one device function writes both), the command of the ending episode, user and
+ * pad columns zero. Rows of envs that go on are NOT written. Everything kbj_env_step writes is written bit for bit as kbj_env_step writes it;
+ * the extra row draws no random number and moves no state. Its own kernels (env_step_term_kernel / env_step_term_cg_kernel): kbj_env_step's are
+ * untouched. Not together with an armed kbj_env_record_state (refused; the record is disarmed). */
+int kbj_env_step_terminal(kbj_ctx* ctx, const float* action_d, float* aux_t_d, float* actor_next_d, float* critic_next_d,
+                          float* aux_next_d, float* critic_term_d /* [N][ld_critic] */);
 /* One-shot: the NEXT kbj_env_step of this context also writes the step's state record (KBJ_QSTATE_*: qpos, qvel after the step and the
  * positions its last forward pass ran on) into qstate_t_d [N][KBJ_QSTATE_SIZE]. kbj_rollout does the same per step for kbj_traj.qstate_d;
  * this entry serves hosts that drive the steps themselves (user Termination / Observation / Command terms). NULL cancels. */
@@ -150,6 +159,17 @@ int kbj_carry_reset(kbj_ctx* ctx, kbj_carry* carry, const float* done_d, int don
  * kbj_traj.value_tail_d, BEFORE the update changes the parameters. */
 int kbj_critic_value(kbj_ctx* ctx, const float* params_d, const float* critic_obs_d, const kbj_carry* carry, float* value_d);
 
+/* The critic's value of the TERMINAL observations (kbj_config.gae_terminal_value), sparse: value_term_d[n] = 0.0f exactly where
+ * done_d[n * done_stride] <= 0 (running, or failed: a failure bootstraps from nothing); where it is > 0 (time-out, or a user term's +1) the critic's
+ * step - input projection of row n of critic_term_d [N][ld_critic], the LSTM layers from row n of carry->critic_hc_d, the value head - for that
+ * one row, as matrix-vector products on the vector units, one workgroup per env (csrc/kbj_terminal_value.h). All N entries are written by every
+ * call. Nothing else is written: carries and rows are read only. Call it between kbj_env_step_terminal of step t and kbj_carry_reset, when the
+ * critic's carry is the one kbj_policy_step of step t left. Parameters and carries in the caller's layout at its own hidden_size (any size
+ * kbj_create serves); works on every context, whatever its switches. Summation order differs from kbj_policy_step's matrix-core path: the same
+ * value to fp32 rounding, not bit for bit. */
+int kbj_critic_terminal_value(kbj_ctx* ctx, const float* params_d, const float* critic_term_d, const kbj_carry* carry,
+                              const float* done_d, int done_stride, float* value_term_d /* [N] */);
+
 /* ---- deployment, convert.py ------------------------------------------------------------------ */
 /* replaces: the two functions convert.py exports for the robot (convert.py:74-119), served from the parameter vector itself. The deployed
  * function takes RAW sensor values and one FLAT carry per row, not the packed 68-float rows and plane carries of kbj_policy_step; it runs the
@@ -205,6 +225,14 @@ typedef struct kbj_traj {
  * traj->value_tail_d it also runs the critic once more, on observation row T with a COPY of the carries the last carry reset left (the
  * caller's carries do not advance), with the rollout's parameters: exactly kbj_critic_value below. */
 int kbj_rollout(kbj_ctx* ctx, const float* params_d, kbj_carry* carry, uint32_t seed, uint32_t first_step_index, kbj_traj* traj);
+/* The buffer of terminal values, value_term_d [T][N] (kbj_config.gae_terminal_value; NULL unsets it): the following kbj_rollout calls of this
+ * context write it, the following kbj_gae calls read it (hosts that drive the steps themselves fill row t with kbj_critic_terminal_value). A
+ * context setting like kbj_set_advantage_sums, because kbj_traj cannot grow. With the switch on every step of kbj_rollout becomes (policy_step,
+ * env_step_terminal, critic_terminal_value, carry_reset): the env phase runs its terminal form into a scratch of the context (allocated with
+ * the switch on only), the sparse value kernel runs on the critic's lane in front of the critic's carry reset and writes row t. With the switch
+ * on and no buffer set, kbj_rollout and kbj_gae fail before launching anything and the context stays usable; so does kbj_rollout with
+ * traj->qstate_d (no env kernel writes both the state record and the terminal rows). Ignored with the switch off. */
+int kbj_set_terminal_values(kbj_ctx* ctx, float* value_term_d);
 
 /* replaces: `argmax=True` of sample_action during ksim's validation rollouts (train.py:1564, valid_every_n_steps train.py:1789): the following
  * kbj_rollout calls of this context act with the distribution's mode (the filtered mean) instead of a sample; the stored log-probs are those of the
@@ -232,16 +260,20 @@ int kbj_episode_stats(kbj_ctx* ctx, const kbj_traj* traj, float* acc_d, double* 
  * Per env n, for t = T-1 .. 0, with d = aux[t][n][KBJ_AUX_DONE], v = value[t][n], r = reward[t][n] and A_T = 0:
  *   d < 0, or d > 0 with gae_bootstrap_truncation == 0:  delta = r - v                          A_t = delta   (terminal: the chain is cut)
  *   d > 0 with gae_bootstrap_truncation == 1:            delta = r + gamma v - v                A_t = delta   (truncation: cut, but bootstrapped)
+ *   d > 0 with gae_terminal_value == 1:                  delta = r + gamma value_term[t][n] - v A_t = delta   (the same, from the terminal observation's value)
  *   d == 0, t < T-1:                                     delta = r + gamma value[t+1][n] - v    A_t = delta + gamma lam A_{t+1}
  *   d == 0, t == T-1:                                    delta = r + gamma vn - v               A_t = delta
  *                                                        vn = traj->value_tail_d[n] if gae_tail_value == 1, else v
  *   adv = A_t, target = A_t + v.
- * Both switches are kbj_config fields, default 0 (this build's conventions: every non-zero DONE is terminal, V_T := V_{T-1}); with both at 0
- * the kernel of the earlier releases runs, bit for bit. At a truncation v stands in for the value of the terminal observation, which is never
- * recorded (the env kernel resets in place: observation row t+1 already belongs to the next episode) - so a truncation in the LAST row
+ * The switches are kbj_config fields, default 0 (this build's conventions: every non-zero DONE is terminal, V_T := V_{T-1}); with all at 0
+ * the kernel of the earlier releases runs, bit for bit, and with gae_terminal_value at 0 the kernels of the two older switches do. At a
+ * truncation v stands in for the value of the terminal observation, which observation row t+1 never shows (the env kernel resets in place:
+ * that row already belongs to the next episode), unless gae_terminal_value = 1 (needs gae_bootstrap_truncation = 1): then value_term, the
+ * [T][N] buffer of kbj_set_terminal_values, holds the critic's value of that observation (kbj_rollout / kbj_critic_terminal_value) and
+ * stands there instead; without a buffer set the call fails like the NULL value_tail_d below. Either way a truncation in the LAST row
  * follows the truncation rule, not the tail rule (row T is a post-reset observation there). A user Termination term that writes +1 into the
  * DONE column gets the same treatment. gae_tail_value == 1 with traj->value_tail_d == NULL is an error: nothing is launched, the context
- * stays usable. tests/gae_ref.py restates this table in float64. */
+ * stays usable. tests/gae_ref.py restates this table in float64, tests/gae_terminal_ref.py its gae_terminal_value row. */
 int kbj_gae(kbj_ctx* ctx, const kbj_traj* traj, float* adv_d, float* target_d);
 /* replaces: the loss/grad of one minibatch: get_ppo_variables under grad (BPTT through T LSTM steps,
  * train.py:1435-1524) + ksim's clipped PPO loss. env_idx_d [B] int32 env indices of the minibatch.

@@ -191,7 +191,11 @@ typedef struct kbj_config {
   /* terrain ("sine" scene, train.py:1081; the surface is this build's own definition):
    * z = terrain_amp * sin(2 pi x / terrain_wavelength) * sin(2 pi y / terrain_wavelength); terrain_amp = 0 is the plane z = 0 */
   float terrain_amp, terrain_wavelength;
-  float reserved_f[4];
+  int32_t gae_terminal_value; /* kbj_gae at a TRUNCATION once gae_bootstrap_truncation = 1: 0 (default) = bootstrap from V(s_t); 1 = from the critic's value of
+                                the TERMINAL observation - the state the episode ended in, before the reset - which kbj_rollout / kbj_env_step_terminal +
+                                kbj_critic_terminal_value record into the buffer of kbj_set_terminal_values. 1 with gae_bootstrap_truncation = 0 is refused.
+                                (One word of the former reserved_f[4]: the struct's size and every other offset are unchanged.) */
+  float reserved_f[3];
   /* reward stack (train.py:1224-1256): the scale of every term in KBJ_REW_* order, then the constructor arguments the reference
    * passes to its reward classes (error scales, heights, grace period, touchdown penalty). User-editable like the reference's
    * get_rewards(); a scale of 0 switches a term off. */

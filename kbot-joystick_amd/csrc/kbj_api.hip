@@ -69,6 +69,11 @@ int kbj_check_config(const kbj_config* cfg, char* why, size_t why_bytes) {
   if (cfg->gae_tail_value != 0 && cfg->gae_tail_value != 1)
     return fail("gae_tail_value must be 0 (V_T := V_{T-1}) or 1 (V_T = the critic's value of observation row T, kbj_traj.value_tail_d), not " +
                 std::to_string(cfg->gae_tail_value));
+  if (cfg->gae_terminal_value != 0 && cfg->gae_terminal_value != 1)
+    return fail("gae_terminal_value must be 0 (a truncation bootstraps from V(s_t)) or 1 (from the critic's value of the terminal observation, kbj_set_terminal_values), not " +
+                std::to_string(cfg->gae_terminal_value));
+  if (cfg->gae_terminal_value == 1 && cfg->gae_bootstrap_truncation == 0)
+    return fail("gae_terminal_value = 1 needs gae_bootstrap_truncation = 1: it chooses what stands for the terminal value once truncations bootstrap");
   const unsigned long long lim = 1ull << 31;
   const unsigned long long Hp = (unsigned long long)((cfg->hidden_size + 63) / 64 * 64), T = (unsigned long long)cfg->rollout_len;
   const unsigned long long B = (unsigned long long)(cfg->batch_size > 0 ? cfg->batch_size : cfg->num_envs), N = (unsigned long long)cfg->num_envs;
@@ -153,6 +158,7 @@ int kbj_create(kbj_ctx** out, const void* model_blob, size_t model_bytes, const 
   KBJ_TRY(hipEventCreateWithFlags(&ctx->ev_prefetch, hipEventDisableTiming));
   KBJ_TRY(hipEventCreateWithFlags(&ctx->ev_obs, hipEventDisableTiming));
   KBJ_TRY(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+  KBJ_TRY(hipEventCreateWithFlags(&ctx->ev_term, hipEventDisableTiming));
   KBJ_TRY(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
 #undef KBJ_TRY
   if (kbj_nn_create(ctx) != 0) { std::string msg = ctx->error; kbj_destroy(ctx); return kbj_fail(nullptr, msg); }
@@ -180,6 +186,7 @@ int kbj_destroy(kbj_ctx* ctx) {
   if (ctx->ev_prefetch) hipEventDestroy(ctx->ev_prefetch);
   if (ctx->ev_obs) hipEventDestroy(ctx->ev_obs);
   if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
+  if (ctx->ev_term) hipEventDestroy(ctx->ev_term);
   if (ctx->ev_join) hipEventDestroy(ctx->ev_join);
   if (ctx->stream2) hipStreamDestroy(ctx->stream2);
   for (int n = 0; n < 2; ++n) {

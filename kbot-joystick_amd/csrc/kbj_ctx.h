@@ -70,6 +70,7 @@ struct kbj_ctx {
   hipEvent_t ev_obs = nullptr;                // the critic's gathered observation rows are in place (side lane, kbj_nn.hip Update::input_projections)
   hipEvent_t ev_prefetch = nullptr;           // kbj_ppo_prefetch: the next minibatch's head gathers are done
   hipEvent_t ev_small = nullptr;              // the minibatch's small gathers / clears on the actor's side lane are done (kbj_nn.hip Update::gathers)
+  hipEvent_t ev_term = nullptr;               // kbj_rollout with kbj_config.gae_terminal_value: the critic lane's terminal-value kernel of a step has read the terminal scratch (RolloutPlan::ev_term)
   hipEvent_t ev_actor_grad = nullptr;         // recorded by kbj_ppo_grad once the ACTOR's slice of the gradient is final (kbj_stream_wait_actor_grad)
   hipEvent_t ev_critic_loss = nullptr;        // kbj_ppo_grad without the fused critic head: the critic lane's loss half is queued (UpdatePlan::ev_critic_loss)
   kbj_model model_h;

@@ -142,10 +142,12 @@ __global__ __launch_bounds__(256) void env_set_command_kernel(int N, int lda, in
 // REC: the form that also writes the per-step state record (kbj_traj.qstate_d / kbj_env_record_state). The default rollout runs the other
 // one, whose code is exactly the kernel without the feature (two more pointers live through the substep loop cost 2 VGPR / 8 SGPR spills);
 // the two are separate __global__ functions so that the hot kernel keeps its name in every profile.
-template <bool REC, bool CG>
+// TERM: the form that also writes the terminal critic row of the envs whose episode ends in this step (kbj_env_step_terminal; task_step's
+// critic_term), stamped out the same way: the four kernels without it pass a constant null pointer and carry none of it.
+template <bool REC, bool CG, bool TERM = false>
 __device__ __forceinline__ void env_step_body(const kbj_model* __restrict__ m, const kbj_config* __restrict__ c, const float* __restrict__ mc, const PhysConst* __restrict__ pcp, uint32_t seed,
                                               float* __restrict__ ep, float* __restrict__ es, const float* __restrict__ action,
-                                              float* aux_t, float* actor_next, float* critic_next, float* aux_next, int env0, float* qstate_t) {
+                                              float* aux_t, float* actor_next, float* critic_next, float* aux_next, int env0, float* qstate_t, float* critic_term = nullptr) {
   __shared__ KbjShared S;
   const int env = env0 + blockIdx.x;   // a launch covers the env range [env0, env0 + gridDim.x)
   PFOR(k, (int)(sizeof(KbjModelLds) / sizeof(float))) reinterpret_cast<float*>(&S.mc)[k] = mc[k];
@@ -159,7 +161,7 @@ __device__ __forceinline__ void env_step_body(const kbj_model* __restrict__ m, c
   KBJ_STAMP(18);
   task_step<CG>(S, *m, *c, pc, rng, action + (size_t)env * KBJ_NU, aux_t + (size_t)env * KBJ_AUX_SIZE, actor_next + (size_t)env * KBJ_LD_OF(KBJ_NOBS_ACTOR + c->extra_obs_actor),
             critic_next + (size_t)env * KBJ_LD_OF(KBJ_NOBS_CRITIC + c->extra_obs_critic), aux_next + (size_t)env * KBJ_AUX_SIZE,
-            REC ? qstate_t + (size_t)env * KBJ_QSTATE_SIZE : nullptr);
+            REC ? qstate_t + (size_t)env * KBJ_QSTATE_SIZE : nullptr, TERM ? critic_term + (size_t)env * KBJ_LD_OF(KBJ_NOBS_CRITIC + c->extra_obs_critic) : nullptr);
   if (S.done) PFOR(k, KBJ_EP_SIZE) ep[(size_t)env * KBJ_EP_SIZE + k] = S.ep[k];
   PFOR(k, KBJ_ES_SIZE) es[(size_t)env * KBJ_ES_SIZE + k] = S.es[k];
   KBJ_STAMP(19);
@@ -184,6 +186,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(KBJ_ENV_NUM_VGPR
                                                       float* __restrict__ ep, float* __restrict__ es, const float* __restrict__ action,
                                                       float* aux_t, float* actor_next, float* critic_next, float* aux_next, int env0, float* qstate_t) {
   env_step_body<true, true>(m, c, mc, pcp, seed, ep, es, action, aux_t, actor_next, critic_next, aux_next, env0, qstate_t);
+}
+// the step with the terminal critic rows (kbj_env_step_terminal), both solvers: critic_term [N][ld_critic], rows of envs that go on untouched
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(KBJ_ENV_NUM_VGPR))) void env_step_term_kernel(const kbj_model* __restrict__ m, const kbj_config* __restrict__ c, const float* __restrict__ mc, const PhysConst* __restrict__ pcp, uint32_t seed,
+                                                      float* __restrict__ ep, float* __restrict__ es, const float* __restrict__ action,
+                                                      float* aux_t, float* actor_next, float* critic_next, float* aux_next, int env0, float* critic_term) {
+  env_step_body<false, false, true>(m, c, mc, pcp, seed, ep, es, action, aux_t, actor_next, critic_next, aux_next, env0, nullptr, critic_term);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(KBJ_ENV_NUM_VGPR))) void env_step_term_cg_kernel(const kbj_model* __restrict__ m, const kbj_config* __restrict__ c, const float* __restrict__ mc, const PhysConst* __restrict__ pcp, uint32_t seed,
+                                                      float* __restrict__ ep, float* __restrict__ es, const float* __restrict__ action,
+                                                      float* aux_t, float* actor_next, float* critic_next, float* aux_next, int env0, float* critic_term) {
+  env_step_body<false, true, true>(m, c, mc, pcp, seed, ep, es, action, aux_t, actor_next, critic_next, aux_next, env0, nullptr, critic_term);
 }
 // the kernel of the context's solver: NAME_kernel (Newton, the default) or NAME_cg_kernel
 #define KBJ_LAUNCH_SOLVER(ctx, NAME, ...) do { \
@@ -312,12 +325,17 @@ __global__ void init_reward_carry_kernel(float* carry, int N) {
 
 void kbj_nn_drop_prefetch(kbj_ctx* ctx);   // kbj_nn.hip: a pending next-minibatch hint dies with the trajectory contents it was made from
 
-// one control step of all envs on stream s (the kernels' first-env parameter: 0)
+// one control step of all envs on stream s (the kernels' first-env parameter: 0). qstate_t_d: the form with the state record; critic_term_d: the
+// form with the terminal critic rows. Both at once is not served (no caller needs it: kbj_rollout and kbj_env_step_terminal refuse it)
 int kbj_env_step_all(kbj_ctx* ctx, hipStream_t s, const float* action_d, float* aux_t_d, float* actor_next_d, float* critic_next_d, float* aux_next_d,
-                     float* qstate_t_d) {
+                     float* qstate_t_d, float* critic_term_d) {
+  if (qstate_t_d && critic_term_d) return kbj_fail(ctx, "env step: the state record and the terminal critic rows cannot be written by one step");
   KbjKernelTimer timer(s, KBJ_KIND_ENV_STEP, 0.0);
   const int N = ctx->cfg_h.num_envs;
-  if (qstate_t_d)
+  if (critic_term_d)
+    KBJ_LAUNCH_SOLVER(ctx, env_step_term, dim3(N), dim3(64), 0, s, ctx->model_d, ctx->cfg_d, ctx->mc_d, (const PhysConst*)ctx->pc_d, ctx->seed, ctx->ep_d, ctx->es_d, action_d, aux_t_d,
+                       actor_next_d, critic_next_d, aux_next_d, 0, critic_term_d);
+  else if (qstate_t_d)
     KBJ_LAUNCH_SOLVER(ctx, env_step_record, dim3(N), dim3(64), 0, s, ctx->model_d, ctx->cfg_d, ctx->mc_d, (const PhysConst*)ctx->pc_d, ctx->seed, ctx->ep_d, ctx->es_d, action_d, aux_t_d,
                        actor_next_d, critic_next_d, aux_next_d, 0, qstate_t_d);
   else
@@ -352,7 +370,19 @@ int kbj_env_step(kbj_ctx* ctx, const float* action_d, float* aux_t_d, float* act
   if (!action_d || !aux_t_d || !actor_next_d || !critic_next_d || !aux_next_d) return kbj_fail(ctx, "kbj_env_step: null pointer");
   KBJ_HIP(ctx, hipSetDevice(ctx->device));
   kbj_nn_drop_prefetch(ctx);
-  return kbj_env_step_all(ctx, ctx->stream, action_d, aux_t_d, actor_next_d, critic_next_d, aux_next_d, q);
+  return kbj_env_step_all(ctx, ctx->stream, action_d, aux_t_d, actor_next_d, critic_next_d, aux_next_d, q, nullptr);
+}
+
+int kbj_env_step_terminal(kbj_ctx* ctx, const float* action_d, float* aux_t_d, float* actor_next_d, float* critic_next_d, float* aux_next_d, float* critic_term_d) {
+  if (!ctx) return kbj_fail(nullptr, "kbj_env_step_terminal: null ctx");
+  float* q = ctx->qstate_next;
+  ctx->qstate_next = nullptr;     // one-shot, consumed by this call as by kbj_env_step
+  if (!action_d || !aux_t_d || !actor_next_d || !critic_next_d || !aux_next_d || !critic_term_d) return kbj_fail(ctx, "kbj_env_step_terminal: null pointer");
+  if (q) return kbj_fail(ctx, "kbj_env_step_terminal: a state record is armed (kbj_env_record_state); no step kernel writes both the record and the terminal rows - "
+                              "record with kbj_env_step, or drop the record");
+  KBJ_HIP(ctx, hipSetDevice(ctx->device));
+  kbj_nn_drop_prefetch(ctx);
+  return kbj_env_step_all(ctx, ctx->stream, action_d, aux_t_d, actor_next_d, critic_next_d, aux_next_d, nullptr, critic_term_d);
 }
 
 int kbj_env_record_state(kbj_ctx* ctx, float* qstate_t_d) {

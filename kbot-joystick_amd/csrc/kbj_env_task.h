@@ -199,55 +199,32 @@ KBJ_DEV float task_com_distance(const KbjShared& S) {
   return sqrtf((cx - S.com2[0]) * (cx - S.com2[0]) + (cy - S.com2[1]) * (cy - S.com2[1]));
 }
 
-// observation packing (train.py:1329-1433) from the derived data of the last forward pass; rows live in HBM
-KBJ_DEV void task_write_obs(KbjShared& S, const kbj_model& m, const kbj_config& c, const Rng& rng, float* actor, float* critic, float* aux) {
-  float* es = S.es;
-  uint32_t st = f2u(es[KBJ_ES_STEP]);
-  bool noise = c.enable_noise != 0;
-  const float* cmd = es + KBJ_ES_CMD;
-  float zc = sqrtf(cmd[0] * cmd[0] + cmd[1] * cmd[1] + cmd[2] * cmd[2]) < 1e-3f ? 1.0f : 0.0f;
+// the critic's columns of a packed observation row (train.py:1381-1433) from the derived data of the last forward pass, the state as it is and
+// `cmd` (zc: its zero-command flag); user columns and the pad to the row stride are zeroed. Reads only: the env state does not move, nothing is
+// drawn. task_write_obs calls it for the critic's half of every observation row; task_step calls it on the state an episode ENDS in, before the
+// reset, for the terminal row (kbj_env_step_terminal) - so both rows come from the same expressions. The caller synchronises.
+KBJ_DEV void task_write_critic(const KbjShared& S, const kbj_model& m, const kbj_config& c, const float* cmd, float zc, float* critic) {
+  const float* es = S.es;
   PFOR(u, NU) {
     float range = fmaxf(m.joint_bias[u] - m.joint_lo[u], m.joint_hi[u] - m.joint_bias[u]);
     float q = es[KBJ_ES_QPOS + 7 + u], v = es[KBJ_ES_QVEL + 6 + u];
-    float qn = q + S.ep[KBJ_EP_JPBIAS + u] + (noise ? rng_uniform(rng, KBJ_RNG_OBS_NOISE, st, u, -c.jpos_noise, c.jpos_noise) : 0.0f);
-    float vn = v + (noise ? rng_uniform(rng, KBJ_RNG_OBS_NOISE, st, 20 + u, -c.jvel_noise, c.jvel_noise) : 0.0f);
-    actor[KBJ_OBS_JPOS + u] = (qn - m.joint_bias[u]) / range; actor[KBJ_OBS_JVEL + u] = vn / KBJ_OBS_JVEL_DIV;
     critic[KBJ_OBS_JPOS + u] = (q - m.joint_bias[u]) / range; critic[KBJ_OBS_JVEL + u] = v / KBJ_OBS_JVEL_DIV;
     critic[KBJ_OBS_ACTFRC + u] = S.qfrc_act[6 + u] / KBJ_OBS_ACTFRC_DIV;
   }
-  // The four one-lane jobs below are different code, so the wavefront runs them one after the other: keep each short. The six normal
-  // draws of the imu noise (Box-Muller: threefry + log + cos + sqrt, ~150 vector instructions each) run on six lanes at once.
-  float* nrm6 = S.u.cfrc[0];     // scratch: the RNE buffers are dead once the solver has run
-  PFOR(w, 6) nrm6[w] = noise ? rng_normal(rng, KBJ_RNG_OBS_NOISE, st, 40 + w) : 0.0f;    // 40..42 gyro, 43..45 projected gravity
-  KBJ_SYNC();
-  PFOR(w, 4) {
-    if (w == 0) {  // lagged / biased / noisy projected gravity for the actor, clean one for the critic
-      float lag = S.ep[KBJ_EP_PGLAG], pgn[3], o[5];
-      for (int k = 0; k < 3; ++k) {
-        float pgl = lag * es[KBJ_ES_PGLAG + k] + (1 - lag) * S.pg[k];
-        es[KBJ_ES_PGLAG + k] = pgl;
-        pgn[k] = pgl + S.ep[KBJ_EP_PGBIAS + k] + (noise ? c.pg_noise_std * nrm6[3 + k] : 0.0f);
-      }
-      encode_pg(pgn, o);
-      for (int k = 0; k < 5; ++k) actor[KBJ_OBS_PG + k] = o[k];
-      for (int k = 0; k < 3; ++k) {
-        actor[KBJ_OBS_GYRO + k] = S.gyro[k] + (noise ? c.gyro_noise_std * nrm6[k] : 0.0f);
-        critic[KBJ_OBS_GYRO + k] = S.gyro[k];
-      }
-    } else if (w == 1) {
+  PFOR(w, 2) {   // two one-lane jobs of different code: the wavefront runs them one after the other
+    if (w == 0) {
       float o[5];
       encode_pg(S.pg, o);
       for (int k = 0; k < 5; ++k) critic[KBJ_OBS_PG + k] = o[k];
-      actor[KBJ_OBS_ZEROCMD] = zc; critic[KBJ_OBS_ZEROCMD] = zc;
+      for (int k = 0; k < 3; ++k) critic[KBJ_OBS_GYRO + k] = S.gyro[k];
+      critic[KBJ_OBS_ZEROCMD] = zc;
       // behind the reference's columns: user observation slots (the host fills them after the step) and the pad to the 16-byte row stride
-      for (int k = KBJ_NOBS_ACTOR; k < KBJ_LD_OF(KBJ_NOBS_ACTOR + c.extra_obs_actor); ++k) actor[k] = 0;
       for (int k = KBJ_NOBS_CRITIC; k < KBJ_LD_OF(KBJ_NOBS_CRITIC + c.extra_obs_critic); ++k) critic[k] = 0;
       critic[KBJ_OBS_TOUCH] = S.touch[0]; critic[KBJ_OBS_TOUCH + 1] = S.touch[1];
-      aux[KBJ_AUX_TOUCH] = S.touch[0]; aux[KBJ_AUX_TOUCH + 1] = S.touch[1];
       for (int k = 0; k < 3; ++k) { critic[KBJ_OBS_BASEPOS + k] = es[KBJ_ES_QPOS + k]; critic[KBJ_OBS_LINVEL + k] = es[KBJ_ES_QVEL + k]; critic[KBJ_OBS_ANGVEL + k] = es[KBJ_ES_QVEL + 3 + k]; }
       for (int k = 0; k < 4; ++k) critic[KBJ_OBS_BASEQUAT + k] = es[KBJ_ES_QPOS + 3 + k];
       critic[KBJ_OBS_HEIGHT] = S.xpos[1][2];  // BaseHeightObservation (train.py:706-707)
-    } else if (w == 2) {  // FeetPositionObservation (train.py:682-699): foot offsets in the base's yaw frame
+    } else {  // FeetPositionObservation (train.py:682-699): foot offsets in the base's yaw frame
       // the reference goes quat -> euler -> (0, 0, yaw) -> quat -> rotate; the yaw rotation is cos / sin of atan2(sn, cs), i.e. (cs, sn)
       // normalised - no trigonometry needed
       const float* q = S.xquat[1];
@@ -261,11 +238,53 @@ KBJ_DEV void task_write_obs(KbjShared& S, const kbj_model& m, const kbj_config& 
         critic[KBJ_OBS_FEETPOS + 3 * f + 1] = cy * rel[1] - sy * rel[0];
         critic[KBJ_OBS_FEETPOS + 3 * f + 2] = rel[2];
       }
-    } else aux[KBJ_AUX_COMDIST] = task_com_distance(S);
+    }
   }
-  PFOR(k, KBJ_NCMD) { actor[KBJ_OBS_CMD + k] = cmd[k]; critic[KBJ_OBS_CMD + k] = cmd[k]; aux[KBJ_AUX_CMD + k] = cmd[k]; }
+  PFOR(k, KBJ_NCMD) critic[KBJ_OBS_CMD + k] = cmd[k];
   PFOR(k, 230) critic[KBJ_OBS_CINERT + k] = S.cinert[1 + k / 10][k % 10];
   PFOR(k, 138) critic[KBJ_OBS_CVEL + k] = S.cvel[1 + k / 6][k % 6];
+}
+
+// observation packing (train.py:1329-1433) from the derived data of the last forward pass; rows live in HBM. The actor's row and the aux
+// record here (they draw the observation noise and advance the lagged projected gravity), the critic's row in task_write_critic.
+KBJ_DEV void task_write_obs(KbjShared& S, const kbj_model& m, const kbj_config& c, const Rng& rng, float* actor, float* critic, float* aux) {
+  float* es = S.es;
+  uint32_t st = f2u(es[KBJ_ES_STEP]);
+  bool noise = c.enable_noise != 0;
+  const float* cmd = es + KBJ_ES_CMD;
+  float zc = sqrtf(cmd[0] * cmd[0] + cmd[1] * cmd[1] + cmd[2] * cmd[2]) < 1e-3f ? 1.0f : 0.0f;
+  PFOR(u, NU) {
+    float range = fmaxf(m.joint_bias[u] - m.joint_lo[u], m.joint_hi[u] - m.joint_bias[u]);
+    float q = es[KBJ_ES_QPOS + 7 + u], v = es[KBJ_ES_QVEL + 6 + u];
+    float qn = q + S.ep[KBJ_EP_JPBIAS + u] + (noise ? rng_uniform(rng, KBJ_RNG_OBS_NOISE, st, u, -c.jpos_noise, c.jpos_noise) : 0.0f);
+    float vn = v + (noise ? rng_uniform(rng, KBJ_RNG_OBS_NOISE, st, 20 + u, -c.jvel_noise, c.jvel_noise) : 0.0f);
+    actor[KBJ_OBS_JPOS + u] = (qn - m.joint_bias[u]) / range; actor[KBJ_OBS_JVEL + u] = vn / KBJ_OBS_JVEL_DIV;
+  }
+  // The one-lane jobs below are different code, so the wavefront runs them one after the other: keep each short. The six normal
+  // draws of the imu noise (Box-Muller: threefry + log + cos + sqrt, ~150 vector instructions each) run on six lanes at once.
+  float* nrm6 = S.u.cfrc[0];     // scratch: the RNE buffers are dead once the solver has run
+  PFOR(w, 6) nrm6[w] = noise ? rng_normal(rng, KBJ_RNG_OBS_NOISE, st, 40 + w) : 0.0f;    // 40..42 gyro, 43..45 projected gravity
+  KBJ_SYNC();
+  PFOR(w, 3) {
+    if (w == 0) {  // lagged / biased / noisy projected gravity for the actor
+      float lag = S.ep[KBJ_EP_PGLAG], pgn[3], o[5];
+      for (int k = 0; k < 3; ++k) {
+        float pgl = lag * es[KBJ_ES_PGLAG + k] + (1 - lag) * S.pg[k];
+        es[KBJ_ES_PGLAG + k] = pgl;
+        pgn[k] = pgl + S.ep[KBJ_EP_PGBIAS + k] + (noise ? c.pg_noise_std * nrm6[3 + k] : 0.0f);
+      }
+      encode_pg(pgn, o);
+      for (int k = 0; k < 5; ++k) actor[KBJ_OBS_PG + k] = o[k];
+      for (int k = 0; k < 3; ++k) actor[KBJ_OBS_GYRO + k] = S.gyro[k] + (noise ? c.gyro_noise_std * nrm6[k] : 0.0f);
+    } else if (w == 1) {
+      actor[KBJ_OBS_ZEROCMD] = zc;
+      // behind the reference's columns: user observation slots (the host fills them after the step) and the pad to the 16-byte row stride
+      for (int k = KBJ_NOBS_ACTOR; k < KBJ_LD_OF(KBJ_NOBS_ACTOR + c.extra_obs_actor); ++k) actor[k] = 0;
+      aux[KBJ_AUX_TOUCH] = S.touch[0]; aux[KBJ_AUX_TOUCH + 1] = S.touch[1];
+    } else aux[KBJ_AUX_COMDIST] = task_com_distance(S);
+  }
+  PFOR(k, KBJ_NCMD) { actor[KBJ_OBS_CMD + k] = cmd[k]; aux[KBJ_AUX_CMD + k] = cmd[k]; }
+  task_write_critic(S, m, c, cmd, zc, critic);
   KBJ_SYNC();
 }
 
@@ -274,7 +293,8 @@ KBJ_DEV void task_write_obs(KbjShared& S, const kbj_model& m, const kbj_config& 
 // reset or command switch -> next observation.
 // CG: the constraint solver of every forward pass (kbj_env_phys.h phys_solve), a compile-time choice so that neither form carries the other.
 template <bool CG> KBJ_DEV void task_step(KbjShared& S, const kbj_model& m, const kbj_config& c, const PhysConst& pc, const Rng& rng, const float* action,
-                                          float* aux_t, float* actor_next, float* critic_next, float* aux_next, float* qstate = nullptr) {
+                                          float* aux_t, float* actor_next, float* critic_next, float* aux_next, float* qstate = nullptr,
+                                          float* critic_term = nullptr) {
   float* es = S.es;
   uint32_t st = f2u(es[KBJ_ES_STEP]);
   bool drop = rng_u01(rng, KBJ_RNG_DROP, st, 0) < c.drop_action_prob;
@@ -329,8 +349,16 @@ template <bool CG> KBJ_DEV void task_step(KbjShared& S, const kbj_model& m, cons
     aux_t[KBJ_AUX_DONE + 1] = 0;
   }
   KBJ_SYNC();
-  if (S.done) task_reset<CG>(S, m, c, pc, rng);
-  else {
+  if (S.done) {
+    // the terminal row (kbj_env_step_terminal): the critic's observation of the state the episode ended in, with the ending episode's command,
+    // before the reset replaces both (uniform branch: null unless the caller asks; rows of envs that go on are not written)
+    if (critic_term) {
+      const float* cmd = es + KBJ_ES_CMD;
+      task_write_critic(S, m, c, cmd, sqrtf(cmd[0] * cmd[0] + cmd[1] * cmd[1] + cmd[2] * cmd[2]) < 1e-3f ? 1.0f : 0.0f, critic_term);
+      KBJ_SYNC();
+    }
+    task_reset<CG>(S, m, c, pc, rng);
+  } else {
     PFOR(w, 1) {  // UnifiedCommand.__call__ (train.py:768-785)
       if (c.command_mode == 0 && rng_u01(rng, KBJ_RNG_COMMAND, st + 1, 0) < c.switch_prob) task_sample_command(m, c, rng, st + 1, 0, es + KBJ_ES_CMD);
       if (c.command_mode == 2) {   // the same with jax.random's key handling: rng_a, rng_b = split(rng); bernoulli(rng_a, switch_prob); initial_command(rng_b)
@@ -349,9 +377,9 @@ static inline void task_reset(KbjShared& S, const kbj_model& m, const kbj_config
   if (pc.cg) task_reset<true>(S, m, c, pc, rng); else task_reset<false>(S, m, c, pc, rng);
 }
 static inline void task_step(KbjShared& S, const kbj_model& m, const kbj_config& c, const PhysConst& pc, const Rng& rng, const float* action,
-                             float* aux_t, float* actor_next, float* critic_next, float* aux_next, float* qstate = nullptr) {
-  if (pc.cg) task_step<true>(S, m, c, pc, rng, action, aux_t, actor_next, critic_next, aux_next, qstate);
-  else task_step<false>(S, m, c, pc, rng, action, aux_t, actor_next, critic_next, aux_next, qstate);
+                             float* aux_t, float* actor_next, float* critic_next, float* aux_next, float* qstate = nullptr, float* critic_term = nullptr) {
+  if (pc.cg) task_step<true>(S, m, c, pc, rng, action, aux_t, actor_next, critic_next, aux_next, qstate, critic_term);
+  else task_step<false>(S, m, c, pc, rng, action, aux_t, actor_next, critic_next, aux_next, qstate, critic_term);
 }
 #endif
 

@@ -13,6 +13,7 @@
 #include "kbj_lstm_seq.h"
 #include "kbj_lstm_bwd16.h"
 #include "kbj_deploy.h"
+#include "kbj_terminal_value.h"
 
 using namespace kbj;
 
@@ -65,6 +66,9 @@ struct NnWs : ParamLayout {   // (the base: the layout at the kernels' H)
   float *rObsM[2] = {nullptr, nullptr};   // rollout: mirrored observation rows [N][ld]
   float* rH[4][MAXD] = {};                  // rollout: the h planes' ping-pong partners [N][H] per (net, layer)
   float* tail_hc = nullptr;                 // kbj_config.gae_tail_value: the critic carry copy [D][2][N][H] that kbj_critic_value / the rollout's tail pass steps instead of the caller's
+  // kbj_config.gae_terminal_value: the env step's terminal critic rows [N][ld_critic] (allocated with the switch on only) and the caller's
+  // [T][N] buffer of their values (kbj_set_terminal_values: kbj_rollout writes it, kbj_gae reads it)
+  float *term_rows = nullptr, *value_term = nullptr;
   float *y_m = nullptr, *sd_m = nullptr, *value_m = nullptr, *lpf0_m = nullptr, *dy = nullptr, *dy_m = nullptr, *dvalue_m = nullptr, *zeroR = nullptr;
   // training
   TrainBufs tb[4];
@@ -389,6 +393,7 @@ int nn_rollout_scratch(kbj_ctx* ctx, NnWs* w) {
     for (int l = 0; l < w->D; ++l) if (dalloc(ctx, *w, &w->rH[n][l], N * H)) return -1;
   }
   if (ctx->cfg_h.gae_tail_value && dalloc(ctx, *w, &w->tail_hc, 2 * (size_t)w->D * N * H)) return -1;
+  if (ctx->cfg_h.gae_terminal_value && dalloc(ctx, *w, &w->term_rows, N * (size_t)w->net[1].ld_obs)) return -1;
   if (dalloc(ctx, *w, &w->joint_bias_d, KBJ_NU)) return -1;
   if (hipMemcpy(w->joint_bias_d, ctx->model_h.joint_bias, KBJ_NU * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return kbj_fail(ctx, "hipMemcpy joint_bias");
   return 0;
@@ -508,7 +513,7 @@ void kbj_nn_destroy(kbj_ctx* ctx) {
 
 
 int kbj_env_step_all(kbj_ctx* ctx, hipStream_t s, const float* action_d, float* aux_t_d, float* actor_next_d, float* critic_next_d, float* aux_next_d,
-                     float* qstate_t_d);   // kbj_env.hip
+                     float* qstate_t_d, float* critic_term_d);   // kbj_env.hip
 
 namespace {
 
@@ -572,17 +577,26 @@ kbj_traj pad_traj_carry0(kbj_ctx* ctx, hipStream_t s, const kbj_traj& tr) {
 //   mirrored      its observation rows are mirrored first (train.py:1463-1481, 1555-1560)
 //   hc, lpf       its carries [D][2][N][H] and low-pass state [N][KBJ_NU] (null: the net has none) in the call's kbj_carry
 //   X, G, Out, obs_m, rH   its scratch rows and its h planes' partners: private to the net, lanes never share them
+//   terminal      between the env step and its carry reset the net values the terminal rows of the envs that timed out (the critic under
+//                 kbj_config.gae_terminal_value; Rollout::terminal_value)
 enum HeadKind {
   HEAD_SAMPLE,   // output projection + low-pass + sample + log-prob as one launch (the chain env -> actor -> env waits for it)
   HEAD_VALUE,    // output projection to the value, one launch
   HEAD_LPF,      // the mirrored actor only advances its low-pass state (no sample)
   HEAD_NONE      // the mirrored critic's value is only needed under the gradient; at rollout time only its carry advances
 };
-struct RolloutNet { hipStream_t lane; int type; bool step_kernel, folded0, mirrored; int tile; HeadKind head; float *hc, *lpf, *X, *G, *Out, *obs_m, **rH; };
+struct RolloutNet { hipStream_t lane; int type; bool step_kernel, folded0, mirrored, terminal; int tile; HeadKind head; float *hc, *lpf, *X, *G, *Out, *obs_m, **rH; };
 // the call
 //   serial   every net on the caller's stream: kbj_policy_step, kbj_critic_value, kbj_carry_reset; kbj_rollout under KBJ_ROLLOUT_PIPELINE=0
 //   side     the lane of the critic and the mirror branches (serial: the caller's stream)
-struct RolloutPlan { RolloutNet net[4]; int nnets; bool serial; hipStream_t side; };
+//   term_rows   kbj_config.gae_terminal_value: where the env phase writes the terminal critic rows [N][ld_critic] (its terminal form runs
+//               instead of the plain one); null with the switch off - then nothing of the terminal value is launched anywhere
+//   ev_term     the terminal rows are ONE scratch, rewritten by every env step on the caller's stream and read by the value kernel on the side
+//               lane - the only buffer the two lanes share that is not indexed by the step. So the side lane records this event behind the
+//               value kernel of step t and the caller's stream waits for it in front of env step t + 1 (Rollout::terminal_rows_free): however
+//               far the side lane lags, no env step overwrites rows that are still to be read. Null where there is nothing to order: the
+//               switch off, or a serial plan (one stream)
+struct RolloutPlan { RolloutNet net[4]; int nnets; bool serial; hipStream_t side; float* term_rows; hipEvent_t ev_term; };
 
 RolloutPlan rollout_plan(kbj_ctx* ctx, const kbj_carry& carry, bool serial) {
   NnWs& w = *ws_of(ctx); const Sched& sc = w.sched;
@@ -593,6 +607,8 @@ RolloutPlan rollout_plan(kbj_ctx* ctx, const kbj_carry& carry, bool serial) {
   // order). (A two-lane software pipeline over env halves existed until round 4: with 12 env wavefronts per CU no GEMM workgroup can be
   // co-resident, the lanes only alternated - gone.)
   p.side = serial ? ctx->stream : ctx->side[0];
+  p.term_rows = ctx->cfg_h.gae_terminal_value ? w.term_rows : nullptr;
+  p.ev_term = p.term_rows && !serial ? ctx->ev_term : nullptr;
   const HeadKind heads[4] = {HEAD_SAMPLE, HEAD_VALUE, HEAD_LPF, HEAD_NONE};
   float* const lpf[4] = {carry.lpf_d, nullptr, carry.lpf_mirror_d, nullptr};
   for (int n = 0; n < p.nnets; ++n) {
@@ -613,6 +629,9 @@ RolloutPlan rollout_plan(kbj_ctx* ctx, const kbj_carry& carry, bool serial) {
     // (W_ih0 b_in + b_0), as in kbj_ppo_grad (inside the layer-step kernel only: the GEMM + cell form keeps the projection)
     q.folded0 = q.step_kernel && sc.fold_actor && w.net[0].ld_obs == KBJ_LD_ACTOR;
     q.head = heads[n]; q.mirrored = n >= 2;
+    // The terminal value is the critic's (net 1), on its own lane: it needs the critic's carry as the step left it, so it sits in front of
+    // that net's carry reset, behind the hop that brings the env step's done flags and terminal rows over.
+    q.terminal = n == 1 && p.term_rows != nullptr;
     q.hc = carry_hc(carry, n); q.lpf = lpf[n];
     q.X = w.rX[n]; q.G = w.rG[n]; q.Out = w.rOut[n]; q.obs_m = q.mirrored ? w.rObsM[q.type] : nullptr; q.rH = w.rH[n];
   }
@@ -623,7 +642,19 @@ RolloutPlan rollout_plan(kbj_ctx* ctx, const kbj_carry& carry, bool serial) {
 struct StepRows {
   const float *actor_obs, *critic_obs; float *aux, *action, *logp, *value, *actor_next, *critic_next, *aux_next, *qstate;
   uint32_t step_index; int argmax, parity;   // parity: which copy of the step-kernel nets' h planes is live (0: the caller's arrays)
+  float* value_term;                         // row t of the terminal values [N] (RolloutPlan::term_rows), else null
 };
+
+// the sparse terminal-value launch (kbj_terminal_value.h) for N rows: `par` and `hc` [D][2][N][width] in the layout `o` at hidden size `width`
+void terminal_value_launch(hipStream_t st, const float* par, const NetOff& o, int N, int width, int D, const float* hc, const float* rows, const float* done_d, int done_stride,
+                           float* value) {
+  TermValueArgs a{};
+  a.params = par; a.rows = rows; a.hc = hc; a.done = done_d; a.done_stride = done_stride; a.value = value;
+  a.N = N; a.H = width; a.D = D; a.nin = o.nin; a.ld = o.ld_obs;
+  a.w_in = o.w_in; a.b_in = o.b_in; a.w_out = o.w_out; a.b_out = o.b_out;
+  for (int l = 0; l < D; ++l) { a.w_ih[l] = o.w_ih[l]; a.w_hh[l] = o.w_hh[l]; a.b[l] = o.b[l]; }
+  critic_terminal_value_launch(st, a);
+}
 
 // One call of the rollout half: the parameters (H wide), the plan, the seed - and the phases. Each returns 0 or what kbj_fail returned.
 struct Rollout {
@@ -734,6 +765,17 @@ struct Rollout {
     carry_reset_launch(q.lane, cp, N, H, q.lpf, done_d, done_stride);
   }
 
+  // phase: the values of the terminal rows the env step has just written, for the envs that timed out (0 elsewhere), from the net's carry
+  // BEFORE its reset - one sparse launch (terminal_value_launch) on the net's lane, then the record that frees the scratch for the next env
+  // step (RolloutPlan::ev_term). The critic never runs on the layer-step kernel (rollout_plan), so its live h planes are the carry's own.
+  int terminal_value(const RolloutNet& q, const StepRows& v) {
+    if (!q.terminal) return 0;
+    terminal_value_launch(q.lane, params, w.net[q.type], N, H, w.D, q.hc, p.term_rows, v.aux + KBJ_AUX_DONE, KBJ_AUX_SIZE, v.value_term);
+    return p.ev_term ? ev_record(ctx, p.ev_term, q.lane) : 0;
+  }
+  // phase: in front of an env step that is not the call's first - the caller's stream waits until the previous step's terminal rows have been read
+  int terminal_rows_free(hipStream_t s, bool first_step) { return p.ev_term && !first_step ? ev_wait(ctx, s, p.ev_term) : 0; }
+
   // the h planes of the step-kernel nets back from their ping-pong partners into the caller's arrays, on the caller's stream
   int planes_home() {
     for (int n = 0; n < p.nnets; ++n)
@@ -776,7 +818,7 @@ int policy_step_body(kbj_ctx* ctx, const float* params_d, const float* actor_obs
   return 0;
 }
 
-// snapshot, fork, per step: actor / others / env / resets / hop, tail value, join, home copy, rewards
+// snapshot, fork, per step: actor / others / env / resets (the critic's behind its terminal values) / hop, tail value, join, home copy, rewards
 int rollout_body(kbj_ctx* ctx, const float* params_d, kbj_carry* carry, uint32_t seed, uint32_t first_step_index, kbj_traj* tr) {
   NnWs& w = *ws_of(ctx);
   const size_t N = w.N, T = tr->T, la = w.net[0].ld_obs, lc = w.net[1].ld_obs, lx = KBJ_AUX_SIZE;
@@ -800,14 +842,19 @@ int rollout_body(kbj_ctx* ctx, const float* params_d, kbj_carry* carry, uint32_t
   for (size_t t = 0; t < T; ++t) {
     const StepRows v{tr->actor_obs_d + t * N * la, tr->critic_obs_d + t * N * lc, tr->aux_d + t * N * lx, tr->action_d + t * N * KBJ_NU, tr->logp_d + t * N, tr->value_d + t * N,
                      tr->actor_obs_d + (t + 1) * N * la, tr->critic_obs_d + (t + 1) * N * lc, tr->aux_d + (t + 1) * N * lx,
-                     tr->qstate_d ? tr->qstate_d + t * N * KBJ_QSTATE_SIZE : nullptr, first_step_index + (uint32_t)t, ctx->rollout_argmax, (int)(t & 1)};
+                     tr->qstate_d ? tr->qstate_d + t * N * KBJ_QSTATE_SIZE : nullptr, first_step_index + (uint32_t)t, ctx->rollout_argmax, (int)(t & 1),
+                     p.term_rows ? w.value_term + t * N : nullptr};
     const float* done = v.aux + KBJ_AUX_DONE;
     for (int n = 0; n < p.nnets; ++n) if (r.net_step(p.net[n], v)) return -1;   // the actor on the caller's stream, the others on the side lane
-    const int rc = kbj_env_step_all(ctx, s, v.action, v.aux, v.actor_next, v.critic_next, v.aux_next, v.qstate);
+    if (r.terminal_rows_free(s, t == 0)) return -1;
+    const int rc = kbj_env_step_all(ctx, s, v.action, v.aux, v.actor_next, v.critic_next, v.aux_next, v.qstate, p.term_rows);
     if (rc) return rc;
     r.carry_reset(p.net[0], done, KBJ_AUX_SIZE, (v.parity + 1) & 1);   // the planes step t + 1 reads
     if (!p.serial && hop(ctx, s, p.side, ctx->ev_side[0])) return -1;   // the side lane needs this step's done flags and the next critic observation
-    for (int n = 1; n < p.nnets; ++n) r.carry_reset(p.net[n], done, KBJ_AUX_SIZE, (v.parity + 1) & 1);
+    for (int n = 1; n < p.nnets; ++n) {
+      if (r.terminal_value(p.net[n], v)) return -1;
+      r.carry_reset(p.net[n], done, KBJ_AUX_SIZE, (v.parity + 1) & 1);
+    }
   }
   // kbj_config.gae_tail_value: V(s_T) for kbj_gae - the critic once more, on observation row T with a copy of the carries the last reset left, on the
   // critic's lane in front of the join (under the tail of the last env step's successors: the actor's carry copy-back and kbj_rewards)
@@ -896,6 +943,24 @@ int kbj_critic_value(kbj_ctx* ctx, const float* params_d, const float* critic_ob
   return 0;
 }
 
+int kbj_critic_terminal_value(kbj_ctx* ctx, const float* params_d, const float* critic_term_d, const kbj_carry* carry, const float* done_d, int done_stride,
+                              float* value_term_d) {
+  if (!ctx || !params_d || !critic_term_d || !carry || !carry->critic_hc_d || !done_d || !value_term_d) return kbj_fail(ctx, "kbj_critic_terminal_value: null argument");
+  if (done_stride < 1) return kbj_fail(ctx, "kbj_critic_terminal_value: done_stride must be positive");
+  KBJ_HIP(ctx, hipSetDevice(ctx->device));
+  NnWs& w = *ws_of(ctx);
+  // the caller's own layout throughout: parameters and carry at its hidden_size, nothing padded or copied (kbj_terminal_value.h)
+  terminal_value_launch(ctx->stream, params_d, w.user.net[1], w.N, w.Hu, w.D, carry->critic_hc_d, critic_term_d, done_d, done_stride, value_term_d);
+  KBJ_CHECK_LAUNCH(ctx, "critic_terminal_value_kernel");
+  return 0;
+}
+
+int kbj_set_terminal_values(kbj_ctx* ctx, float* value_term_d) {
+  if (!ctx || !ctx->nn_ws) return kbj_fail(ctx, "kbj_set_terminal_values: null ctx");
+  ws_of(ctx)->value_term = value_term_d;
+  return 0;
+}
+
 // ---- deployment (convert.py init_fn / step_fn): kbj_deploy.h ----
 int kbj_deploy_carry_size(const kbj_config* cfg) {
   if (!cfg) return kbj_fail(nullptr, "kbj_deploy_carry_size: null argument");
@@ -936,6 +1001,11 @@ int kbj_rollout(kbj_ctx* ctx, const float* params_d, kbj_carry* carry, uint32_t 
   NnWs& w = *ws_of(ctx);
   if (tr->N != w.N || tr->T <= 0) return kbj_fail(ctx, "kbj_rollout: trajectory shape does not match the context");
   if (mirror_arrays_missing(w.mirror, carry, tr)) return kbj_fail(ctx, "kbj_rollout: the mirror losses are enabled, carry and trajectory need the mirror-branch arrays");
+  if (ctx->cfg_h.gae_terminal_value && !w.value_term)
+    return kbj_fail(ctx, "kbj_rollout: kbj_config.gae_terminal_value = 1 needs the [T][N] buffer of kbj_set_terminal_values, none is set");
+  if (ctx->cfg_h.gae_terminal_value && tr->qstate_d)
+    return kbj_fail(ctx, "kbj_rollout: kbj_config.gae_terminal_value = 1 with kbj_traj.qstate_d: no env step kernel writes both the state record and the terminal rows - "
+                         "drop the record (record_state) or the terminal value");
   if (!w.padded()) return rollout_body(ctx, params_d, carry, seed, first_step_index, tr);
   // the H-wide schedule on internal copies; the caller's start-carry snapshot is taken here, at its own width
   const size_t ub = (size_t)2 * w.D * w.N * w.Hu * sizeof(float);
@@ -958,7 +1028,15 @@ int kbj_gae(kbj_ctx* ctx, const kbj_traj* tr, float* adv_d, float* target_d) {
   const kbj_config& c = ctx->cfg_h;
   if (c.gae_tail_value && !tr->value_tail_d)
     return kbj_fail(ctx, "kbj_gae: kbj_config.gae_tail_value = 1 needs kbj_traj.value_tail_d (kbj_rollout / kbj_critic_value fill it), it is NULL");
+  if (c.gae_terminal_value && !ws_of(ctx)->value_term)
+    return kbj_fail(ctx, "kbj_gae: kbj_config.gae_terminal_value = 1 needs the [T][N] buffer of kbj_set_terminal_values (kbj_rollout / kbj_critic_terminal_value fill it), none is set");
   kbj_nn_drop_prefetch(ctx);
+  if (c.gae_terminal_value) {   // a truncation bootstraps from the recorded value of the terminal observation (implies gae_bootstrap_truncation: kbj_check_config)
+    hipLaunchKernelGGL(gae_terminal_kernel, g1(tr->N, 64), dim3(64), 0, ctx->stream, tr->value_d, tr->reward_d, tr->aux_d, c.gae_tail_value ? tr->value_tail_d : nullptr,
+                       ws_of(ctx)->value_term, tr->T, tr->N, c.gamma, c.lam, adv_d, target_d);
+    KBJ_CHECK_LAUNCH(ctx, "gae_terminal_kernel");
+    return 0;
+  }
   if (c.gae_bootstrap_truncation || c.gae_tail_value) {   // the selectable boundary conventions (kbj.h); the default below is untouched by them
     hipLaunchKernelGGL(gae_boundary_kernel, g1(tr->N, 64), dim3(64), 0, ctx->stream, tr->value_d, tr->reward_d, tr->aux_d, c.gae_tail_value ? tr->value_tail_d : nullptr,
                        tr->T, tr->N, c.gamma, c.lam, (int)c.gae_bootstrap_truncation, adv_d, target_d);

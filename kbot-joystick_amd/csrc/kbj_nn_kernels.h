@@ -815,6 +815,32 @@ __global__ void gae_boundary_kernel(const float* __restrict__ value, const float
   }
 }
 
+// kbj_config.gae_terminal_value (with gae_bootstrap_truncation, which it needs): the scan of gae_boundary_kernel with one row changed - a
+// truncation (DONE > 0) bootstraps from value_term [T][N], the critic's value of the observation the episode ended in (kbj_rollout /
+// kbj_critic_terminal_value), instead of from V(s_t); the chain is cut as before, in the last row too (row T is a post-reset observation there).
+// A kernel of its own, launched only with the switch on: the two above run untouched, bit for bit, with it off.
+__global__ void gae_terminal_kernel(const float* __restrict__ value, const float* __restrict__ reward, const float* __restrict__ aux,
+                                    const float* __restrict__ value_tail, const float* __restrict__ value_term, int T, int N, float gamma, float lam,
+                                    float* __restrict__ adv, float* __restrict__ target) {
+  int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  float last = 0;
+  for (int t = T - 1; t >= 0; --t) {
+    size_t r = (size_t)t * N + n;
+    const float d = aux[r * KBJ_AUX_SIZE + KBJ_AUX_DONE];
+    const float v = value[r];
+    if (d != 0) {
+      last = d > 0 ? reward[r] + gamma * value_term[r] - v : reward[r] - v;
+    } else if (t + 1 < T) {
+      last = reward[r] + gamma * value[r + N] - v + gamma * lam * last;
+    } else {
+      const float vn = value_tail ? value_tail[n] : v;
+      last = reward[r] + gamma * vn - v;
+    }
+    adv[r] = last; target[r] = last + v;
+  }
+}
+
 // ---- AdamW with global-norm clipping (optax.adamw, train.py:1059-1077) -------------------------------------------------
 __global__ void sumsq_kernel(const float* __restrict__ g, size_t n, float scale, double* __restrict__ out, double* __restrict__ part) {
   __shared__ double red[256];

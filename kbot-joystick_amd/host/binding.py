@@ -66,6 +66,7 @@ SIGNATURES = {
     "kbj_synchronize": (_i, [_vp]),
     "kbj_env_reset_all": (_i, [_vp, _u32, _vp, _vp, _vp]),
     "kbj_env_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "kbj_env_step_terminal": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "kbj_env_record_state": (_i, [_vp, _vp]),
     "kbj_env_reset_where": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "kbj_env_set_command": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
@@ -83,6 +84,8 @@ SIGNATURES = {
     "kbj_policy_step": (_i, [_vp, _vp, _vp, _vp, C.POINTER(Carry), _u32, _u32, _i, _vp, _vp, _vp]),
     "kbj_carry_reset": (_i, [_vp, C.POINTER(Carry), _vp, _i]),
     "kbj_critic_value": (_i, [_vp, _vp, _vp, C.POINTER(Carry), _vp]),
+    "kbj_critic_terminal_value": (_i, [_vp, _vp, _vp, C.POINTER(Carry), _vp, _i, _vp]),
+    "kbj_set_terminal_values": (_i, [_vp, _vp]),
     "kbj_deploy_carry_size": (_i, [_cfgp]),
     "kbj_deploy_init": (_i, [_vp, _i, _vp]),
     "kbj_deploy_step": (_i, [_vp, _vp, C.POINTER(DeployInputs), _i, _vp, _vp, _vp]),
@@ -208,6 +211,11 @@ class Context:
             self.call("kbj_env_record_state", _ptr(qstate_t))
         self.call("kbj_env_step", _ptr(action), _ptr(aux_t), _ptr(actor_next), _ptr(critic_next), _ptr(aux_next))
 
+    def env_step_terminal(self, action, aux_t, actor_next, critic_next, aux_next, critic_term):
+        """kbj_env_step_terminal: env_step, and for the envs whose episode ends in this step their terminal critic row (the state before the
+        reset) into critic_term [N, ld_critic]; rows of envs that go on are not written."""
+        self.call("kbj_env_step_terminal", _ptr(action), _ptr(aux_t), _ptr(actor_next), _ptr(critic_next), _ptr(aux_next), _ptr(critic_term))
+
     def env_reset_where(self, mask, actor_next, critic_next, aux_next):
         self.call("kbj_env_reset_where", _ptr(mask), _ptr(actor_next), _ptr(critic_next), _ptr(aux_next))
 
@@ -273,6 +281,16 @@ class Context:
         """kbj_critic_value: the critic's value [N] of ONE observation row [N, ld_critic] from the critic carries in `carry`; no carry advances.
         Needs a context with kbj_config.gae_tail_value = 1."""
         self.call("kbj_critic_value", _ptr(params), _ptr(critic_obs), C.byref(carry), _ptr(value))
+
+    def critic_terminal_value(self, params, critic_term, carry: Carry, done, stride, value_term):
+        """kbj_critic_terminal_value: value_term [N] = the critic's value of the terminal rows critic_term [N, ld_critic] from the un-reset
+        critic carries where done (base pointer + stride in floats, as carry_reset takes it) > 0, exactly 0 elsewhere; nothing else is written."""
+        self.call("kbj_critic_terminal_value", _ptr(params), _ptr(critic_term), C.byref(carry), _ptr(done), stride, _ptr(value_term))
+
+    def set_terminal_values(self, value_term):
+        """kbj_set_terminal_values: the [T, N] float32 device tensor the following rollout() calls write and gae() calls read
+        (kbj_config.gae_terminal_value), or None. The caller keeps it alive."""
+        self.call("kbj_set_terminal_values", _ptr(value_term))
 
     def deploy_carry_size(self) -> int:
         """kbj_deploy_carry_size: floats of one row's flat carry (depth * 2 * hidden_size + 20, convert.py:71)."""

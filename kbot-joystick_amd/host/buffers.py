@@ -35,8 +35,10 @@ class TrajBuffers:
     """One rollout's worth of trajectory arrays ([T(+1)][N][dim], time-major)."""
 
     def __init__(self, T: int, N: int, H: int, depth: int, device, mirror: bool = False, reward_comps: bool = False,
-                 ld_actor: int = L.LD_ACTOR, ld_critic: int = L.LD_CRITIC, record_state: bool = False):
-        """ld_actor / ld_critic: row strides of the context's observation rows (layout.obs_widths(kbj_config): 68 / 476 plus user columns)."""
+                 ld_actor: int = L.LD_ACTOR, ld_critic: int = L.LD_CRITIC, record_state: bool = False, terminal_value: bool = False):
+        """ld_actor / ld_critic: row strides of the context's observation rows (layout.obs_widths(kbj_config): 68 / 476 plus user columns).
+        terminal_value (kbj_config.gae_terminal_value): also `value_term` [T, N], the buffer kbj_set_terminal_values names (the owner of the
+        context sets it), and `term_rows` [N, ld_critic], the terminal critic rows of ONE step for hosts that drive the steps themselves."""
         self.T, self.N = T, N
         z = lambda *s: torch.zeros(*s, device=device)
         self.actor_obs = z(T + 1, N, ld_actor)
@@ -56,6 +58,9 @@ class TrajBuffers:
         self.qstate = z(T, N, L.QSTATE["SIZE"]) if record_state else None
         # V(s_T) of kbj_config.gae_tail_value (kbj_traj.value_tail_d): always there, 4 N bytes; the library reads and writes it only with the switch on
         self.value_tail = z(N)
+        # the critic's values of the terminal observations (zero where no episode timed out) and one step's terminal rows; None with the switch off
+        self.value_term = z(T, N) if terminal_value else None
+        self.term_rows = z(N, ld_critic) if terminal_value else None
         mptr = [None, None, None]
         if mirror:
             self.carry0_actor_mirror_hc = z(depth, 2, N, H)

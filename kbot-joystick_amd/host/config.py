@@ -91,6 +91,11 @@ class HumanoidWalkingTaskConfig:
     # from V_{T-1}. KBJ_GAE_TRUNCATION / KBJ_GAE_TAIL in the environment override the defaults (A/B runs with tools/ab_bench.py).
     bootstrap_on_truncation: bool = _env_flag("KBJ_GAE_TRUNCATION")
     bootstrap_tail_value: bool = _env_flag("KBJ_GAE_TAIL")
+    # bootstrap_terminal_value: what a bootstrapped truncation bootstraps FROM - the critic's value of the terminal observation (the state the episode
+    # timed out in, before the reset; kbj_config.gae_terminal_value: the env step also writes that row, a sparse critic kernel values it, DESIGN.md
+    # section 3) instead of V(s_t). It chooses among bootstraps, so it needs bootstrap_on_truncation and says so instead of switching it on.
+    # Not with extra_critic_obs (user columns of a terminal row are not filled) nor record_state. KBJ_GAE_TERMINAL in the environment overrides the default.
+    bootstrap_terminal_value: bool = _env_flag("KBJ_GAE_TERMINAL")
     # constraint solver of the physics step (kbj_config.solver_newton): "newton" (the default: the kernel this build is tuned and measured with) or
     # "cg", Polak-Ribiere CG on the M^-1-preconditioned gradient - SURVEY B.1 records it as ksim's default, and at the launch block's
     # iterations=8, ls_iterations=8 (train.py:1777-1778) it is a different dynamics, not a cosmetic switch (DESIGN.md section 3 "Solver").
@@ -152,7 +157,18 @@ class HumanoidWalkingTaskConfig:
                   actor_mirror_loss_scale=self.actor_mirror_loss_scale, critic_mirror_loss_scale=self.critic_mirror_loss_scale,
                   lpf_alpha=self.ctrl_dt / (self.ctrl_dt + 1.0 / (2.0 * math.pi * self.cutoff_frequency)), deterministic=int(bool(self.deterministic)),
                   extra_obs_actor=int(self.extra_actor_obs), extra_obs_critic=int(self.extra_critic_obs), gemm_bf16x3=int(bool(self.gemm_bf16x3)),
-                  gae_bootstrap_truncation=int(bool(self.bootstrap_on_truncation)), gae_tail_value=int(bool(self.bootstrap_tail_value)))
+                  gae_bootstrap_truncation=int(bool(self.bootstrap_on_truncation)), gae_tail_value=int(bool(self.bootstrap_tail_value)),
+                  gae_terminal_value=int(bool(self.bootstrap_terminal_value)))
+        if self.bootstrap_terminal_value:
+            if not self.bootstrap_on_truncation:
+                raise ValueError("bootstrap_terminal_value chooses what a bootstrapped time-out bootstraps from (the terminal observation's value instead of "
+                                 "V(s_t)): it needs bootstrap_on_truncation=True (KBJ_GAE_TRUNCATION=1) and does not switch it on by itself")
+            if self.extra_critic_obs > 0:
+                raise ValueError("bootstrap_terminal_value cannot be combined with extra_critic_obs > 0: the user columns of a terminal critic row are "
+                                 "not filled (the terminal row is written inside the env step, before any observation term runs)")
+            if self.record_state:
+                raise ValueError("bootstrap_terminal_value cannot be combined with record_state: no env step kernel writes both the state record and "
+                                 "the terminal critic rows")
         if not (0 <= self.extra_actor_obs <= L.MAX_EXTRA_OBS and 0 <= self.extra_critic_obs <= L.MAX_EXTRA_OBS):
             raise ValueError(f"extra_actor_obs / extra_critic_obs must be in 0..{L.MAX_EXTRA_OBS}")
         if self.solver not in ("newton", "cg"):
@@ -182,7 +198,8 @@ class HumanoidWalkingTaskConfig:
                 elif (name, k) == ("not_upright", "max_radians"):
                     kw["max_tilt_rad"] = min(v, math.pi)
                 elif (name, k) == ("episode_length", "max_length_sec"):
-                    kw["max_episode_steps"] = int(min(round(v / self.ctrl_dt), 2 ** 30))     # round like T and substeps: 2.3 / 0.02 is 115, not 114
+                    # round like T and substeps: 2.3 / 0.02 is 115, not 114; +inf (the documented "off") has no integer to round to
+                    kw["max_episode_steps"] = 2 ** 30 if math.isinf(v) and v > 0 else int(min(round(v / self.ctrl_dt), 2 ** 30))
                 else:
                     raise KeyError(f"unknown termination parameter {name}.{k} (bad_z.unhealthy_z | not_upright.max_radians | episode_length.max_length_sec)")
         kcfg = L.default_config(**kw)

@@ -118,7 +118,10 @@ class HumanoidWalkingTask:
                              "(extra_observations={name: (term, 'actor' | 'critic' | 'both')})")
         self.terms.bind(config.seed, rank, self.device, self.model_blob, self.nobs_actor, self.nobs_critic)
         self.traj = TrajBuffers(self.T, self.N, self.H, self.kcfg.depth, self.device, mirror=self.mirror, reward_comps=config.log_reward_components,
-                                ld_actor=self.ld_actor, ld_critic=self.ld_critic, record_state=config.record_state)
+                                ld_actor=self.ld_actor, ld_critic=self.ld_critic, record_state=config.record_state,
+                                terminal_value=bool(self.kcfg.gae_terminal_value))
+        if self.kcfg.gae_terminal_value:        # the buffer kbj_rollout writes and kbj_gae reads (bootstrap_terminal_value)
+            self.ctx.set_terminal_values(self.traj.value_term)
         # episode accounting (config.episode_stats; host/episode.py): `ep_acc`, the per-env accumulator rows next to the env state, and
         # `ep_stats`, one call's result, are the object's own tensors; ep_acc is None means off
         self.episodes = EpisodeStats(self.N, self.device) if config.episode_stats else None
@@ -216,7 +219,7 @@ class HumanoidWalkingTask:
             terms.run_hooks(c, tr, 0, first, [terms.apply_resets, terms.apply_command, terms.observe])
             terms.started = True
         terms.run_steps(c, tr, self.carry, self.params, T, seed=self.config.seed, first_step=first, argmax=False, first_index=first,
-                        hooks=[terms.apply_terminations, terms.apply_resets, terms.apply_command, terms.observe])
+                        hooks=[terms.apply_terminations, terms.apply_resets, terms.apply_command, terms.observe], terminal=bool(self.kcfg.gae_terminal_value))
         if self.kcfg.gae_tail_value:          # V(s_T) for GAE, as kbj_rollout computes it: row T, the carries the last reset left, the rollout's parameters
             c.critic_value(self.params, tr.critic_obs[T], self.carry.c, tr.value_tail)
         c.rewards(tr.aux, T, tr.reward, tr.comps)
@@ -495,7 +498,7 @@ class HumanoidWalkingTask:
         if self._valid is None or self._valid.key != key:
             vcfg = self.config.to_kbj(num_envs) if num_envs % self.config.batch_size == 0 else dataclasses.replace(self.config, batch_size=num_envs).to_kbj(num_envs)
             vcfg.rollout_len = T
-            vcfg.gae_bootstrap_truncation = vcfg.gae_tail_value = 0      # validation never runs GAE: no tail pass, no carry copy
+            vcfg.gae_bootstrap_truncation = vcfg.gae_tail_value = vcfg.gae_terminal_value = 0      # validation never runs GAE: no tail pass, no carry copy, no terminal rows
             if terms.command_term is not None:
                 vcfg.command_mode = 1
             vctx = B.Context(self.model_blob, vcfg, self.device.index or 0, torch.cuda.current_stream().cuda_stream)

@@ -15,8 +15,9 @@ _DONE_BYTES = 4 * L.AUX["DONE"]       # the DONE column inside an aux row, as kb
 class Step:
     """Observation row `row` of `tr` as a hook sees it: the state after control step `row - 1` (row 0: after the reset of all envs)."""
 
-    def __init__(self, ctx, tr, row: int, step_index: int, model, qstate=None):
+    def __init__(self, ctx, tr, row: int, step_index: int, model, qstate=None, term_rows=None):
         self.ctx, self.tr, self.row, self.step_index, self.model, self.qstate = ctx, tr, row, step_index, model, qstate
+        self.term_rows = term_rows          # [N, ld_critic] terminal critic rows of the step that wrote this row (kbj_env_step_terminal), or None
         self.rows = (tr.actor_obs[row], tr.critic_obs[row], tr.aux[row])
         self.aux_prev = tr.aux[row - 1] if row else tr.aux[0]
         self._view = None
@@ -80,6 +81,8 @@ class UserTerms:
         done = s.aux_prev[:, L.AUX["DONE"]]
         user = combine_terminations(self.terminations, s.view())
         fire = (user != 0) & (done == 0)                # the kernel's own terminations already reset their envs
+        if s.term_rows is not None:                     # this env's critic row as the step left it IS its terminal row: keep it before the reset rewrites it
+            s.term_rows.copy_(torch.where(fire[:, None], s.rows[1], s.term_rows))
         s.ctx.env_reset_where(fire.to(torch.float32), *s.rows)
         s.aux_prev[:, L.AUX["DONE"]] = torch.where(fire, user, done)
         s.rewritten()
@@ -162,18 +165,26 @@ class UserTerms:
             self.obs_buffers[name][s.row].copy_(v)
 
     # ---- the loop ----
-    def run_hooks(self, ctx, tr, row: int, step_index: int, hooks, qstate=None):
-        s = Step(ctx, tr, row, step_index, self.model, qstate)
+    def run_hooks(self, ctx, tr, row: int, step_index: int, hooks, qstate=None, term_rows=None):
+        s = Step(ctx, tr, row, step_index, self.model, qstate, term_rows)
         for hook in hooks:
             hook(s)
 
-    def run_steps(self, ctx, tr, carry, params, T: int, seed: int, first_step: int, argmax: bool, first_index: int, hooks):
+    def run_steps(self, ctx, tr, carry, params, T: int, seed: int, first_step: int, argmax: bool, first_index: int, hooks, terminal: bool = False):
         """kbj_rollout's T control steps as separate ABI calls - policy step, env step, `hooks` in list order on the row the env step wrote,
         carry reset: the same calls kbj_rollout fuses, bit-identical when no hook changes anything. The policy draws step `first_step + t` of
-        `seed`; the hooks of row t + 1 get the step index `first_index + t + 1`."""
+        `seed`; the hooks of row t + 1 get the step index `first_index + t + 1`. terminal (a context with kbj_config.gae_terminal_value): as
+        kbj_rollout does then, the env step is kbj_env_step_terminal into tr.term_rows, and kbj_critic_terminal_value writes tr.value_term[t]
+        in front of the carry reset - behind the hooks, so that a user Termination term's +1 and its terminal row count."""
         for t in range(T):
             qs = tr.qstate[t] if tr.qstate is not None else None
+            done = tr.aux[t].data_ptr() + _DONE_BYTES
             ctx.policy_step(params, tr.actor_obs[t], tr.critic_obs[t], carry.c, seed, first_step + t, argmax, tr.action[t], tr.logp[t], tr.value[t])
-            ctx.env_step(tr.action[t], tr.aux[t], tr.actor_obs[t + 1], tr.critic_obs[t + 1], tr.aux[t + 1], qs)
-            self.run_hooks(ctx, tr, t + 1, first_index + t + 1, hooks, qs)
-            ctx.carry_reset(carry.c, tr.aux[t].data_ptr() + _DONE_BYTES, L.AUX["SIZE"])
+            if terminal:
+                ctx.env_step_terminal(tr.action[t], tr.aux[t], tr.actor_obs[t + 1], tr.critic_obs[t + 1], tr.aux[t + 1], tr.term_rows)
+            else:
+                ctx.env_step(tr.action[t], tr.aux[t], tr.actor_obs[t + 1], tr.critic_obs[t + 1], tr.aux[t + 1], qs)
+            self.run_hooks(ctx, tr, t + 1, first_index + t + 1, hooks, qs, tr.term_rows if terminal else None)
+            if terminal:
+                ctx.critic_terminal_value(params, tr.term_rows, carry.c, done, L.AUX["SIZE"], tr.value_term[t])
+            ctx.carry_reset(carry.c, done, L.AUX["SIZE"])

@@ -83,7 +83,7 @@ class Config(C.Structure):
         ("log_ratio_clip", f32), ("max_grad_norm", f32),
         ("learning_rate", f32), ("adam_b1", f32), ("adam_b2", f32), ("adam_eps", f32), ("weight_decay", f32),
         ("adv_eps", f32), ("value_clip", f32), ("actor_mirror_loss_scale", f32), ("critic_mirror_loss_scale", f32),
-        ("terrain_amp", f32), ("terrain_wavelength", f32), ("reserved_f", f32 * 4),
+        ("terrain_amp", f32), ("terrain_wavelength", f32), ("gae_terminal_value", i32), ("reserved_f", f32 * 3),
         ("reward_scale", f32 * NREW),
         ("rew_linvel_err", f32), ("rew_angvel_err", f32), ("rew_rollpitch_err", f32), ("rew_rollpitch_err_zero", f32),
         ("rew_height_err", f32), ("rew_standard_height", f32), ("rew_foot_origin_height", f32),
@@ -126,6 +126,7 @@ def default_config(**overrides) -> Config:
     c.command_mode, c.enable_randomizers, c.enable_pushes, c.enable_noise = 0, 1, 1, 1
     c.solver_newton = 1
     c.gae_bootstrap_truncation, c.gae_tail_value = 0, 0   # this build's GAE boundaries: every DONE terminal, V_T := V_{T-1}
+    c.gae_terminal_value = 0                              # (with truncations bootstrapped: from V(s_t), not from the recorded terminal value)
     c.max_episode_steps = 600                                                     # 12 s, train.py:1268
     c.dt, c.ctrl_dt, c.solver_tolerance = 0.004, 0.02, 1e-6   # fp32 gradient noise floor sits above MuJoCo's 1e-8
     c.latency_lo, c.latency_hi, c.drop_action_prob = 0.003, 0.01, 0.05            # train.py:1780-1781
