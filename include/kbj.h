@@ -255,6 +255,29 @@ int kbj_set_rollout_argmax(kbj_ctx* ctx, int argmax);
  * adds to the rewards); asynchronous on the context's stream. acc_d and reward_comps_d must be 16-byte aligned. */
 int kbj_episode_stats(kbj_ctx* ctx, const kbj_traj* traj, float* acc_d, double* stats_d);
 
+/* ---- command-tracking errors ----------------------------------------------------------------- */
+/* replaces: watching the converted policy follow a joystick (the reference's README.md:48-52), as numbers. For every row (t, n) of
+ * traj->aux_d, t = 0 .. T-1, the five tracking errors in fp32 and physical units (kbj_model.h KBJ_TERR_*): the error term of the
+ * reference's reward class before its exp, in rewards_kernel's expressions (train.py:261-264, 274-290, 301-305, 316-330, 377-386), with
+ * kbj_model.joint_bias and rew_standard_height / rew_foot_origin_height of the context's config.
+ * Mode of a row (KBJ_CMODE_*), from its command alone with exact != 0.0f tests (-0.0 counts as zero): nz = which of cmd[0], cmd[1], cmd[2]
+ * are non-zero, pose = any of cmd[3:16] non-zero. nz empty: STAND, or STAND_BEND with pose. nz non-empty with pose: OMNI. Exactly one of
+ * nz without pose: FORWARD / SIDEWAYS / ROTATE. Otherwise OMNI.
+ * Settled rows. acc_d [N][KBJ_TACC_SIZE] fp32 is device memory of the caller (zero it once; save it with the env state), updated in
+ * place: the previous row's command, SINCE, RUNNING. For every env n independently, for t ascending:
+ *   if RUNNING == 0, or cmd[k] != prev[k] for any k (float !=): since = 0 - the row starts an episode (RUNNING == 0: counted in
+ *   KBJ_TRK_EPISODES) or changes the command inside one (counted in KBJ_TRK_CHANGES); otherwise since = min(SINCE + 1, 2^24).
+ *   The row is settled when since >= settle_steps. Then prev = cmd, SINCE = since, RUNNING = (aux[t][n][KBJ_AUX_DONE] == 0).
+ * The terminal row of an episode counts: aux[t] holds the state before the reset.
+ * stats_d [KBJ_TRK_SIZE] doubles is OVERWRITTEN (kbj_model.h KBJ_TRK_*): per mode the rows, the settled rows and over the settled rows
+ * the sum, the sum of squares (taken in double) and the fp32 maximum of each error; the reduction runs in double, in a fixed order,
+ * without atomics: the same inputs give the same bytes on every call, with or without err_d.
+ * err_d: NULL, or [T][N][KBJ_TERR_SIZE] fp32 that receives every row's errors, mode, settled flag and since.
+ * Reads rows 0 .. T-1 of traj->aux_d only (neither rewards nor reward_comps_d); asynchronous on the context's stream. Fails with a message,
+ * before anything is launched, on a NULL acc_d or stats_d, on an acc_d, err_d or traj->aux_d that is not 16-byte aligned, and on
+ * settle_steps < 0. */
+int kbj_tracking_stats(kbj_ctx* ctx, const kbj_traj* traj, int settle_steps, float* acc_d, double* stats_d, float* err_d);
+
 /* ---- PPO update, rows a9, a12, a13 ---------------------------------------------------------- */
 /* replaces: ksim GAE (gamma, lam: train.py:1769-1770). done from aux; adv_d/target_d [T][N].
  * Per env n, for t = T-1 .. 0, with d = aux[t][n][KBJ_AUX_DONE], v = value[t][n], r = reward[t][n] and A_T = 0:

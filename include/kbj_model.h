@@ -310,6 +310,51 @@ enum {
   KBJ_EPST_SIZE            = 32
 };
 
+/* ---- command-tracking errors (kbj_tracking_stats) ----
+ * Mode of a row, from its command alone (exact != 0.0f tests; numbering = the switch list of train.py:752-762). */
+enum {
+  KBJ_CMODE_FORWARD    = 0,   /* only cmd[0] non-zero */
+  KBJ_CMODE_SIDEWAYS   = 1,   /* only cmd[1] non-zero */
+  KBJ_CMODE_ROTATE     = 2,   /* only cmd[2] non-zero */
+  KBJ_CMODE_OMNI       = 3,   /* moving with a pose (any of cmd[3:16] non-zero), or more than one of cmd[0:3] non-zero */
+  KBJ_CMODE_STAND_BEND = 4,   /* cmd[0:3] zero, a pose */
+  KBJ_CMODE_STAND      = 5,   /* all zero */
+  KBJ_CMODE_COUNT      = 6
+};
+#define KBJ_NTERR 5 /* tracking errors per row */
+/* One row of the optional per-row output ("TERR" record, fp32): the five errors in physical units, then three integer-valued floats. */
+enum {
+  KBJ_TERR_LIN     = 0,   /* |qvel_xy - R_yaw(base) cmd[0:2]|, m/s (train.py:274-290) */
+  KBJ_TERR_YAW     = 1,   /* |qvel[5] - cmd[2]|, rad/s (train.py:301-305) */
+  KBJ_TERR_TILT    = 2,   /* 1 - <q(roll, pitch, 0), q(cmd[4], cmd[5], 0)>^2 (train.py:316-330) */
+  KBJ_TERR_HEIGHT  = 3,   /* |BASEZ - min(LFZ, RFZ) + foot_origin_height - (cmd[3] + standard_height)|, m (train.py:377-386) */
+  KBJ_TERR_ARM     = 4,   /* sum_j (ARMQ[j] - cmd[6 + j] - joint_bias[10 + j])^2, rad^2 (train.py:261-264) */
+  KBJ_TERR_MODE    = 5,   /* KBJ_CMODE_* of the row */
+  KBJ_TERR_SETTLED = 6,   /* 1 when the row is counted: since >= settle_steps */
+  KBJ_TERR_SINCE   = 7,   /* rows since the command last changed or the episode started, as used for this row */
+  KBJ_TERR_SIZE    = 8
+};
+/* Per-env carry row ("TACC" record, fp32, owned by the caller on the device like the EACC rows; zeroed once). */
+enum {
+  KBJ_TACC_CMD     = 0,   /* [16] the command of the env's previous row */
+  KBJ_TACC_SINCE   = 16,  /* rows since the command last changed or the episode started (integer valued, stops growing at 2^24) */
+  KBJ_TACC_RUNNING = 17,  /* 1 when a previous row exists and did not end its episode */
+  KBJ_TACC_SIZE    = 20   /* 80-byte rows; the two spare floats are left as they are */
+};
+/* One call's result ("TRK" record, doubles): KBJ_CMODE_COUNT mode blocks of KBJ_TRK_MODE_STRIDE slots (mode m's slot s at
+ * m * KBJ_TRK_MODE_STRIDE + s), then the two counters; every other slot is 0. */
+enum {
+  KBJ_TRK_ROWS        = 0,    /* rows of the mode */
+  KBJ_TRK_SETTLED     = 1,    /* of them settled; the next three groups are over the settled rows only */
+  KBJ_TRK_SUM         = 2,    /* [5] sum of the fp32 error, KBJ_TERR_* order, */
+  KBJ_TRK_SUMSQ       = 7,    /* [5] of its square (taken in double), */
+  KBJ_TRK_MAX         = 12,   /* [5] its maximum (0 without settled rows: the errors are non-negative) */
+  KBJ_TRK_MODE_STRIDE = 20,
+  KBJ_TRK_CHANGES     = 120,  /* rows whose command differs from the previous row's inside a running episode */
+  KBJ_TRK_EPISODES    = 121,  /* rows that start an episode (no previous row, or the previous row ended its episode) */
+  KBJ_TRK_SIZE        = 128
+};
+
 /* reward component order (train.py:1225-1256) */
 enum {
   KBJ_REW_LINVEL = 0, KBJ_REW_ANGVEL, KBJ_REW_ROLL_PITCH, KBJ_REW_BASE_HEIGHT, KBJ_REW_ARM_POS,

@@ -13,7 +13,8 @@ enum { KBJ_KIND_GEMM = 0 /* +4 small tile, +2 A k-contiguous, +1 B k-contiguous 
        // (+2 A k-contiguous, +1 B k-contiguous), 19 = <2, true, true, true>, 20 = <1, true, true, false>, 21 = <1, true, true, true>
        KBJ_KIND_GEMM_X3 = 15, KBJ_KIND_GEMM_X3_GEN = 19, KBJ_KIND_GEMM_X3_SMALL = 20, KBJ_KIND_GEMM_X3_SMALL_GEN = 21,
        KBJ_KIND_SEQ_BWD16 = 22 /* lstm_seq_bwd16_kernel<H> */, KBJ_KIND_GEMM_64x128 = 23 /* gemm_f32_kernel<1, 1, true, true, 2, 4>: the critic's input projection; 24 = <1, 1, true, false, 2, 4>: the input gradients */,
-       KBJ_KIND_COUNT = 25 };
+       KBJ_KIND_TRACKING_STATS = 25 /* tracking_stats_kernel (kbj_tracking_stats) */,
+       KBJ_KIND_COUNT = 26 };
 inline int kbj_kind_gemm_x3(int tm, bool a_kc, bool b_kc, bool gen) {
   if (tm == 2) return gen ? KBJ_KIND_GEMM_X3_GEN : KBJ_KIND_GEMM_X3 + (a_kc ? 2 : 0) + (b_kc ? 1 : 0);
   return gen ? KBJ_KIND_GEMM_X3_SMALL_GEN : KBJ_KIND_GEMM_X3_SMALL;
@@ -88,6 +89,8 @@ struct kbj_ctx {
   float* qstate_next = nullptr; // kbj_env_record_state: where the next kbj_env_step writes its state record (one-shot)
   double* epst_part_d = nullptr;  // kbj_episode_stats: workgroup partials [epst_part_blocks][KBJ_EPST_SIZE], allocated by the first call
   int epst_part_blocks = 0;
+  double* trk_part_d = nullptr;   // kbj_tracking_stats: workgroup partials [trk_part_blocks][KBJ_TRK_SIZE], allocated by the first call
+  int trk_part_blocks = 0;
   // NN workspace (kbj_nn.hip)
   void* nn_ws = nullptr;
   size_t nn_ws_bytes = 0;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include "kbj_env_task.h"
 #include "kbj_episode_stats.h"
+#include "kbj_tracking_stats.h"
 #include "kbj_ctx.h"
 
 using namespace kbj;
@@ -498,6 +499,32 @@ int kbj_episode_stats(kbj_ctx* ctx, const kbj_traj* tr, float* acc_d, double* st
   KBJ_CHECK_LAUNCH(ctx, "episode_stats_kernel");
   hipLaunchKernelGGL(episode_stats_reduce_kernel, dim3(1), dim3(EPST_THREADS), 0, ctx->stream, ctx->epst_part_d, blocks, stats_d);
   KBJ_CHECK_LAUNCH(ctx, "episode_stats_reduce_kernel");
+  return 0;
+}
+
+int kbj_tracking_stats(kbj_ctx* ctx, const kbj_traj* tr, int settle_steps, float* acc_d, double* stats_d, float* err_d) {
+  if (!ctx || !tr || !acc_d || !stats_d) return kbj_fail(ctx, "kbj_tracking_stats: null argument");
+  if (!tr->aux_d || tr->T <= 0 || tr->N <= 0) return kbj_fail(ctx, "kbj_tracking_stats: the trajectory needs aux_d and positive T, N");
+  if (settle_steps < 0) return kbj_fail(ctx, "kbj_tracking_stats: settle_steps must not be negative");
+  if ((reinterpret_cast<uintptr_t>(acc_d) | reinterpret_cast<uintptr_t>(err_d) | reinterpret_cast<uintptr_t>(tr->aux_d)) & 15)
+    return kbj_fail(ctx, "kbj_tracking_stats: acc_d, err_d and aux_d must be 16-byte aligned");
+  KBJ_HIP(ctx, hipSetDevice(ctx->device));
+  kbj_nn_drop_prefetch(ctx);
+  const int blocks = (tr->N + TRK_ENVS - 1) / TRK_ENVS;
+  if (blocks > ctx->trk_part_blocks) {   // first call of the context (or a wider trajectory than any before): never per call
+    if (ctx->trk_part_d) KBJ_HIP(ctx, hipFree(ctx->trk_part_d));
+    ctx->trk_part_d = nullptr; ctx->trk_part_blocks = 0;
+    KBJ_HIP(ctx, hipMalloc(&ctx->trk_part_d, (size_t)blocks * KBJ_TRK_SIZE * sizeof(double)));
+    ctx->trk_part_blocks = blocks;
+  }
+  {
+    KbjKernelTimer timer(ctx->stream, KBJ_KIND_TRACKING_STATS, 0.0);
+    hipLaunchKernelGGL(tracking_stats_kernel, dim3(blocks), dim3(TRK_THREADS), 0, ctx->stream, ctx->model_d, tr->aux_d, tr->T, tr->N, settle_steps,
+                       ctx->cfg_h.rew_standard_height, ctx->cfg_h.rew_foot_origin_height, acc_d, ctx->trk_part_d, err_d);
+  }
+  KBJ_CHECK_LAUNCH(ctx, "tracking_stats_kernel");
+  hipLaunchKernelGGL(tracking_stats_reduce_kernel, dim3(1), dim3(TRK_RED_THREADS), 0, ctx->stream, ctx->trk_part_d, blocks, stats_d);
+  KBJ_CHECK_LAUNCH(ctx, "tracking_stats_reduce_kernel");
   return 0;
 }
 

@@ -94,6 +94,7 @@ SIGNATURES = {
     "kbj_recurrence_residency": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "kbj_gae": (_i, [_vp, C.POINTER(Traj), _vp, _vp]),
     "kbj_episode_stats": (_i, [_vp, C.POINTER(Traj), _vp, _vp]),
+    "kbj_tracking_stats": (_i, [_vp, C.POINTER(Traj), _i, _vp, _vp, _vp]),
     "kbj_ppo_grad": (_i, [_vp, _vp, C.POINTER(Traj), _vp, _i, _vp, _vp, _vp, _vp]),
     "kbj_ppo_forward": (_i, [_vp, _vp, C.POINTER(Traj), _vp, _i, C.POINTER(PpoVars)]),
     "kbj_stream_wait_actor_grad": (_i, [_vp, _vp]),
@@ -324,6 +325,11 @@ class Context:
     def episode_stats(self, traj: Traj, acc, stats):
         """kbj_episode_stats: acc [N, EACC SIZE] float32 (updated in place), stats [EPST SIZE] float64 (overwritten), both on the device."""
         self.call("kbj_episode_stats", C.byref(traj), _ptr(acc), _ptr(stats))
+
+    def tracking_stats(self, traj: Traj, settle_steps: int, acc, stats, err=None):
+        """kbj_tracking_stats: acc [N, TACC SIZE] float32 (updated in place), stats [TRK SIZE] float64 (overwritten), err None or
+        [T, N, TERR SIZE] float32 (every row's errors, mode, settled flag, since), all on the device."""
+        self.call("kbj_tracking_stats", C.byref(traj), int(settle_steps), _ptr(acc), _ptr(stats), _ptr(err))
 
     def ppo_grad(self, params, traj: Traj, env_idx, B, adv, target, grad, metrics):
         self.call("kbj_ppo_grad", _ptr(params), C.byref(traj), _ptr(env_idx), B, _ptr(adv), _ptr(target), _ptr(grad),

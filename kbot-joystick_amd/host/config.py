@@ -84,6 +84,13 @@ class HumanoidWalkingTaskConfig:
     # read with task.episode_stats(), merged into scalars() / validate(). Off (the default; KBJ_EPISODE_STATS in the environment overrides
     # it, for A/B runs with tools/ab_bench.py): nothing is allocated, launched or logged.
     episode_stats: bool = _env_flag("KBJ_EPISODE_STATS")
+    # command-tracking errors on the device (kbj_tracking_stats; host/tracking.py): the five tracking errors of every env-step in physical units
+    # (m/s, rad/s, 1 - cos^2 of the half tilt angle, m, rad^2), split by the six command modes of UnifiedCommand and counted over the rows whose
+    # command has been held for tracking_settle_seconds; merged into scalars() / validate() as track/<mode>/..., carried per env across rollouts
+    # and through checkpoints. Off (the default; KBJ_TRACKING_STATS in the environment overrides it, for A/B runs with tools/ab_bench.py):
+    # nothing is allocated, launched or logged. task.tracking_sweep() - the joystick response table - works with the switch off too.
+    tracking_stats: bool = _env_flag("KBJ_TRACKING_STATS")
+    tracking_settle_seconds: float = 0.5    # settle_steps = round(tracking_settle_seconds / ctrl_dt)
     # GAE boundary conventions (include/kbj.h kbj_gae). Both off by default - this build's choice: every termination ends the
     # return, V_T := V_{T-1} - and selectable, because SURVEY B.2 believes ksim bootstraps through the episode-length "success" termination:
     # bootstrap_on_truncation: at DONE = +1 (time-out, or a user term's +1) delta = r + gamma V(s_t) - V(s_t) instead of r - V(s_t);

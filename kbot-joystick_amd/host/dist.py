@@ -99,3 +99,39 @@ def reduce_episode_stats(vec: torch.Tensor, world_size: int) -> torch.Tensor:
         dist.all_reduce(ext, op=dist.ReduceOp.MAX)
         vec[..., _EPST_MAX], vec[..., _EPST_MIN], vec[..., _EPST_LENGTH_MAX] = ext[..., 0], -ext[..., 1], ext[..., 2]
     return vec
+
+
+# kbj_tracking_stats vectors (kbj_model.h KBJ_TRK_*): every slot is a count or a sum over rows, except the maxima of each mode block
+_TRK_MAX = np.zeros(L.TRK["SIZE"], bool)
+for _m in range(L.CMODE["COUNT"]):
+    _TRK_MAX[_m * L.TRK["MODE_STRIDE"] + L.TRK["MAX"]:_m * L.TRK["MODE_STRIDE"] + L.TRK["MAX"] + L.NTERR] = True
+
+
+def empty_tracking_stats() -> np.ndarray:
+    """The KBJ_TRK vector of no row: zeros (the maxima's identity is 0: the errors are non-negative)."""
+    return np.zeros(L.TRK["SIZE"], np.float64)
+
+
+def combine_tracking_stats(vectors) -> np.ndarray:
+    """Statistics of the union of the row sets that the given KBJ_TRK vectors describe (other ranks' envs, or later rollouts): counts and
+    sums add up in list order, in float64; the maxima are taken over the list."""
+    out = empty_tracking_stats()
+    for v in vectors:
+        v = np.asarray(v, np.float64)
+        out = np.where(_TRK_MAX, np.maximum(out, v), out + v)
+    return out
+
+
+def reduce_tracking_stats(vec: torch.Tensor, world_size: int) -> torch.Tensor:
+    """combine_tracking_stats over the data-parallel ranks: `vec` [..., TRK SIZE] float64 holds this rank's KBJ_TRK vector(s); returns the
+    vector(s) of all ranks' envs together. ONE SUM all-reduce over the counts and sums, ONE MAX all-reduce over the maxima. Collective:
+    every rank calls it, at logging cadence (HumanoidWalkingTask.tracking_stats()), never inside the update."""
+    if world_size > 1 or FORCE_COLLECTIVE:
+        import torch.distributed as dist
+        is_max = torch.from_numpy(_TRK_MAX).to(vec.device)
+        hi = torch.where(is_max, vec, torch.zeros_like(vec))
+        vec = torch.where(is_max, torch.zeros_like(vec), vec)
+        dist.all_reduce(vec, op=dist.ReduceOp.SUM)
+        dist.all_reduce(hi, op=dist.ReduceOp.MAX)
+        vec = torch.where(is_max, hi, vec)
+    return vec

@@ -28,6 +28,7 @@ from .buffers import CarryBuffers, TrajBuffers
 from .ckpt import ModelView
 from .config import HumanoidWalkingTaskConfig, cosine_decay_lr, launch_config      # launch_config: re-exported with the rest
 from .episode import EpisodeStats, episode_stats_scalars, fresh_episode_stats
+from .tracking import TrackingStats, format_tracking_table, fresh_tracking_stats, settle_steps, tracking_scalars, tracking_sweep      # noqa: F401 (re-exported)
 from .user_terms import UserTerms
 
 
@@ -126,6 +127,9 @@ class HumanoidWalkingTask:
         # `ep_stats`, one call's result, are the object's own tensors; ep_acc is None means off
         self.episodes = EpisodeStats(self.N, self.device) if config.episode_stats else None
         self.ep_acc, self.ep_stats = (self.episodes.acc, self.episodes.stats) if self.episodes is not None else (None, None)
+        # command-tracking errors (config.tracking_stats; host/tracking.py): `trk_acc`, the per-env carry rows next to the env state; None means off
+        self.tracking = TrackingStats(self.N, settle_steps(config.tracking_settle_seconds, config.ctrl_dt), self.device) if config.tracking_stats else None
+        self.trk_acc = self.tracking.acc if self.tracking is not None else None
         self.opt_step = 0
         self.iteration = 0
         self._perm_gen = torch.Generator(device="cpu")
@@ -165,6 +169,41 @@ class HumanoidWalkingTask:
             self.extra_reward_means = apply_extra_rewards(self.extra_rewards, self._extra_carries, self.trajectory(), self.traj.reward)
         if self.episodes is not None:             # behind the user rewards, so that they count; user terminations are in the DONE column already
             self.episodes.after_rollout(self.ctx, self.traj.c)
+        if self.tracking is not None:             # the aux rows are all it reads: neither rewards nor reward_comps
+            self.tracking.after_rollout(self.ctx, self.traj.c)
+
+    def tracking_stats_vectors(self):
+        """(last, total): this rank's raw KBJ_TRK vectors (float64 numpy, layout.TRK) behind tracking_stats() - the rows of the last rollout
+        and all since creation / resume."""
+        if self.tracking is None:
+            raise B.KbjError("tracking_stats_vectors() needs HumanoidWalkingTaskConfig.tracking_stats=True")
+        last, total = self.tracking.vectors()
+        return last.copy(), total.copy()
+
+    def tracking_stats(self, total: bool = False) -> dict:
+        """Command-tracking errors (needs `tracking_stats=True` in the config) of the LAST rollout - or, with `total`, of all rollouts since the
+        task was created or resumed, as `track_total/...`: per command mode that has settled rows `track/<mode>/<err>_mean`, `_rms`, `_max`
+        for lin_vel_err (m/s), yaw_rate_err (rad/s), tilt_err, height_err (m), arm_sq_err (rad^2) over the rows whose command has been held
+        for `tracking_settle_seconds`, `rows_frac` (the mode's share of all rows) and `settled_frac`. In a multi-rank job the vectors are
+        reduced over the ranks (dist.reduce_tracking_stats): every rank must call it."""
+        if self.tracking is None:
+            raise B.KbjError("tracking_stats() needs HumanoidWalkingTaskConfig.tracking_stats=True")
+        vec = self.tracking.vectors()[1 if total else 0]
+        if self.world_size > 1 or dist_util.FORCE_COLLECTIVE:
+            vec = dist_util.reduce_tracking_stats(torch.from_numpy(vec).to(self.device), self.world_size).cpu().numpy()
+        return tracking_scalars(vec, "track_total/" if total else "track/")
+
+    def tracking_sweep(self, commands=None, repeats: int = 2, seconds: Optional[float] = None, settle_seconds: Optional[float] = None) -> list:
+        """The joystick response table: how well the CURRENT policy follows each of `commands` ([K][<= 16] floats, missing components zero;
+        default: host/tracking.default_command_grid - stand, the six directions at half and full range, one omni, one stand-bend command, from
+        the config's command ranges). A validation-style context of K * repeats envs (env e follows command e % K) runs `seconds`
+        (default render_length_seconds) with argmax actions through the step-wise loop, driven by a scripted Command term that hands every env
+        its own command again after an in-episode reset; the user's Reset and network-input Observation terms apply as in validate(). One
+        kbj_tracking_stats call then gives every row's errors. Returns one dict per command: `command`, `mode`, the five settled-row mean
+        errors (per env over its rows whose command has been held for `settle_seconds`, default tracking_settle_seconds, then averaged over
+        the repeats), `settled_rows` and `failures_per_s`. `format_tracking_table` renders it. Works with `tracking_stats` off. Every call
+        creates a library context for its env count and length and closes it again (it is not cached as validate()'s is)."""
+        return tracking_sweep(self, commands, repeats, seconds, settle_seconds)[0]
 
     def episode_stats_vectors(self):
         """(last, total): this rank's raw KBJ_EPST vectors (float64 numpy, layout.EPST) behind episode_stats() - the episodes that finished in
@@ -381,6 +420,8 @@ class HumanoidWalkingTask:
                           lpf_mirror=self.carry.lpf_mirror.cpu().numpy())
         if self.episodes is not None:
             extras.update(self.episodes.checkpoint_state())
+        if self.tracking is not None:
+            extras.update(self.tracking.checkpoint_state())
         # carries of Python StatefulReward terms (extra_rewards): tensors (or tuples / lists of tensors) per term name
         for name, carry in self._extra_carries.items():
             leaves = list(carry) if isinstance(carry, (tuple, list)) else [carry]
@@ -441,6 +482,8 @@ class HumanoidWalkingTask:
         x = z["extras"]
         if self.episodes is not None:
             self.episodes.load_checkpoint_state(x)
+        if self.tracking is not None:
+            self.tracking.load_checkpoint_state(x)
         if "es" not in x:
             return            # a model-only checkpoint (e.g. written by the reference): parameters and optimizer only
         if x["es"].shape[0] != self.N:
@@ -536,6 +579,8 @@ class HumanoidWalkingTask:
             vctx.rewards(tr.aux, T, tr.reward, tr.comps)
         if self.episodes is not None:   # the same kernel on the validation trajectory: every validation starts its episodes afresh
             vstats = fresh_episode_stats(vctx, tr.c, num_envs, self.device)
+        if self.tracking is not None:   # a fresh carry likewise, on the fused and on the step-wise path
+            vtrack = fresh_tracking_stats(vctx, tr.c, num_envs, self.tracking.settle_steps, self.device)
         vctx.synchronize()
         done = tr.done
         fails, succ = float((done < 0).sum()), float((done > 0).sum())
@@ -545,6 +590,8 @@ class HumanoidWalkingTask:
             out[f"valid/reward/{name}"] = v
         if self.episodes is not None:
             out.update(episode_stats_scalars(vstats.cpu().numpy(), self.config.ctrl_dt, "valid/episode/", terms=True))
+        if self.tracking is not None:
+            out.update(tracking_scalars(vtrack.cpu().numpy(), "valid/track/"))
         return out
 
     def close_validation(self):
@@ -599,6 +646,8 @@ class HumanoidWalkingTask:
                 out[f"reward/{name}"] = v
         if self.ep_acc is not None:      # the result came back behind the kernel: the sync above is already past it
             out.update(self.episode_stats())
+        if self.tracking is not None:
+            out.update(self.tracking_stats())
         return out
 
     def export_actor(self, path: str):

@@ -1,0 +1,230 @@
+"""Command-tracking errors on the device (kbj_tracking_stats; HumanoidWalkingTaskConfig.tracking_stats): the per-env carry rows that live next
+to the env state, the hand-over of one call's result to the host, the result vectors as logger scalars - and the sweep, the joystick
+response table: a scripted Command term that holds one command per env through in-episode resets, the default command grid, the table."""
+from __future__ import annotations
+
+import dataclasses
+import math
+
+import numpy as np
+import torch
+
+from ..spec import constants, layout as L
+from . import binding as B
+from . import dist as dist_util
+from .buffers import CarryBuffers, TrajBuffers
+from .user_terms import UserTerms
+
+K, A, R = L.TRK, L.TACC, L.TERR
+
+
+def settle_steps(settle_seconds: float, ctrl_dt: float) -> int:
+    """Rows a command must have been held for before a row counts (kbj_tracking_stats settle_steps)."""
+    return max(0, int(round(settle_seconds / ctrl_dt)))
+
+
+def command_mode(cmd) -> int:
+    """The KBJ_CMODE of one command (include/kbj.h kbj_tracking_stats): which of cmd[0:3] are non-zero, and whether any of cmd[3:16] is."""
+    c = np.asarray(cmd, np.float32)
+    nz, pose = c[:3] != 0, bool((c[3:] != 0).any())
+    if not nz.any():
+        return L.CMODE["STAND_BEND"] if pose else L.CMODE["STAND"]
+    if pose or nz.sum() != 1:
+        return L.CMODE["OMNI"]
+    return int(np.argmax(nz))
+
+
+def tracking_scalars(vec, prefix: str = "track/") -> dict:
+    """One KBJ_TRK vector (kbj_model.h; layout.TRK) as logger scalars: per mode that has settled rows the mean, rms and maximum of every error
+    over them, the mode's share of all rows and the settled share of its rows. A mode without settled rows is omitted: a mean of nothing
+    is not a number worth plotting."""
+    vec = np.asarray(vec, np.float64)
+    rows_all = sum(float(vec[m * K["MODE_STRIDE"] + K["ROWS"]]) for m in range(L.CMODE["COUNT"]))
+    out = {}
+    for m, mode in enumerate(constants.COMMAND_MODE_NAMES):
+        b = vec[m * K["MODE_STRIDE"]:(m + 1) * K["MODE_STRIDE"]]
+        rows, n = float(b[K["ROWS"]]), float(b[K["SETTLED"]])
+        if n <= 0:
+            continue
+        for k, name in enumerate(constants.TRACKING_ERROR_NAMES):
+            out[f"{prefix}{mode}/{name}_mean"] = float(b[K["SUM"] + k]) / n
+            out[f"{prefix}{mode}/{name}_rms"] = math.sqrt(float(b[K["SUMSQ"] + k]) / n)
+            out[f"{prefix}{mode}/{name}_max"] = float(b[K["MAX"] + k])
+        out[f"{prefix}{mode}/rows_frac"] = rows / rows_all
+        out[f"{prefix}{mode}/settled_frac"] = n / rows
+    return out
+
+
+def fresh_tracking_stats(ctx, traj, num_envs: int, steps: int, device, err=None) -> torch.Tensor:
+    """kbj_tracking_stats on a trajectory whose episodes all start with it (every validation rollout): its KBJ_TRK vector, on the device."""
+    acc = torch.zeros(num_envs, A["SIZE"], device=device)
+    stats = torch.zeros(K["SIZE"], dtype=torch.float64, device=device)
+    ctx.tracking_stats(traj, steps, acc, stats, err)
+    return stats
+
+
+class TrackingStats:
+    """Per-env carry rows (`acc`, carried across rollouts and through checkpoints), one call's result (`stats`), and on the host the last
+    rollout's vector and the totals since creation / resume. The result comes back through a pinned buffer behind the kernel (no sync in
+    the loop); it is folded into the totals when the next rollout starts or when somebody asks."""
+
+    def __init__(self, num_envs: int, steps: int, device):
+        self.settle_steps = steps
+        self.acc = torch.zeros(num_envs, A["SIZE"], device=device)
+        self.stats = torch.zeros(K["SIZE"], dtype=torch.float64, device=device)
+        self._host = torch.zeros(K["SIZE"], dtype=torch.float64).pin_memory()
+        self._event = torch.cuda.Event()
+        self._pending = False
+        self._last = dist_util.empty_tracking_stats()
+        self._total = dist_util.empty_tracking_stats()
+
+    def after_rollout(self, ctx, traj):
+        """Account the rollout in `traj`: its aux rows are all the kernel reads."""
+        self._fold()
+        ctx.tracking_stats(traj, self.settle_steps, self.acc, self.stats)
+        self._host.copy_(self.stats, non_blocking=True)
+        self._event.record()
+        self._pending = True
+
+    def _fold(self):
+        """The last kbj_tracking_stats result, once its copy has landed, becomes `_last` and joins the totals."""
+        if self._pending:
+            self._event.synchronize()
+            self._last = self._host.numpy().copy()
+            self._total = dist_util.combine_tracking_stats([self._total, self._last])
+            self._pending = False
+
+    def vectors(self):
+        """(last, total): the KBJ_TRK vectors (float64 numpy) of the last rollout's rows and of all so far."""
+        self._fold()
+        return self._last, self._total
+
+    def checkpoint_state(self) -> dict:
+        """The commands being held and the totals so far (the last rollout's own vector is not state)."""
+        self._fold()
+        return dict(trk_acc=self.acc.cpu().numpy(), trk_total=self._total.copy())
+
+    def load_checkpoint_state(self, x):
+        """The members when the saved run kept them (same env count), else from zero - every env then counts as starting an episode (an old
+        checkpoint, a run saved with the switch off, a model-only file)."""
+        self._pending = False
+        self._last = dist_util.empty_tracking_stats()
+        if "trk_acc" in x and "trk_total" in x and tuple(x["trk_acc"].shape) == tuple(self.acc.shape) and x["trk_total"].shape == (K["SIZE"],):
+            self.acc.copy_(torch.from_numpy(np.ascontiguousarray(x["trk_acc"], np.float32)))
+            self._total = np.array(x["trk_total"], np.float64)
+        else:
+            self.acc.zero_()
+            self._total = dist_util.empty_tracking_stats()
+
+
+# ---- the sweep ----
+class ScriptedCommand:
+    """A Command term (train.py:724, 768) that holds one fixed command per env: `initial_command` is the env's row of `table` [N, 16],
+    `__call__` the previous command - so a command survives an in-episode reset, after which the kernel's own reset (command_mode = 1)
+    has returned the env to the context's single fixed_command."""
+
+    def __init__(self, table: torch.Tensor):
+        self.table = table
+
+    def initial_command(self, state, curriculum_level, rng):
+        return self.table
+
+    def __call__(self, prev_command, state, curriculum_level, rng):
+        return prev_command
+
+
+def default_command_grid(kcfg) -> list:
+    """The sweep's default commands, from the command ranges of a kbj_config (train.py:1211-1217): stand; forward (vx_hi), backward (vx_lo),
+    left (vy_hi), right (vy_lo), turn left (wz_hi) and turn right (wz_lo), each at half and at full range; one omni command (half of vx_hi,
+    vy_hi and wz_hi at once); one stand-bend command (half of bh_lo, rx_hi and ry_hi). 15 rows of 16 floats, arms at zero."""
+    def cmd(**kw):
+        c = [0.0] * L.NCMD
+        for k, v in kw.items():
+            c[constants.COMMAND_NAMES.index(k)] = float(v)
+        return tuple(c)
+    grid = [cmd()]
+    for name, end in (("xvel", kcfg.vx_hi), ("xvel", kcfg.vx_lo), ("yvel", kcfg.vy_hi), ("yvel", kcfg.vy_lo), ("yawrate", kcfg.wz_hi), ("yawrate", kcfg.wz_lo)):
+        grid += [cmd(**{name: 0.5 * end}), cmd(**{name: end})]
+    grid.append(cmd(xvel=0.5 * kcfg.vx_hi, yvel=0.5 * kcfg.vy_hi, yawrate=0.5 * kcfg.wz_hi))
+    grid.append(cmd(baseheight=0.5 * kcfg.bh_lo, baseroll=0.5 * kcfg.rx_hi, basepitch=0.5 * kcfg.ry_hi))
+    return grid
+
+
+@dataclasses.dataclass
+class SweepRecord:
+    """What a sweep left on the device, for whoever wants more than the table: the aux rows [T + 1, N, AUX SIZE] and the per-row output
+    [T, N, TERR SIZE] of kbj_tracking_stats; env n follows command n % len(commands)."""
+    aux: torch.Tensor
+    err: torch.Tensor
+    stats: np.ndarray
+
+
+def tracking_sweep(task, commands=None, repeats: int = 2, seconds=None, settle_seconds=None, seed_offset: int = 7919):
+    """The sweep behind HumanoidWalkingTask.tracking_sweep (see there): returns (entries, record) - one entry per command, and the SweepRecord
+    of what the run left on the device. Every call builds a context of its own for its env count and length and closes it again (validate()
+    caches its context; a response table is asked for now and then, and its env count follows the command list)."""
+    cfg = task.config
+    commands = default_command_grid(task.kcfg) if commands is None else commands
+    table = np.zeros((len(commands), L.NCMD), np.float32)
+    for i, c in enumerate(commands):
+        c = np.asarray(c, np.float32).reshape(-1)
+        if c.size > L.NCMD:
+            raise ValueError(f"command {i} has {c.size} components, a command has {L.NCMD}")
+        table[i, :c.size] = c
+    if len(commands) == 0 or repeats < 1:
+        raise ValueError("tracking_sweep needs at least one command and one repeat")
+    ncmd, n = len(commands), len(commands) * repeats
+    T = max(1, int(round((cfg.render_length_seconds if seconds is None else seconds) / cfg.ctrl_dt)))
+    steps = settle_steps(cfg.tracking_settle_seconds if settle_seconds is None else settle_seconds, cfg.ctrl_dt)
+    dev = task.device
+    vcfg = dataclasses.replace(cfg, batch_size=n).to_kbj(n)
+    vcfg.rollout_len = T
+    vcfg.gae_bootstrap_truncation = vcfg.gae_tail_value = vcfg.gae_terminal_value = 0     # no GAE here: no tail pass, no terminal rows
+    vcfg.command_mode = 1
+    per_env = torch.from_numpy(np.tile(table, (repeats, 1))).to(dev)                      # env e follows command e % ncmd
+    terms = UserTerms(None, {name: (term, task.terms.obs_into[name]) for name, term in task.terms.observations.items() if task.terms.obs_into[name]},
+                      ScriptedCommand(per_env), task.terms.resets)
+    terms.bind(cfg.seed, task.rank, dev, task.model_blob, task.nobs_actor, task.nobs_critic)
+    ctx = B.Context(task.model_blob, vcfg, dev.index or 0, torch.cuda.current_stream().cuda_stream)
+    try:
+        carry = CarryBuffers(n, task.H, task.kcfg.depth, dev, mirror=task.mirror)
+        tr = TrajBuffers(T, n, task.H, task.kcfg.depth, dev, mirror=task.mirror, ld_actor=task.ld_actor, ld_critic=task.ld_critic)
+        seed = cfg.seed + seed_offset
+        ctx.env_reset_all(seed, tr.actor_obs[0], tr.critic_obs[0], tr.aux[0])
+        feeds = [terms.observe_rows] if any(task.extra_obs) else []
+        terms.run_hooks(ctx, tr, 0, seed_offset, [terms.apply_resets, terms.apply_command] + feeds)
+        terms.run_steps(ctx, tr, carry, task.params, T, seed=seed, first_step=0, argmax=True, first_index=seed_offset,
+                        hooks=[terms.apply_resets] + feeds + [terms.apply_command])       # validate()'s order
+        err = torch.empty(T, n, R["SIZE"], device=dev)
+        stats = fresh_tracking_stats(ctx, tr.c, n, steps, dev, err)
+        ctx.synchronize()
+        e, done, vec = err.cpu().numpy().astype(np.float64), tr.done.cpu().numpy(), stats.cpu().numpy()
+    finally:
+        ctx.close()
+    settled = e[:, :, R["SETTLED"]] != 0
+    out = []
+    for i in range(ncmd):
+        envs = range(i, n, ncmd)
+        entry = dict(command=tuple(float(x) for x in table[i]), mode=constants.COMMAND_MODE_NAMES[command_mode(table[i])])
+        for k, name in enumerate(constants.TRACKING_ERROR_NAMES):      # per env the mean over its settled rows, then the mean over the repeats that have any
+            means = [e[settled[:, j], j, k].mean() for j in envs if settled[:, j].any()]
+            entry[name] = float(np.mean(means)) if means else float("nan")
+        entry["settled_rows"] = int(sum(settled[:, j].sum() for j in envs))
+        entry["failures_per_s"] = float(sum((done[:, j] < 0).sum() for j in envs)) / (repeats * T * cfg.ctrl_dt)
+        out.append(entry)
+    return out, SweepRecord(tr.aux, err, vec)
+
+
+def format_tracking_table(entries) -> str:
+    """tracking_sweep's result as a text table: one line per command (its non-zero components by name), the five settled-row mean errors,
+    the settled row count and the failures per second."""
+    def label(cmd):
+        parts = [f"{constants.COMMAND_NAMES[k]}={v:+.2f}" for k, v in enumerate(cmd) if v != 0]
+        return " ".join(parts) if parts else "(zero)"
+    names = constants.TRACKING_ERROR_NAMES
+    labels = [label(x["command"]) for x in entries]
+    w = max([len("command")] + [len(s) for s in labels])
+    lines = [f"{'command':{w}s}  {'mode':10s}" + "".join(f"  {n:>12s}" for n in names) + f"  {'settled':>8s}  {'fail/s':>8s}"]
+    for s, x in zip(labels, entries):
+        lines.append(f"{s:{w}s}  {x['mode']:10s}" + "".join(f"  {x[n]:12.4f}" for n in names) + f"  {x['settled_rows']:8d}  {x['failures_per_s']:8.3f}")
+    return "\n".join(lines)

@@ -53,6 +53,11 @@ COMMAND_NAMES = (
 # 65-float actor row exactly as run_actor packs it, `carry` is the flat (depth, 2, H) LSTM carry followed by the 20 low-pass floats
 STEP_FN_INPUTS = ("joint_angles", "joint_angular_velocities", "projected_gravity", "gyroscope", "command", "carry")
 
+# the command modes of UnifiedCommand in the order of its switch list (train.py:752-762; kbj_model.h KBJ_CMODE_*), and the five tracking
+# errors kbj_tracking_stats keeps per row (kbj_model.h KBJ_TERR_*)
+COMMAND_MODE_NAMES = ("forward", "sideways", "rotate", "omni", "stand_bend", "stand")
+TRACKING_ERROR_NAMES = ("lin_vel_err", "yaw_rate_err", "tilt_err", "height_err", "arm_sq_err")
+
 REWARD_NAMES = (
     "linvel", "angvel", "roll_pitch", "base_height", "arm_pos", "single_contact", "no_contact_p",
     "feet_airtime", "feet_orient", "com_distance", "base_accel", "torque",

@@ -104,6 +104,13 @@ QSTATE = dict(QPOS=0, QVEL=27, QPOS_KIN=53, SIZE=80)      # kbj_model.h KBJ_QSTA
 EACC = dict(RETURN=0, LENGTH=1, TERM=2, SIZE=16)
 EPST = dict(EPISODES=0, FAIL_HEIGHT=1, FAIL_OTHER=2, TRUNCATED=3, RETURN_SUM=4, RETURN_SUMSQ=5, RETURN_MIN=6, RETURN_MAX=7,
             LENGTH_SUM=8, LENGTH_MAX=9, FAIL_LENGTH_SUM=10, TERM_SUM=12, SIZE=32)
+# kbj_model.h KBJ_CMODE_* / KBJ_TERR_* / KBJ_TACC_* / KBJ_TRK_*: command mode of a row, one row of the per-row output (fp32), the per-env carry row
+# (fp32) and one kbj_tracking_stats call's result (float64: mode m's slot s at m * MODE_STRIDE + s, then the two counters)
+NTERR = 5
+CMODE = dict(FORWARD=0, SIDEWAYS=1, ROTATE=2, OMNI=3, STAND_BEND=4, STAND=5, COUNT=6)
+TERR = dict(LIN=0, YAW=1, TILT=2, HEIGHT=3, ARM=4, MODE=5, SETTLED=6, SINCE=7, SIZE=8)
+TACC = dict(CMD=0, SINCE=16, RUNNING=17, SIZE=20)
+TRK = dict(ROWS=0, SETTLED=1, SUM=2, SUMSQ=7, MAX=12, MODE_STRIDE=20, CHANGES=120, EPISODES=121, SIZE=128)
 # pieces of a packed observation row in the reference's concatenation order (kbj_model.h KBJ_OBS_*; train.py:1367-1374, 1410-1430):
 # name -> (offset, width); the first six are common to the actor and the critic row
 OBS = dict(JPOS=(0, 20), JVEL=(20, 20), PG=(40, 5), GYRO=(45, 3), ZEROCMD=(48, 1), CMD=(49, 16), TOUCH=(65, 2), FEETPOS=(67, 6), BASEPOS=(73, 3),
