@@ -86,6 +86,21 @@ int kbj_env_reset_where(kbj_ctx* ctx, const float* mask_d, float* actor_next_d, 
  * their joystick command - in the env state (the next kbj_env_step starts from it; run with command_mode = 1 so the kernel's own
  * switch draw does not replace it) and in the command columns + zero-command flag of the NEXT observation rows and aux record. */
 int kbj_env_set_command(kbj_ctx* ctx, const float* mask_d, const float* cmd_d, float* actor_next_d, float* critic_next_d, float* aux_next_d);
+/* replaces: a user-written Event term evaluated by the host between two control steps (the reference lists its events in get_events,
+ * train.py:1134-1144; ksim's Event protocol itself is un-vendored, so the protocol of host/user_terms.py is this build's own). Writes the
+ * event state the step kernel's ForcePushEvent reads at the start of every control step - nothing else: no observation, no aux row (a push
+ * is in no observation). For every env whose mask_d [N] float entry is non-zero (NULL = every env):
+ *   KBJ_ES_PUSH[0:6] = wrench_d's row [N][6]: force (N) then torque (N m), world frame, applied at the base body as the built-in event's;
+ *   KBJ_ES_PUSH_REM  = steps_d[env];
+ *   KBJ_ES_PUSH_NXT  = next_d[env] when next_d is given (NULL: untouched).
+ * Both counters are floats holding whole numbers of CONTROL steps, as the kernel keeps them: steps = s pushes exactly the next s env
+ * steps (the kernel counts REM down once per step while it is > 0 and applies the wrench on those steps); while REM > 0 it does not count
+ * NXT down; when REM is 0 and NXT <= 0 the built-in event draws its own wrench, duration and interval. next = KBJ_PUSH_NEVER (kbj_model.h)
+ * keeps the built-in event from drawing. An in-step reset (a termination inside kbj_env_step, kbj_env_reset_where) clears the wrench and REM
+ * and re-arms the built-in schedule with a fresh NXT draw: a host that scripts pushes must write NXT again on the envs whose episode has
+ * just started. Values are taken as they are; the host checks them (host/user_terms.py apply_events). Asynchronous on the context's stream;
+ * other envs are untouched. A context with enable_pushes == 0 is refused with that reason: its step kernel ignores the event state. */
+int kbj_env_set_push(kbj_ctx* ctx, const float* mask_d, const float* wrench_d /* [N][6] */, const float* steps_d /* [N] */, const float* next_d /* [N] or NULL */);
 /* replaces: user-written Reset terms in the reference's protocol (`Reset.__call__(data, curriculum_level, rng) -> data`, train.py:833-844: the in-tree
  * PlaneXYPositionReset reads `data.qpos` and returns the data with a new one), evaluated by the host on the envs that have just been re-initialised
  * (by the step kernel's own terminations, kbj_env_reset_where or kbj_env_reset_all), AFTER the built-in resets of train.py:1146-1153 as in the
@@ -277,6 +292,43 @@ int kbj_episode_stats(kbj_ctx* ctx, const kbj_traj* traj, float* acc_d, double* 
  * before anything is launched, on a NULL acc_d or stats_d, on an acc_d, err_d or traj->aux_d that is not 16-byte aligned, and on
  * settle_steps < 0. */
 int kbj_tracking_stats(kbj_ctx* ctx, const kbj_traj* traj, int settle_steps, float* acc_d, double* stats_d, float* err_d);
+
+/* ---- push recovery ---------------------------------------------------------------------------- */
+/* replaces: shoving the robot and watching whether it stays up (what a locomotion policy is judged by before it goes on the robot), as
+ * numbers: for one scheduled push per env, what became of it. Reads err_d [T][N][KBJ_TERR_SIZE], the per-row output of kbj_tracking_stats on
+ * the same trajectory, the DONE column of rows 0 .. T-1 of traj->aux_d, and sched_d [N][2] int32 = (s, d): the push is applied during the d
+ * rows s .. s + d - 1 (d < 0 counts as 0); s < 0 = no push for this env.
+ * "Within" on row t: err[t][k] <= crit->tol[k] for every error k (KBJ_TERR_* order) whose tolerance is not +inf. A NaN error is not within;
+ * a column whose tolerance is +inf is not looked at, whatever it holds (a NaN too). The tolerances are SETTINGS of the caller, not measured
+ * thresholds.
+ * Per env, with hold = crit->hold_steps >= 1 and window = crit->window_steps >= 0 (kbj_model.h KBJ_POUT_*, KBJ_PREC_*):
+ *   s < 0: NONE.
+ *   VOID: s >= T, or s < hold, or any of the rows [s - hold, s) is not within or has DONE != 0 (the env was not tracking its command, or
+ *   had just ended an episode, when the push came: the push says nothing about recovery).
+ *   Otherwise the rows t = s .. min(T, s + d + window) - 1 are scanned in order. On each row first the peaks: PEAK_LIN, PEAK_YAW, PEAK_TILT,
+ *   PEAK_HEIGHT become the row's error where it is greater (they start at -1; a NaN is never greater), PEAK_ROW = t whenever PEAK_TILT
+ *   rises. Then, in this order:
+ *     1. DONE[t] < 0: FELL, FALL_STEPS = t - s. Stop.
+ *     2. DONE[t] > 0: CENSORED. Stop.
+ *     3. for t >= s + d the length of the run of consecutive within rows is kept (a row that is not within returns it to 0); when it reaches
+ *        hold: RECOVERED, RECOVER_STEPS = (t - hold + 1) - (s + d), the rows from the end of the push to the first row of the run. Stop.
+ *   Undecided at the end: CENSORED if s + d + window > T (the trajectory cut the window), else UNRECOVERED.
+ * rec_d [N][KBJ_PREC_SIZE] fp32 is overwritten; fields that do not apply are -1 (all but the outcome for NONE and VOID). It holds whole
+ * numbers and maxima of fp32 inputs: a host restatement reproduces it exactly (tests/push_ref.py).
+ * stats_d: NULL, or [G][KBJ_PSTAT_SIZE] doubles, overwritten (spare slots 0): per group g the envs per outcome; over its RECOVERED envs the sum,
+ * sum of squares and maximum of RECOVER_STEPS; over its FELL envs those of FALL_STEPS; over its FELL, RECOVERED, UNRECOVERED and CENSORED
+ * envs the sum and maximum of each peak. A maximum over nothing is -1. group_d [N] int32 names every env's group (NULL: all in group 0; a
+ * value outside [0, G) puts the env in no group), 1 <= G <= 256. A group's envs are combined in env order, in doubles, without atomics: a call
+ * is bit-reproducible, with or without stats_d.
+ * Asynchronous on the context's stream; crit is read before the call returns. Fails with a message, before anything is launched, on a NULL
+ * traj, err_d, sched_d, crit or rec_d, on a trajectory without aux_d or positive T, N, on an err_d or rec_d that is not 16-byte aligned or a
+ * sched_d that is not 8-byte aligned, on hold_steps < 1, window_steps < 0, a NaN tolerance, and with stats_d on G outside [1, 256]. */
+typedef struct kbj_push_criteria {
+  float tol[KBJ_NTERR];
+  int32_t hold_steps, window_steps;
+} kbj_push_criteria;
+int kbj_push_recovery(kbj_ctx* ctx, const kbj_traj* traj, const float* err_d, const int32_t* sched_d, const kbj_push_criteria* crit,
+                      float* rec_d, const int32_t* group_d, int G, double* stats_d);
 
 /* ---- PPO update, rows a9, a12, a13 ---------------------------------------------------------- */
 /* replaces: ksim GAE (gamma, lam: train.py:1769-1770). done from aux; adv_d/target_d [T][N].

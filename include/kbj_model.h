@@ -237,8 +237,8 @@ enum {
   KBJ_ES_ACT_PREV = 80,   /* [20] action applied during the previous control step */
   KBJ_ES_CMD      = 100,  /* [16] */
   KBJ_ES_PUSH     = 116,  /* [6] force(3) torque(3) world frame */
-  KBJ_ES_PUSH_REM = 122,  /* substeps of push remaining */
-  KBJ_ES_PUSH_NXT = 123,  /* substeps until the next push starts */
+  KBJ_ES_PUSH_REM = 122,  /* control steps of push remaining (a float holding a whole number; the step kernel counts it down once per control step) */
+  KBJ_ES_PUSH_NXT = 123,  /* control steps until the built-in event draws its next push (not counted down while PUSH_REM > 0); KBJ_PUSH_NEVER holds it off */
   KBJ_ES_TIME     = 124,  /* control steps since episode start */
   KBJ_ES_PGLAG    = 125,  /* [3] lagged projected gravity */
   KBJ_ES_EPISODE  = 128,  /* uint32 episode counter (RNG stream) */
@@ -353,6 +353,47 @@ enum {
   KBJ_TRK_CHANGES     = 120,  /* rows whose command differs from the previous row's inside a running episode */
   KBJ_TRK_EPISODES    = 121,  /* rows that start an episode (no previous row, or the previous row ended its episode) */
   KBJ_TRK_SIZE        = 128
+};
+
+/* ---- scripted pushes and push recovery (kbj_env_set_push, kbj_push_recovery) ----
+ * The KBJ_ES_PUSH_NXT value that keeps the built-in ForcePushEvent from drawing: 2^24, an exactly countable fp32 (x - 1 is exact all the way
+ * down), about 93 h of control steps at 50 Hz. */
+#define KBJ_PUSH_NEVER 16777216.0f
+/* Outcome of one env's scheduled push (kbj.h kbj_push_recovery). */
+enum {
+  KBJ_POUT_NONE        = 0,   /* no push scheduled (start row < 0) */
+  KBJ_POUT_VOID        = 1,   /* the push says nothing: it starts outside the trajectory, or the env was not tracking / had just ended an episode before it */
+  KBJ_POUT_FELL        = 2,   /* a failure (DONE < 0) inside the window */
+  KBJ_POUT_RECOVERED   = 3,   /* hold_steps consecutive rows within the tolerances after the push ended */
+  KBJ_POUT_UNRECOVERED = 4,   /* the whole window was seen, without a fall and without such a run */
+  KBJ_POUT_CENSORED    = 5,   /* a time-out (DONE > 0) or the end of the trajectory cut the window before a decision */
+  KBJ_POUT_COUNT       = 6
+};
+#define KBJ_NPEAK 4 /* peak errors kept per push: KBJ_TERR_LIN, _YAW, _TILT, _HEIGHT */
+/* One env's result row ("PREC" record, fp32: whole numbers and maxima of fp32 inputs). A field that does not apply is -1. */
+enum {
+  KBJ_PREC_OUTCOME       = 0,   /* KBJ_POUT_* */
+  KBJ_PREC_RECOVER_STEPS = 1,   /* RECOVERED: rows from the end of the push to the first row of the hold run */
+  KBJ_PREC_FALL_STEPS    = 2,   /* FELL: rows from the start of the push to the failing row */
+  KBJ_PREC_PEAK_LIN      = 3,   /* largest KBJ_TERR_LIN over the scanned rows (FELL, RECOVERED, UNRECOVERED, CENSORED), */
+  KBJ_PREC_PEAK_YAW      = 4,   /* KBJ_TERR_YAW, */
+  KBJ_PREC_PEAK_TILT     = 5,   /* KBJ_TERR_TILT, */
+  KBJ_PREC_PEAK_HEIGHT   = 6,   /* KBJ_TERR_HEIGHT */
+  KBJ_PREC_PEAK_ROW      = 7,   /* the first row at which PEAK_TILT is reached */
+  KBJ_PREC_SIZE          = 8
+};
+/* One group's statistics ("PSTAT" record, doubles). A maximum over nothing is -1; spare slots are 0. */
+enum {
+  KBJ_PSTAT_COUNT      = 0,   /* [6] envs per outcome, KBJ_POUT_* order */
+  KBJ_PSTAT_REC_SUM    = 6,   /* over the RECOVERED envs: sum of RECOVER_STEPS, */
+  KBJ_PSTAT_REC_SUMSQ  = 7,   /* of its square, */
+  KBJ_PSTAT_REC_MAX    = 8,   /* its maximum */
+  KBJ_PSTAT_FALL_SUM   = 9,   /* over the FELL envs: sum of FALL_STEPS, */
+  KBJ_PSTAT_FALL_SUMSQ = 10,  /* of its square, */
+  KBJ_PSTAT_FALL_MAX   = 11,  /* its maximum */
+  KBJ_PSTAT_PEAK_SUM   = 12,  /* [4] over the FELL, RECOVERED, UNRECOVERED and CENSORED envs: sum of each peak, KBJ_PREC_PEAK_LIN.. order, */
+  KBJ_PSTAT_PEAK_MAX   = 16,  /* [4] its maximum */
+  KBJ_PSTAT_SIZE       = 24
 };
 
 /* reward component order (train.py:1225-1256) */

@@ -1,11 +1,12 @@
 // kbj_env.hip — HIP kernels + C-ABI entry points of the environment side of the hot path:
 // kbj_env_reset_all / kbj_env_step (one wavefront = one env, state in LDS; kbj_env_*.h), kbj_rewards and kbj_episode_stats
-// (kbj_episode_stats.h).
+// (kbj_episode_stats.h), kbj_tracking_stats (kbj_tracking_stats.h), kbj_env_set_push and kbj_push_recovery (kbj_push_recovery.h).
 #include <hip/hip_runtime.h>
 #include "kbj_env_task.h"
 #include "kbj_episode_stats.h"
 #include "kbj_tracking_stats.h"
 #include "kbj_ctx.h"
+#include "kbj_push_recovery.h"
 
 using namespace kbj;
 
@@ -130,6 +131,18 @@ __global__ __launch_bounds__(256) void env_set_command_kernel(int N, int lda, in
     actor_next[(size_t)env * lda + KBJ_OBS_ZEROCMD] = zc;
     critic_next[(size_t)env * ldc + KBJ_OBS_ZEROCMD] = zc;
   }
+}
+
+// overwrite the push-event state of the envs whose mask entry is non-zero (mask == nullptr: all envs): the wrench, the control steps it is
+// still applied for and, when `next` is given, the control steps until the built-in event draws again - the words task_step's ForcePushEvent
+// reads at the start of the next control step. No observation row holds any of it. One thread per (env, slot): slots 0-5 the wrench, 6 REM, 7 NXT.
+__global__ __launch_bounds__(256) void env_set_push_kernel(int N, float* __restrict__ es, const float* __restrict__ mask, const float* __restrict__ wrench, const float* __restrict__ steps,
+                                                           const float* __restrict__ next) {
+  static_assert(KBJ_ES_PUSH_REM == KBJ_ES_PUSH + 6 && KBJ_ES_PUSH_NXT == KBJ_ES_PUSH + 7, "the push block of the env state row");
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, env = i / 8, k = i % 8;
+  if (env >= N || (mask && mask[env] == 0.0f)) return;
+  if (k == 7 && !next) return;
+  es[(size_t)env * KBJ_ES_SIZE + KBJ_ES_PUSH + k] = k < 6 ? wrench[(size_t)env * 6 + k] : k == 6 ? steps[env] : next[env];
 }
 
 // register budget of the step kernel: 13.4 KB of LDS lets 12 single-wavefront workgroups share a CU (3 waves/SIMD), which
@@ -413,6 +426,16 @@ int kbj_env_set_command(kbj_ctx* ctx, const float* mask_d, const float* cmd_d, f
   return 0;
 }
 
+int kbj_env_set_push(kbj_ctx* ctx, const float* mask_d, const float* wrench_d, const float* steps_d, const float* next_d) {
+  if (!ctx || !wrench_d || !steps_d) return kbj_fail(ctx, "kbj_env_set_push: null argument");
+  if (!ctx->cfg_h.enable_pushes) return kbj_fail(ctx, "kbj_env_set_push: this context was created with enable_pushes = 0: its step kernel ignores the push-event state");
+  KBJ_HIP(ctx, hipSetDevice(ctx->device));
+  const int N = ctx->cfg_h.num_envs, n = N * 8;
+  hipLaunchKernelGGL(env_set_push_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, N, ctx->es_d, mask_d, wrench_d, steps_d, next_d);
+  KBJ_CHECK_LAUNCH(ctx, "env_set_push_kernel");
+  return 0;
+}
+
 int kbj_env_get_qstate(kbj_ctx* ctx, float* qpos_d, float* qvel_d) {
   if (!ctx || !qpos_d || !qvel_d) return kbj_fail(ctx, "kbj_env_get_qstate: null argument");
   KBJ_HIP(ctx, hipSetDevice(ctx->device));
@@ -525,6 +548,28 @@ int kbj_tracking_stats(kbj_ctx* ctx, const kbj_traj* tr, int settle_steps, float
   KBJ_CHECK_LAUNCH(ctx, "tracking_stats_kernel");
   hipLaunchKernelGGL(tracking_stats_reduce_kernel, dim3(1), dim3(TRK_RED_THREADS), 0, ctx->stream, ctx->trk_part_d, blocks, stats_d);
   KBJ_CHECK_LAUNCH(ctx, "tracking_stats_reduce_kernel");
+  return 0;
+}
+
+int kbj_push_recovery(kbj_ctx* ctx, const kbj_traj* tr, const float* err_d, const int32_t* sched_d, const kbj_push_criteria* crit, float* rec_d,
+                      const int32_t* group_d, int G, double* stats_d) {
+  if (!ctx || !tr || !err_d || !sched_d || !crit || !rec_d) return kbj_fail(ctx, "kbj_push_recovery: null argument");
+  if (!tr->aux_d || tr->T <= 0 || tr->N <= 0) return kbj_fail(ctx, "kbj_push_recovery: the trajectory needs aux_d and positive T, N");
+  if ((reinterpret_cast<uintptr_t>(err_d) | reinterpret_cast<uintptr_t>(rec_d)) & 15) return kbj_fail(ctx, "kbj_push_recovery: err_d and rec_d must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(sched_d) & 7) return kbj_fail(ctx, "kbj_push_recovery: sched_d must be 8-byte aligned");
+  if (crit->hold_steps < 1) return kbj_fail(ctx, "kbj_push_recovery: hold_steps must be at least 1");
+  if (crit->window_steps < 0) return kbj_fail(ctx, "kbj_push_recovery: window_steps must not be negative");
+  for (int k = 0; k < KBJ_NTERR; ++k)
+    if (crit->tol[k] != crit->tol[k]) return kbj_fail(ctx, "kbj_push_recovery: a tolerance is NaN (+inf ignores a column)");
+  if (stats_d && (G < 1 || G > PR_RED_THREADS)) return kbj_fail(ctx, "kbj_push_recovery: G must be in [1, 256]");
+  static_assert(PR_RED_THREADS == 256, "the G range kbj.h documents");
+  KBJ_HIP(ctx, hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(push_recovery_kernel, dim3((tr->N + PR_ENVS - 1) / PR_ENVS), dim3(PR_ENVS), 0, ctx->stream, err_d, tr->aux_d, tr->T, tr->N, sched_d, *crit, rec_d);
+  KBJ_CHECK_LAUNCH(ctx, "push_recovery_kernel");
+  if (stats_d) {
+    hipLaunchKernelGGL(push_recovery_reduce_kernel, dim3(1), dim3(PR_RED_THREADS), 0, ctx->stream, rec_d, group_d, tr->N, G, stats_d);
+    KBJ_CHECK_LAUNCH(ctx, "push_recovery_reduce_kernel");
+  }
   return 0;
 }
 

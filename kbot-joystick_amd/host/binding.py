@@ -44,6 +44,12 @@ class DeployInputs(C.Structure):
                 ("gyroscope_d", C.c_void_p), ("command_d", C.c_void_p)]
 
 
+class PushCriteria(C.Structure):
+    """kbj_push_criteria: the tolerance of each tracking error (layout.TERR order; +inf ignores a column), the rows a recovery must hold and
+    the rows behind the push that are watched."""
+    _fields_ = [("tol", C.c_float * L.NTERR), ("hold_steps", C.c_int32), ("window_steps", C.c_int32)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("launches", C.c_int32), ("total_ms", C.c_float), ("flops", C.c_double)]
 
@@ -70,6 +76,7 @@ SIGNATURES = {
     "kbj_env_record_state": (_i, [_vp, _vp]),
     "kbj_env_reset_where": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "kbj_env_set_command": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "kbj_env_set_push": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "kbj_env_get_qstate": (_i, [_vp, _vp, _vp]),
     "kbj_env_set_qstate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "kbj_env_get_state": (_i, [_vp, _vp, _vp]),
@@ -95,6 +102,7 @@ SIGNATURES = {
     "kbj_gae": (_i, [_vp, C.POINTER(Traj), _vp, _vp]),
     "kbj_episode_stats": (_i, [_vp, C.POINTER(Traj), _vp, _vp]),
     "kbj_tracking_stats": (_i, [_vp, C.POINTER(Traj), _i, _vp, _vp, _vp]),
+    "kbj_push_recovery": (_i, [_vp, C.POINTER(Traj), _vp, _vp, C.POINTER(PushCriteria), _vp, _vp, _i, _vp]),
     "kbj_ppo_grad": (_i, [_vp, _vp, C.POINTER(Traj), _vp, _i, _vp, _vp, _vp, _vp]),
     "kbj_ppo_forward": (_i, [_vp, _vp, C.POINTER(Traj), _vp, _i, C.POINTER(PpoVars)]),
     "kbj_stream_wait_actor_grad": (_i, [_vp, _vp]),
@@ -224,6 +232,12 @@ class Context:
         """mask None = every env; cmd [N, 16] float32 on the device."""
         self.call("kbj_env_set_command", _ptr(mask) if mask is not None else None, _ptr(cmd), _ptr(actor_next), _ptr(critic_next), _ptr(aux_next))
 
+    def env_set_push(self, mask, wrench, steps, next=None):
+        """kbj_env_set_push: for the envs of mask [N] float32 (None = every env) the push wrench [N, 6] (force, torque; world frame), the control
+        steps it is applied for [N] and, with `next` [N], the control steps until the built-in event draws again (layout.PUSH_NEVER: never);
+        float32 device tensors. Asynchronous; no observation row changes."""
+        self.call("kbj_env_set_push", _ptr(mask), _ptr(wrench), _ptr(steps), _ptr(next))
+
     def env_get_qstate(self, qpos, qvel):
         """kbj_env_get_qstate: every env's qpos [N, 27] / qvel [N, 26] into device tensors (asynchronous)."""
         self.call("kbj_env_get_qstate", _ptr(qpos), _ptr(qvel))
@@ -330,6 +344,12 @@ class Context:
         """kbj_tracking_stats: acc [N, TACC SIZE] float32 (updated in place), stats [TRK SIZE] float64 (overwritten), err None or
         [T, N, TERR SIZE] float32 (every row's errors, mode, settled flag, since), all on the device."""
         self.call("kbj_tracking_stats", C.byref(traj), int(settle_steps), _ptr(acc), _ptr(stats), _ptr(err))
+
+    def push_recovery(self, traj: Traj, err, sched, criteria: PushCriteria, rec, group=None, G: int = 1, stats=None):
+        """kbj_push_recovery: err [T, N, TERR SIZE] float32 (kbj_tracking_stats' per-row output), sched [N, 2] int32 (start row, pushed steps;
+        start < 0: no push), rec [N, PREC SIZE] float32 (overwritten), group None or [N] int32 in [0, G), stats None or [G, PSTAT SIZE]
+        float64 (overwritten), all on the device."""
+        self.call("kbj_push_recovery", C.byref(traj), _ptr(err), _ptr(sched), C.byref(criteria) if criteria is not None else None, _ptr(rec), _ptr(group), int(G), _ptr(stats))
 
     def ppo_grad(self, params, traj: Traj, env_idx, B, adv, target, grad, metrics):
         self.call("kbj_ppo_grad", _ptr(params), C.byref(traj), _ptr(env_idx), B, _ptr(adv), _ptr(target), _ptr(grad),

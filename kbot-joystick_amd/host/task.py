@@ -28,6 +28,7 @@ from .buffers import CarryBuffers, TrajBuffers
 from .ckpt import ModelView
 from .config import HumanoidWalkingTaskConfig, cosine_decay_lr, launch_config      # launch_config: re-exported with the rest
 from .episode import EpisodeStats, episode_stats_scalars, fresh_episode_stats
+from .push import PushRecord, ScriptedPush, format_push_table, push_sweep      # noqa: F401 (re-exported)
 from .tracking import TrackingStats, format_tracking_table, fresh_tracking_stats, settle_steps, tracking_scalars, tracking_sweep      # noqa: F401 (re-exported)
 from .user_terms import UserTerms
 
@@ -52,7 +53,7 @@ class HumanoidWalkingTask:
 
     def __init__(self, config: HumanoidWalkingTaskConfig, device: Optional[torch.device] = None, rank: int = 0, world_size: int = 1,
                  extra_rewards: Optional[dict] = None, extra_terminations: Optional[dict] = None, extra_observations: Optional[dict] = None,
-                 command=None, extra_resets: Optional[list] = None):
+                 command=None, extra_resets: Optional[list] = None, extra_events: Optional[dict] = None):
         """extra_rewards: {name: term} of Python reward terms in ksim's Reward protocol (`scale`, `get_reward(trajectory)` or the stateful
         pair), evaluated on `TrajectoryView` after every rollout and added to the built-in stack's reward (host/traj_view.py).
         extra_terminations: {name: term}, `term(state, curriculum_level) -> [N] in {-1, 0, 1}` (train.py:817) on a `StepView` after every
@@ -69,10 +70,18 @@ class HumanoidWalkingTask:
         `data.qpos` / `data.qvel`), applied in list order - behind the built-in resets of train.py:1146-1153, as further entries of that list would
         be - to the envs that have just been re-initialised; the result is written back by kbj_env_set_qstate, which also rewrites their next
         observation rows (host/traj_view.ResetData; `rng` is a torch.Generator seeded from (seed, step index)).
+        extra_events: {name: term} of Event terms - scripted disturbances beside the built-in ForcePushEvent of get_events() (train.py:1134-1144).
+        ksim's Event class is un-vendored, so the protocol is this build's own (host/user_terms.py apply_events): optional
+        `term.initial_event_state(state, curriculum_level, rng)`, and `term(state, event_state, curriculum_level, rng) -> (push, event_state)` with
+        `push` None or a `traj_view.PushRequest(mask, wrench, steps[, next])`, evaluated after every control step behind the Reset terms and in
+        front of the Command term; the wrench is written into the env state by kbj_env_set_push and acts from the next control step on. Needs
+        the built-in event's switch on (`enable_pushes`; checked here): the step kernel reads the event state only then. Event state is kept per
+        library context - validate() runs the terms on a state of its own, started afresh every time - and is not checkpointed: a resumed
+        run starts it from `initial_event_state`.
         With any of these the rollout runs step by step from the host (policy step, env step, user terms, carry reset: the same calls
         kbj_rollout fuses, bit-identical when no user term fires) instead of as one kbj_rollout call."""
         self.extra_rewards = dict(extra_rewards or {})
-        self.terms = UserTerms(extra_terminations, extra_observations, command, extra_resets)     # host/user_terms.py
+        self.terms = UserTerms(extra_terminations, extra_observations, command, extra_resets, extra_events)     # host/user_terms.py
         self.extra_obs_buffers = self.terms.obs_buffers
         self._extra_carries: dict = {}
         self.extra_reward_means: dict = {}
@@ -99,6 +108,9 @@ class HumanoidWalkingTask:
         self.kcfg = config.to_kbj(self.N, env_id_offset=env_off)
         if command is not None:
             self.kcfg.command_mode = 1          # resets write fixed_command (zeros unless configured); the term overwrites it every step
+        if self.terms.events and not self.kcfg.enable_pushes:
+            raise ValueError("extra_events needs the push event's switch on (kbj_config.enable_pushes = 1): with it off the step kernel ignores the event "
+                             "state kbj_env_set_push writes, and the library refuses the call")
         self.T, self.H, self.B = self.kcfg.rollout_len, self.kcfg.hidden_size, self.kcfg.batch_size
         self.model_blob = self.get_mujoco_model()
         torch.cuda.set_device(self.device)     # torch ops of this task and the library's launches must target the same GPU
@@ -202,8 +214,28 @@ class HumanoidWalkingTask:
         kbj_tracking_stats call then gives every row's errors. Returns one dict per command: `command`, `mode`, the five settled-row mean
         errors (per env over its rows whose command has been held for `settle_seconds`, default tracking_settle_seconds, then averaged over
         the repeats), `settled_rows` and `failures_per_s`. `format_tracking_table` renders it. Works with `tracking_stats` off. Every call
-        creates a library context for its env count and length and closes it again (it is not cached as validate()'s is)."""
+        creates a library context for its env count and length and closes it again (it is not cached as validate()'s is). Event terms
+        (`extra_events`) do NOT run here: the table is about following the stick; push_sweep() is the one that shoves."""
         return tracking_sweep(self, commands, repeats, seconds, settle_seconds)[0]
+
+    def push_sweep(self, forces=(50.0, 100.0, 150.0, 200.0), directions_deg=(0, 45, 90, 135, 180, 225, 270, 315), duration: float = 0.2, command=None,
+                   push_at: float = 2.0, window: float = 3.0, hold: float = 0.5, tolerances: Optional[dict] = None, repeats: int = 4, torque=None,
+                   seed_offset: int = 7919):
+        """The robustness table: what push the CURRENT policy survives and how fast it is back on its command. One case per (force in N,
+        direction in degrees): a horizontal shove of `duration` seconds at the base, its direction in the robot's HEADING frame at the moment
+        of the push (0 = from behind, pushing it forward; 90 = to its left), plus `torque` (N m, same frame) if given. A context of its own
+        with len(forces) * len(directions_deg) * repeats envs (env e runs case e % cases; at most 256 cases) holds `command` (default: stand)
+        with argmax actions through the step-wise loop; the Event term host/push.ScriptedPush switches the built-in push event off (again
+        after every in-episode reset) and applies every env's push at row round(push_at / ctrl_dt); the user's Reset and network-input
+        Observation terms apply as in validate(), other Event terms and the Command term do not. kbj_tracking_stats then gives every row's
+        errors and kbj_push_recovery the outcome per env and the statistics per case: a push is VOID when the env was not within the
+        tolerances for `hold` seconds before it (or had just been reset); otherwise the env FELL, RECOVERED (within the tolerances for
+        `hold` seconds, inside `window` seconds after the push ended), stayed UNRECOVERED, or was CENSORED by a time-out. `tolerances`
+        ({error name: bound}, constants.TRACKING_ERROR_NAMES; missing names keep host/push.DEFAULT_TOLERANCES) are SETTINGS, echoed in every
+        entry - not measured thresholds. Returns (entries, record): per case the settings, `valid` pushes and `void` count, `fell_frac` /
+        `recovered_frac` / `unrecovered_frac` / `censored_frac` of the valid ones, `recovery_s_mean` / `_max`, `peak_tilt_mean` / `_max`,
+        `peak_lin_vel_err_mean` / `_max` (nan over nothing); and the PushRecord of the device data. `format_push_table` renders the entries."""
+        return push_sweep(self, forces, directions_deg, duration, command, push_at, window, hold, tolerances, repeats, torque, seed_offset)
 
     def episode_stats_vectors(self):
         """(last, total): this rank's raw KBJ_EPST vectors (float64 numpy, layout.EPST) behind episode_stats() - the episodes that finished in
@@ -255,10 +287,11 @@ class HumanoidWalkingTask:
         for buf in self.extra_obs_buffers.values():
             buf[0].copy_(buf[T])
         if not terms.started:                   # the state and the rows env_reset_all wrote: every env starts an episode, the user columns are zero
-            terms.run_hooks(c, tr, 0, first, [terms.apply_resets, terms.apply_command, terms.observe])
+            terms.run_hooks(c, tr, 0, first, [terms.apply_resets, terms.apply_events, terms.apply_command, terms.observe])
             terms.started = True
         terms.run_steps(c, tr, self.carry, self.params, T, seed=self.config.seed, first_step=first, argmax=False, first_index=first,
-                        hooks=[terms.apply_terminations, terms.apply_resets, terms.apply_command, terms.observe], terminal=bool(self.kcfg.gae_terminal_value))
+                        hooks=[terms.apply_terminations, terms.apply_resets, terms.apply_events, terms.apply_command, terms.observe],
+                        terminal=bool(self.kcfg.gae_terminal_value))
         if self.kcfg.gae_tail_value:          # V(s_T) for GAE, as kbj_rollout computes it: row T, the carries the last reset left, the rollout's parameters
             c.critic_value(self.params, tr.critic_obs[T], self.carry.c, tr.value_tail)
         c.rewards(tr.aux, T, tr.reward, tr.comps)
@@ -348,7 +381,8 @@ class HumanoidWalkingTask:
         return wiring.physics_randomizers(self.kcfg)
 
     def get_events(self) -> dict:
-        return wiring.events(self.kcfg)
+        """train.py:1134-1144: the built-in ForcePushEvent as a frozen view, then the user's Event terms (`extra_events`) under their names."""
+        return {**wiring.events(self.kcfg), **self.terms.events}
 
     def get_resets(self) -> list:
         return wiring.resets(self.kcfg)
@@ -532,7 +566,7 @@ class HumanoidWalkingTask:
     def validate(self, num_envs: int = 64, seconds: Optional[float] = None, seed_offset: int = 7919, _capture=None, _stepwise: bool = False) -> dict:
         """Deterministic validation rollout: a separate small env set (its own context, carries and buffers, so training state is
         untouched), actions = the distribution's mode, `render_length_seconds` long. Returns scalar statistics.
-        User Reset / Command / Observation terms are applied as in training; user TERMINATION terms (`extra_terminations`) are NOT - validation
+        User Reset / Event / Command / Observation terms are applied as in training; user TERMINATION terms (`extra_terminations`) are NOT - validation
         episodes end by the built-in terminations (bad z, tilt, episode length) only, on the fused and on the step-wise path alike.
         `_capture(ctx, frame)` (view()): called after the reset (frame 0) and after every control step."""
         seconds = self.config.render_length_seconds if seconds is None else seconds
@@ -551,14 +585,15 @@ class HumanoidWalkingTask:
         _, vctx, carry, tr = self._valid
         seed = self.config.seed + seed_offset
         carry.zero_()
+        terms.event_state_of(vctx).clear()      # every validation starts its Event terms afresh, in a state of its own (the context's): training's is untouched
         vctx.env_reset_all(seed, tr.actor_obs[0], tr.critic_obs[0], tr.aux[0])
         # the user's Reset and Command terms shape and drive the validation episodes as they do the training ones; of the Observation terms
         # only those that are network inputs matter here (they drive the validation policy too). The terms' step index is seed_offset + row.
         feeds = any(self.extra_obs)
-        terms.run_hooks(vctx, tr, 0, seed_offset, [terms.apply_resets, terms.apply_command] + ([terms.observe_rows] if feeds else []))
+        terms.run_hooks(vctx, tr, 0, seed_offset, [terms.apply_resets, terms.apply_events, terms.apply_command] + ([terms.observe_rows] if feeds else []))
         if _capture is not None:
             _capture(vctx, 0)
-        if _capture is None and not feeds and terms.command_term is None and not terms.resets and not _stepwise:
+        if _capture is None and not feeds and terms.command_term is None and not terms.resets and not terms.events and not _stepwise:
             # no user term and nothing to capture between the steps: ONE kbj_rollout call in argmax mode (the same kernels, bit-identical to the
             # step-by-step loop below, ~3 x fewer host calls: 0.05 instead of 0.15 s for 64 envs x 500 steps). kbj_rollout takes its first
             # observation from row T (the previous rollout's last), so the reset rows move there first.
@@ -572,7 +607,7 @@ class HumanoidWalkingTask:
             # NOT training's order (terminations, resets, command, observations): here the observations come BEFORE the command, so an Observation
             # term that reads the command columns of the row being written sees the previous command where training shows it the new one.
             # Kept as it is; unifying the two is a behaviour change of its own.
-            hooks = [terms.apply_resets] + ([terms.observe_rows] if feeds else []) + [terms.apply_command]
+            hooks = [terms.apply_resets, terms.apply_events] + ([terms.observe_rows] if feeds else []) + [terms.apply_command]
             if _capture is not None:
                 hooks.append(lambda s: _capture(vctx, s.row))
             terms.run_steps(vctx, tr, carry, self.params, T, seed=seed, first_step=0, argmax=True, first_index=seed_offset, hooks=hooks)

@@ -10,7 +10,7 @@ Nothing here touches the hot path's kernels: it is a plain torch epilogue after 
 """
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, NamedTuple, Optional
 
 import torch
 
@@ -81,6 +81,7 @@ class StepView:
         A, O = L.AUX, L.OBS
         self.N = aux_t.shape[0]
         self._model, self._qstate, self._kin = model, qstate_t, None
+        self.row = None                                          # the trajectory row this view shows (user_terms.Step.view sets it; Event terms schedule by it)
         # ---- post-step, pre-reset (what the kernel's own terminations and the reward stack read) ----
         self.base_qvel = aux_t[:, A["QVEL"]:A["QVEL"] + 6]
         self.base_quat = aux_t[:, A["BQUAT"]:A["BQUAT"] + 4]
@@ -170,6 +171,17 @@ def combine_terminations(terms: Dict[str, object], view: StepView, curriculum_le
             raise ValueError(f"termination {name!r} returned shape {tuple(v.shape)}, expected {tuple(out.shape)}")
         out = torch.where(out != 0, out, torch.sign(v))
     return out
+
+
+class PushRequest(NamedTuple):
+    """What a user-written Event term asks for (host/user_terms.py apply_events -> kbj_env_set_push): for the envs of `mask` [N] bool the
+    `wrench` [N, 6] - force (N) then torque (N m), world frame, applied at the base - for the next `steps` [N] control steps (whole numbers
+    in [0, layout.PUSH_NEVER]). `next` ([N], optional): the control steps until the BUILT-IN push event draws again, layout.PUSH_NEVER to
+    keep it from drawing; None leaves the built-in schedule alone. Rows of envs outside the mask are not read."""
+    mask: torch.Tensor
+    wrench: torch.Tensor
+    steps: torch.Tensor
+    next: Optional[torch.Tensor] = None
 
 
 class ResetData:

@@ -1,13 +1,15 @@
 """User-written Reset / Command / Observation / Termination terms in the reference's protocols (train.py:635, 682, 706, 724, 768, 817, 833),
-and the step-wise rollout that runs them between the env step and the carry reset. Training (HumanoidWalkingTask.rollout) and
+Event terms in this build's own protocol (apply_events), and the step-wise rollout that runs them between the env step and the carry reset. Training (HumanoidWalkingTask.rollout) and
 HumanoidWalkingTask.validate run the same loop, `UserTerms.run_steps`; each passes the hooks it wants, in the order it wants them."""
 from __future__ import annotations
+
+import weakref
 
 import torch
 
 from ..spec import layout as L
 from . import binding as B
-from .traj_view import ResetData, StepView, combine_terminations
+from .traj_view import PushRequest, ResetData, StepView, combine_terminations
 
 _DONE_BYTES = 4 * L.AUX["DONE"]       # the DONE column inside an aux row, as kbj_carry_reset takes it (base pointer + row stride)
 
@@ -27,6 +29,7 @@ class Step:
         `rewritten()` and the next hook gets a fresh one. (The command and the user columns, which the other hooks write, feed none of them.)"""
         if self._view is None:
             self._view = StepView(self.aux_prev, *self.rows, self.model, self.qstate)
+            self._view.row = self.row
         return self._view
 
     def rewritten(self):
@@ -37,11 +40,44 @@ class Step:
         return self.aux_prev[:, L.AUX["DONE"]] != 0 if self.row else None
 
 
+def check_push_request(name: str, req, n: int) -> PushRequest:
+    """An Event term's PushRequest for n envs, checked by field - shapes, then (one read-back) the values of the masked envs: finite, steps and
+    next whole numbers in [0, PUSH_NEVER] - and returned with float32 fields. Raises KbjError naming the term and the field."""
+    if not isinstance(req, PushRequest):
+        raise B.KbjError(f"Event term {name!r} returned {type(req).__name__} as its push, expected None or a PushRequest")
+    shapes = dict(mask=(n,), wrench=(n, 6), steps=(n,), next=(n,))
+    for field, shape in shapes.items():
+        v = getattr(req, field)
+        if field == "next" and v is None:
+            continue
+        if not torch.is_tensor(v) or tuple(v.shape) != shape:
+            raise B.KbjError(f"Event term {name!r} returned {field} of shape {tuple(v.shape) if torch.is_tensor(v) else type(v).__name__}, expected {shape}")
+    if req.mask.dtype != torch.bool:
+        raise B.KbjError(f"Event term {name!r} returned a mask of dtype {req.mask.dtype}, expected torch.bool")
+    m = req.mask
+    wrench, steps = req.wrench.to(torch.float32), req.steps.to(torch.float32)
+    nxt = None if req.next is None else req.next.to(torch.float32)
+    counts = lambda v: torch.isfinite(v) & (v == torch.floor(v)) & (v >= 0) & (v <= L.PUSH_NEVER)
+    bad = [(m[:, None] & ~torch.isfinite(wrench)).any(), (m & ~counts(steps)).any()] + ([(m & ~counts(nxt)).any()] if nxt is not None else [])
+    bad = torch.stack(bad).tolist()
+    if bad[0]:
+        raise B.KbjError(f"Event term {name!r} returned non-finite values in wrench")
+    for field, b in zip(("steps", "next"), bad[1:]):
+        if b:
+            raise B.KbjError(f"Event term {name!r} returned {field} that are not whole numbers in [0, {int(L.PUSH_NEVER)}] (control steps)")
+    return PushRequest(m, wrench, steps, nxt)
+
+
 class UserTerms:
     """The user's terms of one task, what they have produced (`obs_buffers`), and whether row 0 of a fresh task has been served (`started`)."""
 
-    def __init__(self, terminations=None, observations=None, command=None, resets=None):
+    def __init__(self, terminations=None, observations=None, command=None, resets=None, events=None):
         self.terminations = dict(terminations or {})
+        self.events = dict(events or {})
+        # what each Event term carries from row to row, PER CONTEXT ({ctx: {name: [N, ...] tensor or None}}): the training rollout and a
+        # validation run drive different env sets through the same terms, and neither may see the other's state
+        self.event_states = weakref.WeakKeyDictionary()
+        self.push_keep = None                 # the last kbj_env_set_push arguments: alive until the call has run (stream-ordered)
         # an observation term may be given as (term, into) with into in {"actor", "critic", "both"}: its output is then ALSO written into the
         # networks' input rows, behind the reference's columns (config.extra_actor_obs / extra_critic_obs floats, in dictionary order)
         self.observations, self.obs_into = {}, {}
@@ -66,7 +102,7 @@ class UserTerms:
         self.nobs = {"actor": nobs_actor, "critic": nobs_critic}
 
     def __bool__(self):
-        return bool(self.terminations or self.observations or self.command_term is not None or self.resets)
+        return bool(self.terminations or self.observations or self.command_term is not None or self.resets or self.events)
 
     def _generator(self, a: int, b: int, step_index: int) -> torch.Generator:
         g = torch.Generator(device=self.device)
@@ -113,6 +149,67 @@ class UserTerms:
         fresh = s.fresh()
         s.ctx.env_set_qstate(None if fresh is None else fresh.to(torch.float32), *self.reset_keep, *s.rows)
         s.rewritten()
+
+    def event_state_of(self, ctx) -> dict:
+        """{name: event state} of the Event terms for the env set of `ctx` (created empty; dropped with the context)."""
+        if ctx not in self.event_states:
+            self.event_states[ctx] = {}
+        return self.event_states[ctx]
+
+    def apply_events(self, s: Step):
+        """The user's Event terms, in dictionary order. The reference lists its events in get_events (train.py:1134-1144), but ksim's Event
+        class is un-vendored: THIS PROTOCOL IS THIS BUILD'S OWN, shaped after the Command protocol beside it. A term is called once per row:
+          `term.initial_event_state(state, curriculum_level, rng) -> [N, ...] tensor` (optional): the state the term carries, for the envs whose
+              episode starts at this row (all of them on row 0); without it the term carries what its first call returns, or None;
+          `term(state, event_state, curriculum_level, rng) -> (push, event_state)`: `push` is None or a traj_view.PushRequest.
+        `state` is the row's StepView (state.row: the trajectory row), `rng` a torch.Generator seeded from (seed, step index). Later terms win
+        on the envs they mask. The merged request goes to kbj_env_set_push: the wrench acts from the NEXT control step on, for `steps` steps;
+        no observation changes. An in-step reset clears a running push and re-arms the built-in event: a term that scripts pushes writes
+        `next` again on fresh envs. Checked here, on the host (this is the step-wise path, as in apply_resets): shapes, finite values, and
+        whole-numbered steps / next in [0, PUSH_NEVER] - on the masked envs, the only ones read. The event state belongs to the context the
+        row was stepped by (`event_state_of`): a validation run starts its own and leaves the training run's alone."""
+        if not self.events:
+            return
+        state = self.event_state_of(s.ctx)
+        view, fresh = s.view(), s.fresh()
+        n = s.rows[2].shape[0]
+        g = self._generator(1597334677, 2869860233, s.step_index)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        mask, wrench, steps, nxt = torch.zeros(n, dtype=torch.bool, device=self.device), torch.zeros(n, 6, **f32), torch.zeros(n, **f32), torch.zeros(n, **f32)
+        has_next = torch.zeros(n, dtype=torch.bool, device=self.device)
+        asked, with_next = 0, 0
+        for name, term in self.events.items():
+            st = state.get(name)
+            if hasattr(term, "initial_event_state"):      # both are evaluated and selected on the device, as apply_command does
+                init = term.initial_event_state(view, 1.0, g)
+                st = init if fresh is None or st is None else torch.where(fresh.reshape((n,) + (1,) * (init.dim() - 1)), init, st)
+            out = term(view, st, 1.0, g)
+            if not (isinstance(out, tuple) and len(out) == 2):
+                raise B.KbjError(f"Event term {name!r} must return (push, event_state), got {type(out).__name__}")
+            req, state[name] = out
+            if req is None:
+                continue
+            req = check_push_request(name, req, n)
+            m = req.mask
+            mask = mask | m
+            wrench, steps = torch.where(m[:, None], req.wrench, wrench), torch.where(m, req.steps, steps)
+            asked += 1
+            if req.next is not None:
+                nxt, has_next = torch.where(m, req.next, nxt), has_next | m
+                with_next += 1
+            else:
+                has_next = has_next & ~m
+        if not asked:
+            return
+        self.push_keep = (mask.to(torch.float32), wrench.contiguous(), steps.contiguous(), nxt.contiguous(), (mask & has_next).to(torch.float32), (mask & ~has_next).to(torch.float32))
+        m_all, w, st_, nx, m_next, m_plain = self.push_keep
+        if with_next == 0:
+            s.ctx.env_set_push(m_all, w, st_, None)
+        elif with_next == asked:          # every request names `next`: has_next covers the mask
+            s.ctx.env_set_push(m_all, w, st_, nx)
+        else:                             # which envs end up with a `next` is only known on the device: one call for each kind
+            s.ctx.env_set_push(m_plain, w, st_, None)
+            s.ctx.env_set_push(m_next, w, st_, nx)
 
     def apply_command(self, s: Step):
         """The user's Command term (train.py:724, 768): `initial_command` for the envs whose episode starts at this row, `__call__(prev_command,

@@ -58,6 +58,9 @@ STEP_FN_INPUTS = ("joint_angles", "joint_angular_velocities", "projected_gravity
 COMMAND_MODE_NAMES = ("forward", "sideways", "rotate", "omni", "stand_bend", "stand")
 TRACKING_ERROR_NAMES = ("lin_vel_err", "yaw_rate_err", "tilt_err", "height_err", "arm_sq_err")
 
+# the outcomes of a scheduled push (kbj_model.h KBJ_POUT_*) and the peak errors kbj_push_recovery keeps (KBJ_PREC_PEAK_*: the first four tracking errors)
+PUSH_OUTCOME_NAMES = ("none", "void", "fell", "recovered", "unrecovered", "censored")
+
 REWARD_NAMES = (
     "linvel", "angvel", "roll_pitch", "base_height", "arm_pos", "single_contact", "no_contact_p",
     "feet_airtime", "feet_orient", "com_distance", "base_accel", "torque",

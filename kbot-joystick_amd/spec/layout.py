@@ -111,6 +111,13 @@ CMODE = dict(FORWARD=0, SIDEWAYS=1, ROTATE=2, OMNI=3, STAND_BEND=4, STAND=5, COU
 TERR = dict(LIN=0, YAW=1, TILT=2, HEIGHT=3, ARM=4, MODE=5, SETTLED=6, SINCE=7, SIZE=8)
 TACC = dict(CMD=0, SINCE=16, RUNNING=17, SIZE=20)
 TRK = dict(ROWS=0, SETTLED=1, SUM=2, SUMSQ=7, MAX=12, MODE_STRIDE=20, CHANGES=120, EPISODES=121, SIZE=128)
+# kbj_model.h KBJ_PUSH_NEVER / KBJ_POUT_* / KBJ_PREC_* / KBJ_PSTAT_*: the PUSH_NXT value that keeps the built-in push event from drawing, the outcome
+# of a scheduled push, one env's result row of kbj_push_recovery (fp32) and one group's statistics (float64)
+PUSH_NEVER = 16777216.0
+NPEAK = 4
+POUT = dict(NONE=0, VOID=1, FELL=2, RECOVERED=3, UNRECOVERED=4, CENSORED=5, COUNT=6)
+PREC = dict(OUTCOME=0, RECOVER_STEPS=1, FALL_STEPS=2, PEAK_LIN=3, PEAK_YAW=4, PEAK_TILT=5, PEAK_HEIGHT=6, PEAK_ROW=7, SIZE=8)
+PSTAT = dict(COUNT=0, REC_SUM=6, REC_SUMSQ=7, REC_MAX=8, FALL_SUM=9, FALL_SUMSQ=10, FALL_MAX=11, PEAK_SUM=12, PEAK_MAX=16, SIZE=24)
 # pieces of a packed observation row in the reference's concatenation order (kbj_model.h KBJ_OBS_*; train.py:1367-1374, 1410-1430):
 # name -> (offset, width); the first six are common to the actor and the critic row
 OBS = dict(JPOS=(0, 20), JVEL=(20, 20), PG=(40, 5), GYRO=(45, 3), ZEROCMD=(48, 1), CMD=(49, 16), TOUCH=(65, 2), FEETPOS=(67, 6), BASEPOS=(73, 3),
