@@ -33,10 +33,6 @@ bool topology_ok(const kbj_model& m, std::string& why) {
 
 }  // namespace
 
-int kbj_nn_create(kbj_ctx* ctx);   // kbj_nn.hip
-void kbj_nn_destroy(kbj_ctx* ctx);
-int kbj_nn_check_errors(kbj_ctx* ctx);
-
 extern "C" {
 
 int kbj_sizeof_model(void) { return (int)sizeof(kbj_model); }
@@ -177,8 +173,7 @@ int kbj_destroy(kbj_ctx* ctx) {
   if (ctx->ep_d) hipFree(ctx->ep_d);
   if (ctx->es_d) hipFree(ctx->es_d);
   if (ctx->rcarry_d) hipFree(ctx->rcarry_d);
-  if (ctx->epst_part_d) hipFree(ctx->epst_part_d);
-  if (ctx->trk_part_d) hipFree(ctx->trk_part_d);
+  if (ctx->stats_part_d) hipFree(ctx->stats_part_d);
   if (ctx->ev0) hipEventDestroy(ctx->ev0);
   if (ctx->ev1) hipEventDestroy(ctx->ev1);
   if (ctx->ev_critic_loss) hipEventDestroy(ctx->ev_critic_loss);

@@ -87,10 +87,8 @@ struct kbj_ctx {
   uint32_t seed = 0;
   int rollout_argmax = 0;       // kbj_set_rollout_argmax: kbj_rollout acts with the distribution's mode (validation rollouts, train.py:1564)
   float* qstate_next = nullptr; // kbj_env_record_state: where the next kbj_env_step writes its state record (one-shot)
-  double* epst_part_d = nullptr;  // kbj_episode_stats: workgroup partials [epst_part_blocks][KBJ_EPST_SIZE], allocated by the first call
-  int epst_part_blocks = 0;
-  double* trk_part_d = nullptr;   // kbj_tracking_stats: workgroup partials [trk_part_blocks][KBJ_TRK_SIZE], allocated by the first call
-  int trk_part_blocks = 0;
+  double* stats_part_d = nullptr;   // kbj_episode_stats / kbj_tracking_stats: the workgroup partials of the call's scan, stats_part_doubles doubles,
+  size_t stats_part_doubles = 0;    // grown by the first call that needs more (kbj_traj_stats.hip stats_partials)
   // NN workspace (kbj_nn.hip)
   void* nn_ws = nullptr;
   size_t nn_ws_bytes = 0;
@@ -103,6 +101,16 @@ struct kbj_ctx {
   kbj_kernel_stat kstats[KBJ_KIND_COUNT];
   std::string error;
 };
+
+// what one translation unit serves to the others
+int kbj_nn_create(kbj_ctx* ctx);           // kbj_nn.hip, for kbj_create / kbj_destroy / kbj_synchronize
+void kbj_nn_destroy(kbj_ctx* ctx);
+int kbj_nn_check_errors(kbj_ctx* ctx);
+void kbj_nn_drop_prefetch(kbj_ctx* ctx);   // kbj_nn.hip: a pending next-minibatch hint dies with the trajectory contents it was made from
+// kbj_env.hip: one control step of all envs on stream s. qstate_t_d: the form with the state record; critic_term_d: the form with the terminal
+// critic rows. Both at once is not served
+int kbj_env_step_all(kbj_ctx* ctx, hipStream_t s, const float* action_d, float* aux_t_d, float* actor_next_d, float* critic_next_d, float* aux_next_d,
+                     float* qstate_t_d, float* critic_term_d);
 
 extern thread_local std::string kbj_global_error;
 

@@ -1,5 +1,5 @@
 // kbj_episode_stats.h — episode accounting over one trajectory (kbj_episode_stats): per-env running sums carried across rollouts
-// (KBJ_EACC_*) and the statistics of the episodes that finished inside this trajectory (KBJ_EPST_*). Included by kbj_env.hip.
+// (KBJ_EACC_*) and the statistics of the episodes that finished inside this trajectory (KBJ_EPST_*). Included by kbj_traj_stats.hip.
 //
 // The scan over t is serial per env by definition, and 8192 envs are only 128 wavefronts: one thread per env reading global memory
 // would sit on 100 dependent load latencies. So one workgroup of four wavefronts owns 64 consecutive envs. Wavefronts 1-3 stage chunks
@@ -29,12 +29,16 @@ struct EpstChunk {
   float comps[EPST_TC][KBJ_NREW][EPST_LD];   // [t][term][env]: the scan reads lane-contiguous rows
 };
 
-__device__ inline double epst_identity(int j) { return j == KBJ_EPST_RETURN_MIN ? (double)INFINITY : j == KBJ_EPST_RETURN_MAX ? -(double)INFINITY : 0.0; }
-__device__ inline double epst_combine(int j, double a, double b) {
-  if (j == KBJ_EPST_RETURN_MIN) return b < a ? b : a;
-  if (j == KBJ_EPST_RETURN_MAX || j == KBJ_EPST_LENGTH_MAX) return b > a ? b : a;
-  return a + b;
-}
+// the slots of a KBJ_EPST vector (kbj_ordered_reduce.h): counts and sums, but for the extreme returns and the longest episode
+struct EpstSlots {
+  static constexpr int SIZE = KBJ_EPST_SIZE;
+  static __device__ inline double identity(int j) { return j == KBJ_EPST_RETURN_MIN ? (double)INFINITY : j == KBJ_EPST_RETURN_MAX ? -(double)INFINITY : 0.0; }
+  static __device__ inline double combine(int j, double a, double b) {
+    if (j == KBJ_EPST_RETURN_MIN) return b < a ? b : a;
+    if (j == KBJ_EPST_RETURN_MAX || j == KBJ_EPST_LENGTH_MAX) return b > a ? b : a;
+    return a + b;
+  }
+};
 
 // grid = ceil(N / 64) workgroups of 256 threads; part_out [gridDim.x][KBJ_EPST_SIZE]
 __global__ __launch_bounds__(EPST_THREADS) void episode_stats_kernel(const float* __restrict__ aux, const float* __restrict__ reward, const float* __restrict__ comps, int T, int N,
@@ -134,7 +138,7 @@ __global__ __launch_bounds__(EPST_THREADS) void episode_stats_kernel(const float
   double* lp = reinterpret_cast<double*>(&buf[0]);
   if (wave == 0) {
     double* p = lp + lane * KBJ_EPST_SIZE;
-    for (int j = 0; j < KBJ_EPST_SIZE; ++j) p[j] = epst_identity(j);      // lanes beyond the last env contribute the identity
+    for (int j = 0; j < KBJ_EPST_SIZE; ++j) p[j] = EpstSlots::identity(j);      // lanes beyond the last env contribute the identity
     p[KBJ_EPST_EPISODES] = (double)(n_height + n_other + n_trunc);
     p[KBJ_EPST_FAIL_HEIGHT] = (double)n_height; p[KBJ_EPST_FAIL_OTHER] = (double)n_other; p[KBJ_EPST_TRUNCATED] = (double)n_trunc;
     p[KBJ_EPST_RETURN_SUM] = ret_sum; p[KBJ_EPST_RETURN_SUMSQ] = ret_sq; p[KBJ_EPST_RETURN_MIN] = (double)ret_min; p[KBJ_EPST_RETURN_MAX] = (double)ret_max;
@@ -145,24 +149,8 @@ __global__ __launch_bounds__(EPST_THREADS) void episode_stats_kernel(const float
   __syncthreads();
   if (tid < KBJ_EPST_SIZE) {
     double v = lp[tid];
-    for (int l = 1; l < EPST_ENVS; ++l) v = epst_combine(tid, v, lp[l * KBJ_EPST_SIZE + tid]);
+    for (int l = 1; l < EPST_ENVS; ++l) v = EpstSlots::combine(tid, v, lp[l * KBJ_EPST_SIZE + tid]);
     part_out[(size_t)blockIdx.x * KBJ_EPST_SIZE + tid] = v;
-  }
-}
-
-// one workgroup: the workgroup partials in block order (8 contiguous ranges of blocks, then the ranges in order) -> stats [KBJ_EPST_SIZE]
-__global__ __launch_bounds__(EPST_THREADS) void episode_stats_reduce_kernel(const double* __restrict__ part, int nblocks, double* __restrict__ stats) {
-  constexpr int R = EPST_THREADS / KBJ_EPST_SIZE;
-  __shared__ double s[R][KBJ_EPST_SIZE];
-  const int j = threadIdx.x % KBJ_EPST_SIZE, r = threadIdx.x / KBJ_EPST_SIZE;
-  const int per = (nblocks + R - 1) / R, b1 = min(nblocks, (r + 1) * per);
-  double v = epst_identity(j);
-  for (int b = r * per; b < b1; ++b) v = epst_combine(j, v, part[(size_t)b * KBJ_EPST_SIZE + j]);
-  s[r][j] = v;
-  __syncthreads();
-  if (r == 0) {
-    for (int q = 1; q < R; ++q) v = epst_combine(j, v, s[q][j]);
-    stats[j] = v;
   }
 }
 

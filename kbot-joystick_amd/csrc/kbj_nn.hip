@@ -511,10 +511,6 @@ void kbj_nn_destroy(kbj_ctx* ctx) {
   ctx->nn_ws = nullptr;
 }
 
-
-int kbj_env_step_all(kbj_ctx* ctx, hipStream_t s, const float* action_d, float* aux_t_d, float* actor_next_d, float* critic_next_d, float* aux_next_d,
-                     float* qstate_t_d, float* critic_term_d);   // kbj_env.hip
-
 namespace {
 
 // Lane hops. Every ordering between two lanes, of the rollout and of the update, is one of these: an event recorded on one stream, waited for

@@ -1,0 +1,38 @@
+// kbj_ordered_reduce.h — the second stage of the trajectory scans (kbj_episode_stats.h, kbj_tracking_stats.h): the workgroup partials of a
+// scan, [nblocks][SIZE] doubles, combined slot by slot in block order by ONE workgroup. Doubles, a fixed order, no atomics: the same partials
+// give the same bytes on every call. Included by kbj_traj_stats.hip.
+//
+// `Slots` says what a statistics vector is made of:
+//   static constexpr int SIZE;                              slots per vector, a divisor of ORDERED_REDUCE_THREADS
+//   static __device__ double identity(int j);               the value of slot j over nothing
+//   static __device__ double combine(int j, double a, double b);   slot j of the union, `a` being the earlier part
+// The scans use the same combine for their lanes, in lane order.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace kbj {
+namespace {
+
+constexpr int ORDERED_REDUCE_THREADS = 256;
+
+// one workgroup of ORDERED_REDUCE_THREADS: thread (r, j) folds slot j over the r-th of R = THREADS / SIZE contiguous ranges of blocks, in
+// block order; then the threads of range 0 fold the ranges 1 .. R - 1 onto theirs, in order -> stats [SIZE]
+template <class Slots>
+__global__ __launch_bounds__(ORDERED_REDUCE_THREADS) void ordered_reduce_kernel(const double* __restrict__ part, int nblocks, double* __restrict__ stats) {
+  constexpr int SIZE = Slots::SIZE, R = ORDERED_REDUCE_THREADS / SIZE;
+  static_assert(ORDERED_REDUCE_THREADS % SIZE == 0 && R >= 1, "every thread owns one (range, slot) of the LDS array");
+  __shared__ double s[R][SIZE];
+  const int j = threadIdx.x % SIZE, r = threadIdx.x / SIZE;
+  const int per = (nblocks + R - 1) / R, b1 = min(nblocks, (r + 1) * per);
+  double v = Slots::identity(j);
+  for (int b = r * per; b < b1; ++b) v = Slots::combine(j, v, part[(size_t)b * SIZE + j]);
+  s[r][j] = v;
+  __syncthreads();
+  if (r == 0) {
+    for (int q = 1; q < R; ++q) v = Slots::combine(j, v, s[q][j]);
+    stats[j] = v;
+  }
+}
+
+}  // namespace
+}  // namespace kbj

@@ -1,6 +1,6 @@
 // kbj_push_recovery.h — what became of one scheduled push per env (kbj_push_recovery): from the per-row tracking errors kbj_tracking_stats
 // left in err_d and the DONE column of the aux rows, the outcome of the push, the rows to recovery or to the fall and the peak errors on the
-// way (KBJ_POUT_*, KBJ_PREC_*), then per group of envs their ordered statistics (KBJ_PSTAT_*). Included by kbj_env.hip.
+// way (KBJ_POUT_*, KBJ_PREC_*), then per group of envs their ordered statistics (KBJ_PSTAT_*). Included by kbj_traj_stats.hip.
 //
 // The rule. "Within" on row t: err[t][k] <= tol[k] for every error k whose tolerance is not +inf (a NaN error is not within; a column whose
 // tolerance is +inf is not looked at, whatever it holds - a NaN too).

@@ -1,6 +1,6 @@
 // kbj_tracking_stats.h — command-tracking errors over one trajectory (kbj_tracking_stats): the five tracking errors of every aux row in
 // physical units, split by the command mode of the row, counted over the rows whose command has been held for settle_steps rows
-// (KBJ_TACC_*, KBJ_TRK_*, KBJ_TERR_*, KBJ_CMODE_*). Included by kbj_env.hip, behind kbj_env_core.h (quat_to_euler & co).
+// (KBJ_TACC_*, KBJ_TRK_*, KBJ_TERR_*, KBJ_CMODE_*). Included by kbj_traj_stats.hip, behind kbj_env_core.h (quat_to_euler & co).
 //
 // Shape: episode_stats_kernel's. One workgroup of seven wavefronts owns 64 consecutive envs. For a fixed t the block's aux rows are 18 KB of
 // contiguous floats: wavefronts 1-6 each fetch one time step of a 6-step chunk with 18 coalesced 16-byte loads per lane (issued one chunk
@@ -11,7 +11,7 @@
 // started, the settled test, the per-mode sums.
 // The per-mode accumulators are indexed by a run-time mode, so they do not live in registers (they would become scratch): they are an LDS
 // image [mode][slot][lane] of doubles (52 KB; the lane is the fastest index: conflict-free). Lanes are combined in lane order, the
-// workgroup partials in block order by a second, single-workgroup kernel: doubles, fixed order, no atomics - a call is bit-reproducible.
+// workgroup partials in block order by a second, single-workgroup kernel (kbj_ordered_reduce.h over TrkSlots): doubles, fixed order, no atomics - a call is bit-reproducible.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -22,7 +22,6 @@ namespace {
 
 constexpr int TRK_ENVS = 64;        // envs per workgroup = lanes of every wavefront
 constexpr int TRK_THREADS = 448;    // wavefront 0 scans, wavefronts 1-6 stage and evaluate
-constexpr int TRK_RED_THREADS = 256;   // the second, single-workgroup kernel: TRK_RED_THREADS / KBJ_TRK_SIZE ranges of blocks, one thread per range and slot
 constexpr int TRK_TC = 6;           // time steps per chunk: one per staging wavefront
 constexpr int TRK_LD = 49;          // row stride of the staged image, in words: the 12 staged 16-byte pieces of an aux row and one word (odd: one env per lane is conflict-free)
 constexpr int TRK_V4 = KBJ_AUX_SIZE / 4;             // 16-byte pieces per aux row = loads per lane and time step
@@ -33,7 +32,6 @@ static_assert(KBJ_AUX_SIZE % 4 == 0 && KBJ_TACC_SIZE % 4 == 0 && KBJ_TACC_SINCE 
 static_assert(KBJ_TRK_SUM == 2 && KBJ_TRK_SUMSQ == KBJ_TRK_SUM + KBJ_NTERR && KBJ_TRK_MAX == KBJ_TRK_SUMSQ + KBJ_NTERR && TRK_SLOTS <= KBJ_TRK_MODE_STRIDE &&
               KBJ_CMODE_COUNT * KBJ_TRK_MODE_STRIDE == KBJ_TRK_CHANGES && KBJ_TRK_EPISODES < KBJ_TRK_SIZE && KBJ_TRK_SIZE <= TRK_THREADS, "tracking statistics layout");
 static_assert(TRK_THREADS == 64 * (TRK_TC + 1), "one scanning wavefront and one staging wavefront per time step of a chunk");
-static_assert(TRK_RED_THREADS % KBJ_TRK_SIZE == 0 && TRK_RED_THREADS >= KBJ_TRK_SIZE, "every thread of the reduce kernel owns one (range, slot) of its LDS array");
 
 // where the 16-byte piece `p` of an aux row (columns 4 p .. 4 p + 3) lives in its staged row, or -1: the pieces the errors read are 0-3 (QVEL,
 // BQUAT, BASEZ, LFZ, RFZ), 5-7 (ARMQ) and 13-17 (CMD, DONE)
@@ -54,8 +52,15 @@ struct TrkShared {
   float last[2][KBJ_NCMD][TRK_ENVS];             // the command of the last row of chunk c in last[c & 1]
 };
 
-__device__ inline bool trk_is_max(int j) { return j < KBJ_TRK_CHANGES && j % KBJ_TRK_MODE_STRIDE >= KBJ_TRK_MAX && j % KBJ_TRK_MODE_STRIDE < KBJ_TRK_MAX + KBJ_NTERR; }
-__device__ inline double trk_combine(bool is_max, double a, double b) { return is_max ? (b > a ? b : a) : a + b; }
+// the slots of a KBJ_TRK vector (kbj_ordered_reduce.h): counts and sums, but for the maxima of each mode block. The identity of every slot
+// is 0: the errors are non-negative
+struct TrkSlots {
+  static constexpr int SIZE = KBJ_TRK_SIZE;
+  static __device__ inline bool is_max(int j) { return j < KBJ_TRK_CHANGES && j % KBJ_TRK_MODE_STRIDE >= KBJ_TRK_MAX && j % KBJ_TRK_MODE_STRIDE < KBJ_TRK_MAX + KBJ_NTERR; }
+  static __device__ inline double identity(int) { return 0.0; }
+  static __device__ inline double combine_as(bool is_max, double a, double b) { return is_max ? (b > a ? b : a) : a + b; }   // is_max(j), hoisted by the caller
+  static __device__ inline double combine(int j, double a, double b) { return combine_as(is_max(j), a, b); }
+};
 
 // the mode of a command (kbj.h kbj_tracking_stats; the switch list of train.py:752-762)
 template <class Cmd> __device__ inline int trk_mode(const Cmd& cmd) {
@@ -68,7 +73,9 @@ template <class Cmd> __device__ inline int trk_mode(const Cmd& cmd) {
   return x ? KBJ_CMODE_FORWARD : y ? KBJ_CMODE_SIDEWAYS : KBJ_CMODE_ROTATE;
 }
 
-// the five errors of one staged aux row: rewards_kernel's expressions, before their exp
+// the five errors of one staged aux row: rewards_kernel's expressions (kbj_traj_stats.hip), before their exp. Restated, not shared: called
+// from one template over the row type, rewards_kernel contracts its multiply-adds differently (other fma / packed-fma counts), so reward
+// bits could move. tests/test_gpu_tracking_stats.py test_reward_terms_follow_from_the_error_rows ties the two restatements together
 __device__ inline void trk_errors(const TrkRow a, const float* __restrict__ joint_bias, float standard_height, float foot_origin_height, float* e) {
   float cmd[KBJ_NCMD];
 #pragma unroll
@@ -235,28 +242,11 @@ __global__ __launch_bounds__(TRK_THREADS) void tracking_stats_kernel(const kbj_m
     const int r = tid < KBJ_TRK_CHANGES ? (slot < TRK_SLOTS ? mode * TRK_SLOTS + slot : -1) : tid <= KBJ_TRK_EPISODES ? TRK_IMG - 2 + (tid - KBJ_TRK_CHANGES) : -1;
     double x = 0.0;
     if (r >= 0) {
-      const bool is_max = trk_is_max(tid);
+      const bool is_max = TrkSlots::is_max(tid);
       x = S.img[r][0];
-      for (int l = 1; l < TRK_ENVS; ++l) x = trk_combine(is_max, x, S.img[r][l]);
+      for (int l = 1; l < TRK_ENVS; ++l) x = TrkSlots::combine_as(is_max, x, S.img[r][l]);
     }
     part_out[(size_t)blockIdx.x * KBJ_TRK_SIZE + tid] = x;
-  }
-}
-
-// one workgroup of TRK_RED_THREADS: the workgroup partials in block order (R = 2 contiguous ranges of blocks, then the ranges in order) -> stats [KBJ_TRK_SIZE]
-__global__ __launch_bounds__(TRK_RED_THREADS) void tracking_stats_reduce_kernel(const double* __restrict__ part, int nblocks, double* __restrict__ stats) {
-  constexpr int R = TRK_RED_THREADS / KBJ_TRK_SIZE;      // threadIdx.x / KBJ_TRK_SIZE < R for every thread (static_assert above)
-  __shared__ double s[R][KBJ_TRK_SIZE];
-  const int j = threadIdx.x % KBJ_TRK_SIZE, r = threadIdx.x / KBJ_TRK_SIZE;
-  const int per = (nblocks + R - 1) / R, b1 = min(nblocks, (r + 1) * per);
-  const bool is_max = trk_is_max(j);
-  double x = 0.0;        // the identity of every slot: the errors are non-negative
-  for (int b = r * per; b < b1; ++b) x = trk_combine(is_max, x, part[(size_t)b * KBJ_TRK_SIZE + j]);
-  s[r][j] = x;
-  __syncthreads();
-  if (r == 0) {
-    for (int q = 1; q < R; ++q) x = trk_combine(is_max, x, s[q][j]);
-    stats[j] = x;
   }
 }
 

@@ -1,0 +1,64 @@
+"""The host carrier of a statistic the device accumulates over rollouts (kbj_episode_stats, kbj_tracking_stats; host/episode.py and
+host/tracking.py construct one each): the per-env rows that live next to the env state, the hand-over of one call's result to the host, the
+totals."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+
+class DeviceStats:
+    """Per-env rows (`acc` [num_envs, acc_width], carried across rollouts and through checkpoints), one call's result (`stats`, a vector of
+    `layout`: dist.StatsLayout), and on the host the last rollout's vector and the totals since creation / resume. `call(ctx, traj, acc,
+    stats)` queues the ABI call. The result comes back through a pinned buffer behind the kernel (no sync in the loop); it is folded into the
+    totals when the next rollout starts or when somebody asks. Checkpoints hold `acc` and the totals under `acc_key` and `total_key`."""
+
+    def __init__(self, num_envs: int, acc_width: int, layout, call, acc_key: str, total_key: str, device):
+        self.layout, self._call, self._acc_key, self._total_key = layout, call, acc_key, total_key
+        size = layout.empty().size
+        self.acc = torch.zeros(num_envs, acc_width, device=device)
+        self.stats = torch.zeros(size, dtype=torch.float64, device=device)
+        self._host = torch.zeros(size, dtype=torch.float64).pin_memory()
+        self._event = torch.cuda.Event()
+        self._pending = False
+        self._last = layout.empty()
+        self._total = layout.empty()
+
+    def after_rollout(self, ctx, traj):
+        """Account the rollout in `traj` (behind the user rewards and terminations, so that they count)."""
+        self._fold()
+        self._call(ctx, traj, self.acc, self.stats)
+        self._host.copy_(self.stats, non_blocking=True)
+        self._event.record()
+        self._pending = True
+
+    def _fold(self):
+        """The last call's result, once its copy has landed, becomes `_last` and joins the totals."""
+        if self._pending:
+            self._event.synchronize()
+            self._last = self._host.numpy().copy()
+            self._total = self.layout.combine([self._total, self._last])
+            self._pending = False
+
+    def vectors(self):
+        """(last, total): the vectors (float64 numpy) of the last rollout and of all rollouts so far."""
+        self._fold()
+        return self._last, self._total
+
+    def checkpoint_state(self) -> dict:
+        """What is in flight per env and the totals so far (the last rollout's own vector is not state)."""
+        self._fold()
+        return {self._acc_key: self.acc.cpu().numpy(), self._total_key: self._total.copy()}
+
+    def load_checkpoint_state(self, x):
+        """The members when the saved run kept them (same env count), else from zero - what is in flight is then counted from here on (an old
+        checkpoint, a run saved with the switch off, a model-only file)."""
+        a, t = self._acc_key, self._total_key
+        self._pending = False
+        self._last = self.layout.empty()
+        if a in x and t in x and tuple(x[a].shape) == tuple(self.acc.shape) and x[t].shape == self._last.shape:
+            self.acc.copy_(torch.from_numpy(np.ascontiguousarray(x[a], np.float32)))
+            self._total = np.array(x[t], np.float64)
+        else:
+            self.acc.zero_()
+            self._total = self.layout.empty()

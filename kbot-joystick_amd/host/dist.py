@@ -62,76 +62,56 @@ def global_advantage_sums(adv_minibatch: torch.Tensor, world_size: int) -> torch
     return sums
 
 
-# kbj_episode_stats vectors (kbj_model.h KBJ_EPST_*): every slot is a count or a sum over the finished episodes, except these three
-_EPST_MIN, _EPST_MAX, _EPST_LENGTH_MAX = L.EPST["RETURN_MIN"], L.EPST["RETURN_MAX"], L.EPST["LENGTH_MAX"]
+class StatsLayout:
+    """The slot rule of a statistics vector that the device builds from partials (kbj_episode_stats, kbj_tracking_stats): every slot is a
+    count or a sum, except `max_slots` (maxima, -inf over nothing), `max0_slots` (maxima of non-negative quantities, 0 over nothing) and
+    `min_slots` (minima, +inf over nothing). One rule, three uses: the vector of nothing, the union of several vectors on the host, the
+    union over the data-parallel ranks."""
+
+    def __init__(self, size: int, max_slots=(), max0_slots=(), min_slots=()):
+        self.hi, self.lo = np.array(list(max_slots) + list(max0_slots), np.int64), np.array(list(min_slots), np.int64)
+        self._empty = np.zeros(size, np.float64)
+        self._empty[list(max_slots)], self._empty[self.lo] = -np.inf, np.inf
+        self._ext = np.concatenate([self.hi, self.lo])                                               # what travels through the MAX all-reduce:
+        self._sign = np.concatenate([np.ones(len(self.hi)), -np.ones(len(self.lo))])                 # [maxima, -minima]
+
+    def empty(self) -> np.ndarray:
+        return self._empty.copy()
+
+    def combine(self, vectors) -> np.ndarray:
+        """Statistics of the union of the sets that the given vectors describe (other ranks' envs, or later rollouts): counts and sums add up
+        in list order, in float64; maxima and minima are taken over the list. Pure host arithmetic, the same that reduce() performs with
+        collectives."""
+        out = self.empty()
+        for v in vectors:
+            v = np.asarray(v, np.float64)
+            hi, lo = np.maximum(out[self.hi], v[self.hi]), np.minimum(out[self.lo], v[self.lo])
+            out = out + v
+            out[self.hi], out[self.lo] = hi, lo
+        return out
+
+    def reduce(self, vec: torch.Tensor, world_size: int) -> torch.Tensor:
+        """combine() over the data-parallel ranks: `vec` [..., size] float64 holds this rank's vector(s); returns the vector(s) of all ranks'
+        envs together. ONE SUM all-reduce over the counts and sums (the other slots zeroed meanwhile: they may be infinite), ONE MAX
+        all-reduce over [maxima, -minima]. Collective: every rank calls it, at logging cadence, never inside the update."""
+        if world_size > 1 or FORCE_COLLECTIVE:
+            import torch.distributed as dist
+            slots, sign = torch.from_numpy(self._ext).to(vec.device), torch.from_numpy(self._sign).to(vec.device)
+            ext = (vec[..., slots] * sign).contiguous()
+            vec = vec.clone()
+            vec[..., slots] = 0.0
+            dist.all_reduce(vec, op=dist.ReduceOp.SUM)
+            dist.all_reduce(ext, op=dist.ReduceOp.MAX)
+            vec[..., slots] = ext * sign
+        return vec
 
 
-def empty_episode_stats() -> np.ndarray:
-    """The KBJ_EPST vector of no finished episode: zeros, RETURN_MIN = +inf, RETURN_MAX = -inf."""
-    v = np.zeros(L.EPST["SIZE"], np.float64)
-    v[_EPST_MIN], v[_EPST_MAX] = np.inf, -np.inf
-    return v
+# kbj_episode_stats vectors (kbj_model.h KBJ_EPST_*): every slot is a count or a sum over the finished episodes, except the extreme returns
+# and the longest episode. HumanoidWalkingTask.episode_stats() reduces them
+EPISODE_STATS = StatsLayout(L.EPST["SIZE"], max_slots=[L.EPST["RETURN_MAX"]], max0_slots=[L.EPST["LENGTH_MAX"]], min_slots=[L.EPST["RETURN_MIN"]])
+empty_episode_stats, combine_episode_stats, reduce_episode_stats = EPISODE_STATS.empty, EPISODE_STATS.combine, EPISODE_STATS.reduce
 
-
-def combine_episode_stats(vectors) -> np.ndarray:
-    """Statistics of the union of the episode sets that the given KBJ_EPST vectors describe (other ranks' envs, or later rollouts): counts
-    and sums add up in list order, in float64; minimum, maximum and longest episode are taken over the list. Pure host arithmetic, the same
-    that reduce_episode_stats performs with collectives."""
-    out = empty_episode_stats()
-    for v in vectors:
-        v = np.asarray(v, np.float64)
-        lo, hi, longest = min(out[_EPST_MIN], v[_EPST_MIN]), max(out[_EPST_MAX], v[_EPST_MAX]), max(out[_EPST_LENGTH_MAX], v[_EPST_LENGTH_MAX])
-        out = out + v
-        out[_EPST_MIN], out[_EPST_MAX], out[_EPST_LENGTH_MAX] = lo, hi, longest
-    return out
-
-
-def reduce_episode_stats(vec: torch.Tensor, world_size: int) -> torch.Tensor:
-    """combine_episode_stats over the data-parallel ranks: `vec` [..., EPST SIZE] float64 holds this rank's KBJ_EPST vector(s); returns the
-    vector(s) of all ranks' envs together. ONE SUM all-reduce over the counts and sums, ONE MAX all-reduce over (max, -min, longest).
-    Collective: every rank calls it, at logging cadence (HumanoidWalkingTask.episode_stats()), never inside the update."""
-    if world_size > 1 or FORCE_COLLECTIVE:
-        import torch.distributed as dist
-        ext = torch.stack([vec[..., _EPST_MAX], -vec[..., _EPST_MIN], vec[..., _EPST_LENGTH_MAX]], dim=-1).contiguous()
-        vec = vec.clone()
-        vec[..., _EPST_MIN] = 0.0; vec[..., _EPST_MAX] = 0.0       # summed with the rest, overwritten below: keep them finite
-        dist.all_reduce(vec, op=dist.ReduceOp.SUM)
-        dist.all_reduce(ext, op=dist.ReduceOp.MAX)
-        vec[..., _EPST_MAX], vec[..., _EPST_MIN], vec[..., _EPST_LENGTH_MAX] = ext[..., 0], -ext[..., 1], ext[..., 2]
-    return vec
-
-
-# kbj_tracking_stats vectors (kbj_model.h KBJ_TRK_*): every slot is a count or a sum over rows, except the maxima of each mode block
-_TRK_MAX = np.zeros(L.TRK["SIZE"], bool)
-for _m in range(L.CMODE["COUNT"]):
-    _TRK_MAX[_m * L.TRK["MODE_STRIDE"] + L.TRK["MAX"]:_m * L.TRK["MODE_STRIDE"] + L.TRK["MAX"] + L.NTERR] = True
-
-
-def empty_tracking_stats() -> np.ndarray:
-    """The KBJ_TRK vector of no row: zeros (the maxima's identity is 0: the errors are non-negative)."""
-    return np.zeros(L.TRK["SIZE"], np.float64)
-
-
-def combine_tracking_stats(vectors) -> np.ndarray:
-    """Statistics of the union of the row sets that the given KBJ_TRK vectors describe (other ranks' envs, or later rollouts): counts and
-    sums add up in list order, in float64; the maxima are taken over the list."""
-    out = empty_tracking_stats()
-    for v in vectors:
-        v = np.asarray(v, np.float64)
-        out = np.where(_TRK_MAX, np.maximum(out, v), out + v)
-    return out
-
-
-def reduce_tracking_stats(vec: torch.Tensor, world_size: int) -> torch.Tensor:
-    """combine_tracking_stats over the data-parallel ranks: `vec` [..., TRK SIZE] float64 holds this rank's KBJ_TRK vector(s); returns the
-    vector(s) of all ranks' envs together. ONE SUM all-reduce over the counts and sums, ONE MAX all-reduce over the maxima. Collective:
-    every rank calls it, at logging cadence (HumanoidWalkingTask.tracking_stats()), never inside the update."""
-    if world_size > 1 or FORCE_COLLECTIVE:
-        import torch.distributed as dist
-        is_max = torch.from_numpy(_TRK_MAX).to(vec.device)
-        hi = torch.where(is_max, vec, torch.zeros_like(vec))
-        vec = torch.where(is_max, torch.zeros_like(vec), vec)
-        dist.all_reduce(vec, op=dist.ReduceOp.SUM)
-        dist.all_reduce(hi, op=dist.ReduceOp.MAX)
-        vec = torch.where(is_max, hi, vec)
-    return vec
+# kbj_tracking_stats vectors (kbj_model.h KBJ_TRK_*): every slot is a count or a sum over rows, except the maxima of each mode block (the
+# errors are non-negative). HumanoidWalkingTask.tracking_stats() reduces them
+TRACKING_STATS = StatsLayout(L.TRK["SIZE"], max0_slots=[m * L.TRK["MODE_STRIDE"] + L.TRK["MAX"] + k for m in range(L.CMODE["COUNT"]) for k in range(L.NTERR)])
+empty_tracking_stats, combine_tracking_stats, reduce_tracking_stats = TRACKING_STATS.empty, TRACKING_STATS.combine, TRACKING_STATS.reduce

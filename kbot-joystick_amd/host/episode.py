@@ -4,11 +4,11 @@ from __future__ import annotations
 
 import math
 
-import numpy as np
 import torch
 
 from ..spec import constants, layout as L
 from . import dist as dist_util
+from .device_stats import DeviceStats
 
 
 def episode_stats_scalars(vec, ctrl_dt: float, prefix: str = "episode/", terms: bool = False) -> dict:
@@ -44,54 +44,10 @@ def fresh_episode_stats(ctx, traj, num_envs: int, device) -> torch.Tensor:
     return stats
 
 
-class EpisodeStats:
-    """Per-env accumulator rows (`acc`, carried across rollouts and through checkpoints), one call's result (`stats`), and on the host the
-    last rollout's vector and the totals since creation / resume. The result comes back through a pinned buffer behind the kernel (no sync
-    in the loop); it is folded into the totals when the next rollout starts or when somebody asks."""
+class EpisodeStats(DeviceStats):
+    """kbj_episode_stats over the rollouts of a run: the episodes in flight per env (KBJ_EACC rows), the KBJ_EPST vectors of the episodes that
+    finished in the last rollout and of all so far."""
 
     def __init__(self, num_envs: int, device):
-        self.acc = torch.zeros(num_envs, L.EACC["SIZE"], device=device)
-        self.stats = torch.zeros(L.EPST["SIZE"], dtype=torch.float64, device=device)
-        self._host = torch.zeros(L.EPST["SIZE"], dtype=torch.float64).pin_memory()
-        self._event = torch.cuda.Event()
-        self._pending = False
-        self._last = dist_util.empty_episode_stats()
-        self._total = dist_util.empty_episode_stats()
-
-    def after_rollout(self, ctx, traj):
-        """Account the rollout in `traj` (behind the user rewards, so that they count; user terminations are in the DONE column already)."""
-        self._fold()
-        ctx.episode_stats(traj, self.acc, self.stats)
-        self._host.copy_(self.stats, non_blocking=True)
-        self._event.record()
-        self._pending = True
-
-    def _fold(self):
-        """The last kbj_episode_stats result, once its copy has landed, becomes `_last` and joins the totals."""
-        if self._pending:
-            self._event.synchronize()
-            self._last = self._host.numpy().copy()
-            self._total = dist_util.combine_episode_stats([self._total, self._last])
-            self._pending = False
-
-    def vectors(self):
-        """(last, total): the KBJ_EPST vectors (float64 numpy) of the episodes that finished in the last rollout and of all so far."""
-        self._fold()
-        return self._last, self._total
-
-    def checkpoint_state(self) -> dict:
-        """Episodes in flight and the totals so far (the last rollout's own vector is not state)."""
-        self._fold()
-        return dict(ep_acc=self.acc.cpu().numpy(), ep_total=self._total.copy())
-
-    def load_checkpoint_state(self, x):
-        """The members when the saved run kept them (same env count), else from zero - episodes already running are then counted from here
-        on (an old checkpoint, a run saved with the switch off, a model-only file)."""
-        self._pending = False
-        self._last = dist_util.empty_episode_stats()
-        if "ep_acc" in x and "ep_total" in x and tuple(x["ep_acc"].shape) == tuple(self.acc.shape) and x["ep_total"].shape == (L.EPST["SIZE"],):
-            self.acc.copy_(torch.from_numpy(np.ascontiguousarray(x["ep_acc"], np.float32)))
-            self._total = np.array(x["ep_total"], np.float64)
-        else:
-            self.acc.zero_()
-            self._total = dist_util.empty_episode_stats()
+        super().__init__(num_envs, L.EACC["SIZE"], dist_util.EPISODE_STATS, lambda ctx, traj, acc, stats: ctx.episode_stats(traj, acc, stats),
+                         "ep_acc", "ep_total", device)

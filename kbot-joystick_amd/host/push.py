@@ -11,10 +11,9 @@ import torch
 
 from ..spec import constants, layout as L
 from . import binding as B
-from .buffers import CarryBuffers, TrajBuffers
+from .sweep import sweep_rollout, sweep_terms
 from .tracking import fresh_tracking_stats
 from .traj_view import PushRequest
-from .user_terms import UserTerms
 
 P, S, O = L.PREC, L.PSTAT, L.POUT
 
@@ -79,7 +78,7 @@ def steps_of(seconds: float, ctrl_dt: float) -> int:
 def push_sweep(task, forces=(50.0, 100.0, 150.0, 200.0), directions_deg=(0, 45, 90, 135, 180, 225, 270, 315), duration: float = 0.2, command=None,
                push_at: float = 2.0, window: float = 3.0, hold: float = 0.5, tolerances=None, repeats: int = 4, torque=None, seed_offset: int = 7919):
     """The sweep behind HumanoidWalkingTask.push_sweep (see there): returns (entries, record) - one entry per (force, direction) case, and the
-    PushRecord of what the run left on the device. Every call builds a context of its own and closes it again, as tracking_sweep does."""
+    PushRecord of what the run left on the device. Every call builds a context of its own and closes it again (host/sweep.py sweep_rollout)."""
     cfg = task.config
     forces, directions_deg = [float(f) for f in forces], [float(a) for a in directions_deg]
     cases = [(f, a) for f in forces for a in directions_deg]
@@ -103,32 +102,22 @@ def push_sweep(task, forces=(50.0, 100.0, 150.0, 200.0), directions_deg=(0, 45, 
         raise ValueError("push_sweep: push_at must leave room for the hold rows in front of the push; duration and window must not be negative")
     ncases, n, T = len(cases), len(cases) * repeats, row + d + win
     dev = task.device
-    vcfg = dataclasses.replace(cfg, batch_size=n).to_kbj(n)
-    vcfg.rollout_len = max(1, T)
-    vcfg.gae_bootstrap_truncation = vcfg.gae_tail_value = vcfg.gae_terminal_value = 0     # no GAE here
-    vcfg.command_mode, vcfg.enable_pushes = 1, 1                                          # one held command (resets write it too); the step kernel reads the event state
-    for k in range(L.NCMD):
-        vcfg.fixed_command[k] = float(cmd[k])
     tq = np.zeros(3, np.float32) if torque is None else np.asarray(torque, np.float32).reshape(3)
     local = np.zeros((n, 6), np.float32)
     for e in range(n):                                                                    # env e runs case e % ncases
         f, a = cases[e % ncases]
         local[e] = (f * math.cos(math.radians(a)), f * math.sin(math.radians(a)), 0.0, *tq)
     event = ScriptedPush(torch.from_numpy(local).to(dev), torch.full((n,), float(d), device=dev), row)
-    terms = UserTerms(None, {name: (term, task.terms.obs_into[name]) for name, term in task.terms.observations.items() if task.terms.obs_into[name]},
-                      None, task.terms.resets, {"scripted_push": event})
-    terms.bind(cfg.seed, task.rank, dev, task.model_blob, task.nobs_actor, task.nobs_critic)
+    terms = sweep_terms(task, events={"scripted_push": event})
+    hooks = [terms.apply_resets, terms.apply_events] + ([terms.observe_rows] if any(task.extra_obs) else [])
     T = max(1, T)
-    ctx = B.Context(task.model_blob, vcfg, dev.index or 0, torch.cuda.current_stream().cuda_stream)
-    try:
-        carry = CarryBuffers(n, task.H, task.kcfg.depth, dev, mirror=task.mirror)
-        tr = TrajBuffers(T, n, task.H, task.kcfg.depth, dev, mirror=task.mirror, ld_actor=task.ld_actor, ld_critic=task.ld_critic)
-        seed = cfg.seed + seed_offset
-        ctx.env_reset_all(seed, tr.actor_obs[0], tr.critic_obs[0], tr.aux[0])
-        feeds = [terms.observe_rows] if any(task.extra_obs) else []
-        terms.run_hooks(ctx, tr, 0, seed_offset, [terms.apply_resets, terms.apply_events] + feeds)
-        terms.run_steps(ctx, tr, carry, task.params, T, seed=seed, first_step=0, argmax=True, first_index=seed_offset,
-                        hooks=[terms.apply_resets, terms.apply_events] + feeds)
+
+    def configure(vcfg):
+        vcfg.command_mode, vcfg.enable_pushes = 1, 1                                      # one held command (resets write it too); the step kernel reads the event state
+        for k in range(L.NCMD):
+            vcfg.fixed_command[k] = float(cmd[k])
+
+    with sweep_rollout(task, n, T, configure, terms, hooks, hooks, seed_offset) as (ctx, tr):
         err = torch.empty(T, n, L.TERR["SIZE"], device=dev)
         fresh_tracking_stats(ctx, tr.c, n, 0, dev, err)
         sched = torch.tensor([[row, d]] * n, dtype=torch.int32, device=dev)
@@ -140,8 +129,6 @@ def push_sweep(task, forces=(50.0, 100.0, 150.0, 200.0), directions_deg=(0, 45, 
         ctx.synchronize()
         st = stats.cpu().numpy()
         push_state = ctx.env_get_state()[1][:, L.ES["PUSH"]:L.ES["PUSH"] + 8].copy()
-    finally:
-        ctx.close()
     settings = dict(duration=d * dt, push_at=row * dt, window=win * dt, hold=hld * dt, command=tuple(float(x) for x in cmd), torque=tuple(float(x) for x in tq),
                     tolerances=dict(tol), repeats=repeats)
     entries = [dict(force=f, direction_deg=a, **settings, **case_summary(st[i], dt)) for i, (f, a) in enumerate(cases)]

@@ -10,10 +10,9 @@ import numpy as np
 import torch
 
 from ..spec import constants, layout as L
-from . import binding as B
 from . import dist as dist_util
-from .buffers import CarryBuffers, TrajBuffers
-from .user_terms import UserTerms
+from .device_stats import DeviceStats
+from .sweep import sweep_rollout, sweep_terms
 
 K, A, R = L.TRK, L.TACC, L.TERR
 
@@ -63,58 +62,14 @@ def fresh_tracking_stats(ctx, traj, num_envs: int, steps: int, device, err=None)
     return stats
 
 
-class TrackingStats:
-    """Per-env carry rows (`acc`, carried across rollouts and through checkpoints), one call's result (`stats`), and on the host the last
-    rollout's vector and the totals since creation / resume. The result comes back through a pinned buffer behind the kernel (no sync in
-    the loop); it is folded into the totals when the next rollout starts or when somebody asks."""
+class TrackingStats(DeviceStats):
+    """kbj_tracking_stats over the rollouts of a run: the command each env holds and for how long (KBJ_TACC rows), the KBJ_TRK vectors of the
+    last rollout's rows and of all so far. A row counts once its command has been held for `settle_steps` rows."""
 
     def __init__(self, num_envs: int, steps: int, device):
         self.settle_steps = steps
-        self.acc = torch.zeros(num_envs, A["SIZE"], device=device)
-        self.stats = torch.zeros(K["SIZE"], dtype=torch.float64, device=device)
-        self._host = torch.zeros(K["SIZE"], dtype=torch.float64).pin_memory()
-        self._event = torch.cuda.Event()
-        self._pending = False
-        self._last = dist_util.empty_tracking_stats()
-        self._total = dist_util.empty_tracking_stats()
-
-    def after_rollout(self, ctx, traj):
-        """Account the rollout in `traj`: its aux rows are all the kernel reads."""
-        self._fold()
-        ctx.tracking_stats(traj, self.settle_steps, self.acc, self.stats)
-        self._host.copy_(self.stats, non_blocking=True)
-        self._event.record()
-        self._pending = True
-
-    def _fold(self):
-        """The last kbj_tracking_stats result, once its copy has landed, becomes `_last` and joins the totals."""
-        if self._pending:
-            self._event.synchronize()
-            self._last = self._host.numpy().copy()
-            self._total = dist_util.combine_tracking_stats([self._total, self._last])
-            self._pending = False
-
-    def vectors(self):
-        """(last, total): the KBJ_TRK vectors (float64 numpy) of the last rollout's rows and of all so far."""
-        self._fold()
-        return self._last, self._total
-
-    def checkpoint_state(self) -> dict:
-        """The commands being held and the totals so far (the last rollout's own vector is not state)."""
-        self._fold()
-        return dict(trk_acc=self.acc.cpu().numpy(), trk_total=self._total.copy())
-
-    def load_checkpoint_state(self, x):
-        """The members when the saved run kept them (same env count), else from zero - every env then counts as starting an episode (an old
-        checkpoint, a run saved with the switch off, a model-only file)."""
-        self._pending = False
-        self._last = dist_util.empty_tracking_stats()
-        if "trk_acc" in x and "trk_total" in x and tuple(x["trk_acc"].shape) == tuple(self.acc.shape) and x["trk_total"].shape == (K["SIZE"],):
-            self.acc.copy_(torch.from_numpy(np.ascontiguousarray(x["trk_acc"], np.float32)))
-            self._total = np.array(x["trk_total"], np.float64)
-        else:
-            self.acc.zero_()
-            self._total = dist_util.empty_tracking_stats()
+        super().__init__(num_envs, A["SIZE"], dist_util.TRACKING_STATS, lambda ctx, traj, acc, stats: ctx.tracking_stats(traj, self.settle_steps, acc, stats),
+                         "trk_acc", "trk_total", device)
 
 
 # ---- the sweep ----
@@ -161,8 +116,8 @@ class SweepRecord:
 
 def tracking_sweep(task, commands=None, repeats: int = 2, seconds=None, settle_seconds=None, seed_offset: int = 7919):
     """The sweep behind HumanoidWalkingTask.tracking_sweep (see there): returns (entries, record) - one entry per command, and the SweepRecord
-    of what the run left on the device. Every call builds a context of its own for its env count and length and closes it again (validate()
-    caches its context; a response table is asked for now and then, and its env count follows the command list)."""
+    of what the run left on the device. Every call builds a context of its own for its env count and length and closes it again
+    (host/sweep.py sweep_rollout)."""
     cfg = task.config
     commands = default_command_grid(task.kcfg) if commands is None else commands
     table = np.zeros((len(commands), L.NCMD), np.float32)
@@ -177,30 +132,19 @@ def tracking_sweep(task, commands=None, repeats: int = 2, seconds=None, settle_s
     T = max(1, int(round((cfg.render_length_seconds if seconds is None else seconds) / cfg.ctrl_dt)))
     steps = settle_steps(cfg.tracking_settle_seconds if settle_seconds is None else settle_seconds, cfg.ctrl_dt)
     dev = task.device
-    vcfg = dataclasses.replace(cfg, batch_size=n).to_kbj(n)
-    vcfg.rollout_len = T
-    vcfg.gae_bootstrap_truncation = vcfg.gae_tail_value = vcfg.gae_terminal_value = 0     # no GAE here: no tail pass, no terminal rows
-    vcfg.command_mode = 1
     per_env = torch.from_numpy(np.tile(table, (repeats, 1))).to(dev)                      # env e follows command e % ncmd
-    terms = UserTerms(None, {name: (term, task.terms.obs_into[name]) for name, term in task.terms.observations.items() if task.terms.obs_into[name]},
-                      ScriptedCommand(per_env), task.terms.resets)
-    terms.bind(cfg.seed, task.rank, dev, task.model_blob, task.nobs_actor, task.nobs_critic)
-    ctx = B.Context(task.model_blob, vcfg, dev.index or 0, torch.cuda.current_stream().cuda_stream)
-    try:
-        carry = CarryBuffers(n, task.H, task.kcfg.depth, dev, mirror=task.mirror)
-        tr = TrajBuffers(T, n, task.H, task.kcfg.depth, dev, mirror=task.mirror, ld_actor=task.ld_actor, ld_critic=task.ld_critic)
-        seed = cfg.seed + seed_offset
-        ctx.env_reset_all(seed, tr.actor_obs[0], tr.critic_obs[0], tr.aux[0])
-        feeds = [terms.observe_rows] if any(task.extra_obs) else []
-        terms.run_hooks(ctx, tr, 0, seed_offset, [terms.apply_resets, terms.apply_command] + feeds)
-        terms.run_steps(ctx, tr, carry, task.params, T, seed=seed, first_step=0, argmax=True, first_index=seed_offset,
-                        hooks=[terms.apply_resets] + feeds + [terms.apply_command])       # validate()'s order
+    terms = sweep_terms(task, command=ScriptedCommand(per_env))
+    feeds = [terms.observe_rows] if any(task.extra_obs) else []
+
+    def configure(vcfg):
+        vcfg.command_mode = 1
+
+    with sweep_rollout(task, n, T, configure, terms, [terms.apply_resets, terms.apply_command] + feeds,
+                       [terms.apply_resets] + feeds + [terms.apply_command], seed_offset) as (ctx, tr):       # validate()'s order
         err = torch.empty(T, n, R["SIZE"], device=dev)
         stats = fresh_tracking_stats(ctx, tr.c, n, steps, dev, err)
         ctx.synchronize()
         e, done, vec = err.cpu().numpy().astype(np.float64), tr.done.cpu().numpy(), stats.cpu().numpy()
-    finally:
-        ctx.close()
     settled = e[:, :, R["SETTLED"]] != 0
     out = []
     for i in range(ncmd):

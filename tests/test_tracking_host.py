@@ -135,7 +135,8 @@ def test_combine_is_associative_with_the_empty_vector_as_identity():
     e = D.empty_tracking_stats()
     assert np.array_equal(D.combine_tracking_stats([]), e) and np.array_equal(D.combine_tracking_stats([a, e]), a) and np.array_equal(D.combine_tracking_stats([e, a]), a)
     left, right = D.combine_tracking_stats([D.combine_tracking_stats([a, b]), c]), D.combine_tracking_stats([a, D.combine_tracking_stats([b, c])])
-    hi = D._TRK_MAX
+    hi = np.zeros(K["SIZE"], bool)
+    hi[D.TRACKING_STATS.hi] = True
     assert hi.sum() == M["COUNT"] * L.NTERR
     assert np.array_equal(left[hi], right[hi]) and np.array_equal(left[hi], np.maximum(np.maximum(a, b), c)[hi])
     assert np.allclose(left, right, rtol=1e-15, atol=0) and np.allclose(left[~hi], (a + b + c)[~hi], rtol=1e-15, atol=0)     # float64 adds: associative to a rounding

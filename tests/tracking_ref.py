@@ -18,7 +18,7 @@ STANDARD_HEIGHT, FOOT_ORIGIN_HEIGHT = 0.80, 0.06   # layout.default_config's rew
 
 # ---- part 1 and 2: the five errors, in `dtype` arithmetic ----
 def errors(aux, joint_bias, standard_height, foot_origin_height, dtype=np.float64):
-    """aux [..., 72] float32 -> (err [..., 5], mag [5]) in `dtype`: rewards_kernel's expressions before their exp (kbj_env.hip; quat_to_euler,
+    """aux [..., 72] float32 -> (err [..., 5], mag [5]) in `dtype`: rewards_kernel's expressions before their exp (kbj_traj_stats.hip; quat_to_euler,
     euler_to_quat, rotate_by_quat of kbj_env_core.h), operation by operation. mag[k] = the largest operand magnitude of expression k."""
     f = dtype
     a = np.asarray(aux, np.float32).astype(f)
