@@ -293,6 +293,47 @@ int kbj_episode_stats(kbj_ctx* ctx, const kbj_traj* traj, float* acc_d, double* 
  * settle_steps < 0. */
 int kbj_tracking_stats(kbj_ctx* ctx, const kbj_traj* traj, int settle_steps, float* acc_d, double* stats_d, float* err_d);
 
+/* ---- gait statistics --------------------------------------------------------------------------- */
+/* replaces: watching HOW the converted policy walks (the viewer and a pair of eyes): swing and stance times, support shares, hops, foot
+ * clearance, ground force and torque level, as numbers, split by the command mode of the row (KBJ_CMODE_*, the rule of kbj_tracking_stats).
+ * The reference rewards this behaviour with single_contact, no_contact, feet_airtime and torque (train.py:138-213, 503-506); nobody reads
+ * those in seconds, metres or newtons.
+ * Row quantities. For row (t, n), a = aux[t][n], foot f = 0 left, 1 right:
+ *   c[f] = a[KBJ_AUX_TOUCH + f] > 0.1f (rewards_kernel's own contact test; a NaN is no contact), F[f] = a[KBJ_AUX_TOUCH + f],
+ *   z[0] = a[KBJ_AUX_LFZ], z[1] = a[KBJ_AUX_RFZ], mode = the row's KBJ_CMODE_*,
+ *   q = sum over u = 0 .. 19, ascending, of (double)ctrl[u] * (double)ctrl[u], qmax = max over u of fabsf(ctrl[u]) (fmaxf, from 0).
+ *   TOUCH is the observation BEFORE the step, the foot heights are those AFTER it: a one-row skew that is part of the definition.
+ * Carry. acc_d [N][KBJ_GACC_SIZE] fp32 is device memory of the caller (zero it once; save it with the env state), updated in place: per
+ * foot CON, RUN, VALID, ZST, PEAK, then RUNNING and LAST_TD (kbj_model.h KBJ_GACC_*); the spare floats are left as they are.
+ * Scan. For every env n independently, for t ascending:
+ *   1. ROWS[mode] += 1; DOUBLE, SINGLE or FLIGHT[mode] += 1 for c[0] + c[1] = 2, 1, 0; TORQUE_SQ[mode] += q; TORQUE_MAX[mode] = max(.., qmax).
+ *   2. Per foot with c[f]: CONTACT_ROWS[mode][f] += 1; FORCE_SUM[mode][f] += (double)F[f]; FORCE_MAX[mode][f] = max(.., F[f]).
+ *   3. If RUNNING == 0 the row starts an episode: EPISODES += 1; per foot CON = c[f], RUN = 1, VALID = 0, ZST = z[f], PEAK = 0;
+ *      LAST_TD = -1. No events.
+ *   4. Otherwise, per foot, left then right: if c[f] == CON, RUN = min(RUN + 1, 2^24). Otherwise a phase ends:
+ *        touchdown (c[f]): TOUCHDOWNS[mode][f] += 1; if VALID: SWING_N += 1, SWING_SUM += RUN, SWING_SUMSQ += RUN^2, SWING_MAX = max(.., RUN),
+ *          CLEAR_SUM += PEAK, CLEAR_SUMSQ += PEAK^2 (in double), CLEAR_MAX = max(.., PEAK); if LAST_TD == f: REPEATS[mode] += 1; LAST_TD = f.
+ *        lift-off: LIFTOFFS[mode][f] += 1; if VALID: STANCE_N, STANCE_SUM, STANCE_SUMSQ, STANCE_MAX likewise from RUN.
+ *        then CON = c[f], RUN = 1, VALID = 1, PEAK = 0.
+ *   5. In either case, per foot: if c[f], ZST = z[f]; else PEAK = fmaxf(PEAK, z[f] - ZST).
+ *   6. RUNNING = (a[KBJ_AUX_DONE] == 0).
+ * So: a phase that began before the episode's first row has an unknown start - its end is counted as a touchdown or lift-off, its duration
+ * and clearance are not; a phase the episode's end cuts is dropped; durations are in rows; clearance is the rise of the foot origin over its
+ * height on the last contact row, which means the same on the terrain as on the plane. An event lands in the mode of the row that ends
+ * the phase.
+ * stats_d [KBJ_GAIT_SIZE] doubles is OVERWRITTEN (kbj_model.h KBJ_GAIT_*, KBJ_GFOOT_*): KBJ_CMODE_COUNT mode blocks, KBJ_GAIT_EPISODES, every
+ * other slot 0. Every maximum is of a non-negative quantity: 0 over nothing. The reduction runs in double, in a fixed order (one env's rows
+ * ascending, lanes in lane order, workgroups in block order), without atomics: the same inputs give the same bytes on every call, with or
+ * without env_d.
+ * env_d: NULL, or [N][KBJ_GENV_SIZE] fp32, overwritten: env n's totals of THIS call over all modes (kbj_model.h KBJ_GENV_*): ROWS, DOUBLE,
+ * SINGLE, FLIGHT, REPEATS, TORQUE_SQ, TORQUE_MAX, 0, then per foot TOUCHDOWNS, SWING_N, SWING_SUM, STANCE_N, STANCE_SUM, CLEAR_SUM,
+ * CLEAR_MAX, FORCE_MAX. Sums are accumulated in double in row order and rounded to fp32 once at the end: a float64 host loop in the same
+ * order reproduces every word (tests/gait_ref.py).
+ * Reads rows 0 .. T-1 of traj->aux_d only and writes no trajectory row; asynchronous on the context's stream. Fails with a message, before
+ * anything is launched, on a NULL ctx, traj, acc_d or stats_d, on a trajectory without aux_d or positive T, N, and on an acc_d, env_d or
+ * traj->aux_d that is not 16-byte aligned. */
+int kbj_gait_stats(kbj_ctx* ctx, const kbj_traj* traj, float* acc_d, double* stats_d, float* env_d);
+
 /* ---- push recovery ---------------------------------------------------------------------------- */
 /* replaces: shoving the robot and watching whether it stays up (what a locomotion policy is judged by before it goes on the robot), as
  * numbers: for one scheduled push per env, what became of it. Reads err_d [T][N][KBJ_TERR_SIZE], the per-row output of kbj_tracking_stats on

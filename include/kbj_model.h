@@ -355,6 +355,74 @@ enum {
   KBJ_TRK_SIZE        = 128
 };
 
+/* ---- gait statistics (kbj_gait_stats) ----
+ * Per-env carry row ("GACC" record, fp32, owned by the caller on the device like the TACC rows; zeroed once). Foot f (0 left, 1 right) keeps
+ * its five floats at KBJ_GACC_FOOT_STRIDE * f. */
+enum {
+  KBJ_GACC_CON         = 0,   /* 1 when the foot was in contact on the env's previous row */
+  KBJ_GACC_RUN         = 1,   /* rows the current phase (stance or swing) has lasted, the previous row included (integer valued, stops growing at 2^24) */
+  KBJ_GACC_VALID       = 2,   /* 1 when the current phase began inside the episode: its duration and clearance count when it ends */
+  KBJ_GACC_ZST         = 3,   /* the foot height on its last contact row (on the episode's first row while it has had none) */
+  KBJ_GACC_PEAK        = 4,   /* the largest rise over ZST in the current swing */
+  KBJ_GACC_FOOT_STRIDE = 6,   /* one spare float per foot, left as it is */
+  KBJ_GACC_RUNNING     = 12,  /* 1 when a previous row exists and did not end its episode */
+  KBJ_GACC_LAST_TD     = 13,  /* the foot of the episode's last touchdown, -1 before the first */
+  KBJ_GACC_SIZE        = 16   /* 64-byte rows; the two spare floats at the end are left as they are */
+};
+/* One call's result ("GAIT" record, doubles): KBJ_CMODE_COUNT mode blocks of KBJ_GAIT_MODE_STRIDE slots (mode m's slot s at
+ * m * KBJ_GAIT_MODE_STRIDE + s): seven row slots, then one block of KBJ_GAIT_FOOT_STRIDE foot slots per foot at KBJ_GAIT_FOOT +
+ * KBJ_GAIT_FOOT_STRIDE * f; then the episode counter. Every other slot is 0. Durations are in rows. */
+enum {
+  KBJ_GAIT_ROWS         = 0,    /* rows of the mode */
+  KBJ_GAIT_DOUBLE       = 1,    /* of them with both feet in contact, */
+  KBJ_GAIT_SINGLE       = 2,    /* with one, */
+  KBJ_GAIT_FLIGHT       = 3,    /* with none */
+  KBJ_GAIT_REPEATS      = 4,    /* touchdowns of the foot that had the episode's previous touchdown too (a hop) */
+  KBJ_GAIT_TORQUE_SQ    = 5,    /* sum over the rows of sum_u ctrl[u]^2 (taken in double) */
+  KBJ_GAIT_TORQUE_MAX   = 6,    /* largest |ctrl[u]| */
+  KBJ_GAIT_FOOT         = 8,    /* the first foot block */
+  KBJ_GAIT_FOOT_STRIDE  = 16,
+  KBJ_GAIT_MODE_STRIDE  = 40,
+  KBJ_GAIT_EPISODES     = 240,  /* rows that start an episode (no previous row, or the previous row ended its episode) */
+  KBJ_GAIT_SIZE         = 256
+};
+/* Slots of a foot block ("GFOOT"). A swing or stance enters SWING_* / STANCE_* / CLEAR_* when it ends, in the mode of the row that ends it,
+ * and only when it also began inside the episode. */
+enum {
+  KBJ_GFOOT_TOUCHDOWNS   = 0,   /* rows on which the foot gains contact inside a running episode */
+  KBJ_GFOOT_LIFTOFFS     = 1,   /* rows on which it loses contact */
+  KBJ_GFOOT_SWING_N      = 2,   /* counted swings, */
+  KBJ_GFOOT_SWING_SUM    = 3,   /* the sum of their durations, */
+  KBJ_GFOOT_SWING_SUMSQ  = 4,   /* of the squares, */
+  KBJ_GFOOT_SWING_MAX    = 5,   /* the longest */
+  KBJ_GFOOT_STANCE_N     = 6,   /* the same of the counted stances */
+  KBJ_GFOOT_STANCE_SUM   = 7,
+  KBJ_GFOOT_STANCE_SUMSQ = 8,
+  KBJ_GFOOT_STANCE_MAX   = 9,
+  KBJ_GFOOT_CLEAR_SUM    = 10,  /* over the counted swings: sum of the clearance (m), */
+  KBJ_GFOOT_CLEAR_SUMSQ  = 11,  /* of its square (taken in double), */
+  KBJ_GFOOT_CLEAR_MAX    = 12,  /* the largest */
+  KBJ_GFOOT_FORCE_SUM    = 13,  /* over the foot's contact rows: sum of the normal force (N), */
+  KBJ_GFOOT_FORCE_MAX    = 14,  /* the largest */
+  KBJ_GFOOT_CONTACT_ROWS = 15,  /* rows with the foot in contact */
+  KBJ_GFOOT_SIZE         = 16
+};
+/* One env's totals of one call over all modes ("GENV" record, fp32): the seven row slots of a mode block, then per foot f eight slots at
+ * KBJ_GENV_FOOT + KBJ_GENV_FOOT_STRIDE * f. */
+enum {
+  KBJ_GENV_FOOT        = 8,
+  KBJ_GENV_TOUCHDOWNS  = 0,   /* foot slots: */
+  KBJ_GENV_SWING_N     = 1,
+  KBJ_GENV_SWING_SUM   = 2,
+  KBJ_GENV_STANCE_N    = 3,
+  KBJ_GENV_STANCE_SUM  = 4,
+  KBJ_GENV_CLEAR_SUM   = 5,
+  KBJ_GENV_CLEAR_MAX   = 6,
+  KBJ_GENV_FORCE_MAX   = 7,
+  KBJ_GENV_FOOT_STRIDE = 8,
+  KBJ_GENV_SIZE        = 24
+};
+
 /* ---- scripted pushes and push recovery (kbj_env_set_push, kbj_push_recovery) ----
  * The KBJ_ES_PUSH_NXT value that keeps the built-in ForcePushEvent from drawing: 2^24, an exactly countable fp32 (x - 1 is exact all the way
  * down), about 93 h of control steps at 50 Hz. */

@@ -1,11 +1,13 @@
 // kbj_traj_stats.hip — HIP kernels + C-ABI entry points of everything that reads a finished trajectory: kbj_rewards (rewards_kernel below),
-// kbj_episode_stats (kbj_episode_stats.h), kbj_tracking_stats (kbj_tracking_stats.h) and kbj_push_recovery (kbj_push_recovery.h). None of it
+// kbj_episode_stats (kbj_episode_stats.h), kbj_tracking_stats (kbj_tracking_stats.h), kbj_gait_stats (kbj_gait_stats.h) and kbj_push_recovery
+// (kbj_push_recovery.h). None of it
 // is on the hot path, and none of it shares a translation unit with the env kernels (kbj_env.hip): an edit here recompiles no step kernel.
 #include <hip/hip_runtime.h>
 #include "kbj_env_core.h"
 #include "kbj_ordered_reduce.h"
 #include "kbj_episode_stats.h"
 #include "kbj_tracking_stats.h"
+#include "kbj_gait_stats.h"
 #include "kbj_ctx.h"
 #include "kbj_push_recovery.h"
 
@@ -116,8 +118,8 @@ __global__ void rewards_kernel(const kbj_model* __restrict__ m, const kbj_config
   rc[KBJ_RC_CONTACT] = pcon[0] ? 1.0f : 0.0f; rc[KBJ_RC_CONTACT + 1] = pcon[1] ? 1.0f : 0.0f;
 }
 
-// The workgroup partials of the two scans that end in ordered_reduce_kernel: one buffer per context, grown on first use (or for a wider
-// trajectory than any before), never per call. Both scans run on the context's stream, so a call's reduce has read the partials before the
+// The workgroup partials of the scans that end in ordered_reduce_kernel: one buffer per context, grown on first use (or for a wider
+// trajectory than any before), never per call. The scans run on the context's stream, so a call's reduce has read the partials before the
 // next call's scan writes them; the hipFree of a growth synchronises the device.
 int stats_partials(kbj_ctx* ctx, size_t doubles) {
   if (doubles <= ctx->stats_part_doubles) return 0;
@@ -179,6 +181,24 @@ int kbj_tracking_stats(kbj_ctx* ctx, const kbj_traj* tr, int settle_steps, float
   KBJ_CHECK_LAUNCH(ctx, "tracking_stats_kernel");
   hipLaunchKernelGGL(ordered_reduce_kernel<TrkSlots>, dim3(1), dim3(ORDERED_REDUCE_THREADS), 0, ctx->stream, ctx->stats_part_d, blocks, stats_d);
   KBJ_CHECK_LAUNCH(ctx, "ordered_reduce_kernel<TrkSlots>");
+  return 0;
+}
+
+int kbj_gait_stats(kbj_ctx* ctx, const kbj_traj* tr, float* acc_d, double* stats_d, float* env_d) {
+  if (!ctx || !tr || !acc_d || !stats_d) return kbj_fail(ctx, "kbj_gait_stats: null argument");
+  if (!tr->aux_d || tr->T <= 0 || tr->N <= 0) return kbj_fail(ctx, "kbj_gait_stats: the trajectory needs aux_d and positive T, N");
+  if ((reinterpret_cast<uintptr_t>(acc_d) | reinterpret_cast<uintptr_t>(env_d) | reinterpret_cast<uintptr_t>(tr->aux_d)) & 15)
+    return kbj_fail(ctx, "kbj_gait_stats: acc_d, env_d and aux_d must be 16-byte aligned");
+  KBJ_HIP(ctx, hipSetDevice(ctx->device));      // no kbj_nn_drop_prefetch: no trajectory row is written
+  const int blocks = (tr->N + GAIT_ENVS - 1) / GAIT_ENVS;
+  if (stats_partials(ctx, (size_t)blocks * KBJ_GAIT_SIZE) != 0) return -1;
+  {
+    KbjKernelTimer timer(ctx->stream, KBJ_KIND_GAIT_STATS, 0.0);
+    hipLaunchKernelGGL(gait_stats_kernel, dim3(blocks), dim3(GAIT_THREADS), 0, ctx->stream, tr->aux_d, tr->T, tr->N, acc_d, ctx->stats_part_d, env_d);
+  }
+  KBJ_CHECK_LAUNCH(ctx, "gait_stats_kernel");
+  hipLaunchKernelGGL(ordered_reduce_kernel<GaitSlots>, dim3(1), dim3(ORDERED_REDUCE_THREADS), 0, ctx->stream, ctx->stats_part_d, blocks, stats_d);
+  KBJ_CHECK_LAUNCH(ctx, "ordered_reduce_kernel<GaitSlots>");
   return 0;
 }
 

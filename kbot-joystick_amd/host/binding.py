@@ -102,6 +102,7 @@ SIGNATURES = {
     "kbj_gae": (_i, [_vp, C.POINTER(Traj), _vp, _vp]),
     "kbj_episode_stats": (_i, [_vp, C.POINTER(Traj), _vp, _vp]),
     "kbj_tracking_stats": (_i, [_vp, C.POINTER(Traj), _i, _vp, _vp, _vp]),
+    "kbj_gait_stats": (_i, [_vp, C.POINTER(Traj), _vp, _vp, _vp]),
     "kbj_push_recovery": (_i, [_vp, C.POINTER(Traj), _vp, _vp, C.POINTER(PushCriteria), _vp, _vp, _i, _vp]),
     "kbj_ppo_grad": (_i, [_vp, _vp, C.POINTER(Traj), _vp, _i, _vp, _vp, _vp, _vp]),
     "kbj_ppo_forward": (_i, [_vp, _vp, C.POINTER(Traj), _vp, _i, C.POINTER(PpoVars)]),
@@ -344,6 +345,11 @@ class Context:
         """kbj_tracking_stats: acc [N, TACC SIZE] float32 (updated in place), stats [TRK SIZE] float64 (overwritten), err None or
         [T, N, TERR SIZE] float32 (every row's errors, mode, settled flag, since), all on the device."""
         self.call("kbj_tracking_stats", C.byref(traj), int(settle_steps), _ptr(acc), _ptr(stats), _ptr(err))
+
+    def gait_stats(self, traj: Traj, acc, stats, env=None):
+        """kbj_gait_stats: acc [N, GACC SIZE] float32 (updated in place), stats [GAIT SIZE] float64 (overwritten), env None or
+        [N, GENV SIZE] float32 (every env's totals of this call, overwritten), all on the device."""
+        self.call("kbj_gait_stats", C.byref(traj), _ptr(acc), _ptr(stats), _ptr(env))
 
     def push_recovery(self, traj: Traj, err, sched, criteria: PushCriteria, rec, group=None, G: int = 1, stats=None):
         """kbj_push_recovery: err [T, N, TERR SIZE] float32 (kbj_tracking_stats' per-row output), sched [N, 2] int32 (start row, pushed steps;

@@ -91,6 +91,12 @@ class HumanoidWalkingTaskConfig:
     # nothing is allocated, launched or logged. task.tracking_sweep() - the joystick response table - works with the switch off too.
     tracking_stats: bool = _env_flag("KBJ_TRACKING_STATS")
     tracking_settle_seconds: float = 0.5    # settle_steps = round(tracking_settle_seconds / ctrl_dt)
+    # gait statistics on the device (kbj_gait_stats; host/gait.py): how the robot walks - swing and stance times, duty factor, step rate, double-support
+    # and flight share, foot clearance, left/right asymmetry, hops, peak ground force and torque level, in seconds, metres and newtons, split by the
+    # six command modes; merged into scalars() / validate() as gait/<mode>/..., carried per env across rollouts and through checkpoints. Off (the
+    # default; KBJ_GAIT_STATS in the environment overrides it, for A/B runs with tools/ab_bench.py): nothing is allocated, launched or logged.
+    # task.gait_sweep() - the gait table per command - works with the switch off too.
+    gait_stats: bool = _env_flag("KBJ_GAIT_STATS")
     # GAE boundary conventions (include/kbj.h kbj_gae). Both off by default - this build's choice: every termination ends the
     # return, V_T := V_{T-1} - and selectable, because SURVEY B.2 believes ksim bootstraps through the episode-length "success" termination:
     # bootstrap_on_truncation: at DONE = +1 (time-out, or a user term's +1) delta = r + gamma V(s_t) - V(s_t) instead of r - V(s_t);

@@ -115,3 +115,10 @@ empty_episode_stats, combine_episode_stats, reduce_episode_stats = EPISODE_STATS
 # errors are non-negative). HumanoidWalkingTask.tracking_stats() reduces them
 TRACKING_STATS = StatsLayout(L.TRK["SIZE"], max0_slots=[m * L.TRK["MODE_STRIDE"] + L.TRK["MAX"] + k for m in range(L.CMODE["COUNT"]) for k in range(L.NTERR)])
 empty_tracking_stats, combine_tracking_stats, reduce_tracking_stats = TRACKING_STATS.empty, TRACKING_STATS.combine, TRACKING_STATS.reduce
+
+# kbj_gait_stats vectors (kbj_model.h KBJ_GAIT_*, KBJ_GFOOT_*): every slot is a count or a sum, except the largest torque of each mode block and the
+# longest swing, longest stance, largest clearance and largest force of each of its foot blocks (all non-negative).
+# HumanoidWalkingTask.gait_stats() reduces them
+GAIT_STATS = StatsLayout(L.GAIT["SIZE"], max0_slots=[L.gait_slot(m, "TORQUE_MAX") for m in range(L.CMODE["COUNT"])] +
+                         [L.gait_slot(m, k, f) for m in range(L.CMODE["COUNT"]) for f in range(2) for k in ("SWING_MAX", "STANCE_MAX", "CLEAR_MAX", "FORCE_MAX")])
+empty_gait_stats, combine_gait_stats, reduce_gait_stats = GAIT_STATS.empty, GAIT_STATS.combine, GAIT_STATS.reduce

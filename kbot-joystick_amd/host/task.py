@@ -28,6 +28,7 @@ from .buffers import CarryBuffers, TrajBuffers
 from .ckpt import ModelView
 from .config import HumanoidWalkingTaskConfig, cosine_decay_lr, launch_config      # launch_config: re-exported with the rest
 from .episode import EpisodeStats, episode_stats_scalars, fresh_episode_stats
+from .gait import GaitStats, format_gait_table, fresh_gait_stats, gait_scalars, gait_sweep      # noqa: F401 (re-exported)
 from .push import PushRecord, ScriptedPush, format_push_table, push_sweep      # noqa: F401 (re-exported)
 from .tracking import TrackingStats, format_tracking_table, fresh_tracking_stats, settle_steps, tracking_scalars, tracking_sweep      # noqa: F401 (re-exported)
 from .user_terms import UserTerms
@@ -142,6 +143,8 @@ class HumanoidWalkingTask:
         # command-tracking errors (config.tracking_stats; host/tracking.py): `trk_acc`, the per-env carry rows next to the env state; None means off
         self.tracking = TrackingStats(self.N, settle_steps(config.tracking_settle_seconds, config.ctrl_dt), self.device) if config.tracking_stats else None
         self.trk_acc = self.tracking.acc if self.tracking is not None else None
+        # gait statistics (config.gait_stats; host/gait.py): `gait.acc`, the per-env carry rows next to the env state; None means off
+        self.gait = GaitStats(self.N, self.device) if config.gait_stats else None
         self.opt_step = 0
         self.iteration = 0
         self._perm_gen = torch.Generator(device="cpu")
@@ -183,6 +186,42 @@ class HumanoidWalkingTask:
             self.episodes.after_rollout(self.ctx, self.traj.c)
         if self.tracking is not None:             # the aux rows are all it reads: neither rewards nor reward_comps
             self.tracking.after_rollout(self.ctx, self.traj.c)
+        if self.gait is not None:                 # the aux rows likewise
+            self.gait.after_rollout(self.ctx, self.traj.c)
+
+    def gait_stats_vectors(self):
+        """(last, total): this rank's raw KBJ_GAIT vectors (float64 numpy, layout.GAIT / GFOOT) behind gait_stats() - the rows of the last
+        rollout and all since creation / resume."""
+        if self.gait is None:
+            raise B.KbjError("gait_stats_vectors() needs HumanoidWalkingTaskConfig.gait_stats=True")
+        last, total = self.gait.vectors()
+        return last.copy(), total.copy()
+
+    def gait_stats(self, total: bool = False) -> dict:
+        """How the robot walks (needs `gait_stats=True` in the config) over the LAST rollout - or, with `total`, over all rollouts since the
+        task was created or resumed, as `gait_total/...`: per command mode that has rows `gait/<mode>/double_support_frac`,
+        `single_support_frac`, `flight_frac`, `step_rate_hz`, `repeat_frac` (hops), `torque_rms`, `torque_max`, per foot
+        `left_` / `right_` `swing_s_mean` / `_std` / `_max`, `stance_s_mean` / `_std` / `_max`, `duty`, `clearance_m_mean` / `_max`,
+        `force_n_mean` / `_max`, and `swing_asymmetry` (host/gait.py gait_scalars; the definitions: include/kbj.h kbj_gait_stats). In a
+        multi-rank job the vectors are reduced over the ranks (dist.reduce_gait_stats): every rank must call it."""
+        if self.gait is None:
+            raise B.KbjError("gait_stats() needs HumanoidWalkingTaskConfig.gait_stats=True")
+        vec = self.gait.vectors()[1 if total else 0]
+        if self.world_size > 1 or dist_util.FORCE_COLLECTIVE:
+            vec = dist_util.reduce_gait_stats(torch.from_numpy(vec).to(self.device), self.world_size).cpu().numpy()
+        return gait_scalars(vec, self.config.ctrl_dt, "gait_total/" if total else "gait/")
+
+    def gait_sweep(self, commands=None, repeats: int = 2, seconds: Optional[float] = None, seed_offset: int = 7919) -> list:
+        """The gait table: how the CURRENT policy walks under each of `commands` (as tracking_sweep takes them; default:
+        host/tracking.default_command_grid). tracking_sweep's rollout - a context of its own with len(commands) * repeats envs (env e follows
+        command e % K), `seconds` (default render_length_seconds) of argmax actions under a scripted Command term, the user's Reset and
+        network-input Observation terms applied as in validate(), Event terms not - then ONE kbj_gait_stats call on a fresh carry with the
+        per-env record. Returns one dict per command, pooled over its envs: `command`, `mode`, per foot `left_` / `right_` `swing_s`,
+        `stance_s` (mean, seconds), `clearance_m_mean` / `_max`, `force_n_max`; `step_rate_hz`, `double_support_frac` /
+        `single_support_frac` / `flight_frac`, `repeat_frac`, `torque_rms`, `failures_per_s` (nan over nothing). `format_gait_table`
+        renders it. Works with `gait_stats` off. Like the push table, this one has NOT been taken on a trained policy: what a
+        good gait looks like in it is not known from this build."""
+        return gait_sweep(self, commands, repeats, seconds, seed_offset)[0]
 
     def tracking_stats_vectors(self):
         """(last, total): this rank's raw KBJ_TRK vectors (float64 numpy, layout.TRK) behind tracking_stats() - the rows of the last rollout
@@ -456,6 +495,8 @@ class HumanoidWalkingTask:
             extras.update(self.episodes.checkpoint_state())
         if self.tracking is not None:
             extras.update(self.tracking.checkpoint_state())
+        if self.gait is not None:
+            extras.update(self.gait.checkpoint_state())
         # carries of Python StatefulReward terms (extra_rewards): tensors (or tuples / lists of tensors) per term name
         for name, carry in self._extra_carries.items():
             leaves = list(carry) if isinstance(carry, (tuple, list)) else [carry]
@@ -518,6 +559,8 @@ class HumanoidWalkingTask:
             self.episodes.load_checkpoint_state(x)
         if self.tracking is not None:
             self.tracking.load_checkpoint_state(x)
+        if self.gait is not None:
+            self.gait.load_checkpoint_state(x)
         if "es" not in x:
             return            # a model-only checkpoint (e.g. written by the reference): parameters and optimizer only
         if x["es"].shape[0] != self.N:
@@ -616,6 +659,8 @@ class HumanoidWalkingTask:
             vstats = fresh_episode_stats(vctx, tr.c, num_envs, self.device)
         if self.tracking is not None:   # a fresh carry likewise, on the fused and on the step-wise path
             vtrack = fresh_tracking_stats(vctx, tr.c, num_envs, self.tracking.settle_steps, self.device)
+        if self.gait is not None:
+            vgait = fresh_gait_stats(vctx, tr.c, num_envs, self.device)
         vctx.synchronize()
         done = tr.done
         fails, succ = float((done < 0).sum()), float((done > 0).sum())
@@ -627,6 +672,8 @@ class HumanoidWalkingTask:
             out.update(episode_stats_scalars(vstats.cpu().numpy(), self.config.ctrl_dt, "valid/episode/", terms=True))
         if self.tracking is not None:
             out.update(tracking_scalars(vtrack.cpu().numpy(), "valid/track/"))
+        if self.gait is not None:
+            out.update(gait_scalars(vgait.cpu().numpy(), self.config.ctrl_dt, "valid/gait/"))
         return out
 
     def close_validation(self):
@@ -683,6 +730,8 @@ class HumanoidWalkingTask:
             out.update(self.episode_stats())
         if self.tracking is not None:
             out.update(self.tracking_stats())
+        if self.gait is not None:
+            out.update(self.gait_stats())
         return out
 
     def export_actor(self, path: str):

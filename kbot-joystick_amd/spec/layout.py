@@ -111,6 +111,22 @@ CMODE = dict(FORWARD=0, SIDEWAYS=1, ROTATE=2, OMNI=3, STAND_BEND=4, STAND=5, COU
 TERR = dict(LIN=0, YAW=1, TILT=2, HEIGHT=3, ARM=4, MODE=5, SETTLED=6, SINCE=7, SIZE=8)
 TACC = dict(CMD=0, SINCE=16, RUNNING=17, SIZE=20)
 TRK = dict(ROWS=0, SETTLED=1, SUM=2, SUMSQ=7, MAX=12, MODE_STRIDE=20, CHANGES=120, EPISODES=121, SIZE=128)
+# kbj_model.h KBJ_GACC_* / KBJ_GAIT_* / KBJ_GFOOT_* / KBJ_GENV_*: the per-env carry row of kbj_gait_stats (fp32; foot f at FOOT_STRIDE * f), one call's
+# result (float64: mode m's slot s at m * MODE_STRIDE + s, foot f's GFOOT slot k of the mode at FOOT + FOOT_STRIDE * f + k, then the episode
+# counter) and one env's totals of a call (fp32: the GAIT row slots, then foot f's slot k at FOOT + FOOT_STRIDE * f + k)
+GACC = dict(CON=0, RUN=1, VALID=2, ZST=3, PEAK=4, FOOT_STRIDE=6, RUNNING=12, LAST_TD=13, SIZE=16)
+GAIT = dict(ROWS=0, DOUBLE=1, SINGLE=2, FLIGHT=3, REPEATS=4, TORQUE_SQ=5, TORQUE_MAX=6, FOOT=8, FOOT_STRIDE=16, MODE_STRIDE=40, EPISODES=240, SIZE=256)
+GFOOT = dict(TOUCHDOWNS=0, LIFTOFFS=1, SWING_N=2, SWING_SUM=3, SWING_SUMSQ=4, SWING_MAX=5, STANCE_N=6, STANCE_SUM=7, STANCE_SUMSQ=8, STANCE_MAX=9,
+             CLEAR_SUM=10, CLEAR_SUMSQ=11, CLEAR_MAX=12, FORCE_SUM=13, FORCE_MAX=14, CONTACT_ROWS=15, SIZE=16)
+GENV = dict(FOOT=8, TOUCHDOWNS=0, SWING_N=1, SWING_SUM=2, STANCE_N=3, STANCE_SUM=4, CLEAR_SUM=5, CLEAR_MAX=6, FORCE_MAX=7, FOOT_STRIDE=8, SIZE=24)
+
+
+def gait_slot(mode: int, name: str, foot=None) -> int:
+    """The slot of a KBJ_GAIT vector: a row slot (`name` in GAIT) of mode block `mode`, or with `foot` (0 left, 1 right) the foot slot `name` (in GFOOT)."""
+    base = mode * GAIT["MODE_STRIDE"]
+    return base + GAIT[name] if foot is None else base + GAIT["FOOT"] + GAIT["FOOT_STRIDE"] * foot + GFOOT[name]
+
+
 # kbj_model.h KBJ_PUSH_NEVER / KBJ_POUT_* / KBJ_PREC_* / KBJ_PSTAT_*: the PUSH_NXT value that keeps the built-in push event from drawing, the outcome
 # of a scheduled push, one env's result row of kbj_push_recovery (fp32) and one group's statistics (float64)
 PUSH_NEVER = 16777216.0
