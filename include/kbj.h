@@ -371,6 +371,72 @@ typedef struct kbj_push_criteria {
 int kbj_push_recovery(kbj_ctx* ctx, const kbj_traj* traj, const float* err_d, const int32_t* sched_d, const kbj_push_criteria* crit,
                       float* rec_d, const int32_t* group_d, int G, double* stats_d);
 
+/* ---- command step response -------------------------------------------------------------------- */
+/* replaces: moving the stick and watching what the robot does (the first thing a joystick user feels), as numbers: for one scheduled
+ * command change per env, how long the robot takes to reach the new command, how far it overshoots, when it settles, how far it travels
+ * on the way, how much the channels that did not move are disturbed, and whether it falls. Channel k = 0 forward, 1 sideways, 2 yaw is
+ * signal word k against command word k. The criteria are SETTINGS of the caller, not measured thresholds.
+ * Stage 1, the signal. For every row (t, n), t = 0 .. T-1, with a = aux[t][n] and (w, x, y, z) = a[KBJ_AUX_BQUAT ..]:
+ *   sn = 2 (w z + x y), cs = 1 - 2 (y^2 + z^2), h = sqrtf(sn^2 + cs^2); (c, s) = (cs / h, sn / h) if h > 0, else (1, 0)
+ *   (the trigonometry-free heading of the env kernel's feet observation), and with (vx, vy) = a[KBJ_AUX_QVEL + 0 .. 1]:
+ *   VX = c vx + s vy, VY = -s vx + c vy, WZ = a[KBJ_AUX_QVEL + 5], DONE = a[KBJ_AUX_DONE], CMD = a[KBJ_AUX_CMD + 0 .. 2] copied bit for
+ *   bit, the spare word 0 (kbj_model.h KBJ_SSIG_*). Plain fp32: VX and VY agree with a double evaluation within rounding, not bit for bit.
+ *   sig_d [T][N][KBJ_SSIG_SIZE] fp32 is OVERWRITTEN. Everything below is an exact function of sig_d.
+ * Stage 2, per env n. s = sched_d[n] is the first row whose command is the new one; m = crit->smooth_steps, hold = crit->hold_steps,
+ * window = crit->window_steps. All index arithmetic is in 64 bits: the schedule is the caller's.
+ *   1. s < 0: NONE.
+ *   2. c0 = CMD of row s - 1, c1 = CMD of row s, D_k = c1[k] - c0[k] in fp32, sg_k = +1 if D_k > 0, else -1.
+ *      Channel k is active iff fabsf(D_k) >= min_step[k]. band_k = fmaxf(band_abs[k], band_frac * fabsf(D_k)),
+ *      thr_k = rise_level * fabsf(D_k), each product rounded to fp32 once (round to nearest; no contraction).
+ *      Every fmaxf here is taken as "replaced where the new value is greater": a NaN or a -0 never replaces the old value.
+ *   3. The smoothed value S_k(t) = (float)((sum over u = max(s - hold, t - m + 1) .. t of (double)sig[u][n][k]) / (double)count): the sum
+ *      ascends in u and is rounded once.
+ *   4. VOID if any of: s >= T, or s < hold; a row in [s - hold, s) has DONE != 0; a row in [s - hold, s) has a CMD word that differs
+ *      from c0 (float !=); no channel is active; |S_k(s - 1) - c0[k]| <= band_k is false for any of the three channels (the robot was
+ *      not on its old command when the stick moved; a NaN is not within).
+ *   5. Otherwise the rows t = s .. min(T, s + window) - 1 are scanned in order. On each row, in this order:
+ *        1. DONE < 0: FELL, FALL_STEPS = t - s. Stop.
+ *        2. DONE > 0: CENSORED. Stop.
+ *        3. any CMD word != c1: CENSORED (the stick moved again). Stop.
+ *        4. d_k = S_k(t) - c1[k] and p_k = sg_k (S_k(t) - c0[k]), each one fp32 subtraction, the sign applied by negation.
+ *           Active channel: if RISE_k is still -1 and p_k >= thr_k, RISE_k = t - s; OVER_k = fmaxf(OVER_k, sg_k d_k), from 0.
+ *           Inactive channel: DEV_k = fmaxf(DEV_k, fabsf(d_k)), from 0 (the cross-coupling).
+ *        5. the travel sums, in double, add the RAW VX, VY, WZ of the row.
+ *        6. within = fabsf(d_k) <= band_k for all three channels; run = within ? run + 1 : 0; when run reaches hold: SETTLED,
+ *           SETTLE_STEPS = (t - hold + 1) - s. Stop.
+ *   6. Undecided at the end: CENSORED if s + window > T (the trajectory cut the window), else UNSETTLED.
+ *   7. rec_d [N][KBJ_SREC_SIZE] fp32 is OVERWRITTEN (kbj_model.h KBJ_SREC_*). TRAVEL_X, _Y, _YAW = the three double sums, each rounded
+ *      to fp32 once, over the rows on which step 5.5 ran: up to and including the deciding row of a SETTLED env, up to the row in front
+ *      of the one that stopped the scan in 5.1 - 5.3. Their unit is (m/s or rad/s) x rows: multiply by ctrl_dt. They are a path
+ *      integral in the heading frame, and equal a displacement only while the heading barely turns. ACTIVE = sum of 2^k over the
+ *      active channels. Fields that do not apply are -1: RISE / OVER of an inactive channel, DEV of an active one, and everything but
+ *      OUTCOME for NONE and VOID. The spare words are 0.
+ * stats_d: NULL, or [G][KBJ_SSTAT_SIZE] doubles, overwritten (spare slots 0; kbj_model.h KBJ_SSTAT_*): per group g the envs per outcome;
+ * over its SETTLED envs the sum, sum of squares and maximum of SETTLE_STEPS; over its FELL envs those of FALL_STEPS; per channel over the
+ * valid envs (FELL and above) with the channel active ACTIVE_N, the sum and maximum of OVER and, over those of them with RISE >= 0,
+ * RISE_N and the sum and maximum of RISE; per channel over the valid envs with the channel inactive DEV_N and the sum and maximum of
+ * DEV; over the SETTLED envs the signed sum and the largest magnitude of each TRAVEL word. A maximum over nothing is -1, and a NaN
+ * never becomes one. group_d [N] int32 names every env's group (NULL: all in group 0; a value outside [0, G) puts the env in no group),
+ * 1 <= G <= 256. A group's envs are combined in env order, in doubles, without atomics: the same inputs give the same bytes on every
+ * call, with or without stats_d.
+ * Reads rows 0 .. T-1 of traj->aux_d (40 bytes at the head of a row, three command words and DONE) and sched_d [N] int32; overwrites
+ * sig_d, rec_d and stats_d. Asynchronous on the context's stream; crit is read before the call returns. Fails with a message, before
+ * anything is launched, on a NULL ctx, traj, sched_d, crit, sig_d or rec_d, on a trajectory without aux_d or positive T, N, on a
+ * traj->aux_d, sig_d or rec_d that is not 16-byte aligned, on smooth_steps outside [1, 32], hold_steps < 1, window_steps < 1,
+ * rise_level outside (0, 1], a negative or NaN band_frac, band_abs or min_step, and with stats_d on G outside [1, 256]. The context
+ * stays usable after such a failure. */
+typedef struct kbj_step_criteria {
+  float min_step[3];   /* a channel is active when |c1[k] - c0[k]| >= min_step[k] */
+  float band_abs[3];   /* settle band floor per channel: m/s, m/s, rad/s */
+  float band_frac;     /* settle band as a share of the step size */
+  float rise_level;    /* in (0, 1] */
+  int32_t smooth_steps, hold_steps, window_steps;   /* 1..32, >= 1, >= 1 */
+} kbj_step_criteria;
+int kbj_sizeof_step_criteria(void);   /* sizeof(kbj_step_criteria), for a binding's mirror */
+int kbj_step_response(kbj_ctx* ctx, const kbj_traj* traj, const int32_t* sched_d /* [N] */, const kbj_step_criteria* crit,
+                      float* sig_d /* [T][N][KBJ_SSIG_SIZE] */, float* rec_d /* [N][KBJ_SREC_SIZE] */,
+                      const int32_t* group_d, int G, double* stats_d);
+
 /* ---- PPO update, rows a9, a12, a13 ---------------------------------------------------------- */
 /* replaces: ksim GAE (gamma, lam: train.py:1769-1770). done from aux; adv_d/target_d [T][N].
  * Per env n, for t = T-1 .. 0, with d = aux[t][n][KBJ_AUX_DONE], v = value[t][n], r = reward[t][n] and A_T = 0:

@@ -464,6 +464,68 @@ enum {
   KBJ_PSTAT_SIZE       = 24
 };
 
+/* ---- command step response (kbj_step_response) ----
+ * One row of the response signal ("SSIG" record, fp32): the base velocity in the robot's heading frame, the yaw rate, and the words of the
+ * aux row the scan needs beside them. Channel k of a step (0 forward, 1 sideways, 2 yaw) is signal word k and command word k. */
+enum {
+  KBJ_SSIG_VX    = 0,   /* c qvel[0] + s qvel[1], (c, s) the trigonometry-free heading of the base quaternion, m/s */
+  KBJ_SSIG_VY    = 1,   /* -s qvel[0] + c qvel[1], m/s */
+  KBJ_SSIG_WZ    = 2,   /* qvel[5], rad/s (copied) */
+  KBJ_SSIG_DONE  = 3,   /* KBJ_AUX_DONE of the row (copied) */
+  KBJ_SSIG_CMD   = 4,   /* [3] KBJ_AUX_CMD + 0..2 of the row (copied) */
+  KBJ_SSIG_SPARE = 7,   /* written 0 */
+  KBJ_SSIG_SIZE  = 8
+};
+#define KBJ_NSCH 3 /* channels of a command step: forward, sideways, yaw */
+/* Outcome of one env's scheduled command step (kbj.h kbj_step_response). Valid = KBJ_SOUT_FELL and above, as with KBJ_POUT_*. */
+enum {
+  KBJ_SOUT_NONE      = 0,   /* no step scheduled (row < 0) */
+  KBJ_SOUT_VOID      = 1,   /* the step says nothing: outside the trajectory, no channel moved, or the env was not on its old command / had just ended an episode */
+  KBJ_SOUT_FELL      = 2,   /* a failure (DONE < 0) inside the window */
+  KBJ_SOUT_SETTLED   = 3,   /* hold_steps consecutive rows with every channel inside its band of the new command */
+  KBJ_SOUT_UNSETTLED = 4,   /* the whole window was seen, without a fall and without such a run */
+  KBJ_SOUT_CENSORED  = 5,   /* a time-out (DONE > 0), another command change, or the end of the trajectory cut the window before a decision */
+  KBJ_SOUT_COUNT     = 6
+};
+/* One env's record ("SREC" record, fp32). A field that does not apply is -1; the spare words are 0. Times are in rows from the step row. */
+enum {
+  KBJ_SREC_OUTCOME      = 0,    /* KBJ_SOUT_* */
+  KBJ_SREC_SETTLE_STEPS = 1,    /* SETTLED: rows from the step to the first row of the hold run */
+  KBJ_SREC_FALL_STEPS   = 2,    /* FELL: rows from the step to the failing row */
+  KBJ_SREC_ACTIVE       = 3,    /* valid outcomes: bit k set = channel k is active (its command moved by at least min_step[k]), held as a float */
+  KBJ_SREC_TRAVEL_X     = 4,    /* valid outcomes: sum of the raw VX over the scanned rows, (m/s) x rows */
+  KBJ_SREC_TRAVEL_Y     = 5,    /* of VY */
+  KBJ_SREC_TRAVEL_YAW   = 6,    /* of WZ, (rad/s) x rows */
+  KBJ_SREC_SPARE        = 7,    /* written 0 */
+  KBJ_SREC_RISE         = 8,    /* [3] active channel: rows from the step to the first row at or beyond rise_level of the step, -1 if never */
+  KBJ_SREC_OVER         = 11,   /* [3] active channel: largest excursion of the smoothed value beyond the new command, in the step's direction (>= 0) */
+  KBJ_SREC_DEV          = 14,   /* [3] inactive channel: largest |smoothed value - command| (the cross-coupling) */
+  KBJ_SREC_SPARE_TAIL   = 17,   /* [3] written 0 */
+  KBJ_SREC_SIZE         = 20    /* 80-byte rows */
+};
+/* One group's statistics ("SSTAT" record, doubles). A maximum over nothing is -1; spare slots are 0. */
+enum {
+  KBJ_SSTAT_COUNT         = 0,    /* [6] envs per outcome, KBJ_SOUT_* order */
+  KBJ_SSTAT_SETTLE_SUM    = 6,    /* over the SETTLED envs: sum of SETTLE_STEPS, */
+  KBJ_SSTAT_SETTLE_SUMSQ  = 7,    /* of its square, */
+  KBJ_SSTAT_SETTLE_MAX    = 8,    /* its maximum */
+  KBJ_SSTAT_FALL_SUM      = 9,    /* over the FELL envs: sum of FALL_STEPS, */
+  KBJ_SSTAT_FALL_SUMSQ    = 10,   /* of its square, */
+  KBJ_SSTAT_FALL_MAX      = 11,   /* its maximum */
+  KBJ_SSTAT_ACTIVE_N      = 12,   /* [3] per channel: valid envs with the channel active */
+  KBJ_SSTAT_RISE_N        = 15,   /* [3] of them those with RISE >= 0, */
+  KBJ_SSTAT_RISE_SUM      = 18,   /* [3] the sum of their RISE, */
+  KBJ_SSTAT_RISE_MAX      = 21,   /* [3] its maximum */
+  KBJ_SSTAT_OVER_SUM      = 24,   /* [3] over the valid envs with the channel active: sum of OVER, */
+  KBJ_SSTAT_OVER_MAX      = 27,   /* [3] its maximum */
+  KBJ_SSTAT_DEV_N         = 30,   /* [3] per channel: valid envs with the channel inactive, */
+  KBJ_SSTAT_DEV_SUM       = 33,   /* [3] the sum of their DEV, */
+  KBJ_SSTAT_DEV_MAX       = 36,   /* [3] its maximum */
+  KBJ_SSTAT_TRAVEL_SUM    = 39,   /* [3] over the SETTLED envs: signed sum of TRAVEL_X, _Y, _YAW, */
+  KBJ_SSTAT_TRAVEL_ABSMAX = 42,   /* [3] the largest magnitude */
+  KBJ_SSTAT_SIZE          = 48    /* three spare slots, written 0 */
+};
+
 /* reward component order (train.py:1225-1256) */
 enum {
   KBJ_REW_LINVEL = 0, KBJ_REW_ANGVEL, KBJ_REW_ROLL_PITCH, KBJ_REW_BASE_HEIGHT, KBJ_REW_ARM_POS,

@@ -1,6 +1,6 @@
 // kbj_traj_stats.hip — HIP kernels + C-ABI entry points of everything that reads a finished trajectory: kbj_rewards (rewards_kernel below),
-// kbj_episode_stats (kbj_episode_stats.h), kbj_tracking_stats (kbj_tracking_stats.h), kbj_gait_stats (kbj_gait_stats.h) and kbj_push_recovery
-// (kbj_push_recovery.h). None of it
+// kbj_episode_stats (kbj_episode_stats.h), kbj_tracking_stats (kbj_tracking_stats.h), kbj_gait_stats (kbj_gait_stats.h), kbj_push_recovery
+// (kbj_push_recovery.h) and kbj_step_response (kbj_step_response.h). None of it
 // is on the hot path, and none of it shares a translation unit with the env kernels (kbj_env.hip): an edit here recompiles no step kernel.
 #include <hip/hip_runtime.h>
 #include "kbj_env_core.h"
@@ -10,6 +10,7 @@
 #include "kbj_gait_stats.h"
 #include "kbj_ctx.h"
 #include "kbj_push_recovery.h"
+#include "kbj_step_response.h"
 
 using namespace kbj;
 
@@ -220,6 +221,37 @@ int kbj_push_recovery(kbj_ctx* ctx, const kbj_traj* tr, const float* err_d, cons
   if (stats_d) {
     hipLaunchKernelGGL(push_recovery_reduce_kernel, dim3(1), dim3(PR_RED_THREADS), 0, ctx->stream, rec_d, group_d, tr->N, G, stats_d);
     KBJ_CHECK_LAUNCH(ctx, "push_recovery_reduce_kernel");
+  }
+  return 0;
+}
+
+int kbj_step_response(kbj_ctx* ctx, const kbj_traj* tr, const int32_t* sched_d, const kbj_step_criteria* crit, float* sig_d, float* rec_d,
+                      const int32_t* group_d, int G, double* stats_d) {
+  if (!ctx || !tr || !sched_d || !crit || !sig_d || !rec_d) return kbj_fail(ctx, "kbj_step_response: null argument");
+  if (!tr->aux_d || tr->T <= 0 || tr->N <= 0) return kbj_fail(ctx, "kbj_step_response: the trajectory needs aux_d and positive T, N");
+  if ((reinterpret_cast<uintptr_t>(tr->aux_d) | reinterpret_cast<uintptr_t>(sig_d) | reinterpret_cast<uintptr_t>(rec_d)) & 15)
+    return kbj_fail(ctx, "kbj_step_response: aux_d, sig_d and rec_d must be 16-byte aligned");
+  if (crit->smooth_steps < 1 || crit->smooth_steps > SR_RING) return kbj_fail(ctx, "kbj_step_response: smooth_steps must be in [1, 32]");
+  static_assert(SR_RING == 32 && SR_RED_THREADS == 256, "the smooth_steps and G ranges kbj.h documents");
+  if (crit->hold_steps < 1) return kbj_fail(ctx, "kbj_step_response: hold_steps must be at least 1");
+  if (crit->window_steps < 1) return kbj_fail(ctx, "kbj_step_response: window_steps must be at least 1");
+  if (!(crit->rise_level > 0.0f && crit->rise_level <= 1.0f)) return kbj_fail(ctx, "kbj_step_response: rise_level must be in (0, 1]");
+  if (!(crit->band_frac >= 0.0f)) return kbj_fail(ctx, "kbj_step_response: band_frac is negative or NaN");
+  for (int k = 0; k < KBJ_NSCH; ++k) {
+    if (!(crit->band_abs[k] >= 0.0f)) return kbj_fail(ctx, "kbj_step_response: a band_abs is negative or NaN");
+    if (!(crit->min_step[k] >= 0.0f)) return kbj_fail(ctx, "kbj_step_response: a min_step is negative or NaN");
+  }
+  if (stats_d && (G < 1 || G > SR_RED_THREADS)) return kbj_fail(ctx, "kbj_step_response: G must be in [1, 256]");
+  KBJ_HIP(ctx, hipSetDevice(ctx->device));      // no kbj_nn_drop_prefetch: no trajectory row is written
+  const size_t rows = (size_t)tr->T * (size_t)tr->N;
+  const size_t sig_blocks = (rows + SR_SIG_THREADS - 1) / SR_SIG_THREADS;
+  hipLaunchKernelGGL(step_signal_kernel, dim3((unsigned)(sig_blocks < (1u << 20) ? sig_blocks : (1u << 20))), dim3(SR_SIG_THREADS), 0, ctx->stream, tr->aux_d, rows, sig_d);
+  KBJ_CHECK_LAUNCH(ctx, "step_signal_kernel");
+  hipLaunchKernelGGL(step_scan_kernel, dim3((tr->N + SR_ENVS - 1) / SR_ENVS), dim3(SR_ENVS), 0, ctx->stream, sig_d, tr->T, tr->N, sched_d, *crit, rec_d);
+  KBJ_CHECK_LAUNCH(ctx, "step_scan_kernel");
+  if (stats_d) {
+    hipLaunchKernelGGL(step_reduce_kernel, dim3(1), dim3(SR_RED_THREADS), 0, ctx->stream, rec_d, group_d, tr->N, G, stats_d);
+    KBJ_CHECK_LAUNCH(ctx, "step_reduce_kernel");
   }
   return 0;
 }

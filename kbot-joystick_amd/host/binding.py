@@ -50,6 +50,14 @@ class PushCriteria(C.Structure):
     _fields_ = [("tol", C.c_float * L.NTERR), ("hold_steps", C.c_int32), ("window_steps", C.c_int32)]
 
 
+class StepCriteria(C.Structure):
+    """kbj_step_criteria: per channel (forward, sideways, yaw) the smallest command change that makes it active and the floor of its settle
+    band, the band as a share of the step, the rise level in (0, 1], the rows of the smoothing window (1..32), the rows a settled run must
+    hold and the rows behind the step that are watched. Settings of the caller, not measured thresholds."""
+    _fields_ = [("min_step", C.c_float * L.NSCH), ("band_abs", C.c_float * L.NSCH), ("band_frac", C.c_float), ("rise_level", C.c_float),
+                ("smooth_steps", C.c_int32), ("hold_steps", C.c_int32), ("window_steps", C.c_int32)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("launches", C.c_int32), ("total_ms", C.c_float), ("flops", C.c_double)]
 
@@ -69,6 +77,7 @@ SIGNATURES = {
     "kbj_sizeof_config": (_i, []),
     "kbj_sizeof_traj": (_i, []),
     "kbj_sizeof_carry": (_i, []),
+    "kbj_sizeof_step_criteria": (_i, []),
     "kbj_synchronize": (_i, [_vp]),
     "kbj_env_reset_all": (_i, [_vp, _u32, _vp, _vp, _vp]),
     "kbj_env_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
@@ -104,6 +113,7 @@ SIGNATURES = {
     "kbj_tracking_stats": (_i, [_vp, C.POINTER(Traj), _i, _vp, _vp, _vp]),
     "kbj_gait_stats": (_i, [_vp, C.POINTER(Traj), _vp, _vp, _vp]),
     "kbj_push_recovery": (_i, [_vp, C.POINTER(Traj), _vp, _vp, C.POINTER(PushCriteria), _vp, _vp, _i, _vp]),
+    "kbj_step_response": (_i, [_vp, C.POINTER(Traj), _vp, C.POINTER(StepCriteria), _vp, _vp, _vp, _i, _vp]),
     "kbj_ppo_grad": (_i, [_vp, _vp, C.POINTER(Traj), _vp, _i, _vp, _vp, _vp, _vp]),
     "kbj_ppo_forward": (_i, [_vp, _vp, C.POINTER(Traj), _vp, _i, C.POINTER(PpoVars)]),
     "kbj_stream_wait_actor_grad": (_i, [_vp, _vp]),
@@ -356,6 +366,13 @@ class Context:
         start < 0: no push), rec [N, PREC SIZE] float32 (overwritten), group None or [N] int32 in [0, G), stats None or [G, PSTAT SIZE]
         float64 (overwritten), all on the device."""
         self.call("kbj_push_recovery", C.byref(traj), _ptr(err), _ptr(sched), C.byref(criteria) if criteria is not None else None, _ptr(rec), _ptr(group), int(G), _ptr(stats))
+
+    def step_response(self, traj: Traj, sched, criteria: StepCriteria, sig, rec, group=None, G: int = 1, stats=None):
+        """kbj_step_response: sched [N] int32 (the first row of the new command; < 0: no step), sig [T, N, SSIG SIZE] float32 and rec
+        [N, SREC SIZE] float32 (both overwritten), group None or [N] int32 in [0, G), stats None or [G, SSTAT SIZE] float64 (overwritten),
+        all on the device."""
+        self.call("kbj_step_response", C.byref(traj) if traj is not None else None, _ptr(sched), C.byref(criteria) if criteria is not None else None, _ptr(sig), _ptr(rec),
+                  _ptr(group), int(G), _ptr(stats))
 
     def ppo_grad(self, params, traj: Traj, env_idx, B, adv, target, grad, metrics):
         self.call("kbj_ppo_grad", _ptr(params), C.byref(traj), _ptr(env_idx), B, _ptr(adv), _ptr(target), _ptr(grad),

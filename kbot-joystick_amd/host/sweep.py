@@ -1,4 +1,4 @@
-"""What the evaluation sweeps (host/tracking.py tracking_sweep, host/push.py push_sweep) share: a context of their own for n envs and T rows,
+"""What the evaluation sweeps (host/tracking.py tracking_sweep, host/push.py push_sweep, host/gait.py gait_sweep, host/step.py step_sweep) share: a context of their own for n envs and T rows,
 one rollout with the task's policy acting with the distribution's mode, the user terms the sweep scripts."""
 from __future__ import annotations
 

@@ -30,6 +30,7 @@ from .config import HumanoidWalkingTaskConfig, cosine_decay_lr, launch_config   
 from .episode import EpisodeStats, episode_stats_scalars, fresh_episode_stats
 from .gait import GaitStats, format_gait_table, fresh_gait_stats, gait_scalars, gait_sweep      # noqa: F401 (re-exported)
 from .push import PushRecord, ScriptedPush, format_push_table, push_sweep      # noqa: F401 (re-exported)
+from .step import StepRecord, SteppedCommand, format_step_table, step_sweep      # noqa: F401 (re-exported)
 from .tracking import TrackingStats, format_tracking_table, fresh_tracking_stats, settle_steps, tracking_scalars, tracking_sweep      # noqa: F401 (re-exported)
 from .user_terms import UserTerms
 
@@ -275,6 +276,26 @@ class HumanoidWalkingTask:
         `recovered_frac` / `unrecovered_frac` / `censored_frac` of the valid ones, `recovery_s_mean` / `_max`, `peak_tilt_mean` / `_max`,
         `peak_lin_vel_err_mean` / `_max` (nan over nothing); and the PushRecord of the device data. `format_push_table` renders the entries."""
         return push_sweep(self, forces, directions_deg, duration, command, push_at, window, hold, tolerances, repeats, torque, seed_offset)
+
+    def step_sweep(self, transitions=None, step_at: float = 3.0, window: float = 4.0, hold: float = 0.5, smooth: float = 0.5, rise_level: float = 0.9,
+                   band_frac: float = 0.1, band_abs=(0.15, 0.15, 0.25), min_step=(0.05, 0.05, 0.05), repeats: int = 4, seed_offset: int = 7919):
+        """The step-response table: what the CURRENT policy does when the stick MOVES. One case per transition (from command, to command;
+        [<= 16] floats each, missing components zero; default: host/step.default_step_grid - starts, stops, a speed-up, the reversal and a
+        turn reversal at the config's full command ranges). A context of its own with len(transitions) * repeats envs (env e runs case
+        e % cases; at most 256 cases) and round(step_at / ctrl_dt) + round(window / ctrl_dt) rows runs argmax actions through the step-wise
+        loop under the Command term host/step.SteppedCommand: every env holds its old command until row round(step_at / ctrl_dt) and its new
+        one from there on, again after every in-episode reset; the user's Reset and network-input Observation terms apply as in validate(),
+        Event terms do not. ONE kbj_step_response call then scores every env on the device, with one group per case: per channel (forward
+        and sideways velocity in the robot's heading frame, yaw rate), smoothed over `smooth` seconds (at most 32 rows), a step is VOID when
+        the env was not inside the band of its OLD command (or had just been reset) when the stick moved; otherwise the env FELL, SETTLED
+        (every channel inside max(band_abs, band_frac x step size) of the new command for `hold` seconds, inside `window` seconds), stayed
+        UNSETTLED, or was CENSORED by a time-out. Beside that: the rise time to `rise_level` of the step, the overshoot, the cross-coupling
+        into the channels whose command moved by less than `min_step`, and the travel until settled - the stopping distance of a stop; it
+        is a path integral in the heading frame and a displacement only while the heading barely turns. All of these are SETTINGS, echoed
+        in every entry - not measured thresholds. Returns (entries, record): per case the settings and host/step.case_summary's figures
+        (nan over nothing), and the StepRecord of the device data. `format_step_table` renders the entries. Like the push and gait
+        tables, this one has NOT been taken on a trained policy."""
+        return step_sweep(self, transitions, step_at, window, hold, smooth, rise_level, band_frac, band_abs, min_step, repeats, seed_offset)
 
     def episode_stats_vectors(self):
         """(last, total): this rank's raw KBJ_EPST vectors (float64 numpy, layout.EPST) behind episode_stats() - the episodes that finished in

@@ -61,6 +61,10 @@ TRACKING_ERROR_NAMES = ("lin_vel_err", "yaw_rate_err", "tilt_err", "height_err",
 # the outcomes of a scheduled push (kbj_model.h KBJ_POUT_*) and the peak errors kbj_push_recovery keeps (KBJ_PREC_PEAK_*: the first four tracking errors)
 PUSH_OUTCOME_NAMES = ("none", "void", "fell", "recovered", "unrecovered", "censored")
 
+# the outcomes of a scheduled command step (kbj_model.h KBJ_SOUT_*) and the channels kbj_step_response scores: signal word k against command word k
+STEP_OUTCOME_NAMES = ("none", "void", "fell", "settled", "unsettled", "censored")
+STEP_CHANNEL_NAMES = ("forward", "sideways", "yaw")
+
 REWARD_NAMES = (
     "linvel", "angvel", "roll_pitch", "base_height", "arm_pos", "single_contact", "no_contact_p",
     "feet_airtime", "feet_orient", "com_distance", "base_accel", "torque",

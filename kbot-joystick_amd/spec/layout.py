@@ -134,6 +134,14 @@ NPEAK = 4
 POUT = dict(NONE=0, VOID=1, FELL=2, RECOVERED=3, UNRECOVERED=4, CENSORED=5, COUNT=6)
 PREC = dict(OUTCOME=0, RECOVER_STEPS=1, FALL_STEPS=2, PEAK_LIN=3, PEAK_YAW=4, PEAK_TILT=5, PEAK_HEIGHT=6, PEAK_ROW=7, SIZE=8)
 PSTAT = dict(COUNT=0, REC_SUM=6, REC_SUMSQ=7, REC_MAX=8, FALL_SUM=9, FALL_SUMSQ=10, FALL_MAX=11, PEAK_SUM=12, PEAK_MAX=16, SIZE=24)
+# kbj_model.h KBJ_SSIG_* / KBJ_SOUT_* / KBJ_SREC_* / KBJ_SSTAT_*: one row of kbj_step_response's signal (fp32), the outcome of a scheduled command
+# step, one env's record (fp32) and one group's statistics (float64); NSCH channels: forward, sideways, yaw (constants.STEP_CHANNEL_NAMES)
+NSCH = 3
+SSIG = dict(VX=0, VY=1, WZ=2, DONE=3, CMD=4, SPARE=7, SIZE=8)
+SOUT = dict(NONE=0, VOID=1, FELL=2, SETTLED=3, UNSETTLED=4, CENSORED=5, COUNT=6)
+SREC = dict(OUTCOME=0, SETTLE_STEPS=1, FALL_STEPS=2, ACTIVE=3, TRAVEL_X=4, TRAVEL_Y=5, TRAVEL_YAW=6, SPARE=7, RISE=8, OVER=11, DEV=14, SPARE_TAIL=17, SIZE=20)
+SSTAT = dict(COUNT=0, SETTLE_SUM=6, SETTLE_SUMSQ=7, SETTLE_MAX=8, FALL_SUM=9, FALL_SUMSQ=10, FALL_MAX=11, ACTIVE_N=12, RISE_N=15, RISE_SUM=18, RISE_MAX=21,
+             OVER_SUM=24, OVER_MAX=27, DEV_N=30, DEV_SUM=33, DEV_MAX=36, TRAVEL_SUM=39, TRAVEL_ABSMAX=42, SIZE=48)
 # pieces of a packed observation row in the reference's concatenation order (kbj_model.h KBJ_OBS_*; train.py:1367-1374, 1410-1430):
 # name -> (offset, width); the first six are common to the actor and the critic row
 OBS = dict(JPOS=(0, 20), JVEL=(20, 20), PG=(40, 5), GYRO=(45, 3), ZEROCMD=(48, 1), CMD=(49, 16), TOUCH=(65, 2), FEETPOS=(67, 6), BASEPOS=(73, 3),
