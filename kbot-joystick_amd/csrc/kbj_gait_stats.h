@@ -1,6 +1,6 @@
 // kbj_gait_stats.h — the contact pattern of one trajectory (kbj_gait_stats): swing and stance durations, support shares, foot clearance, hops,
 // ground force and torque level, split by the command mode of the row (KBJ_GACC_*, KBJ_GAIT_*, KBJ_GFOOT_*, KBJ_GENV_*). Included by
-// kbj_traj_stats.hip, behind kbj_tracking_stats.h (trk_mode).
+// kbj_traj_stats.hip.
 //
 // One-row skew, by definition: KBJ_AUX_TOUCH is the observation the policy saw BEFORE the step, KBJ_AUX_LFZ / _RFZ are the foot heights AFTER
 // it. The contact bit of row t therefore belongs to the state that row t - 1 left, the heights to the state row t leaves. rewards_kernel reads
@@ -8,8 +8,7 @@
 //
 // Shape: tracking_stats_kernel's. One workgroup of five wavefronts owns 32 consecutive envs. Wavefronts 1-4 each fetch one time step of a
 // 4-step chunk as coalesced 16-byte pieces (one chunk ahead, so the loads fly under the evaluation and the scan of the chunk before), put the
-// 13 pieces that are read (LFZ / RFZ, CTRL, TOUCH, CMD, DONE) into LDS with a row stride of 53 words (odd: one env per lane reads it
-// conflict-free) and evaluate there, one env per lane, everything of a row that does not depend on the row before: the contact bits, the
+// 13 pieces that are read (LFZ / RFZ, CTRL, TOUCH, CMD, DONE) into LDS (kbj_aux_stage.h: a row stride of 53 words) and evaluate there, one env per lane, everything of a row that does not depend on the row before: the contact bits, the
 // mode, DONE, q = sum ctrl^2 and qmax = max |ctrl|. What is left per row is six words and one double. Wavefront 0 runs the ordered part from
 // them, one env per lane: phases, events, clearance.
 // The per-mode accumulators are indexed by a run-time mode, so they do not live in registers (they would become scratch): they are two LDS
@@ -30,7 +29,8 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "kbj_model.h"
-#include "kbj_tracking_stats.h"
+#include "kbj_aux_stage.h"
+#include "kbj_ordered_reduce.h"
 
 namespace kbj {
 namespace {
@@ -38,10 +38,7 @@ namespace {
 constexpr int GAIT_ENVS = 32;        // envs per workgroup: the lower half of every wavefront's lanes holds one env each
 constexpr int GAIT_TC = 4;           // time steps per chunk: one per staging wavefront
 constexpr int GAIT_THREADS = 64 * (GAIT_TC + 1);   // wavefront 0 scans, wavefronts 1-4 stage and evaluate
-constexpr int GAIT_NPIECE = 13;      // staged 16-byte pieces of an aux row
-constexpr int GAIT_LD = 4 * GAIT_NPIECE + 1;       // row stride of the staged image, in words
-constexpr int GAIT_V4 = KBJ_AUX_SIZE / 4;          // 16-byte pieces per aux row
-constexpr int GAIT_KL = GAIT_ENVS * GAIT_V4 / 64;  // loads per lane and time step
+constexpr int GAIT_KL = GAIT_ENVS * AUX_V4 / 64;   // pieces per lane and time step
 constexpr int GAIT_RES = 6;          // words per evaluated row: flags, z[2], F[2], qmax
 constexpr float GAIT_CONTACT_FORCE = 0.1f;         // rewards_kernel's contact test: TOUCH > 0.1f
 constexpr float GAIT_RUN_CAP = 16777216.0f;        // 2^24: the last fp32 a + 1 still counts up to
@@ -67,29 +64,22 @@ constexpr int GAIT_W_TORQUE_MAX = 5;                                            
 __host__ __device__ constexpr int gait_w(int f, int k) { return GAIT_ROW_WORDS + GAIT_FOOT_WORDS * f + gait_foot_index(k); }
 __host__ __device__ constexpr int gait_d(int f, int k) { return 1 + GAIT_FOOT_DBLS * f + gait_foot_index(k); }
 
-static_assert(GAIT_ENVS <= 64 && GAIT_ENVS * GAIT_V4 % 64 == 0 && KBJ_AUX_SIZE % 4 == 0 && KBJ_GACC_SIZE == 16 && KBJ_GACC_FOOT_STRIDE == 6 && KBJ_GACC_RUNNING == 12 && KBJ_GACC_LAST_TD == 13, "gait carry layout: four 16-byte pieces");
+static_assert(GAIT_ENVS <= 64 && GAIT_ENVS * AUX_V4 % 64 == 0 && KBJ_AUX_SIZE % 4 == 0 && KBJ_GACC_SIZE == 16 && KBJ_GACC_FOOT_STRIDE == 6 && KBJ_GACC_RUNNING == 12 && KBJ_GACC_LAST_TD == 13, "gait carry layout: four 16-byte pieces");
 static_assert(GAIT_FOOT_WORDS == 11 && GAIT_FOOT_DBLS == 5 && GAIT_FOOT_WORDS + GAIT_FOOT_DBLS == KBJ_GFOOT_SIZE && KBJ_GFOOT_SIZE == KBJ_GAIT_FOOT_STRIDE, "foot block");
 static_assert(KBJ_GAIT_REPEATS == 4 && KBJ_GAIT_TORQUE_SQ == 5 && KBJ_GAIT_TORQUE_MAX == 6 && KBJ_GAIT_FOOT == 8 && KBJ_GAIT_FOOT + 2 * KBJ_GAIT_FOOT_STRIDE == KBJ_GAIT_MODE_STRIDE &&
               KBJ_CMODE_COUNT * KBJ_GAIT_MODE_STRIDE == KBJ_GAIT_EPISODES && KBJ_GAIT_EPISODES < KBJ_GAIT_SIZE && KBJ_GAIT_SIZE <= GAIT_THREADS, "gait statistics layout");
 static_assert(KBJ_GENV_FOOT == 8 && KBJ_GENV_FOOT + 2 * KBJ_GENV_FOOT_STRIDE == KBJ_GENV_SIZE && KBJ_GENV_SIZE % 4 == 0, "per-env record layout");
 
-// where the 16-byte piece `p` of an aux row (columns 4 p .. 4 p + 3) lives in its staged row, or -1: the pieces read are 2-3 (LFZ, RFZ) and
-// 7-17 (CTRL, TOUCH, CMD, DONE)
-__device__ constexpr int gait_piece(int p) { return (p == 2 || p == 3) ? p - 2 : (p >= 7 && p <= 17) ? p - 5 : -1; }
-__device__ constexpr int gait_col(int col) { return 4 * gait_piece(col / 4) + col % 4; }
-static_assert(gait_piece(KBJ_AUX_LFZ / 4) == 0 && gait_piece(KBJ_AUX_RFZ / 4) == 1 && gait_piece(KBJ_AUX_CTRL / 4) == 2 && gait_piece((KBJ_AUX_CTRL + KBJ_NU - 1) / 4) >= 2 &&
-              gait_piece((KBJ_AUX_TOUCH + 1) / 4) >= 2 && gait_piece(KBJ_AUX_CMD / 4) >= 2 && gait_piece(KBJ_AUX_DONE / 4) == GAIT_NPIECE - 1 && gait_piece(1) == -1 &&
-              gait_piece(6) == -1 && KBJ_AUX_SIZE / 4 == 18 && KBJ_AUX_CTRL / 4 == 7, "staged pieces");
-// a staged row, read by aux column
-struct GaitRow {
-  const float* p;
-  __device__ float operator[](int col) const { return p[gait_col(col)]; }
+// the staged pieces of an aux row (kbj_aux_stage.h): those read are 2-3 (LFZ, RFZ) and 7-17 (CTRL, TOUCH, CMD, DONE)
+struct GaitMap {
+  static constexpr int NPIECE = 13;
+  static __device__ constexpr int piece(int p) { return (p == 2 || p == 3) ? p - 2 : (p >= 7 && p <= 17) ? p - 5 : -1; }
 };
-// the command of a staged row, as trk_mode reads one
-struct GaitCmd {
-  GaitRow a;
-  __device__ float operator[](int k) const { return a[KBJ_AUX_CMD + k]; }
-};
+using GaitRow = StagedRow<GaitMap>;
+constexpr int GAIT_LD = GaitRow::LD;
+static_assert(GaitMap::piece(KBJ_AUX_LFZ / 4) == 0 && GaitMap::piece(KBJ_AUX_RFZ / 4) == 1 && GaitMap::piece(KBJ_AUX_CTRL / 4) == 2 && GaitMap::piece((KBJ_AUX_CTRL + KBJ_NU - 1) / 4) >= 2 &&
+              GaitMap::piece((KBJ_AUX_TOUCH + 1) / 4) >= 2 && GaitMap::piece(KBJ_AUX_CMD / 4) >= 2 && GaitMap::piece(KBJ_AUX_DONE / 4) == GaitMap::NPIECE - 1 && GaitMap::piece(1) == -1 &&
+              GaitMap::piece(6) == -1 && GAIT_LD == 53 && KBJ_AUX_SIZE / 4 == 18 && KBJ_AUX_CTRL / 4 == 7, "staged pieces");
 
 struct GaitShared {
   double dimg[KBJ_CMODE_COUNT * GAIT_MODE_DBLS][GAIT_ENVS];     // [mode * GAIT_MODE_DBLS + row][lane]
@@ -101,18 +91,15 @@ struct GaitShared {
 };
 static_assert(sizeof(GaitShared) <= 160 * 1024, "one workgroup per CU");
 
-// the slots of a KBJ_GAIT vector (kbj_ordered_reduce.h): counts and sums, but for the maxima of each mode block. The identity of every slot is
-// 0: every maximum is of a non-negative quantity
-struct GaitSlots {
+// the slots of a KBJ_GAIT vector (kbj_ordered_reduce.h): counts and sums, but for the maxima of each mode block (each of a non-negative
+// quantity)
+struct GaitSlots : SumMaxSlots<GaitSlots> {
   static constexpr int SIZE = KBJ_GAIT_SIZE;
   static __device__ inline bool is_max(int j) {
     if (j >= KBJ_GAIT_EPISODES) return false;
     const int s = j % KBJ_GAIT_MODE_STRIDE;
     return s == KBJ_GAIT_TORQUE_MAX || (s >= KBJ_GAIT_FOOT && gait_foot_kind((s - KBJ_GAIT_FOOT) % KBJ_GAIT_FOOT_STRIDE) == 1);
   }
-  static __device__ inline double identity(int) { return 0.0; }
-  static __device__ inline double combine_as(bool is_max, double a, double b) { return is_max ? (b > a ? b : a) : a + b; }   // is_max(j), hoisted by the caller
-  static __device__ inline double combine(int j, double a, double b) { return combine_as(is_max(j), a, b); }
 };
 
 // accessors of one lane's cells of a mode block
@@ -132,7 +119,7 @@ __global__ __launch_bounds__(GAIT_THREADS) void gait_stats_kernel(const float* _
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int e0 = blockIdx.x * GAIT_ENVS, nb = min(GAIT_ENVS, N - e0);
   const int nchunk = (T + GAIT_TC - 1) / GAIT_TC;
-  const int npiece = nb * GAIT_V4;                // 16-byte pieces of the block's rows of one time step
+  const int npiece = nb * AUX_V4;                 // 16-byte pieces of the block's rows of one time step
   const bool live = lane < nb;
 
   for (int i = tid; i < KBJ_CMODE_COUNT * GAIT_MODE_DBLS * GAIT_ENVS; i += GAIT_THREADS) (&S.dimg[0][0])[i] = 0.0;
@@ -161,7 +148,7 @@ __global__ __launch_bounds__(GAIT_THREADS) void gait_stats_kernel(const float* _
 #pragma unroll
     for (int k = 0; k < GAIT_KL; ++k) {
       const int i = k * 64 + lane;
-      if (i < npiece && gait_piece(i % GAIT_V4) >= 0) v[k] = src[i];
+      if (i < npiece && GaitMap::piece(i % AUX_V4) >= 0) v[k] = src[i];
     }
   };
   fetch(0);
@@ -170,13 +157,8 @@ __global__ __launch_bounds__(GAIT_THREADS) void gait_stats_kernel(const float* _
     const int tt = wave - 1, t = c * GAIT_TC + tt;
     const bool mine = wave > 0 && c < nchunk && t < T;     // this wavefront has a time step in chunk c
     if (mine) {
-      float* dst = S.raw[tt];
 #pragma unroll
-      for (int k = 0; k < GAIT_KL; ++k) {
-        const int i = k * 64 + lane;
-        const int slot = gait_piece(i % GAIT_V4);
-        if (i < npiece && slot >= 0) { float* d = dst + (i / GAIT_V4) * GAIT_LD + 4 * slot; d[0] = v[k].x; d[1] = v[k].y; d[2] = v[k].z; d[3] = v[k].w; }
-      }
+      for (int k = 0; k < GAIT_KL; ++k) stage_piece<GaitMap>(S.raw[tt], v[k], k * 64 + lane, npiece);
     }
     __syncthreads();
     if (wave > 0) {
@@ -188,7 +170,7 @@ __global__ __launch_bounds__(GAIT_THREADS) void gait_stats_kernel(const float* _
         float qmax = 0.0f;
 #pragma unroll
         for (int u = 0; u < KBJ_NU; ++u) { const float x = a[KBJ_AUX_CTRL + u]; q += (double)x * (double)x; qmax = fmaxf(qmax, fabsf(x)); }
-        const int flags = trk_mode(GaitCmd{a}) | (F0 > GAIT_CONTACT_FORCE ? 8 : 0) | (F1 > GAIT_CONTACT_FORCE ? 16 : 0) | (a[KBJ_AUX_DONE] == 0.0f ? 32 : 0);
+        const int flags = cmd_mode(a) | (F0 > GAIT_CONTACT_FORCE ? 8 : 0) | (F1 > GAIT_CONTACT_FORCE ? 16 : 0) | (a[KBJ_AUX_DONE] == 0.0f ? 32 : 0);
         float (*r)[GAIT_ENVS] = S.res[c & 1][tt];
         r[0][lane] = __int_as_float(flags);
         r[1][lane] = a[KBJ_AUX_LFZ]; r[2][lane] = a[KBJ_AUX_RFZ];

@@ -1,6 +1,7 @@
-// kbj_ordered_reduce.h — the second stage of the trajectory scans (kbj_episode_stats.h, kbj_tracking_stats.h): the workgroup partials of a
-// scan, [nblocks][SIZE] doubles, combined slot by slot in block order by ONE workgroup. Doubles, a fixed order, no atomics: the same partials
-// give the same bytes on every call. Included by kbj_traj_stats.hip.
+// kbj_ordered_reduce.h — the second stage of the trajectory scans that leave workgroup partials (kbj_episode_stats.h, kbj_tracking_stats.h,
+// kbj_gait_stats.h): the partials of a scan, [nblocks][SIZE] doubles, combined slot by slot in block order by ONE workgroup. Doubles, a fixed
+// order, no atomics: the same partials give the same bytes on every call. Included by kbj_traj_stats.hip. (The event statistics,
+// kbj_push_recovery.h and kbj_step_response.h, leave a record per env and have a second stage of their own: kbj_window_scan.h.)
 //
 // `Slots` says what a statistics vector is made of:
 //   static constexpr int SIZE;                              slots per vector, a divisor of ORDERED_REDUCE_THREADS
@@ -14,6 +15,14 @@ namespace kbj {
 namespace {
 
 constexpr int ORDERED_REDUCE_THREADS = 256;
+
+// the slots of a vector of counts and sums, but for some maxima of non-negative quantities: the identity of every slot is 0. `Derived`
+// supplies SIZE and is_max(j). A loop over one slot hoists is_max(j) and calls combine_as
+template <class Derived> struct SumMaxSlots {
+  static __device__ inline double identity(int) { return 0.0; }
+  static __device__ inline double combine_as(bool is_max, double a, double b) { return is_max ? (b > a ? b : a) : a + b; }   // is_max(j), hoisted by the caller
+  static __device__ inline double combine(int j, double a, double b) { return combine_as(Derived::is_max(j), a, b); }
+};
 
 // one workgroup of ORDERED_REDUCE_THREADS: thread (r, j) folds slot j over the r-th of R = THREADS / SIZE contiguous ranges of blocks, in
 // block order; then the threads of range 0 fold the ranges 1 .. R - 1 onto theirs, in order -> stats [SIZE]

@@ -18,27 +18,21 @@
 //   Undecided at the end: CENSORED if s + d + window > T (the trajectory cut the window), else UNRECOVERED.
 //   Fields that do not apply are -1 (every field but the outcome for NONE and VOID).
 //
-// Shape. One env per lane, one wavefront per workgroup of 64 consecutive envs. For a fixed t the workgroup's err_d rows are 2 KB of
-// contiguous floats, 32 bytes per lane: a lane fetches its own row (one 16-byte load, one 4-byte load for the fifth error) and its DONE
-// word from the aux row. The scan is ordered in t, the fetches are not: a chunk of PR_TC rows is loaded into registers while the chunk
-// before it is scanned (two register images, swapped by unrolling the chunk loop twice), so a chunk costs one memory round trip that flies
-// under the scan of its predecessor. Only the rows any lane of the wavefront needs are touched: [min (s - hold), max end), chunks aligned
-// to multiples of PR_TC, and the walk ends as soon as every lane has its outcome. No LDS, no atomics.
-// Second stage (when stats are asked for): one workgroup, thread g owns group g and walks ALL envs in env order - the result rows are
-// staged through LDS 256 envs at a time (coalesced loads; every thread reads the same LDS word: a broadcast) - adding in doubles. A fixed
-// order without atomics: the same inputs give the same bytes on every call.
+// Shape. window_walk (kbj_window_scan.h) over chunks of PR_TC rows. For a fixed t the workgroup's err_d rows are 2 KB of contiguous floats,
+// 32 bytes per lane: a lane fetches its own row (one 16-byte load, one 4-byte load for the fifth error) and its DONE word from the aux row.
+// The common early end of the walk: an untrained policy's pushes are VOID on the hold rows. No LDS, no atomics.
+// Second stage (when stats are asked for): push_recovery_reduce_kernel, the group reduce of kbj_window_scan.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
 #include "kbj.h"
+#include "kbj_window_scan.h"
 
 namespace kbj {
 namespace {
 
-constexpr int PR_ENVS = 64;          // envs per workgroup = lanes of its one wavefront
 constexpr int PR_TC = 8;             // rows per chunk: 6 registers a row, two images
-constexpr int PR_RED_THREADS = 256;  // the second stage: one thread per group, and the envs staged per round
 static_assert(KBJ_TERR_SIZE == 8 && KBJ_NTERR == 5 && KBJ_TERR_LIN == 0 && KBJ_TERR_HEIGHT == 3 && KBJ_TERR_ARM == 4, "an err_d row: four peak errors in the first 16 bytes, the fifth error behind them");
 static_assert(KBJ_PREC_SIZE == 8 && KBJ_PREC_PEAK_LIN + KBJ_NPEAK == KBJ_PREC_PEAK_ROW && KBJ_PSTAT_PEAK_MAX + KBJ_NPEAK <= KBJ_PSTAT_SIZE, "push recovery layout");
 static_assert(KBJ_POUT_COUNT == KBJ_PSTAT_REC_SUM - KBJ_PSTAT_COUNT, "one count per outcome");
@@ -48,54 +42,37 @@ struct PrRow { float4 e; float arm, done; };
 __device__ inline bool pr_within(float e, float tol) { return tol == INFINITY || e <= tol; }
 
 // grid = ceil(N / 64) workgroups of one wavefront; err [T][N][KBJ_TERR_SIZE], aux [T + 1][N][KBJ_AUX_SIZE], sched [N][2], rec [N][KBJ_PREC_SIZE]
-__global__ __launch_bounds__(PR_ENVS) void push_recovery_kernel(const float* __restrict__ err, const float* __restrict__ aux, int T, int N, const int32_t* __restrict__ sched,
-                                                                 kbj_push_criteria crit, float* __restrict__ rec) {
-  const int lane = threadIdx.x, env = blockIdx.x * PR_ENVS + lane;
+__global__ __launch_bounds__(WINDOW_ENVS) void push_recovery_kernel(const float* __restrict__ err, const float* __restrict__ aux, int T, int N, const int32_t* __restrict__ sched,
+                                                                     kbj_push_criteria crit, float* __restrict__ rec) {
+  const int lane = threadIdx.x, env = blockIdx.x * WINDOW_ENVS + lane;
   const bool live = env < N;
-  const int hold = crit.hold_steps, window = crit.window_steps;
+  const int hold = crit.hold_steps;
   int s = -1, d = 0;
   if (live) { const int2 sd = reinterpret_cast<const int2*>(sched)[env]; s = sd.x; d = max(sd.y, 0); }
-  const bool scan = live && s >= hold && s < T;             // hold >= 1: s >= 0 too
-  const long long end64 = (long long)s + d + window;        // the schedule is the caller's: no 32-bit overflow whatever it holds
-  const int end = scan ? (int)(end64 < (long long)T ? end64 : (long long)T) : 0;     // scanned rows: [s, end); end >= s
+  const Window w(live, s, hold, (long long)d + crit.window_steps, T);     // hold >= 1: a scanned s is >= 0 too
   const long long post64 = (long long)s + d;
   const int post = post64 < (long long)INT_MAX ? (int)post64 : INT_MAX;              // first row behind the push
 
-  // the rows this wavefront touches: [lo, hi)
-  int lo = scan ? s - hold : INT_MAX, hi = scan ? max(end, s) : 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { lo = min(lo, __shfl_xor(lo, o)); hi = max(hi, __shfl_xor(hi, o)); }
-
   int outcome = !live || s < 0 ? KBJ_POUT_NONE : KBJ_POUT_VOID;     // a scanned env: VOID until its pre-push rows have passed
-  bool decided = !scan;
+  bool decided = !w.scan;
   int run = 0;
   float peak[KBJ_NPEAK] = {-1.0f, -1.0f, -1.0f, -1.0f}, peak_row = -1.0f, rec_steps = -1.0f, fall_steps = -1.0f;
 
-  PrRow a[PR_TC], b[PR_TC];
-  auto fetch = [&](PrRow (&r)[PR_TC], int c) {               // chunk c = rows [c PR_TC, (c + 1) PR_TC); a lane loads what it will read
-#pragma unroll
-    for (int k = 0; k < PR_TC; ++k) {
-      const int t = c * PR_TC + k;
-      if (scan && t >= s - hold && t < max(end, s)) {        // 0 <= t < T and env < N
-        const size_t i = (size_t)t * N + env;
-        r[k].e = *reinterpret_cast<const float4*>(err + i * KBJ_TERR_SIZE);
-        r[k].arm = err[i * KBJ_TERR_SIZE + KBJ_TERR_ARM];
-        r[k].done = aux[i * KBJ_AUX_SIZE + KBJ_AUX_DONE];
-      }
-    }
-  };
-  auto scan_chunk = [&](const PrRow (&r)[PR_TC], int c) {
-#pragma unroll
-    for (int k = 0; k < PR_TC; ++k) {
-      const int t = c * PR_TC + k;
-      if (decided || t < s - hold || t >= max(end, s)) continue;
-      const float e[KBJ_NPEAK] = {r[k].e.x, r[k].e.y, r[k].e.z, r[k].e.w};
-      const float done = r[k].done;
+  window_walk<PR_TC, PrRow>(w, decided,
+    [&](PrRow& r, int t) {
+      const size_t i = (size_t)t * N + env;
+      r.e = *reinterpret_cast<const float4*>(err + i * KBJ_TERR_SIZE);
+      r.arm = err[i * KBJ_TERR_SIZE + KBJ_TERR_ARM];
+      r.done = aux[i * KBJ_AUX_SIZE + KBJ_AUX_DONE];
+    },
+    [&](const PrRow& r, int t) {
+      const float e[KBJ_NPEAK] = {r.e.x, r.e.y, r.e.z, r.e.w};
+      const float done = r.done;
       const bool within = pr_within(e[0], crit.tol[0]) && pr_within(e[1], crit.tol[1]) && pr_within(e[2], crit.tol[2]) && pr_within(e[3], crit.tol[3]) &&
-                          pr_within(r[k].arm, crit.tol[4]);
+                          pr_within(r.arm, crit.tol[4]);
       if (t < s) {                                            // the hold rows in front of the push
         if (!within || done != 0.0f) decided = true;          // stays VOID
-        continue;
+        return;
       }
       if (e[KBJ_TERR_TILT] > peak[KBJ_TERR_TILT]) peak_row = (float)t;
 #pragma unroll
@@ -106,22 +83,8 @@ __global__ __launch_bounds__(PR_ENVS) void push_recovery_kernel(const float* __r
         run = within ? run + 1 : 0;
         if (run >= hold) { outcome = KBJ_POUT_RECOVERED; rec_steps = (float)((t - hold + 1) - post); decided = true; }
       }
-    }
-  };
-
-  if (hi > lo) {
-    const int c0 = lo / PR_TC, c1 = (hi - 1) / PR_TC;         // first and last chunk
-    fetch(a, c0);
-    for (int c = c0; c <= c1; c += 2) {              // every condition here is uniform over the wavefront
-      if (__all(decided)) break;                       // nobody reads another row (the common case: an untrained policy's pushes are VOID on the hold rows)
-      if (c + 1 <= c1) fetch(b, c + 1);
-      scan_chunk(a, c);
-      if (c + 1 > c1 || __all(decided)) break;
-      if (c + 2 <= c1) fetch(a, c + 2);
-      scan_chunk(b, c + 1);
-    }
-  }
-  if (scan && !decided) outcome = end64 > (long long)T ? KBJ_POUT_CENSORED : KBJ_POUT_UNRECOVERED;    // the hold rows passed, the window ran out
+    });
+  if (w.scan && !decided) outcome = w.end64 > (long long)T ? KBJ_POUT_CENSORED : KBJ_POUT_UNRECOVERED;    // the hold rows passed, the window ran out
   if (live) {
     float4* o = reinterpret_cast<float4*>(rec + (size_t)env * KBJ_PREC_SIZE);
     o[0] = make_float4((float)outcome, rec_steps, fall_steps, peak[0]);
@@ -129,22 +92,18 @@ __global__ __launch_bounds__(PR_ENVS) void push_recovery_kernel(const float* __r
   }
 }
 
-// one workgroup of PR_RED_THREADS; thread g < G: group g's statistics over the envs in env order -> stats [G][KBJ_PSTAT_SIZE]. group == null: every
+// one workgroup of GROUP_REDUCE_THREADS; thread g < G: group g's statistics over the envs in env order -> stats [G][KBJ_PSTAT_SIZE]. group == null: every
 // env is in group 0; an env whose group is outside [0, G) is in none.
-__global__ __launch_bounds__(PR_RED_THREADS) void push_recovery_reduce_kernel(const float* __restrict__ rec, const int32_t* __restrict__ group, int N, int G,
+__global__ __launch_bounds__(GROUP_REDUCE_THREADS) void push_recovery_reduce_kernel(const float* __restrict__ rec, const int32_t* __restrict__ group, int N, int G,
                                                                                double* __restrict__ stats) {
-  __shared__ __align__(16) float row[PR_RED_THREADS][KBJ_PREC_SIZE];
-  __shared__ int grp[PR_RED_THREADS];
+  __shared__ __align__(16) float row[GROUP_REDUCE_THREADS][KBJ_PREC_SIZE];
+  __shared__ int grp[GROUP_REDUCE_THREADS];
   const int g = threadIdx.x;
   int cnt[KBJ_POUT_COUNT] = {0, 0, 0, 0, 0, 0};
   double rs = 0, rq = 0, rm = -1, fs = 0, fq = 0, fm = -1, ps[KBJ_NPEAK] = {0, 0, 0, 0}, pm[KBJ_NPEAK] = {-1, -1, -1, -1};
-  for (int n0 = 0; n0 < N; n0 += PR_RED_THREADS) {
-    const int nb = min(PR_RED_THREADS, N - n0);
-    __syncthreads();                                          // the round before has been read
-    for (int i = threadIdx.x; i < nb * (KBJ_PREC_SIZE / 4); i += PR_RED_THREADS)
-      reinterpret_cast<float4*>(&row[0][0])[i] = reinterpret_cast<const float4*>(rec + (size_t)n0 * KBJ_PREC_SIZE)[i];
-    if (threadIdx.x < nb) grp[threadIdx.x] = group ? group[n0 + threadIdx.x] : 0;
-    __syncthreads();
+  for (int n0 = 0; n0 < N; n0 += GROUP_REDUCE_THREADS) {
+    const int nb = min(GROUP_REDUCE_THREADS, N - n0);
+    group_stage_round(row, grp, rec, group, n0, nb);
     if (g < G) {
       for (int i = 0; i < nb; ++i) {
         if (grp[i] != g) continue;

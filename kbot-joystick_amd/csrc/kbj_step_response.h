@@ -8,29 +8,25 @@
 // step_signal_kernel: elementwise over the T N rows, one thread per row. Of the 288 bytes of an aux row it fetches the first 40 (two 16-byte
 // loads, one 8-byte load: QVEL and BQUAT), the three command words (KBJ_AUX_CMD is 8-byte aligned: one 8-byte and one 4-byte load) and DONE
 // (4 bytes), and writes the 32-byte signal row as two float4 stores.
-// step_scan_kernel: push_recovery_kernel's shape - one env per lane, one wavefront per workgroup of 64 consecutive envs; for a fixed t the
-// workgroup's signal rows are 2 KB of contiguous floats, 32 bytes per lane, fetched as two 16-byte loads. A chunk of SR_TC rows is loaded
-// into registers while the chunk before it is scanned (two register images). Only the rows [min (s - hold), max end) of the wavefront are
-// touched, and the walk ends as soon as every lane has its outcome. The trailing window of the smoothed value (up to 32 rows x 3 channels per
-// lane) lives in an LDS ring [32][3][64] floats = 24 KB: slot (t & 31) of a row is uniform over the wavefront and the lane is the fastest
+// step_scan_kernel: window_walk (kbj_window_scan.h) over chunks of SR_TC rows; for a fixed t the workgroup's signal rows are 2 KB of
+// contiguous floats, 32 bytes per lane, fetched as two 16-byte loads. The trailing window of the smoothed value (up to 32 rows x 3 channels
+// per lane) lives in an LDS ring [32][3][64] floats = 24 KB: slot (t & 31) of a row is uniform over the wavefront and the lane is the fastest
 // index, so every access puts consecutive lanes on consecutive banks (no conflict) and no lane ever reads another lane's words (no barrier).
 // The sum of S_k(t) is taken afresh on every row, ascending in u, in double: a running add / subtract would not be the same sum.
-// step_reduce_kernel: push_recovery_reduce_kernel's shape - one workgroup, thread g owns group g and walks all envs in env order, the record
-// rows staged through LDS 256 envs at a time. (ordered_reduce_kernel folds ranges of partials and then the ranges: not an env-order sum.)
+// Second stage (when stats are asked for): step_reduce_kernel, the group reduce of kbj_window_scan.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
 #include "kbj.h"
+#include "kbj_window_scan.h"
 
 namespace kbj {
 namespace {
 
-constexpr int SR_ENVS = 64;           // envs per workgroup of the scan = lanes of its one wavefront
 constexpr int SR_TC = 4;              // rows per chunk: 8 registers a row, two images
 constexpr int SR_RING = 32;           // rows of the smoothing ring = the largest smooth_steps
 constexpr int SR_SIG_THREADS = 256;   // the signal kernel: one row per thread
-constexpr int SR_RED_THREADS = 256;   // the second stage: one thread per group, and the envs staged per round
 static_assert(KBJ_AUX_SIZE % 4 == 0 && KBJ_AUX_QVEL == 0 && KBJ_AUX_BQUAT == 6 && KBJ_AUX_CMD % 2 == 0, "an aux row: QVEL and BQUAT in the first 40 bytes, CMD 8-byte aligned");
 static_assert(KBJ_SSIG_SIZE == 8 && KBJ_SSIG_VX == 0 && KBJ_SSIG_DONE == 3 && KBJ_SSIG_CMD == 4 && KBJ_NSCH == 3, "a signal row: two float4");
 static_assert(KBJ_SREC_SIZE == 20 && KBJ_SREC_RISE == 8 && KBJ_SREC_OVER == 11 && KBJ_SREC_DEV == 14 && KBJ_SREC_SPARE_TAIL == 17, "a record row: five float4");
@@ -62,27 +58,20 @@ __global__ __launch_bounds__(SR_SIG_THREADS) void step_signal_kernel(const float
 struct SrRow { float4 v, c; };   // VX, VY, WZ, DONE; CMD[3], spare
 
 // grid = ceil(N / 64) workgroups of one wavefront; sig [T][N][KBJ_SSIG_SIZE], sched [N], rec [N][KBJ_SREC_SIZE]
-__global__ __launch_bounds__(SR_ENVS) void step_scan_kernel(const float* __restrict__ sig, int T, int N, const int32_t* __restrict__ sched, kbj_step_criteria crit,
-                                                             float* __restrict__ rec) {
-  __shared__ float ring[SR_RING][KBJ_NSCH][SR_ENVS];
-  const int lane = threadIdx.x, env = blockIdx.x * SR_ENVS + lane;
+__global__ __launch_bounds__(WINDOW_ENVS) void step_scan_kernel(const float* __restrict__ sig, int T, int N, const int32_t* __restrict__ sched, kbj_step_criteria crit,
+                                                                 float* __restrict__ rec) {
+  __shared__ float ring[SR_RING][KBJ_NSCH][WINDOW_ENVS];
+  const int lane = threadIdx.x, env = blockIdx.x * WINDOW_ENVS + lane;
   const bool live = env < N;
-  const int m = crit.smooth_steps, hold = crit.hold_steps, window = crit.window_steps;
+  const int m = crit.smooth_steps, hold = crit.hold_steps;
   const int s = live ? sched[env] : -1;
-  const bool scan = live && s >= hold && s < T;               // hold >= 1: s >= 1 too, rows s - 1 and s exist
-  const long long end64 = (long long)s + window;               // the schedule is the caller's: no 32-bit overflow whatever it holds
-  const int end = scan ? (int)(end64 < (long long)T ? end64 : (long long)T) : 0;     // scanned rows: [s, end); window >= 1: end > s
-  const int first = scan ? s - hold : 0;                       // the first row this lane reads
-
-  // the rows this wavefront touches: [lo, hi)
-  int lo = scan ? first : INT_MAX, hi = end;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { lo = min(lo, __shfl_xor(lo, o)); hi = max(hi, __shfl_xor(hi, o)); }
+  const Window w(live, s, hold, (long long)crit.window_steps, T);     // hold >= 1: a scanned s is >= 1, rows s - 1 and s exist; window >= 1: end > s
+  const int first = w.first;
 
   // the step itself: c0, c1 and what follows from them
   float c0[KBJ_NSCH] = {0, 0, 0}, c1[KBJ_NSCH] = {0, 0, 0}, band[KBJ_NSCH], thr[KBJ_NSCH];
   bool neg[KBJ_NSCH], act[KBJ_NSCH];
-  if (scan) {
+  if (w.scan) {
     const float4 a = *reinterpret_cast<const float4*>(sig + ((size_t)(s - 1) * N + env) * KBJ_SSIG_SIZE + KBJ_SSIG_CMD);
     const float4 b = *reinterpret_cast<const float4*>(sig + ((size_t)s * N + env) * KBJ_SSIG_SIZE + KBJ_SSIG_CMD);
     c0[0] = a.x; c0[1] = a.y; c0[2] = a.z; c1[0] = b.x; c1[1] = b.y; c1[2] = b.z;
@@ -99,38 +88,28 @@ __global__ __launch_bounds__(SR_ENVS) void step_scan_kernel(const float* __restr
   }
 
   int outcome = !live || s < 0 ? KBJ_SOUT_NONE : KBJ_SOUT_VOID;     // a scanned env: VOID until its rows in front of the step have passed
-  bool decided = !scan || active == 0;
+  bool decided = !w.scan || active == 0;
   int run = 0;
   float rise[KBJ_NSCH] = {-1.0f, -1.0f, -1.0f}, over[KBJ_NSCH] = {0.0f, 0.0f, 0.0f}, dev[KBJ_NSCH] = {0.0f, 0.0f, 0.0f};
   float settle_steps = -1.0f, fall_steps = -1.0f;
   double travel[KBJ_NSCH] = {0.0, 0.0, 0.0};
 
-  SrRow a[SR_TC], b[SR_TC];
-  auto fetch = [&](SrRow (&r)[SR_TC], int c) {                 // chunk c = rows [c SR_TC, (c + 1) SR_TC); a lane loads what it will read
-#pragma unroll
-    for (int k = 0; k < SR_TC; ++k) {
-      const int t = c * SR_TC + k;
-      if (scan && t >= first && t < end) {                     // 0 <= t < T and env < N
-        const float4* p = reinterpret_cast<const float4*>(sig + ((size_t)t * N + env) * KBJ_SSIG_SIZE);
-        r[k].v = p[0]; r[k].c = p[1];
-      }
-    }
-  };
-  auto scan_chunk = [&](const SrRow (&r)[SR_TC], int c) {
-#pragma unroll
-    for (int k = 0; k < SR_TC; ++k) {
-      const int t = c * SR_TC + k;
-      if (decided || t < first || t >= end) continue;
-      const float v[KBJ_NSCH] = {r[k].v.x, r[k].v.y, r[k].v.z}, cmd[KBJ_NSCH] = {r[k].c.x, r[k].c.y, r[k].c.z};
-      const float done = r[k].v.w;
+  window_walk<SR_TC, SrRow>(w, decided,
+    [&](SrRow& r, int t) {
+      const float4* p = reinterpret_cast<const float4*>(sig + ((size_t)t * N + env) * KBJ_SSIG_SIZE);
+      r.v = p[0]; r.c = p[1];
+    },
+    [&](const SrRow& r, int t) {
+      const float v[KBJ_NSCH] = {r.v.x, r.v.y, r.v.z}, cmd[KBJ_NSCH] = {r.c.x, r.c.y, r.c.z};
+      const float done = r.v.w;
 #pragma unroll
       for (int j = 0; j < KBJ_NSCH; ++j) ring[t & (SR_RING - 1)][j][lane] = v[j];
       if (t < s) {                                             // the hold rows in front of the step
-        if (done != 0.0f || cmd[0] != c0[0] || cmd[1] != c0[1] || cmd[2] != c0[2]) { decided = true; continue; }     // stays VOID
-        if (t < s - 1) continue;
+        if (done != 0.0f || cmd[0] != c0[0] || cmd[1] != c0[1] || cmd[2] != c0[2]) { decided = true; return; }     // stays VOID
+        if (t < s - 1) return;
       } else {
-        if (done < 0.0f) { outcome = KBJ_SOUT_FELL; fall_steps = (float)(t - s); decided = true; continue; }
-        if (done > 0.0f || cmd[0] != c1[0] || cmd[1] != c1[1] || cmd[2] != c1[2]) { outcome = KBJ_SOUT_CENSORED; decided = true; continue; }
+        if (done < 0.0f) { outcome = KBJ_SOUT_FELL; fall_steps = (float)(t - s); decided = true; return; }
+        if (done > 0.0f || cmd[0] != c1[0] || cmd[1] != c1[1] || cmd[2] != c1[2]) { outcome = KBJ_SOUT_CENSORED; decided = true; return; }
       }
       // S_k(t): rows max(first, t - m + 1) .. t of this lane's ring column, ascending, in double, rounded once
       double sum[KBJ_NSCH] = {0.0, 0.0, 0.0};
@@ -148,7 +127,7 @@ __global__ __launch_bounds__(SR_ENVS) void step_scan_kernel(const float* __restr
 #pragma unroll
         for (int j = 0; j < KBJ_NSCH; ++j) on = on && fabsf(__fsub_rn(S[j], c0[j])) <= band[j];
         if (!on) decided = true;                               // stays VOID
-        continue;
+        return;
       }
       bool within = true;
 #pragma unroll
@@ -166,22 +145,8 @@ __global__ __launch_bounds__(SR_ENVS) void step_scan_kernel(const float* __restr
       }
       run = within ? run + 1 : 0;
       if (run >= hold) { outcome = KBJ_SOUT_SETTLED; settle_steps = (float)((t - hold + 1) - s); decided = true; }
-    }
-  };
-
-  if (hi > lo) {
-    const int ch0 = lo / SR_TC, ch1 = (hi - 1) / SR_TC;       // first and last chunk
-    fetch(a, ch0);
-    for (int c = ch0; c <= ch1; c += 2) {                      // every condition here is uniform over the wavefront
-      if (__all(decided)) break;                               // nobody reads another row
-      if (c + 1 <= ch1) fetch(b, c + 1);
-      scan_chunk(a, c);
-      if (c + 1 > ch1 || __all(decided)) break;
-      if (c + 2 <= ch1) fetch(a, c + 2);
-      scan_chunk(b, c + 1);
-    }
-  }
-  if (!decided) outcome = end64 > (long long)T ? KBJ_SOUT_CENSORED : KBJ_SOUT_UNSETTLED;    // the rows in front passed, the window ran out
+    });
+  if (!decided) outcome = w.end64 > (long long)T ? KBJ_SOUT_CENSORED : KBJ_SOUT_UNSETTLED;    // the rows in front passed, the window ran out
   const bool valid = outcome >= KBJ_SOUT_FELL;
   if (live) {
     float4* o = reinterpret_cast<float4*>(rec + (size_t)env * KBJ_SREC_SIZE);
@@ -207,24 +172,20 @@ __global__ __launch_bounds__(SR_ENVS) void step_scan_kernel(const float* __restr
   }
 }
 
-// one workgroup of SR_RED_THREADS; thread g < G: group g's statistics over the envs in env order -> stats [G][KBJ_SSTAT_SIZE]. group == null: every
+// one workgroup of GROUP_REDUCE_THREADS; thread g < G: group g's statistics over the envs in env order -> stats [G][KBJ_SSTAT_SIZE]. group == null: every
 // env is in group 0; an env whose group is outside [0, G) is in none.
-__global__ __launch_bounds__(SR_RED_THREADS) void step_reduce_kernel(const float* __restrict__ rec, const int32_t* __restrict__ group, int N, int G,
+__global__ __launch_bounds__(GROUP_REDUCE_THREADS) void step_reduce_kernel(const float* __restrict__ rec, const int32_t* __restrict__ group, int N, int G,
                                                                       double* __restrict__ stats) {
-  __shared__ __align__(16) float row[SR_RED_THREADS][KBJ_SREC_SIZE];
-  __shared__ int grp[SR_RED_THREADS];
+  __shared__ __align__(16) float row[GROUP_REDUCE_THREADS][KBJ_SREC_SIZE];
+  __shared__ int grp[GROUP_REDUCE_THREADS];
   const int g = threadIdx.x;
   int cnt[KBJ_SOUT_COUNT] = {0, 0, 0, 0, 0, 0}, an[KBJ_NSCH] = {0, 0, 0}, rn[KBJ_NSCH] = {0, 0, 0}, dn[KBJ_NSCH] = {0, 0, 0};
   double ss = 0, sq = 0, sm = -1, fs = 0, fq = 0, fm = -1;
   double rs[KBJ_NSCH] = {0, 0, 0}, rm[KBJ_NSCH] = {-1, -1, -1}, os[KBJ_NSCH] = {0, 0, 0}, om[KBJ_NSCH] = {-1, -1, -1};
   double ds[KBJ_NSCH] = {0, 0, 0}, dm[KBJ_NSCH] = {-1, -1, -1}, ts[KBJ_NSCH] = {0, 0, 0}, tm[KBJ_NSCH] = {-1, -1, -1};
-  for (int n0 = 0; n0 < N; n0 += SR_RED_THREADS) {
-    const int nb = min(SR_RED_THREADS, N - n0);
-    __syncthreads();                                          // the round before has been read
-    for (int i = threadIdx.x; i < nb * (KBJ_SREC_SIZE / 4); i += SR_RED_THREADS)
-      reinterpret_cast<float4*>(&row[0][0])[i] = reinterpret_cast<const float4*>(rec + (size_t)n0 * KBJ_SREC_SIZE)[i];
-    if (threadIdx.x < nb) grp[threadIdx.x] = group ? group[n0 + threadIdx.x] : 0;
-    __syncthreads();
+  for (int n0 = 0; n0 < N; n0 += GROUP_REDUCE_THREADS) {
+    const int nb = min(GROUP_REDUCE_THREADS, N - n0);
+    group_stage_round(row, grp, rec, group, n0, nb);
     if (g < G) {
       for (int i = 0; i < nb; ++i) {
         if (grp[i] != g) continue;

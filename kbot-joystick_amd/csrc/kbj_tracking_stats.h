@@ -4,8 +4,8 @@
 //
 // Shape: episode_stats_kernel's. One workgroup of seven wavefronts owns 64 consecutive envs. For a fixed t the block's aux rows are 18 KB of
 // contiguous floats: wavefronts 1-6 each fetch one time step of a 6-step chunk with 18 coalesced 16-byte loads per lane (issued one chunk
-// ahead, so they fly under the evaluation of the chunk before), put the 12 pieces the errors read into LDS with a row stride of 49 words
-// (one env per lane reads it conflict-free) and evaluate the five errors there, one env per lane: the rows are independent, so the
+// ahead, so they fly under the evaluation of the chunk before), stage the 12 pieces the errors read (kbj_aux_stage.h: a row stride of 49
+// words) and evaluate the five errors there, one env per lane: the rows are independent, so the
 // trigonometry runs on the wide part, two wavefronts per SIMD. What is left per row - five errors, the mode, DONE, "same command as the
 // row before" - is six words. Wavefront 0 runs the ordered part from them, one env per lane: rows since the command changed or the episode
 // started, the settled test, the per-mode sums.
@@ -16,6 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "kbj_model.h"
+#include "kbj_aux_stage.h"
+#include "kbj_ordered_reduce.h"
 
 namespace kbj {
 namespace {
@@ -23,8 +25,7 @@ namespace {
 constexpr int TRK_ENVS = 64;        // envs per workgroup = lanes of every wavefront
 constexpr int TRK_THREADS = 448;    // wavefront 0 scans, wavefronts 1-6 stage and evaluate
 constexpr int TRK_TC = 6;           // time steps per chunk: one per staging wavefront
-constexpr int TRK_LD = 49;          // row stride of the staged image, in words: the 12 staged 16-byte pieces of an aux row and one word (odd: one env per lane is conflict-free)
-constexpr int TRK_V4 = KBJ_AUX_SIZE / 4;             // 16-byte pieces per aux row = loads per lane and time step
+constexpr int TRK_V4 = AUX_V4;      // loads per lane and time step: every 16-byte piece of an aux row
 constexpr int TRK_RES = KBJ_NTERR + 1;               // words per evaluated row: the errors and the flags word
 constexpr int TRK_SLOTS = KBJ_TRK_MAX + KBJ_NTERR;   // used slots of a mode block
 constexpr int TRK_IMG = KBJ_CMODE_COUNT * TRK_SLOTS + 2;   // rows of the accumulator image: the mode blocks, command changes, episodes started
@@ -33,17 +34,17 @@ static_assert(KBJ_TRK_SUM == 2 && KBJ_TRK_SUMSQ == KBJ_TRK_SUM + KBJ_NTERR && KB
               KBJ_CMODE_COUNT * KBJ_TRK_MODE_STRIDE == KBJ_TRK_CHANGES && KBJ_TRK_EPISODES < KBJ_TRK_SIZE && KBJ_TRK_SIZE <= TRK_THREADS, "tracking statistics layout");
 static_assert(TRK_THREADS == 64 * (TRK_TC + 1), "one scanning wavefront and one staging wavefront per time step of a chunk");
 
-// where the 16-byte piece `p` of an aux row (columns 4 p .. 4 p + 3) lives in its staged row, or -1: the pieces the errors read are 0-3 (QVEL,
-// BQUAT, BASEZ, LFZ, RFZ), 5-7 (ARMQ) and 13-17 (CMD, DONE)
-__device__ constexpr int trk_piece(int p) { return p < 4 ? p : (p >= 5 && p <= 7) ? p - 1 : (p >= 13 && p <= 17) ? p - 6 : -1; }
-__device__ constexpr int trk_col(int col) { return 4 * trk_piece(col / 4) + col % 4; }
-static_assert(trk_piece(KBJ_AUX_RFZ / 4) == 3 && trk_piece(4) == -1 && trk_piece(KBJ_AUX_ARMQ / 4) == 4 && trk_piece((KBJ_AUX_ARMQ + 9) / 4) == 6 && trk_piece(8) == -1 &&
-              trk_piece(12) == -1 && trk_piece(KBJ_AUX_CMD / 4) == 7 && trk_piece(KBJ_AUX_DONE / 4) == 11 && 4 * 12 + 1 == TRK_LD && KBJ_AUX_SIZE / 4 == 18, "staged pieces");
-// a staged row, read by aux column
-struct TrkRow {
-  const float* p;
-  __device__ float operator[](int col) const { return p[trk_col(col)]; }
+// the staged pieces of an aux row (kbj_aux_stage.h): those the errors read are 0-3 (QVEL, BQUAT, BASEZ, LFZ, RFZ), 5-7 (ARMQ) and 13-17
+// (CMD, DONE)
+struct TrkMap {
+  static constexpr int NPIECE = 12;
+  static __device__ constexpr int piece(int p) { return p < 4 ? p : (p >= 5 && p <= 7) ? p - 1 : (p >= 13 && p <= 17) ? p - 6 : -1; }
 };
+using TrkRow = StagedRow<TrkMap>;
+constexpr int TRK_LD = TrkRow::LD;
+static_assert(TrkMap::piece(KBJ_AUX_RFZ / 4) == 3 && TrkMap::piece(4) == -1 && TrkMap::piece(KBJ_AUX_ARMQ / 4) == 4 && TrkMap::piece((KBJ_AUX_ARMQ + 9) / 4) == 6 &&
+              TrkMap::piece(8) == -1 && TrkMap::piece(12) == -1 && TrkMap::piece(KBJ_AUX_CMD / 4) == 7 && TrkMap::piece(KBJ_AUX_DONE / 4) == 11 && TRK_LD == 49 &&
+              KBJ_AUX_SIZE / 4 == 18, "staged pieces");
 
 struct TrkShared {
   double img[TRK_IMG][TRK_ENVS];                 // [mode * TRK_SLOTS + slot][lane], then changes, episodes
@@ -52,26 +53,11 @@ struct TrkShared {
   float last[2][KBJ_NCMD][TRK_ENVS];             // the command of the last row of chunk c in last[c & 1]
 };
 
-// the slots of a KBJ_TRK vector (kbj_ordered_reduce.h): counts and sums, but for the maxima of each mode block. The identity of every slot
-// is 0: the errors are non-negative
-struct TrkSlots {
+// the slots of a KBJ_TRK vector (kbj_ordered_reduce.h): counts and sums, but for the maxima of each mode block (the errors are non-negative)
+struct TrkSlots : SumMaxSlots<TrkSlots> {
   static constexpr int SIZE = KBJ_TRK_SIZE;
   static __device__ inline bool is_max(int j) { return j < KBJ_TRK_CHANGES && j % KBJ_TRK_MODE_STRIDE >= KBJ_TRK_MAX && j % KBJ_TRK_MODE_STRIDE < KBJ_TRK_MAX + KBJ_NTERR; }
-  static __device__ inline double identity(int) { return 0.0; }
-  static __device__ inline double combine_as(bool is_max, double a, double b) { return is_max ? (b > a ? b : a) : a + b; }   // is_max(j), hoisted by the caller
-  static __device__ inline double combine(int j, double a, double b) { return combine_as(is_max(j), a, b); }
 };
-
-// the mode of a command (kbj.h kbj_tracking_stats; the switch list of train.py:752-762)
-template <class Cmd> __device__ inline int trk_mode(const Cmd& cmd) {
-  const bool x = cmd[0] != 0.0f, y = cmd[1] != 0.0f, z = cmd[2] != 0.0f;
-  bool pose = false;
-#pragma unroll
-  for (int k = 3; k < KBJ_NCMD; ++k) pose = pose || cmd[k] != 0.0f;
-  if (!(x || y || z)) return pose ? KBJ_CMODE_STAND_BEND : KBJ_CMODE_STAND;
-  if (pose || (int)x + (int)y + (int)z != 1) return KBJ_CMODE_OMNI;
-  return x ? KBJ_CMODE_FORWARD : y ? KBJ_CMODE_SIDEWAYS : KBJ_CMODE_ROTATE;
-}
 
 // the five errors of one staged aux row: rewards_kernel's expressions (kbj_traj_stats.hip), before their exp. Restated, not shared: called
 // from one template over the row type, rewards_kernel contracts its multiply-adds differently (other fma / packed-fma counts), so reward
@@ -152,13 +138,8 @@ __global__ __launch_bounds__(TRK_THREADS) void tracking_stats_kernel(const kbj_m
     const int tt = wave - 1, t = c * TRK_TC + tt;
     const bool mine = wave > 0 && c < nchunk && t < T;     // this wavefront has a time step in chunk c
     if (mine) {
-      float* dst = S.raw[tt];
 #pragma unroll
-      for (int k = 0; k < TRK_V4; ++k) {
-        const int i = k * 64 + lane;
-        const int slot = trk_piece(i % TRK_V4);
-        if (i < npiece && slot >= 0) { float* d = dst + (i / TRK_V4) * TRK_LD + 4 * slot; d[0] = v[k].x; d[1] = v[k].y; d[2] = v[k].z; d[3] = v[k].w; }
-      }
+      for (int k = 0; k < TRK_V4; ++k) stage_piece<TrkMap>(S.raw[tt], v[k], k * 64 + lane, npiece);
     }
     __syncthreads();
     if (wave > 0) {
@@ -182,7 +163,7 @@ __global__ __launch_bounds__(TRK_THREADS) void tracking_stats_kernel(const kbj_m
 #pragma unroll
           for (int k = 0; k < KBJ_NCMD; ++k) same = same && !(cmd[k] != prev[k]);
         }
-        const int flags = trk_mode(cmd) | (same ? 8 : 0) | (a[KBJ_AUX_DONE] != 0.0f ? 16 : 0);
+        const int flags = cmd_mode(a) | (same ? 8 : 0) | (a[KBJ_AUX_DONE] != 0.0f ? 16 : 0);
         float (*r)[TRK_ENVS] = S.res[c & 1][tt];
 #pragma unroll
         for (int k = 0; k < KBJ_NTERR; ++k) r[k][lane] = e[k];

@@ -3,6 +3,7 @@
 // (kbj_push_recovery.h) and kbj_step_response (kbj_step_response.h). None of it
 // is on the hot path, and none of it shares a translation unit with the env kernels (kbj_env.hip): an edit here recompiles no step kernel.
 #include <hip/hip_runtime.h>
+#include <initializer_list>
 #include "kbj_env_core.h"
 #include "kbj_ordered_reduce.h"
 #include "kbj_episode_stats.h"
@@ -131,6 +132,31 @@ int stats_partials(kbj_ctx* ctx, size_t doubles) {
   return 0;
 }
 
+// "<fn>: the trajectory needs <its arrays> and positive T, N"
+int check_traj(kbj_ctx* ctx, const char* fn, const kbj_traj* tr, bool needs_reward) {
+  if (tr->aux_d && (!needs_reward || tr->reward_d) && tr->T > 0 && tr->N > 0) return 0;
+  return kbj_fail(ctx, std::string(fn) + ": the trajectory needs " + (needs_reward ? "aux_d, reward_d" : "aux_d") + " and positive T, N");
+}
+
+// "<fn>: <names> must be 16-byte aligned" (a null pointer is aligned)
+int check_aligned16(kbj_ctx* ctx, const char* fn, const char* names, std::initializer_list<const void*> ptrs) {
+  uintptr_t bits = 0;
+  for (const void* p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
+  return (bits & 15) ? kbj_fail(ctx, std::string(fn) + ": " + names + " must be 16-byte aligned") : 0;
+}
+
+// a scan that leaves `blocks` workgroup partials of Slots::SIZE doubles, then their ordered reduce into stats_d. launch_scan(partials) queues
+// the scan on the context's stream
+template <class Slots, class LaunchScan>
+int scan_then_reduce(kbj_ctx* ctx, int blocks, const char* scan_name, const char* reduce_name, double* stats_d, LaunchScan launch_scan) {
+  if (stats_partials(ctx, (size_t)blocks * Slots::SIZE) != 0) return -1;
+  launch_scan(ctx->stats_part_d);
+  KBJ_CHECK_LAUNCH(ctx, scan_name);
+  hipLaunchKernelGGL(ordered_reduce_kernel<Slots>, dim3(1), dim3(ORDERED_REDUCE_THREADS), 0, ctx->stream, ctx->stats_part_d, blocks, stats_d);
+  KBJ_CHECK_LAUNCH(ctx, reduce_name);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -149,77 +175,57 @@ int kbj_rewards(kbj_ctx* ctx, const float* aux_d, int T, float* reward_d, float*
 
 int kbj_episode_stats(kbj_ctx* ctx, const kbj_traj* tr, float* acc_d, double* stats_d) {
   if (!ctx || !tr || !acc_d || !stats_d) return kbj_fail(ctx, "kbj_episode_stats: null argument");
-  if (!tr->aux_d || !tr->reward_d || tr->T <= 0 || tr->N <= 0) return kbj_fail(ctx, "kbj_episode_stats: the trajectory needs aux_d, reward_d and positive T, N");
-  if ((reinterpret_cast<uintptr_t>(acc_d) | reinterpret_cast<uintptr_t>(tr->reward_comps_d)) & 15)
-    return kbj_fail(ctx, "kbj_episode_stats: acc_d and reward_comps_d must be 16-byte aligned");
+  if (check_traj(ctx, "kbj_episode_stats", tr, true) != 0 || check_aligned16(ctx, "kbj_episode_stats", "acc_d and reward_comps_d", {acc_d, tr->reward_comps_d}) != 0) return -1;
   KBJ_HIP(ctx, hipSetDevice(ctx->device));
   kbj_nn_drop_prefetch(ctx);
   const int blocks = (tr->N + EPST_ENVS - 1) / EPST_ENVS;
-  if (stats_partials(ctx, (size_t)blocks * KBJ_EPST_SIZE) != 0) return -1;
-  hipLaunchKernelGGL(episode_stats_kernel, dim3(blocks), dim3(EPST_THREADS), 0, ctx->stream, tr->aux_d, tr->reward_d, tr->reward_comps_d, tr->T, tr->N,
-                     ctx->cfg_h.unhealthy_z, acc_d, ctx->stats_part_d);
-  KBJ_CHECK_LAUNCH(ctx, "episode_stats_kernel");
-  hipLaunchKernelGGL(ordered_reduce_kernel<EpstSlots>, dim3(1), dim3(ORDERED_REDUCE_THREADS), 0, ctx->stream, ctx->stats_part_d, blocks, stats_d);
-  KBJ_CHECK_LAUNCH(ctx, "ordered_reduce_kernel<EpstSlots>");
-  return 0;
+  return scan_then_reduce<EpstSlots>(ctx, blocks, "episode_stats_kernel", "ordered_reduce_kernel<EpstSlots>", stats_d, [&](double* part_d) {
+    hipLaunchKernelGGL(episode_stats_kernel, dim3(blocks), dim3(EPST_THREADS), 0, ctx->stream, tr->aux_d, tr->reward_d, tr->reward_comps_d, tr->T, tr->N,
+                       ctx->cfg_h.unhealthy_z, acc_d, part_d);
+  });
 }
 
 int kbj_tracking_stats(kbj_ctx* ctx, const kbj_traj* tr, int settle_steps, float* acc_d, double* stats_d, float* err_d) {
   if (!ctx || !tr || !acc_d || !stats_d) return kbj_fail(ctx, "kbj_tracking_stats: null argument");
-  if (!tr->aux_d || tr->T <= 0 || tr->N <= 0) return kbj_fail(ctx, "kbj_tracking_stats: the trajectory needs aux_d and positive T, N");
+  if (check_traj(ctx, "kbj_tracking_stats", tr, false) != 0) return -1;
   if (settle_steps < 0) return kbj_fail(ctx, "kbj_tracking_stats: settle_steps must not be negative");
-  if ((reinterpret_cast<uintptr_t>(acc_d) | reinterpret_cast<uintptr_t>(err_d) | reinterpret_cast<uintptr_t>(tr->aux_d)) & 15)
-    return kbj_fail(ctx, "kbj_tracking_stats: acc_d, err_d and aux_d must be 16-byte aligned");
+  if (check_aligned16(ctx, "kbj_tracking_stats", "acc_d, err_d and aux_d", {acc_d, err_d, tr->aux_d}) != 0) return -1;
   KBJ_HIP(ctx, hipSetDevice(ctx->device));
   kbj_nn_drop_prefetch(ctx);
   const int blocks = (tr->N + TRK_ENVS - 1) / TRK_ENVS;
-  if (stats_partials(ctx, (size_t)blocks * KBJ_TRK_SIZE) != 0) return -1;
-  {
+  return scan_then_reduce<TrkSlots>(ctx, blocks, "tracking_stats_kernel", "ordered_reduce_kernel<TrkSlots>", stats_d, [&](double* part_d) {
     KbjKernelTimer timer(ctx->stream, KBJ_KIND_TRACKING_STATS, 0.0);
     hipLaunchKernelGGL(tracking_stats_kernel, dim3(blocks), dim3(TRK_THREADS), 0, ctx->stream, ctx->model_d, tr->aux_d, tr->T, tr->N, settle_steps,
-                       ctx->cfg_h.rew_standard_height, ctx->cfg_h.rew_foot_origin_height, acc_d, ctx->stats_part_d, err_d);
-  }
-  KBJ_CHECK_LAUNCH(ctx, "tracking_stats_kernel");
-  hipLaunchKernelGGL(ordered_reduce_kernel<TrkSlots>, dim3(1), dim3(ORDERED_REDUCE_THREADS), 0, ctx->stream, ctx->stats_part_d, blocks, stats_d);
-  KBJ_CHECK_LAUNCH(ctx, "ordered_reduce_kernel<TrkSlots>");
-  return 0;
+                       ctx->cfg_h.rew_standard_height, ctx->cfg_h.rew_foot_origin_height, acc_d, part_d, err_d);
+  });
 }
 
 int kbj_gait_stats(kbj_ctx* ctx, const kbj_traj* tr, float* acc_d, double* stats_d, float* env_d) {
   if (!ctx || !tr || !acc_d || !stats_d) return kbj_fail(ctx, "kbj_gait_stats: null argument");
-  if (!tr->aux_d || tr->T <= 0 || tr->N <= 0) return kbj_fail(ctx, "kbj_gait_stats: the trajectory needs aux_d and positive T, N");
-  if ((reinterpret_cast<uintptr_t>(acc_d) | reinterpret_cast<uintptr_t>(env_d) | reinterpret_cast<uintptr_t>(tr->aux_d)) & 15)
-    return kbj_fail(ctx, "kbj_gait_stats: acc_d, env_d and aux_d must be 16-byte aligned");
+  if (check_traj(ctx, "kbj_gait_stats", tr, false) != 0 || check_aligned16(ctx, "kbj_gait_stats", "acc_d, env_d and aux_d", {acc_d, env_d, tr->aux_d}) != 0) return -1;
   KBJ_HIP(ctx, hipSetDevice(ctx->device));      // no kbj_nn_drop_prefetch: no trajectory row is written
   const int blocks = (tr->N + GAIT_ENVS - 1) / GAIT_ENVS;
-  if (stats_partials(ctx, (size_t)blocks * KBJ_GAIT_SIZE) != 0) return -1;
-  {
+  return scan_then_reduce<GaitSlots>(ctx, blocks, "gait_stats_kernel", "ordered_reduce_kernel<GaitSlots>", stats_d, [&](double* part_d) {
     KbjKernelTimer timer(ctx->stream, KBJ_KIND_GAIT_STATS, 0.0);
-    hipLaunchKernelGGL(gait_stats_kernel, dim3(blocks), dim3(GAIT_THREADS), 0, ctx->stream, tr->aux_d, tr->T, tr->N, acc_d, ctx->stats_part_d, env_d);
-  }
-  KBJ_CHECK_LAUNCH(ctx, "gait_stats_kernel");
-  hipLaunchKernelGGL(ordered_reduce_kernel<GaitSlots>, dim3(1), dim3(ORDERED_REDUCE_THREADS), 0, ctx->stream, ctx->stats_part_d, blocks, stats_d);
-  KBJ_CHECK_LAUNCH(ctx, "ordered_reduce_kernel<GaitSlots>");
-  return 0;
+    hipLaunchKernelGGL(gait_stats_kernel, dim3(blocks), dim3(GAIT_THREADS), 0, ctx->stream, tr->aux_d, tr->T, tr->N, acc_d, part_d, env_d);
+  });
 }
 
 int kbj_push_recovery(kbj_ctx* ctx, const kbj_traj* tr, const float* err_d, const int32_t* sched_d, const kbj_push_criteria* crit, float* rec_d,
                       const int32_t* group_d, int G, double* stats_d) {
   if (!ctx || !tr || !err_d || !sched_d || !crit || !rec_d) return kbj_fail(ctx, "kbj_push_recovery: null argument");
-  if (!tr->aux_d || tr->T <= 0 || tr->N <= 0) return kbj_fail(ctx, "kbj_push_recovery: the trajectory needs aux_d and positive T, N");
-  if ((reinterpret_cast<uintptr_t>(err_d) | reinterpret_cast<uintptr_t>(rec_d)) & 15) return kbj_fail(ctx, "kbj_push_recovery: err_d and rec_d must be 16-byte aligned");
+  if (check_traj(ctx, "kbj_push_recovery", tr, false) != 0 || check_aligned16(ctx, "kbj_push_recovery", "err_d and rec_d", {err_d, rec_d}) != 0) return -1;
   if (reinterpret_cast<uintptr_t>(sched_d) & 7) return kbj_fail(ctx, "kbj_push_recovery: sched_d must be 8-byte aligned");
   if (crit->hold_steps < 1) return kbj_fail(ctx, "kbj_push_recovery: hold_steps must be at least 1");
   if (crit->window_steps < 0) return kbj_fail(ctx, "kbj_push_recovery: window_steps must not be negative");
   for (int k = 0; k < KBJ_NTERR; ++k)
     if (crit->tol[k] != crit->tol[k]) return kbj_fail(ctx, "kbj_push_recovery: a tolerance is NaN (+inf ignores a column)");
-  if (stats_d && (G < 1 || G > PR_RED_THREADS)) return kbj_fail(ctx, "kbj_push_recovery: G must be in [1, 256]");
-  static_assert(PR_RED_THREADS == 256, "the G range kbj.h documents");
+  if (stats_d && (G < 1 || G > GROUP_REDUCE_THREADS)) return kbj_fail(ctx, "kbj_push_recovery: G must be in [1, 256]");
   KBJ_HIP(ctx, hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(push_recovery_kernel, dim3((tr->N + PR_ENVS - 1) / PR_ENVS), dim3(PR_ENVS), 0, ctx->stream, err_d, tr->aux_d, tr->T, tr->N, sched_d, *crit, rec_d);
+  hipLaunchKernelGGL(push_recovery_kernel, dim3((tr->N + WINDOW_ENVS - 1) / WINDOW_ENVS), dim3(WINDOW_ENVS), 0, ctx->stream, err_d, tr->aux_d, tr->T, tr->N, sched_d, *crit, rec_d);
   KBJ_CHECK_LAUNCH(ctx, "push_recovery_kernel");
   if (stats_d) {
-    hipLaunchKernelGGL(push_recovery_reduce_kernel, dim3(1), dim3(PR_RED_THREADS), 0, ctx->stream, rec_d, group_d, tr->N, G, stats_d);
+    hipLaunchKernelGGL(push_recovery_reduce_kernel, dim3(1), dim3(GROUP_REDUCE_THREADS), 0, ctx->stream, rec_d, group_d, tr->N, G, stats_d);
     KBJ_CHECK_LAUNCH(ctx, "push_recovery_reduce_kernel");
   }
   return 0;
@@ -228,11 +234,9 @@ int kbj_push_recovery(kbj_ctx* ctx, const kbj_traj* tr, const float* err_d, cons
 int kbj_step_response(kbj_ctx* ctx, const kbj_traj* tr, const int32_t* sched_d, const kbj_step_criteria* crit, float* sig_d, float* rec_d,
                       const int32_t* group_d, int G, double* stats_d) {
   if (!ctx || !tr || !sched_d || !crit || !sig_d || !rec_d) return kbj_fail(ctx, "kbj_step_response: null argument");
-  if (!tr->aux_d || tr->T <= 0 || tr->N <= 0) return kbj_fail(ctx, "kbj_step_response: the trajectory needs aux_d and positive T, N");
-  if ((reinterpret_cast<uintptr_t>(tr->aux_d) | reinterpret_cast<uintptr_t>(sig_d) | reinterpret_cast<uintptr_t>(rec_d)) & 15)
-    return kbj_fail(ctx, "kbj_step_response: aux_d, sig_d and rec_d must be 16-byte aligned");
+  if (check_traj(ctx, "kbj_step_response", tr, false) != 0 || check_aligned16(ctx, "kbj_step_response", "aux_d, sig_d and rec_d", {tr->aux_d, sig_d, rec_d}) != 0) return -1;
   if (crit->smooth_steps < 1 || crit->smooth_steps > SR_RING) return kbj_fail(ctx, "kbj_step_response: smooth_steps must be in [1, 32]");
-  static_assert(SR_RING == 32 && SR_RED_THREADS == 256, "the smooth_steps and G ranges kbj.h documents");
+  static_assert(SR_RING == 32, "the smooth_steps range kbj.h documents");
   if (crit->hold_steps < 1) return kbj_fail(ctx, "kbj_step_response: hold_steps must be at least 1");
   if (crit->window_steps < 1) return kbj_fail(ctx, "kbj_step_response: window_steps must be at least 1");
   if (!(crit->rise_level > 0.0f && crit->rise_level <= 1.0f)) return kbj_fail(ctx, "kbj_step_response: rise_level must be in (0, 1]");
@@ -241,16 +245,16 @@ int kbj_step_response(kbj_ctx* ctx, const kbj_traj* tr, const int32_t* sched_d, 
     if (!(crit->band_abs[k] >= 0.0f)) return kbj_fail(ctx, "kbj_step_response: a band_abs is negative or NaN");
     if (!(crit->min_step[k] >= 0.0f)) return kbj_fail(ctx, "kbj_step_response: a min_step is negative or NaN");
   }
-  if (stats_d && (G < 1 || G > SR_RED_THREADS)) return kbj_fail(ctx, "kbj_step_response: G must be in [1, 256]");
+  if (stats_d && (G < 1 || G > GROUP_REDUCE_THREADS)) return kbj_fail(ctx, "kbj_step_response: G must be in [1, 256]");
   KBJ_HIP(ctx, hipSetDevice(ctx->device));      // no kbj_nn_drop_prefetch: no trajectory row is written
   const size_t rows = (size_t)tr->T * (size_t)tr->N;
   const size_t sig_blocks = (rows + SR_SIG_THREADS - 1) / SR_SIG_THREADS;
   hipLaunchKernelGGL(step_signal_kernel, dim3((unsigned)(sig_blocks < (1u << 20) ? sig_blocks : (1u << 20))), dim3(SR_SIG_THREADS), 0, ctx->stream, tr->aux_d, rows, sig_d);
   KBJ_CHECK_LAUNCH(ctx, "step_signal_kernel");
-  hipLaunchKernelGGL(step_scan_kernel, dim3((tr->N + SR_ENVS - 1) / SR_ENVS), dim3(SR_ENVS), 0, ctx->stream, sig_d, tr->T, tr->N, sched_d, *crit, rec_d);
+  hipLaunchKernelGGL(step_scan_kernel, dim3((tr->N + WINDOW_ENVS - 1) / WINDOW_ENVS), dim3(WINDOW_ENVS), 0, ctx->stream, sig_d, tr->T, tr->N, sched_d, *crit, rec_d);
   KBJ_CHECK_LAUNCH(ctx, "step_scan_kernel");
   if (stats_d) {
-    hipLaunchKernelGGL(step_reduce_kernel, dim3(1), dim3(SR_RED_THREADS), 0, ctx->stream, rec_d, group_d, tr->N, G, stats_d);
+    hipLaunchKernelGGL(step_reduce_kernel, dim3(1), dim3(GROUP_REDUCE_THREADS), 0, ctx->stream, rec_d, group_d, tr->N, G, stats_d);
     KBJ_CHECK_LAUNCH(ctx, "step_reduce_kernel");
   }
   return 0;

@@ -1,10 +1,19 @@
-"""The host carrier of a statistic the device accumulates over rollouts (kbj_episode_stats, kbj_tracking_stats; host/episode.py and
-host/tracking.py construct one each): the per-env rows that live next to the env state, the hand-over of one call's result to the host, the
-totals."""
+"""The host carrier of a statistic the device accumulates over rollouts (kbj_episode_stats, kbj_tracking_stats, kbj_gait_stats;
+host/episode.py, host/tracking.py and host/gait.py construct one each): the per-env rows that live next to the env state, the hand-over of
+one call's result to the host, the totals - and the same call on rows of its own, for a trajectory that stands alone."""
 from __future__ import annotations
 
 import numpy as np
 import torch
+
+
+def fresh_stats(layout, acc_width: int, call, num_envs: int, device) -> torch.Tensor:
+    """`call(acc, stats)` on zeroed per-env rows [num_envs, acc_width] - a trajectory whose episodes all start with it (every validation
+    and sweep rollout): its vector of `layout` (dist.StatsLayout), on the device."""
+    acc = torch.zeros(num_envs, acc_width, device=device)
+    stats = torch.zeros(layout.empty().size, dtype=torch.float64, device=device)
+    call(acc, stats)
+    return stats
 
 
 class DeviceStats:

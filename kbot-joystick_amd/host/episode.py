@@ -8,7 +8,7 @@ import torch
 
 from ..spec import constants, layout as L
 from . import dist as dist_util
-from .device_stats import DeviceStats
+from .device_stats import DeviceStats, fresh_stats
 
 
 def episode_stats_scalars(vec, ctrl_dt: float, prefix: str = "episode/", terms: bool = False) -> dict:
@@ -38,10 +38,7 @@ def episode_stats_scalars(vec, ctrl_dt: float, prefix: str = "episode/", terms: 
 
 def fresh_episode_stats(ctx, traj, num_envs: int, device) -> torch.Tensor:
     """kbj_episode_stats on a trajectory whose episodes all start with it (every validation rollout): its KBJ_EPST vector, on the device."""
-    acc = torch.zeros(num_envs, L.EACC["SIZE"], device=device)
-    stats = torch.zeros(L.EPST["SIZE"], dtype=torch.float64, device=device)
-    ctx.episode_stats(traj, acc, stats)
-    return stats
+    return fresh_stats(dist_util.EPISODE_STATS, L.EACC["SIZE"], lambda acc, stats: ctx.episode_stats(traj, acc, stats), num_envs, device)
 
 
 class EpisodeStats(DeviceStats):

@@ -11,8 +11,8 @@ import torch
 
 from ..spec import constants, layout as L
 from . import dist as dist_util
-from .device_stats import DeviceStats
-from .sweep import sweep_rollout, sweep_terms
+from .device_stats import DeviceStats, fresh_stats
+from .sweep import command_label, command_table, failures_per_s, held_command_rollout, table_cell
 from .tracking import ScriptedCommand, command_mode, default_command_grid
 
 G, F, A, E = L.GAIT, L.GFOOT, L.GACC, L.GENV
@@ -72,10 +72,7 @@ def gait_scalars(vec, ctrl_dt: float, prefix: str = "gait/") -> dict:
 
 def fresh_gait_stats(ctx, traj, num_envs: int, device, env=None) -> torch.Tensor:
     """kbj_gait_stats on a trajectory whose episodes all start with it (every validation rollout): its KBJ_GAIT vector, on the device."""
-    acc = torch.zeros(num_envs, A["SIZE"], device=device)
-    stats = torch.zeros(G["SIZE"], dtype=torch.float64, device=device)
-    ctx.gait_stats(traj, acc, stats, env)
-    return stats
+    return fresh_stats(dist_util.GAIT_STATS, A["SIZE"], lambda acc, stats: ctx.gait_stats(traj, acc, stats, env), num_envs, device)
 
 
 class GaitStats(DeviceStats):
@@ -126,24 +123,12 @@ def gait_sweep(task, commands=None, repeats: int = 2, seconds=None, seed_offset:
     commands = default_command_grid(task.kcfg) if commands is None else commands
     if len(commands) == 0 or repeats < 1:
         raise ValueError("gait_sweep needs at least one command and one repeat")
-    table = np.zeros((len(commands), L.NCMD), np.float32)
-    for i, c in enumerate(commands):
-        c = np.asarray(c, np.float32).reshape(-1)
-        if c.size > L.NCMD:
-            raise ValueError(f"command {i} has {c.size} components, a command has {L.NCMD}")
-        table[i, :c.size] = c
+    table = command_table(commands)
     ncmd, n = len(commands), len(commands) * repeats
     T = max(1, int(round((cfg.render_length_seconds if seconds is None else seconds) / cfg.ctrl_dt)))
     dev = task.device
     per_env = torch.from_numpy(np.tile(table, (repeats, 1))).to(dev)                      # env e follows command e % ncmd
-    terms = sweep_terms(task, command=ScriptedCommand(per_env))
-    feeds = [terms.observe_rows] if any(task.extra_obs) else []
-
-    def configure(vcfg):
-        vcfg.command_mode = 1
-
-    with sweep_rollout(task, n, T, configure, terms, [terms.apply_resets, terms.apply_command] + feeds,
-                       [terms.apply_resets] + feeds + [terms.apply_command], seed_offset) as (ctx, tr):       # validate()'s order
+    with held_command_rollout(task, n, T, ScriptedCommand(per_env), seed_offset) as (ctx, tr):
         env = torch.empty(n, E["SIZE"], device=dev)
         stats = fresh_gait_stats(ctx, tr.c, n, dev, env)
         ctx.synchronize()
@@ -153,7 +138,7 @@ def gait_sweep(task, commands=None, repeats: int = 2, seconds=None, seed_offset:
         envs = list(range(i, n, ncmd))
         entry = dict(command=tuple(float(x) for x in table[i]), mode=constants.COMMAND_MODE_NAMES[command_mode(table[i])])
         entry.update(pool_gait_rows(rows[envs], cfg.ctrl_dt))
-        entry["failures_per_s"] = float(sum((done[:, j] < 0).sum() for j in envs)) / (repeats * T * cfg.ctrl_dt)
+        entry["failures_per_s"] = failures_per_s(done, envs, repeats * T * cfg.ctrl_dt)
         out.append(entry)
     return out, GaitRecord(tr.aux, env, vec)
 
@@ -169,13 +154,9 @@ def format_gait_table(entries) -> str:
     """gait_sweep's result as a text table: one line per command (its non-zero components by name), then per foot the mean swing and stance
     time, mean and largest clearance and peak force, the step rate, the three support shares, the repeat share, the torque level and the
     failures per second ("-" where there was nothing to average)."""
-    def label(cmd):
-        parts = [f"{constants.COMMAND_NAMES[k]}={v:+.2f}" for k, v in enumerate(cmd) if v != 0]
-        return " ".join(parts) if parts else "(zero)"
-    labels = [label(x["command"]) for x in entries]
+    labels = [command_label(x["command"]) for x in entries]
     w = max([len("command")] + [len(s) for s in labels])
-    cell = lambda v: f"  {'-':>10s}" if v != v else f"  {v:10.3f}"
     lines = [f"{'command':{w}s}  {'mode':10s}" + "".join(f"  {title:>10s}" for title, _ in GAIT_TABLE_COLUMNS)]
     for s, x in zip(labels, entries):
-        lines.append(f"{s:{w}s}  {x['mode']:10s}" + "".join(cell(x[key]) for _, key in GAIT_TABLE_COLUMNS))
+        lines.append(f"{s:{w}s}  {x['mode']:10s}" + "".join(table_cell(x[key]) for _, key in GAIT_TABLE_COLUMNS))
     return "\n".join(lines)

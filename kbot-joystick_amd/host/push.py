@@ -11,7 +11,7 @@ import torch
 
 from ..spec import constants, layout as L
 from . import binding as B
-from .sweep import sweep_rollout, sweep_terms
+from .sweep import case_of_env, command_table, steps_of, sweep_rollout, sweep_terms
 from .tracking import fresh_tracking_stats
 from .traj_view import PushRequest
 
@@ -71,10 +71,6 @@ class PushRecord:
     push_state: np.ndarray = None
 
 
-def steps_of(seconds: float, ctrl_dt: float) -> int:
-    return int(round(seconds / ctrl_dt))
-
-
 def push_sweep(task, forces=(50.0, 100.0, 150.0, 200.0), directions_deg=(0, 45, 90, 135, 180, 225, 270, 315), duration: float = 0.2, command=None,
                push_at: float = 2.0, window: float = 3.0, hold: float = 0.5, tolerances=None, repeats: int = 4, torque=None, seed_offset: int = 7919):
     """The sweep behind HumanoidWalkingTask.push_sweep (see there): returns (entries, record) - one entry per (force, direction) case, and the
@@ -90,12 +86,7 @@ def push_sweep(task, forces=(50.0, 100.0, 150.0, 200.0), directions_deg=(0, 45, 
     tol.update(tolerances or {})
     if set(tol) != set(constants.TRACKING_ERROR_NAMES):
         raise ValueError(f"push_sweep: tolerances are named {constants.TRACKING_ERROR_NAMES}, got {sorted(set(tol) - set(constants.TRACKING_ERROR_NAMES))}")
-    cmd = np.zeros(L.NCMD, np.float32)
-    if command is not None:
-        c = np.asarray(command, np.float32).reshape(-1)
-        if c.size > L.NCMD:
-            raise ValueError(f"push_sweep: the command has {c.size} components, a command has {L.NCMD}")
-        cmd[:c.size] = c
+    cmd = command_table([() if command is None else command], "push_sweep: the command")[0]
     dt = cfg.ctrl_dt
     row, d, win, hld = steps_of(push_at, dt), steps_of(duration, dt), steps_of(window, dt), max(1, steps_of(hold, dt))
     if row < hld or d < 0 or win < 0:
@@ -121,7 +112,7 @@ def push_sweep(task, forces=(50.0, 100.0, 150.0, 200.0), directions_deg=(0, 45, 
         err = torch.empty(T, n, L.TERR["SIZE"], device=dev)
         fresh_tracking_stats(ctx, tr.c, n, 0, dev, err)
         sched = torch.tensor([[row, d]] * n, dtype=torch.int32, device=dev)
-        group = (torch.arange(n, device=dev) % ncases).to(torch.int32)
+        group = case_of_env(n, ncases, dev)
         crit = B.PushCriteria((B.C.c_float * L.NTERR)(*[tol[k] for k in constants.TRACKING_ERROR_NAMES]), hld, win)
         rec = torch.empty(n, P["SIZE"], device=dev)
         stats = torch.empty(ncases, S["SIZE"], dtype=torch.float64, device=dev)

@@ -10,8 +10,7 @@ import torch
 
 from ..spec import constants, layout as L
 from . import binding as B
-from .push import steps_of
-from .sweep import sweep_rollout, sweep_terms
+from .sweep import case_of_env, command_label, command_table, held_command_rollout, steps_of, table_cell
 
 R, S, O = L.SREC, L.SSTAT, L.SOUT
 CHANNELS = constants.STEP_CHANNEL_NAMES
@@ -65,16 +64,6 @@ class StepRecord:
     sched: torch.Tensor
 
 
-def _command_table(commands, what: str) -> np.ndarray:
-    table = np.zeros((len(commands), L.NCMD), np.float32)
-    for i, c in enumerate(commands):
-        c = np.asarray(c, np.float32).reshape(-1)
-        if c.size > L.NCMD:
-            raise ValueError(f"step_sweep: the {what} command of transition {i} has {c.size} components, a command has {L.NCMD}")
-        table[i, :c.size] = c
-    return table
-
-
 def step_sweep(task, transitions=None, step_at: float = 3.0, window: float = 4.0, hold: float = 0.5, smooth: float = 0.5, rise_level: float = 0.9,
                band_frac: float = 0.1, band_abs=(0.15, 0.15, 0.25), min_step=(0.05, 0.05, 0.05), repeats: int = 4, seed_offset: int = 7919):
     """The sweep behind HumanoidWalkingTask.step_sweep (see there): returns (entries, record) - one entry per transition, and the StepRecord
@@ -87,7 +76,7 @@ def step_sweep(task, transitions=None, step_at: float = 3.0, window: float = 4.0
         raise ValueError(f"step_sweep: {len(transitions)} transitions, kbj_step_response groups at most 256")
     if any(len(tr) != 2 for tr in transitions):
         raise ValueError("step_sweep: a transition is a pair (from command, to command)")
-    t0, t1 = _command_table([a for a, _ in transitions], "from"), _command_table([b for _, b in transitions], "to")
+    t0, t1 = (command_table([tr[k] for tr in transitions], "step_sweep: the " + end + " command of transition {i}") for k, end in enumerate(("from", "to")))
     dt = cfg.ctrl_dt
     row, win, hld, m = steps_of(step_at, dt), steps_of(window, dt), max(1, steps_of(hold, dt)), max(1, steps_of(smooth, dt))
     if m > MAX_SMOOTH_ROWS:
@@ -101,16 +90,9 @@ def step_sweep(task, transitions=None, step_at: float = 3.0, window: float = 4.0
     ncases, n, T = len(transitions), len(transitions) * repeats, row + win
     dev = task.device
     per_env0, per_env1 = (torch.from_numpy(np.tile(t, (repeats, 1))).to(dev) for t in (t0, t1))       # env e runs case e % ncases
-    terms = sweep_terms(task, command=SteppedCommand(per_env0, per_env1, row))
-    feeds = [terms.observe_rows] if any(task.extra_obs) else []
-
-    def configure(vcfg):
-        vcfg.command_mode = 1
-
-    with sweep_rollout(task, n, T, configure, terms, [terms.apply_resets, terms.apply_command] + feeds,
-                       [terms.apply_resets] + feeds + [terms.apply_command], seed_offset) as (ctx, tr):       # validate()'s order
+    with held_command_rollout(task, n, T, SteppedCommand(per_env0, per_env1, row), seed_offset) as (ctx, tr):
         sched = torch.full((n,), row, dtype=torch.int32, device=dev)
-        group = (torch.arange(n, device=dev) % ncases).to(torch.int32)
+        group = case_of_env(n, ncases, dev)
         crit = B.StepCriteria((B.C.c_float * L.NSCH)(*min_step), (B.C.c_float * L.NSCH)(*band_abs), band_frac, rise_level, m, hld, win)
         sig = torch.empty(T, n, L.SSIG["SIZE"], device=dev)
         rec = torch.empty(n, R["SIZE"], device=dev)
@@ -163,10 +145,6 @@ def format_step_table(entries) -> str:
     voids, the outcome fractions of the valid ones, settling time, then over the channels that moved the rise time, the risen share and
     the overshoot, over those that did not the cross-coupling, and the forward travel of the settled envs ("-" over nothing) - under a line
     that echoes the settings."""
-    def label(cmd):
-        parts = [f"{constants.COMMAND_NAMES[k]}={v:+.2f}" for k, v in enumerate(cmd) if v != 0]
-        return " ".join(parts) if parts else "(zero)"
-
     def pooled(x, key, how):                     # over the channels: the active ones for rise and overshoot, the quiet ones for the coupling
         vals = [x[f"{ch}_{key}"] for ch in CHANNELS]
         vals = [v for v in vals if v == v]
@@ -182,10 +160,9 @@ def format_step_table(entries) -> str:
         bands = " ".join(f"{ch}: band>={b:g} step>={s:g}" for ch, b, s in zip(CHANNELS, x["band_abs"], x["min_step"]))
         lines.append(f"step at {x['step_at']:g} s, window {x['window']:g} s, hold {x['hold']:g} s, smoothing {x['smooth']:g} s, {x['repeats']} repeats; settings, not measured "
                      f"thresholds: rise level {x['rise_level']:g}, band {x['band_frac']:g} of the step, {bands}")
-    labels = [f"{label(x['from_command'])} -> {label(x['to_command'])}" for x in entries]
+    labels = [f"{command_label(x['from_command'])} -> {command_label(x['to_command'])}" for x in entries]
     w = max([len("transition")] + [len(s) for s in labels])
-    cell = lambda v: f"  {'-':>10s}" if v != v else f"  {v:10.3f}"
     lines.append(f"{'transition':{w}s}  {'valid':>5s}  {'void':>4s}" + "".join(f"  {title:>10s}" for title, _ in cols))
     for s, x in zip(labels, entries):
-        lines.append(f"{s:{w}s}  {x['valid']:5d}  {x['void']:4d}" + "".join(cell(get(x)) for _, get in cols))
+        lines.append(f"{s:{w}s}  {x['valid']:5d}  {x['void']:4d}" + "".join(table_cell(get(x)) for _, get in cols))
     return "\n".join(lines)

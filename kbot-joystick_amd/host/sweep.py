@@ -5,11 +5,49 @@ from __future__ import annotations
 import contextlib
 import dataclasses
 
+import numpy as np
 import torch
 
+from ..spec import constants, layout as L
 from . import binding as B
 from .buffers import CarryBuffers, TrajBuffers
 from .user_terms import UserTerms
+
+
+def steps_of(seconds: float, ctrl_dt: float) -> int:
+    return int(round(seconds / ctrl_dt))
+
+
+def command_table(commands, what: str = "command {i}") -> np.ndarray:
+    """Commands of up to 16 components as a [len, 16] float32 table, the missing components zero. `what` names command i in the error."""
+    table = np.zeros((len(commands), L.NCMD), np.float32)
+    for i, c in enumerate(commands):
+        c = np.asarray(c, np.float32).reshape(-1)
+        if c.size > L.NCMD:
+            raise ValueError(f"{what.format(i=i)} has {c.size} components, a command has {L.NCMD}")
+        table[i, :c.size] = c
+    return table
+
+
+def command_label(cmd) -> str:
+    """A command as a table label: its non-zero components by name."""
+    parts = [f"{constants.COMMAND_NAMES[k]}={v:+.2f}" for k, v in enumerate(cmd) if v != 0]
+    return " ".join(parts) if parts else "(zero)"
+
+
+def table_cell(v) -> str:
+    """A figure as a 10-wide table cell, "-" over nothing (nan)."""
+    return f"  {'-':>10s}" if v != v else f"  {v:10.3f}"
+
+
+def case_of_env(n: int, ncases: int, device) -> torch.Tensor:
+    """The group tensor of a sweep's statistics call: env e runs case e % ncases."""
+    return (torch.arange(n, device=device) % ncases).to(torch.int32)
+
+
+def failures_per_s(done, envs, seconds: float) -> float:
+    """Falls (DONE < 0) of the envs `envs` in done [T, N], per second of the `seconds` they ran together."""
+    return float(sum((done[:, j] < 0).sum() for j in envs)) / seconds
 
 
 def sweep_terms(task, command=None, events=None) -> UserTerms:
@@ -43,3 +81,17 @@ def sweep_rollout(task, n: int, T: int, configure, terms: UserTerms, first_hooks
         yield ctx, tr
     finally:
         ctx.close()
+
+
+def held_command_rollout(task, n: int, T: int, command, seed_offset: int):
+    """sweep_rollout under the Command term `command` alone (tracking, gait and step sweeps): command_mode = 1, so that the kernel's own
+    reset writes the context's fixed command and the term's answer then replaces it, and validate()'s hook order - on row 0 the resets, the
+    command, then the observation terms that feed a network; behind every step the resets, those observation terms, then the command."""
+    terms = sweep_terms(task, command=command)
+    feeds = [terms.observe_rows] if any(task.extra_obs) else []
+
+    def configure(vcfg):
+        vcfg.command_mode = 1
+
+    return sweep_rollout(task, n, T, configure, terms, [terms.apply_resets, terms.apply_command] + feeds,
+                         [terms.apply_resets] + feeds + [terms.apply_command], seed_offset)

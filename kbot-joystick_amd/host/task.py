@@ -46,6 +46,15 @@ class _Validation(NamedTuple):
     traj: TrajBuffers
 
 
+class _Accounted(NamedTuple):
+    """One statistic the device keeps over the rollouts, switched on in the config."""
+    carrier: object             # the DeviceStats: per-env rows, the last rollout's vector, the totals
+    logged: object              # () -> dict: the task's own <name>_stats(), what scalars() logs
+    fresh: object               # (ctx, traj, num_envs) -> the vector of a trajectory whose episodes all start with it, on the device
+    as_scalars: object          # (vec, prefix) -> dict: such a vector as logger scalars
+    valid_prefix: str           # the prefix of validate()'s scalars
+
+
 class HumanoidWalkingTask:
     """Rollout + PPO update of the K-Bot joystick task on one GPU of a data-parallel job.
 
@@ -146,6 +155,15 @@ class HumanoidWalkingTask:
         self.trk_acc = self.tracking.acc if self.tracking is not None else None
         # gait statistics (config.gait_stats; host/gait.py): `gait.acc`, the per-env carry rows next to the env state; None means off
         self.gait = GaitStats(self.N, self.device) if config.gait_stats else None
+        # those that are on, in the order of the checkpoint members and of the scalar keys
+        dev, dt = self.device, config.ctrl_dt
+        self._accounted = [a for a in (
+            _Accounted(self.episodes, self.episode_stats, lambda ctx, traj, n: fresh_episode_stats(ctx, traj, n, dev),
+                       lambda vec, prefix: episode_stats_scalars(vec, dt, prefix, terms=True), "valid/episode/"),
+            _Accounted(self.tracking, self.tracking_stats, lambda ctx, traj, n: fresh_tracking_stats(ctx, traj, n, self.tracking.settle_steps, dev),
+                       tracking_scalars, "valid/track/"),
+            _Accounted(self.gait, self.gait_stats, lambda ctx, traj, n: fresh_gait_stats(ctx, traj, n, dev),
+                       lambda vec, prefix: gait_scalars(vec, dt, prefix), "valid/gait/")) if a.carrier is not None]
         self.opt_step = 0
         self.iteration = 0
         self._perm_gen = torch.Generator(device="cpu")
@@ -183,12 +201,8 @@ class HumanoidWalkingTask:
         if self.extra_rewards:
             from .traj_view import apply_extra_rewards
             self.extra_reward_means = apply_extra_rewards(self.extra_rewards, self._extra_carries, self.trajectory(), self.traj.reward)
-        if self.episodes is not None:             # behind the user rewards, so that they count; user terminations are in the DONE column already
-            self.episodes.after_rollout(self.ctx, self.traj.c)
-        if self.tracking is not None:             # the aux rows are all it reads: neither rewards nor reward_comps
-            self.tracking.after_rollout(self.ctx, self.traj.c)
-        if self.gait is not None:                 # the aux rows likewise
-            self.gait.after_rollout(self.ctx, self.traj.c)
+        for a in self._accounted:                 # behind the user rewards, so that the episodes count them (tracking and gait read the aux rows alone);
+            a.carrier.after_rollout(self.ctx, self.traj.c)      # user terminations are in the DONE column already
 
     def gait_stats_vectors(self):
         """(last, total): this rank's raw KBJ_GAIT vectors (float64 numpy, layout.GAIT / GFOOT) behind gait_stats() - the rows of the last
@@ -512,12 +526,8 @@ class HumanoidWalkingTask:
         if self.mirror:
             extras.update(actor_mirror_hc=self.carry.actor_mirror_hc.cpu().numpy(), critic_mirror_hc=self.carry.critic_mirror_hc.cpu().numpy(),
                           lpf_mirror=self.carry.lpf_mirror.cpu().numpy())
-        if self.episodes is not None:
-            extras.update(self.episodes.checkpoint_state())
-        if self.tracking is not None:
-            extras.update(self.tracking.checkpoint_state())
-        if self.gait is not None:
-            extras.update(self.gait.checkpoint_state())
+        for a in self._accounted:
+            extras.update(a.carrier.checkpoint_state())
         # carries of Python StatefulReward terms (extra_rewards): tensors (or tuples / lists of tensors) per term name
         for name, carry in self._extra_carries.items():
             leaves = list(carry) if isinstance(carry, (tuple, list)) else [carry]
@@ -576,12 +586,8 @@ class HumanoidWalkingTask:
         # a resumed run's row 0 already carries the user observation columns and the user command term's commands, its env rows the user Reset terms' state
         self.terms.started = self.iteration > 0
         x = z["extras"]
-        if self.episodes is not None:
-            self.episodes.load_checkpoint_state(x)
-        if self.tracking is not None:
-            self.tracking.load_checkpoint_state(x)
-        if self.gait is not None:
-            self.gait.load_checkpoint_state(x)
+        for a in self._accounted:
+            a.carrier.load_checkpoint_state(x)
         if "es" not in x:
             return            # a model-only checkpoint (e.g. written by the reference): parameters and optimizer only
         if x["es"].shape[0] != self.N:
@@ -676,12 +682,8 @@ class HumanoidWalkingTask:
                 hooks.append(lambda s: _capture(vctx, s.row))
             terms.run_steps(vctx, tr, carry, self.params, T, seed=seed, first_step=0, argmax=True, first_index=seed_offset, hooks=hooks)
             vctx.rewards(tr.aux, T, tr.reward, tr.comps)
-        if self.episodes is not None:   # the same kernel on the validation trajectory: every validation starts its episodes afresh
-            vstats = fresh_episode_stats(vctx, tr.c, num_envs, self.device)
-        if self.tracking is not None:   # a fresh carry likewise, on the fused and on the step-wise path
-            vtrack = fresh_tracking_stats(vctx, tr.c, num_envs, self.tracking.settle_steps, self.device)
-        if self.gait is not None:
-            vgait = fresh_gait_stats(vctx, tr.c, num_envs, self.device)
+        # the same kernels on the validation trajectory, on the fused and on the step-wise path: every validation starts its episodes and carries afresh
+        vecs = [a.fresh(vctx, tr.c, num_envs) for a in self._accounted]
         vctx.synchronize()
         done = tr.done
         fails, succ = float((done < 0).sum()), float((done > 0).sum())
@@ -689,12 +691,8 @@ class HumanoidWalkingTask:
                "valid/episode_length_s": float(T * num_envs / max(1.0, fails + succ + num_envs) * self.config.ctrl_dt), "valid/value_mean": float(tr.value.mean())}
         for name, v in zip(constants.REWARD_NAMES, tr.comps.mean(dim=(0, 1)).cpu().tolist()):
             out[f"valid/reward/{name}"] = v
-        if self.episodes is not None:
-            out.update(episode_stats_scalars(vstats.cpu().numpy(), self.config.ctrl_dt, "valid/episode/", terms=True))
-        if self.tracking is not None:
-            out.update(tracking_scalars(vtrack.cpu().numpy(), "valid/track/"))
-        if self.gait is not None:
-            out.update(gait_scalars(vgait.cpu().numpy(), self.config.ctrl_dt, "valid/gait/"))
+        for a, vec in zip(self._accounted, vecs):
+            out.update(a.as_scalars(vec.cpu().numpy(), a.valid_prefix))
         return out
 
     def close_validation(self):
@@ -747,12 +745,8 @@ class HumanoidWalkingTask:
         if self.traj.comps is not None:
             for name, v in self.reward_components().items():
                 out[f"reward/{name}"] = v
-        if self.ep_acc is not None:      # the result came back behind the kernel: the sync above is already past it
-            out.update(self.episode_stats())
-        if self.tracking is not None:
-            out.update(self.tracking_stats())
-        if self.gait is not None:
-            out.update(self.gait_stats())
+        for a in self._accounted:        # the results came back behind the kernels: the sync above is already past them
+            out.update(a.logged())
         return out
 
     def export_actor(self, path: str):

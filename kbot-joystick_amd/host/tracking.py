@@ -11,8 +11,8 @@ import torch
 
 from ..spec import constants, layout as L
 from . import dist as dist_util
-from .device_stats import DeviceStats
-from .sweep import sweep_rollout, sweep_terms
+from .device_stats import DeviceStats, fresh_stats
+from .sweep import command_label, command_table, failures_per_s, held_command_rollout
 
 K, A, R = L.TRK, L.TACC, L.TERR
 
@@ -56,10 +56,7 @@ def tracking_scalars(vec, prefix: str = "track/") -> dict:
 
 def fresh_tracking_stats(ctx, traj, num_envs: int, steps: int, device, err=None) -> torch.Tensor:
     """kbj_tracking_stats on a trajectory whose episodes all start with it (every validation rollout): its KBJ_TRK vector, on the device."""
-    acc = torch.zeros(num_envs, A["SIZE"], device=device)
-    stats = torch.zeros(K["SIZE"], dtype=torch.float64, device=device)
-    ctx.tracking_stats(traj, steps, acc, stats, err)
-    return stats
+    return fresh_stats(dist_util.TRACKING_STATS, A["SIZE"], lambda acc, stats: ctx.tracking_stats(traj, steps, acc, stats, err), num_envs, device)
 
 
 class TrackingStats(DeviceStats):
@@ -120,12 +117,7 @@ def tracking_sweep(task, commands=None, repeats: int = 2, seconds=None, settle_s
     (host/sweep.py sweep_rollout)."""
     cfg = task.config
     commands = default_command_grid(task.kcfg) if commands is None else commands
-    table = np.zeros((len(commands), L.NCMD), np.float32)
-    for i, c in enumerate(commands):
-        c = np.asarray(c, np.float32).reshape(-1)
-        if c.size > L.NCMD:
-            raise ValueError(f"command {i} has {c.size} components, a command has {L.NCMD}")
-        table[i, :c.size] = c
+    table = command_table(commands)
     if len(commands) == 0 or repeats < 1:
         raise ValueError("tracking_sweep needs at least one command and one repeat")
     ncmd, n = len(commands), len(commands) * repeats
@@ -133,14 +125,7 @@ def tracking_sweep(task, commands=None, repeats: int = 2, seconds=None, settle_s
     steps = settle_steps(cfg.tracking_settle_seconds if settle_seconds is None else settle_seconds, cfg.ctrl_dt)
     dev = task.device
     per_env = torch.from_numpy(np.tile(table, (repeats, 1))).to(dev)                      # env e follows command e % ncmd
-    terms = sweep_terms(task, command=ScriptedCommand(per_env))
-    feeds = [terms.observe_rows] if any(task.extra_obs) else []
-
-    def configure(vcfg):
-        vcfg.command_mode = 1
-
-    with sweep_rollout(task, n, T, configure, terms, [terms.apply_resets, terms.apply_command] + feeds,
-                       [terms.apply_resets] + feeds + [terms.apply_command], seed_offset) as (ctx, tr):       # validate()'s order
+    with held_command_rollout(task, n, T, ScriptedCommand(per_env), seed_offset) as (ctx, tr):
         err = torch.empty(T, n, R["SIZE"], device=dev)
         stats = fresh_tracking_stats(ctx, tr.c, n, steps, dev, err)
         ctx.synchronize()
@@ -154,7 +139,7 @@ def tracking_sweep(task, commands=None, repeats: int = 2, seconds=None, settle_s
             means = [e[settled[:, j], j, k].mean() for j in envs if settled[:, j].any()]
             entry[name] = float(np.mean(means)) if means else float("nan")
         entry["settled_rows"] = int(sum(settled[:, j].sum() for j in envs))
-        entry["failures_per_s"] = float(sum((done[:, j] < 0).sum() for j in envs)) / (repeats * T * cfg.ctrl_dt)
+        entry["failures_per_s"] = failures_per_s(done, envs, repeats * T * cfg.ctrl_dt)
         out.append(entry)
     return out, SweepRecord(tr.aux, err, vec)
 
@@ -162,11 +147,8 @@ def tracking_sweep(task, commands=None, repeats: int = 2, seconds=None, settle_s
 def format_tracking_table(entries) -> str:
     """tracking_sweep's result as a text table: one line per command (its non-zero components by name), the five settled-row mean errors,
     the settled row count and the failures per second."""
-    def label(cmd):
-        parts = [f"{constants.COMMAND_NAMES[k]}={v:+.2f}" for k, v in enumerate(cmd) if v != 0]
-        return " ".join(parts) if parts else "(zero)"
     names = constants.TRACKING_ERROR_NAMES
-    labels = [label(x["command"]) for x in entries]
+    labels = [command_label(x["command"]) for x in entries]
     w = max([len("command")] + [len(s) for s in labels])
     lines = [f"{'command':{w}s}  {'mode':10s}" + "".join(f"  {n:>12s}" for n in names) + f"  {'settled':>8s}  {'fail/s':>8s}"]
     for s, x in zip(labels, entries):

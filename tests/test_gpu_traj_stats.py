@@ -1,10 +1,12 @@
 """kbj_episode_stats and kbj_tracking_stats share one buffer of workgroup partials per context (kbj_traj_stats.hip stats_partials): calls of
-both on ONE context, the second needing a larger buffer than the first left, return the bytes each call returns alone on a fresh context."""
+both on ONE context, the second needing a larger buffer than the first left, return the bytes each call returns alone on a fresh context.
+kbj_push_recovery and kbj_step_response share the staging of their group reduce (kbj_window_scan.h), 256 envs a round: both at N = 257 and
+N = 513, a second round of one env and a third, against their restatements."""
 import numpy as np
 import pytest
 
 from kbot_joystick_amd.spec import layout as L
-from tests import tracking_ref as TR
+from tests import push_ref as PR, step_response_ref as SR, tracking_ref as TR
 from tests.test_gpu_episode_stats import UZ, _problem
 
 pytestmark = pytest.mark.gpu
@@ -77,3 +79,67 @@ def test_one_partial_buffer_serves_both_statistics_in_turn():
     for name, g3, w3 in zip(("tracking", "episode", "tracking again", "episode, wider"), got, want):
         for part, g, w in zip(("acc", "stats", "err"), g3, w3):
             assert g.tobytes() == w.tobytes(), f"{name}: {part} differs from the same call alone on a fresh context"
+
+
+@pytest.fixture(scope="module")
+def gctx():
+    ctx = _context()
+    yield ctx
+    ctx.close()
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+GROUPINGS = [(1, True), (3, True), (256, True), (1, False)]     # (G, with group_d); group_d = NULL: every env in group 0
+
+
+@pytest.mark.parametrize("N", [257, 513])
+def test_push_recovery_group_reduce_over_several_rounds(gctx, N):
+    """T = 24, N = 257 and 513: the record rows equal recovery_ref bit for bit; for G in (1, 3, 256), and for group_d = NULL with G = 1,
+    the statistics equal group_stats_ref of the device's records as uint64."""
+    import torch
+    from kbot_joystick_amd.host import binding as B
+    T, dev = 24, torch.device("cuda", 0)
+    prob = PR.problems(T, N)
+    want_rec, _ = PR.recovery_ref(prob.err, prob.done, prob.sched, prob.tol, prob.hold, prob.window)
+    aux, err, sched = torch.from_numpy(prob.aux).to(dev), torch.from_numpy(prob.err).to(dev), torch.from_numpy(prob.sched).to(dev)
+    crit = B.PushCriteria((B.C.c_float * L.NTERR)(*prob.tol), prob.hold, prob.window)
+    for G, grouped in GROUPINGS:
+        group = PR.groups(N, G) if grouped else None
+        rec = torch.full((N, L.PREC["SIZE"]), -7.0, device=dev)
+        stats = torch.full((G, L.PSTAT["SIZE"]), -7.0, dtype=torch.float64, device=dev)
+        gctx.push_recovery(B.Traj(T=T, N=N, aux_d=aux.data_ptr()), err, sched, crit, rec, None if group is None else torch.from_numpy(group).to(dev), G, stats)
+        gctx.synchronize()
+        rec, stats = rec.cpu().numpy(), stats.cpu().numpy()
+        assert np.array_equal(_bits(rec), _bits(want_rec)), np.argwhere(_bits(rec) != _bits(want_rec))[:5]
+        want = PR.group_stats_ref(rec, group, G)
+        assert np.array_equal(stats.view(np.uint64), want.view(np.uint64)), (G, grouped, np.argwhere(stats.view(np.uint64) != want.view(np.uint64))[:8])
+
+
+@pytest.mark.parametrize("hold", [1, 4])
+@pytest.mark.parametrize("N", [257, 513])
+def test_step_response_group_reduce_over_several_rounds(gctx, N, hold):
+    """T = 75, N = 257 and 513, hold 1 and 4, smoothing over 3 rows: the records equal scan_ref on the device's own signal bit for bit; for
+    G in (1, 3, 256), and for group_d = NULL with G = 1, the statistics equal group_stats_ref of the device's records as uint64."""
+    import torch
+    from kbot_joystick_amd.host import binding as B
+    T, dev = 75, torch.device("cuda", 0)
+    prob = SR.problem(hold, T, N)
+    c = SR.criteria(3, hold)
+    f3 = B.C.c_float * L.NSCH
+    crit = B.StepCriteria(f3(*c.min_step), f3(*c.band_abs), c.band_frac, c.rise_level, c.smooth, c.hold, c.window)
+    aux, sched = torch.from_numpy(prob.aux).to(dev), torch.from_numpy(prob.sched).to(dev)
+    for G, grouped in GROUPINGS:
+        group = SR.groups(N, G) if grouped else None
+        sig = torch.full((T, N, L.SSIG["SIZE"]), -7.0, device=dev)
+        rec = torch.full((N, L.SREC["SIZE"]), -7.0, device=dev)
+        stats = torch.full((G, L.SSTAT["SIZE"]), -7.0, dtype=torch.float64, device=dev)
+        gctx.step_response(B.Traj(T=T, N=N, aux_d=aux.data_ptr()), sched, crit, sig, rec, None if group is None else torch.from_numpy(group).to(dev), G, stats)
+        gctx.synchronize()
+        sig, rec, stats = sig.cpu().numpy(), rec.cpu().numpy(), stats.cpu().numpy()
+        want_rec, _ = SR.scan_ref(sig, prob.sched, c)                      # on the device's own signal
+        assert np.array_equal(_bits(rec), _bits(want_rec)), np.argwhere(_bits(rec) != _bits(want_rec))[:8]
+        want = SR.group_stats_ref(rec, group, G)
+        assert np.array_equal(stats.view(np.uint64), want.view(np.uint64)), (G, grouped, np.argwhere(stats.view(np.uint64) != want.view(np.uint64))[:8])

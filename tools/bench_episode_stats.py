@@ -10,14 +10,13 @@ measured for a streaming kernel of its own: adamw_kernel moves 63.05 MB per laun
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-STREAM_TBPS = 63.052352 / 15.7     # MB per us = TB/s
+from stats_bench import STREAM_TBPS, floor_us, timed_call      # noqa: E402 (tools/ is the script's directory)
 
 
 def main():
@@ -46,21 +45,10 @@ def main():
     traj.aux[:T, :, L.AUX["BASEZ"]] = torch.rand(T, N, device=dev, generator=g)
     acc = torch.zeros(N, L.EACC["SIZE"], device=dev)
     stats = torch.zeros(L.EPST["SIZE"], dtype=torch.float64, device=dev)
-    for _ in range(a.warmup):
-        ctx.episode_stats(traj.c, acc, stats)
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(a.reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); ctx.episode_stats(traj.c, acc, stats); e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
+    us, timed = timed_call(lambda: ctx.episode_stats(traj.c, acc, stats), a.reps, a.warmup, "kernel_")
     nbytes = T * N * 4 + (0 if a.no_comps else T * N * 12 * 4) + T * N * 64
-    us = statistics.median(ms) * 1e3
-    floor_us = nbytes / (STREAM_TBPS * 1e12) * 1e6
-    out = dict(envs=N, steps=T, comps=not a.no_comps, kernel_us_median=round(us, 2), kernel_us_min=round(min(ms) * 1e3, 2), kernel_us_max=round(max(ms) * 1e3, 2),
-               requested_mb=round(nbytes / 1e6, 2), stream_tb_per_s=round(STREAM_TBPS, 2), floor_us=round(floor_us, 2), ratio=round(us / floor_us, 2),
-               episodes_last_call=float(stats[L.EPST["EPISODES"]]))
+    out = dict(envs=N, steps=T, comps=not a.no_comps, **timed, requested_mb=round(nbytes / 1e6, 2), stream_tb_per_s=round(STREAM_TBPS, 2),
+               floor_us=round(floor_us(nbytes), 2), ratio=round(us / floor_us(nbytes), 2), episodes_last_call=float(stats[L.EPST["EPISODES"]]))
     ctx.close()
     if a.scalars:
         from kbot_joystick_amd.host.task import HumanoidWalkingTask, launch_config

@@ -19,21 +19,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-STREAM_TBPS = 63.052352 / 15.7     # MB per us = TB/s
-
-
-def _time(call, reps, warmup):
-    import torch
-    for _ in range(warmup):
-        call()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); call(); e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return ms
+from stats_bench import STREAM_TBPS, floor_us, timed_call      # noqa: E402 (tools/ is the script's directory)
 
 
 def _scalars_cost(envs, steps, reps):
@@ -90,16 +76,15 @@ def main():
     aux[:T, :, X["CTRL"]:X["CTRL"] + L.NU] *= 30.0
     traj = B.Traj(T=T, N=N, aux_d=aux.data_ptr())                                     # the aux rows are all either kernel reads
     nbytes = T * N * X["SIZE"] * 4
-    floor_us = nbytes / (STREAM_TBPS * 1e12) * 1e6
-    out = dict(envs=N, steps=T, stream_tb_per_s=round(STREAM_TBPS, 2), moved_mb=round(nbytes / 1e6, 2), floor_us=round(floor_us, 2))
+    floor = floor_us(nbytes)
+    out = dict(envs=N, steps=T, stream_tb_per_s=round(STREAM_TBPS, 2), moved_mb=round(nbytes / 1e6, 2), floor_us=round(floor, 2))
     gacc, gstats, genv = torch.zeros(N, L.GACC["SIZE"], device=dev), torch.zeros(L.GAIT["SIZE"], dtype=torch.float64, device=dev), torch.zeros(N, L.GENV["SIZE"], device=dev)
     tacc, tstats = torch.zeros(N, L.TACC["SIZE"], device=dev), torch.zeros(L.TRK["SIZE"], dtype=torch.float64, device=dev)
     calls = (("gait_stats_only", lambda: ctx.gait_stats(traj, gacc, gstats)), ("gait_with_env", lambda: ctx.gait_stats(traj, gacc, gstats, genv)),
              ("tracking_stats_only", lambda: ctx.tracking_stats(traj, 25, tacc, tstats)))
     for name, call in calls:
-        ms = _time(call, a.reps, a.warmup)
-        us = statistics.median(ms) * 1e3
-        out[name] = dict(kernel_us_median=round(us, 2), kernel_us_min=round(min(ms) * 1e3, 2), kernel_us_max=round(max(ms) * 1e3, 2), ratio_to_floor=round(us / floor_us, 2))
+        us, out[name] = timed_call(call, a.reps, a.warmup, "kernel_")
+        out[name]["ratio_to_floor"] = round(us / floor, 2)
     v = gstats.cpu().numpy()
     out["rows_per_mode"] = [float(v[L.gait_slot(m, "ROWS")]) for m in range(L.CMODE["COUNT"])]
     out["touchdowns"] = float(sum(v[L.gait_slot(m, "TOUCHDOWNS", f)] for m in range(L.CMODE["COUNT"]) for f in range(2)))

@@ -13,13 +13,12 @@ the aux rows, so the hardware moves more than the floor counts. Prints one JSON 
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-STREAM_TBPS = 63.052352 / 15.7     # MB per us = TB/s
+from stats_bench import STREAM_TBPS, floor_us, timed_call      # noqa: E402 (tools/ is the script's directory)
 
 
 def main():
@@ -50,19 +49,10 @@ def main():
         s = sched[:, 0].cpu().numpy()
         rows = int(sum(min(T, x + d + window) - (x - hold) for x in s))
         nbytes = rows * (R["SIZE"] * 4 + 4) + N * (8 + L.PREC["SIZE"] * 4)
-        res = dict(T=T, N=N, G=G, needed_mb=round(nbytes / 1e6, 3), floor_us=round(nbytes / (STREAM_TBPS * 1e12) * 1e6, 3))
+        res = dict(T=T, N=N, G=G, needed_mb=round(nbytes / 1e6, 3), floor_us=round(floor_us(nbytes), 3))
         for leg, st in (("rec_only", None), ("with_stats", stats)):
-            for _ in range(a.warmup):
-                ctx.push_recovery(traj, err, sched, crit, rec, group, G, st)
-            torch.cuda.synchronize()
-            ms = []
-            for _ in range(a.reps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(); ctx.push_recovery(traj, err, sched, crit, rec, group, G, st); e1.record()
-                e1.synchronize()
-                ms.append(e0.elapsed_time(e1))
-            us = statistics.median(ms) * 1e3
-            res[leg] = dict(us_median=round(us, 2), us_min=round(min(ms) * 1e3, 2), us_max=round(max(ms) * 1e3, 2), ratio_to_floor=round(us / res["floor_us"], 1))
+            us, res[leg] = timed_call(lambda: ctx.push_recovery(traj, err, sched, crit, rec, group, G, st), a.reps, a.warmup)
+            res[leg]["ratio_to_floor"] = round(us / res["floor_us"], 1)
         res["outcomes"] = [int(x) for x in stats.cpu().numpy()[:, :L.POUT["COUNT"]].sum(0)]
         out[name] = res
     ctx.close()

@@ -14,13 +14,12 @@ has measured for a streaming kernel of its own (tools/bench_tracking_stats.py: 4
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-STREAM_TBPS = 63.052352 / 15.7     # MB per us = TB/s
+from stats_bench import STREAM_TBPS, floor_us, timed_call      # noqa: E402 (tools/ is the script's directory)
 
 
 def main():
@@ -63,23 +62,14 @@ def main():
         traj = B.Traj(T=T, N=N, aux_d=aux.data_ptr())
         res = {}
         for leg, st in (("rec_only", None), ("with_stats", stats)):
-            for _ in range(a.warmup):
-                ctx.step_response(traj, sched, crit, sig, rec, group, G, st)
-            torch.cuda.synchronize()
-            ms = []
-            for _ in range(a.reps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(); ctx.step_response(traj, sched, crit, sig, rec, group, G, st); e1.record()
-                e1.synchronize()
-                ms.append(e0.elapsed_time(e1))
-            res[leg] = dict(us_median=round(statistics.median(ms) * 1e3, 2), us_min=round(min(ms) * 1e3, 2), us_max=round(max(ms) * 1e3, 2))
+            res[leg] = timed_call(lambda: ctx.step_response(traj, sched, crit, sig, rec, group, G, st), a.reps, a.warmup)[1]
         r = rec.cpu().numpy()
         oc = r[:, R["OUTCOME"]].astype(int)
         # the rows an env's lane re-reads: the hold rows in front, then up to its deciding row (VOID on a row in front: counted in full, an upper bound)
         scanned = [hold + (int(x[R["SETTLE_STEPS"]]) + hold if o == O["SETTLED"] else int(x[R["FALL_STEPS"]]) + 1 if o == O["FELL"] else min(window, T - s)) if o != O["NONE"] else 0
                    for x, o in zip(r, oc)]
         nbytes = T * N * (14 * 4 + L.SSIG["SIZE"] * 4) + sum(scanned) * L.SSIG["SIZE"] * 4 + N * (4 + R["SIZE"] * 4)
-        res.update(needed_mb=round(nbytes / 1e6, 3), floor_us=round(nbytes / (STREAM_TBPS * 1e12) * 1e6, 3), outcomes=[int((oc == i).sum()) for i in range(O["COUNT"])])
+        res.update(needed_mb=round(nbytes / 1e6, 3), floor_us=round(floor_us(nbytes), 3), outcomes=[int((oc == i).sum()) for i in range(O["COUNT"])])
         for leg in ("rec_only", "with_stats"):
             res[leg]["ratio_to_floor"] = round(res[leg]["us_median"] / res["floor_us"], 1)
         out[name] = res

@@ -9,13 +9,12 @@ rows [T][N][8] fp32 written (26 MB) - over the rate this project has measured fo
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-STREAM_TBPS = 63.052352 / 15.7     # MB per us = TB/s
+from stats_bench import STREAM_TBPS, floor_us, timed_call      # noqa: E402 (tools/ is the script's directory)
 
 
 def main():
@@ -51,19 +50,9 @@ def main():
     err = torch.zeros(T, N, L.TERR["SIZE"], device=dev)
     out = dict(envs=N, steps=T, settle_steps=a.settle, stream_tb_per_s=round(STREAM_TBPS, 2))
     for name, e in (("stats_only", None), ("with_err", err)):
-        for _ in range(a.warmup):
-            ctx.tracking_stats(traj, a.settle, acc, stats, e)
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(a.reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(); ctx.tracking_stats(traj, a.settle, acc, stats, e); e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
+        us, out[name] = timed_call(lambda: ctx.tracking_stats(traj, a.settle, acc, stats, e), a.reps, a.warmup, "kernel_")
         nbytes = T * N * X["SIZE"] * 4 + (0 if e is None else T * N * L.TERR["SIZE"] * 4)
-        us, floor_us = statistics.median(ms) * 1e3, nbytes / (STREAM_TBPS * 1e12) * 1e6
-        out[name] = dict(kernel_us_median=round(us, 2), kernel_us_min=round(min(ms) * 1e3, 2), kernel_us_max=round(max(ms) * 1e3, 2), moved_mb=round(nbytes / 1e6, 2),
-                         floor_us=round(floor_us, 2), ratio=round(us / floor_us, 2))
+        out[name].update(moved_mb=round(nbytes / 1e6, 2), floor_us=round(floor_us(nbytes), 2), ratio=round(us / floor_us(nbytes), 2))
     v = stats.cpu().numpy()
     S = L.TRK["MODE_STRIDE"]
     out["rows_per_mode"] = [float(v[m * S + L.TRK["ROWS"]]) for m in range(L.CMODE["COUNT"])]
