@@ -334,6 +334,61 @@ int kbj_tracking_stats(kbj_ctx* ctx, const kbj_traj* traj, int settle_steps, flo
  * traj->aux_d that is not 16-byte aligned. */
 int kbj_gait_stats(kbj_ctx* ctx, const kbj_traj* traj, float* acc_d, double* stats_d, float* env_d);
 
+/* ---- actuator statistics ----------------------------------------------------------------------- */
+/* replaces: asking what a policy demands of the motors before it goes onto the robot - torque against the limit, joint speed, mechanical
+ * power, joint stops and the action rate - per actuator and split by the command mode of the row (KBJ_CMODE_*, the rule of
+ * kbj_tracking_stats). The reference rewards this with its "sim2real" group, BaseAccelerationReward and TorqueReward (train.py:1253-1255),
+ * and its metadata.json carries a soft_torque_limit per joint; nobody reads those per joint, in N m, rad/s or W.
+ * Levels. kbj_actuator_levels holds the thresholds in physical units, per actuator in the order of spec/constants.JOINT_NAMES. They are
+ * SETTINGS of the caller, not figures of the reference. tau_level and vel_level must be positive (vel_level may be +inf: it then counts
+ * nothing), pos_lo <= pos_hi, nothing may be NaN.
+ * Row quantities. For row (t, n) and actuator u = 0 .. 19, all in fp32 unless stated:
+ *   tau   = aux[t][n][KBJ_AUX_CTRL + u]: the torque of the step's LAST substep, after the env's own clip at its (possibly randomised) limit,
+ *   omega = qstate[t][n][KBJ_QSTATE_QVEL + 6 + u], q = qstate[t][n][KBJ_QSTATE_QPOS + 7 + u]: the joint AFTER the step; on a terminal row
+ *           both hold the state before the reset,
+ *   a     = action[t][n][u],
+ *   P     = tau * omega, ONE fp32 product rounded to nearest. P is sampled at the control rate, from the last substep's torque and the
+ *           end-of-step velocity: an ESTIMATE of the mechanical power, not an integral over the substeps,
+ *   mode  = the row's KBJ_CMODE_* (from aux[t][n][KBJ_AUX_CMD ..]),
+ *   speed = sqrt((double)vx * vx + (double)vy * vy) with vx, vy = aux[t][n][KBJ_AUX_QVEL + 0, 1], in double.
+ *   at_tau[u] = fabsf(tau) >= tau_level[u]; over[u] = fabsf(omega) >= vel_level[u]; at_stop[u] = q <= pos_lo[u] || q >= pos_hi[u]
+ *   (exact fp32 comparisons: a value ON the level counts, a NaN never does).
+ * Carry. acc_d [N][KBJ_AACC_SIZE] fp32 is device memory of the caller (zero it once; save it with the env state), updated in place: PREV[u],
+ * the previous row's action, and RUNNING; the three spare floats are left as they are.
+ * Scan. For every env n independently, for t ascending, with m = mode:
+ *   1. ROWS[m] += 1; SPEED_SUM[m] += speed; ANY_TAU_ROWS[m] += 1 if any at_tau[u]; ANY_STOP_ROWS[m] += 1 if any at_stop[u].
+ *   2. Per actuator u: TAU_SQ[m][u] += (double)tau * (double)tau; TAU_MAX = fmaxf(.., fabsf(tau)); TAU_ROWS += at_tau[u];
+ *      VEL_SQ += (double)omega * (double)omega; VEL_MAX = fmaxf(.., fabsf(omega)); VEL_ROWS += over[u];
+ *      POW_ABS += (double)fabsf(P); POW_POS += (double)fmaxf(P, 0); POW_MAX = fmaxf(.., fabsf(P)); STOP_ROWS += at_stop[u].
+ *   3. If RUNNING == 0 the row starts an episode: EPISODES += 1, and it has no action rate. Otherwise PAIRS[m] += 1 and per actuator
+ *      d = a - PREV[u] (fp32): DACT_SQ[m][u] += (double)d * (double)d; DACT_MAX = fmaxf(.., fabsf(d)).
+ *   4. PREV[u] = a; RUNNING = (aux[t][n][KBJ_AUX_DONE] == 0).
+ * So the first row of an episode contributes no pair, within a call (DONE of the row before) and across calls (the carry's RUNNING).
+ * stats_d [KBJ_ACT_SIZE] doubles is OVERWRITTEN (kbj_model.h KBJ_ACT_*, KBJ_AJNT_*): KBJ_CMODE_COUNT mode blocks of KBJ_ACT_MODE_STRIDE slots
+ * (five head slots, then actuator u's KBJ_AJNT_SIZE slots at KBJ_ACT_JOINT + KBJ_AJNT_SIZE * u), then KBJ_ACT_EPISODES, every other slot 0.
+ * Every maximum is of a non-negative quantity: 0 over nothing. The reduction runs in double, in a fixed order (one (env, actuator)'s rows
+ * ascending - each run of consecutive rows that share a mode is summed by itself and the runs are added in row order -, envs in env order,
+ * workgroups in block order), without atomics: the same inputs give the same bytes on every call, with or without env_d.
+ * env_d: NULL, or [N][KBJ_AENV_SIZE] fp32, overwritten: env n's totals of THIS call over all modes (kbj_model.h KBJ_AENV_*). TAU_SQ,
+ * POW_ABS, POW_POS and DACT_SQ are accumulated per actuator in double in row order, the 20 actuators are then added in ascending u from
+ * 0.0, and the result is rounded to fp32 once; SPEED_SUM likewise over the rows. PEAK_FRAC = the largest fabsf(tau) / tau_level[u] (one fp32
+ * division; fmaxf from 0) over rows and actuators, PEAK_JOINT the lowest u that reaches it (-1 with no rows); the spare float is 0. A
+ * float64 host loop in the same order reproduces every word (tests/actuator_ref.py).
+ * Reads rows 0 .. T-1 of traj->aux_d, traj->qstate_d (the state record: kbj_env_record_state, HumanoidWalkingTaskConfig.record_state) and
+ * traj->action_d and writes no trajectory row; asynchronous on the context's stream; allocates nothing per call (the workgroup partials
+ * live in the context, grown on first use). Fails with a message, before anything is launched or written, on a NULL ctx, traj, levels,
+ * acc_d or stats_d ("null argument"), on a trajectory without aux_d, action_d or qstate_d (named as such, pointing to record_state) or
+ * positive T, N, on an acc_d, env_d, aux_d, action_d or qstate_d that is not 16-byte aligned, on a level that is NaN or a tau_level /
+ * vel_level that is not positive, and on pos_lo > pos_hi. levels is read before the call returns. */
+typedef struct kbj_actuator_levels {   /* thresholds in physical units, per actuator, order of spec/constants.JOINT_NAMES */
+  float tau_level[KBJ_NU];  /* N m:   a row counts as "at the torque level" where |tau_u| >= tau_level[u]  (> 0) */
+  float vel_level[KBJ_NU];  /* rad/s: "over speed" where |omega_u| >= vel_level[u]                          (> 0, +inf allowed: counts nothing) */
+  float pos_lo[KBJ_NU];     /* rad:   "at a joint stop" where q_u <= pos_lo[u] or q_u >= pos_hi[u]          (pos_lo <= pos_hi) */
+  float pos_hi[KBJ_NU];
+} kbj_actuator_levels;
+int kbj_actuator_stats(kbj_ctx* ctx, const kbj_traj* traj, const kbj_actuator_levels* levels,
+                       float* acc_d /* [N][KBJ_AACC_SIZE] */, double* stats_d /* [KBJ_ACT_SIZE] */, float* env_d /* [N][KBJ_AENV_SIZE] or NULL */);
+
 /* ---- push recovery ---------------------------------------------------------------------------- */
 /* replaces: shoving the robot and watching whether it stays up (what a locomotion policy is judged by before it goes on the robot), as
  * numbers: for one scheduled push per env, what became of it. Reads err_d [T][N][KBJ_TERR_SIZE], the per-row output of kbj_tracking_stats on

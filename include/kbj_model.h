@@ -423,6 +423,59 @@ enum {
   KBJ_GENV_SIZE        = 24
 };
 
+/* ---- actuator statistics (kbj_actuator_stats) ----
+ * Per-env carry row ("AACC" record, fp32, owned by the caller on the device like the GACC rows; zeroed once). */
+enum {
+  KBJ_AACC_PREV    = 0,    /* [20] the action of the env's previous row */
+  KBJ_AACC_RUNNING = 20,   /* 1 when a previous row exists and did not end its episode */
+  KBJ_AACC_SIZE    = 24    /* 96-byte rows; the three spare floats at the end are left as they are */
+};
+/* One call's result ("ACT" record, doubles): KBJ_CMODE_COUNT mode blocks of KBJ_ACT_MODE_STRIDE slots (mode m's slot s at
+ * m * KBJ_ACT_MODE_STRIDE + s): five head slots, then one block of KBJ_AJNT_SIZE joint slots per actuator u at KBJ_ACT_JOINT +
+ * KBJ_AJNT_SIZE * u; then the episode counter. Every other slot is 0. */
+enum {
+  KBJ_ACT_ROWS          = 0,     /* rows of the mode */
+  KBJ_ACT_PAIRS         = 1,     /* of them with a previous row in the same episode (the rows an action rate exists on) */
+  KBJ_ACT_SPEED_SUM     = 2,     /* sum over the rows of the horizontal base speed (m/s, taken in double) */
+  KBJ_ACT_ANY_TAU_ROWS  = 3,     /* rows with at least one actuator at its torque level */
+  KBJ_ACT_ANY_STOP_ROWS = 4,     /* rows with at least one joint at a stop */
+  KBJ_ACT_JOINT         = 8,     /* the first joint block */
+  KBJ_ACT_MODE_STRIDE   = 256,
+  KBJ_ACT_EPISODES      = 1536,  /* rows that start an episode (no previous row, or the previous row ended its episode) */
+  KBJ_ACT_SIZE          = 1792
+};
+/* Slots of a joint block ("AJNT"). */
+enum {
+  KBJ_AJNT_TAU_SQ    = 0,    /* sum of tau^2 (N m)^2, taken in double */
+  KBJ_AJNT_TAU_MAX   = 1,    /* largest |tau| */
+  KBJ_AJNT_TAU_ROWS  = 2,    /* rows with |tau| >= tau_level[u] */
+  KBJ_AJNT_VEL_SQ    = 3,    /* sum of omega^2 (rad/s)^2, taken in double */
+  KBJ_AJNT_VEL_MAX   = 4,    /* largest |omega| */
+  KBJ_AJNT_VEL_ROWS  = 5,    /* rows with |omega| >= vel_level[u] */
+  KBJ_AJNT_POW_ABS   = 6,    /* sum of |P| (W), P = tau * omega in fp32 */
+  KBJ_AJNT_POW_POS   = 7,    /* sum of max(P, 0): the work the motor puts in */
+  KBJ_AJNT_POW_MAX   = 8,    /* largest |P| */
+  KBJ_AJNT_STOP_ROWS = 9,    /* rows with q <= pos_lo[u] or q >= pos_hi[u] */
+  KBJ_AJNT_DACT_SQ   = 10,   /* over the mode's PAIRS rows: sum of (a - a_prev)^2 (rad^2), taken in double */
+  KBJ_AJNT_DACT_MAX  = 11,   /* largest |a - a_prev| */
+  KBJ_AJNT_SIZE      = 12
+};
+/* One env's totals of one call over all modes ("AENV" record, fp32). */
+enum {
+  KBJ_AENV_ROWS          = 0,
+  KBJ_AENV_PAIRS         = 1,
+  KBJ_AENV_SPEED_SUM     = 2,
+  KBJ_AENV_TAU_SQ        = 3,    /* the four sums below are over the env's rows and its 20 actuators */
+  KBJ_AENV_POW_ABS       = 4,
+  KBJ_AENV_POW_POS       = 5,
+  KBJ_AENV_DACT_SQ       = 6,
+  KBJ_AENV_ANY_TAU_ROWS  = 7,
+  KBJ_AENV_ANY_STOP_ROWS = 8,
+  KBJ_AENV_PEAK_FRAC     = 9,    /* largest |tau_u| / tau_level[u] over the env's rows and actuators */
+  KBJ_AENV_PEAK_JOINT    = 10,   /* the u it was reached on (the lowest on a tie), -1 with no rows */
+  KBJ_AENV_SIZE          = 12    /* one spare float, written as 0 */
+};
+
 /* ---- scripted pushes and push recovery (kbj_env_set_push, kbj_push_recovery) ----
  * The KBJ_ES_PUSH_NXT value that keeps the built-in ForcePushEvent from drawing: 2^24, an exactly countable fp32 (x - 1 is exact all the way
  * down), about 93 h of control steps at 50 Hz. */

@@ -223,7 +223,7 @@ int kbj_profile_end(kbj_ctx* ctx, float* env_step_ms, int* env_step_launches, fl
       "kbj::gemm_x3_kernel<2, false, false, false>", "kbj::gemm_x3_kernel<2, false, true, false>", "kbj::gemm_x3_kernel<2, true, false, false>",
       "kbj::gemm_x3_kernel<2, true, true, false>", "kbj::gemm_x3_kernel<2, true, true, true>", "kbj::gemm_x3_kernel<1, true, true, false>",
       "kbj::gemm_x3_kernel<1, true, true, true>", "kbj::lstm_seq_bwd16_kernel", "kbj::gemm_f32_kernel<1, 1, true, true, 2, 4>", "kbj::gemm_f32_kernel<1, 1, true, false, 2, 4>",
-      "kbj::tracking_stats_kernel", "kbj::gait_stats_kernel"};
+      "kbj::tracking_stats_kernel", "kbj::gait_stats_kernel", "kbj::actuator_stats_kernel", "kbj::ordered_reduce_wide_kernel<kbj::ActSlots>"};
   for (int k = 0; k < KBJ_KIND_COUNT; ++k) {
     kbj_kernel_stat& st = ctx->kstats[k];
     const int uw = 2;   // wavefront pairs per recurrence workgroup (kbj_nn.hip SEQ_UW), as rocprofv3 prints the template argument

@@ -15,7 +15,8 @@ enum { KBJ_KIND_GEMM = 0 /* +4 small tile, +2 A k-contiguous, +1 B k-contiguous 
        KBJ_KIND_SEQ_BWD16 = 22 /* lstm_seq_bwd16_kernel<H> */, KBJ_KIND_GEMM_64x128 = 23 /* gemm_f32_kernel<1, 1, true, true, 2, 4>: the critic's input projection; 24 = <1, 1, true, false, 2, 4>: the input gradients */,
        KBJ_KIND_TRACKING_STATS = 25 /* tracking_stats_kernel (kbj_tracking_stats) */,
        KBJ_KIND_GAIT_STATS = 26 /* gait_stats_kernel (kbj_gait_stats) */,
-       KBJ_KIND_COUNT = 27 };
+       KBJ_KIND_ACTUATOR_STATS = 27 /* actuator_stats_kernel (kbj_actuator_stats) */, KBJ_KIND_ACTUATOR_REDUCE = 28 /* its ordered_reduce_wide_kernel<ActSlots> */,
+       KBJ_KIND_COUNT = 29 };
 inline int kbj_kind_gemm_x3(int tm, bool a_kc, bool b_kc, bool gen) {
   if (tm == 2) return gen ? KBJ_KIND_GEMM_X3_GEN : KBJ_KIND_GEMM_X3 + (a_kc ? 2 : 0) + (b_kc ? 1 : 0);
   return gen ? KBJ_KIND_GEMM_X3_SMALL_GEN : KBJ_KIND_GEMM_X3_SMALL;
@@ -88,7 +89,7 @@ struct kbj_ctx {
   uint32_t seed = 0;
   int rollout_argmax = 0;       // kbj_set_rollout_argmax: kbj_rollout acts with the distribution's mode (validation rollouts, train.py:1564)
   float* qstate_next = nullptr; // kbj_env_record_state: where the next kbj_env_step writes its state record (one-shot)
-  double* stats_part_d = nullptr;   // kbj_episode_stats / kbj_tracking_stats: the workgroup partials of the call's scan, stats_part_doubles doubles,
+  double* stats_part_d = nullptr;   // kbj_episode_stats / kbj_tracking_stats / kbj_gait_stats / kbj_actuator_stats: the workgroup partials of the call's scan, stats_part_doubles doubles,
   size_t stats_part_doubles = 0;    // grown by the first call that needs more (kbj_traj_stats.hip stats_partials)
   // NN workspace (kbj_nn.hip)
   void* nn_ws = nullptr;

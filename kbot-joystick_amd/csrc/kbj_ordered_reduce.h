@@ -2,9 +2,10 @@
 // kbj_gait_stats.h): the partials of a scan, [nblocks][SIZE] doubles, combined slot by slot in block order by ONE workgroup. Doubles, a fixed
 // order, no atomics: the same partials give the same bytes on every call. Included by kbj_traj_stats.hip. (The event statistics,
 // kbj_push_recovery.h and kbj_step_response.h, leave a record per env and have a second stage of their own: kbj_window_scan.h.)
+// A vector wider than one workgroup (kbj_actuator_stats.h) takes ordered_reduce_wide_kernel, one workgroup per 256 slots.
 //
 // `Slots` says what a statistics vector is made of:
-//   static constexpr int SIZE;                              slots per vector, a divisor of ORDERED_REDUCE_THREADS
+//   static constexpr int SIZE;                              slots per vector, a divisor of ORDERED_REDUCE_THREADS (wide: a multiple)
 //   static __device__ double identity(int j);               the value of slot j over nothing
 //   static __device__ double combine(int j, double a, double b);   slot j of the union, `a` being the earlier part
 // The scans use the same combine for their lanes, in lane order.
@@ -41,6 +42,28 @@ __global__ __launch_bounds__(ORDERED_REDUCE_THREADS) void ordered_reduce_kernel(
     for (int q = 1; q < R; ++q) v = Slots::combine(j, v, s[q][j]);
     stats[j] = v;
   }
+}
+
+// the same second stage for a vector wider than one workgroup (kbj_actuator_stats.h): SIZE a multiple of ORDERED_REDUCE_THREADS, a grid of
+// SIZE / ORDERED_REDUCE_THREADS workgroups, thread j of workgroup g folds slot 256 g + j over all blocks in block order -> stats [SIZE]
+template <class Slots>
+__global__ __launch_bounds__(ORDERED_REDUCE_THREADS) void ordered_reduce_wide_kernel(const double* __restrict__ part, int nblocks, double* __restrict__ stats) {
+  constexpr int SIZE = Slots::SIZE;
+  static_assert(SIZE % ORDERED_REDUCE_THREADS == 0 && SIZE >= ORDERED_REDUCE_THREADS, "every thread of the grid owns one slot");
+  const int j = blockIdx.x * ORDERED_REDUCE_THREADS + threadIdx.x;
+  if (j >= SIZE) return;
+  constexpr int AHEAD = 8;      // loads in flight per thread: the fold is a chain of dependent adds, the loads are not
+  double v = Slots::identity(j);
+  int b = 0;
+  for (; b + AHEAD <= nblocks; b += AHEAD) {
+    double x[AHEAD];
+#pragma unroll
+    for (int k = 0; k < AHEAD; ++k) x[k] = part[(size_t)(b + k) * SIZE + j];
+#pragma unroll
+    for (int k = 0; k < AHEAD; ++k) v = Slots::combine(j, v, x[k]);
+  }
+  for (; b < nblocks; ++b) v = Slots::combine(j, v, part[(size_t)b * SIZE + j]);
+  stats[j] = v;
 }
 
 }  // namespace

@@ -1,6 +1,6 @@
 // kbj_traj_stats.hip — HIP kernels + C-ABI entry points of everything that reads a finished trajectory: kbj_rewards (rewards_kernel below),
 // kbj_episode_stats (kbj_episode_stats.h), kbj_tracking_stats (kbj_tracking_stats.h), kbj_gait_stats (kbj_gait_stats.h), kbj_push_recovery
-// (kbj_push_recovery.h) and kbj_step_response (kbj_step_response.h). None of it
+// (kbj_push_recovery.h), kbj_step_response (kbj_step_response.h) and kbj_actuator_stats (kbj_actuator_stats.h). None of it
 // is on the hot path, and none of it shares a translation unit with the env kernels (kbj_env.hip): an edit here recompiles no step kernel.
 #include <hip/hip_runtime.h>
 #include <initializer_list>
@@ -9,6 +9,7 @@
 #include "kbj_episode_stats.h"
 #include "kbj_tracking_stats.h"
 #include "kbj_gait_stats.h"
+#include "kbj_actuator_stats.h"
 #include "kbj_ctx.h"
 #include "kbj_push_recovery.h"
 #include "kbj_step_response.h"
@@ -209,6 +210,32 @@ int kbj_gait_stats(kbj_ctx* ctx, const kbj_traj* tr, float* acc_d, double* stats
     KbjKernelTimer timer(ctx->stream, KBJ_KIND_GAIT_STATS, 0.0);
     hipLaunchKernelGGL(gait_stats_kernel, dim3(blocks), dim3(GAIT_THREADS), 0, ctx->stream, tr->aux_d, tr->T, tr->N, acc_d, part_d, env_d);
   });
+}
+
+int kbj_actuator_stats(kbj_ctx* ctx, const kbj_traj* tr, const kbj_actuator_levels* lv, float* acc_d, double* stats_d, float* env_d) {
+  if (!ctx || !tr || !lv || !acc_d || !stats_d) return kbj_fail(ctx, "kbj_actuator_stats: null argument");
+  if (!tr->qstate_d) return kbj_fail(ctx, "kbj_actuator_stats: the trajectory has no qstate_d: joint positions and speeds come from the state record (kbj_env_record_state; HumanoidWalkingTaskConfig.record_state)");
+  if (!tr->aux_d || !tr->action_d || tr->T <= 0 || tr->N <= 0) return kbj_fail(ctx, "kbj_actuator_stats: the trajectory needs aux_d, action_d, qstate_d and positive T, N");
+  if (check_aligned16(ctx, "kbj_actuator_stats", "acc_d, env_d, aux_d, action_d and qstate_d", {acc_d, env_d, tr->aux_d, tr->action_d, tr->qstate_d}) != 0) return -1;
+  for (int u = 0; u < KBJ_NU; ++u) {
+    if (!(lv->tau_level[u] > 0.0f)) return kbj_fail(ctx, "kbj_actuator_stats: a tau_level is not positive or NaN");
+    if (!(lv->vel_level[u] > 0.0f)) return kbj_fail(ctx, "kbj_actuator_stats: a vel_level is not positive or NaN (+inf counts nothing)");
+    if (!(lv->pos_lo[u] <= lv->pos_hi[u])) return kbj_fail(ctx, "kbj_actuator_stats: pos_lo > pos_hi, or one of them is NaN");
+  }
+  KBJ_HIP(ctx, hipSetDevice(ctx->device));      // no kbj_nn_drop_prefetch: no trajectory row is written
+  const int blocks = (tr->N + ACT_ENVS - 1) / ACT_ENVS;
+  if (stats_partials(ctx, (size_t)blocks * ActSlots::SIZE) != 0) return -1;
+  {
+    KbjKernelTimer timer(ctx->stream, KBJ_KIND_ACTUATOR_STATS, 0.0);
+    hipLaunchKernelGGL(actuator_stats_kernel, dim3(blocks), dim3(ACT_THREADS), 0, ctx->stream, tr->aux_d, tr->qstate_d, tr->action_d, tr->T, tr->N, *lv, acc_d, ctx->stats_part_d, env_d);
+  }
+  KBJ_CHECK_LAUNCH(ctx, "actuator_stats_kernel");
+  {
+    KbjKernelTimer timer(ctx->stream, KBJ_KIND_ACTUATOR_REDUCE, 0.0);
+    hipLaunchKernelGGL(ordered_reduce_wide_kernel<ActSlots>, dim3(ActSlots::SIZE / ORDERED_REDUCE_THREADS), dim3(ORDERED_REDUCE_THREADS), 0, ctx->stream, ctx->stats_part_d, blocks, stats_d);
+  }
+  KBJ_CHECK_LAUNCH(ctx, "ordered_reduce_wide_kernel<ActSlots>");
+  return 0;
 }
 
 int kbj_push_recovery(kbj_ctx* ctx, const kbj_traj* tr, const float* err_d, const int32_t* sched_d, const kbj_push_criteria* crit, float* rec_d,

@@ -58,6 +58,12 @@ class StepCriteria(C.Structure):
                 ("smooth_steps", C.c_int32), ("hold_steps", C.c_int32), ("window_steps", C.c_int32)]
 
 
+class ActuatorLevels(C.Structure):
+    """kbj_actuator_levels: per actuator (spec/constants.JOINT_NAMES order) the torque level (N m), the speed level (rad/s, +inf counts
+    nothing) and the joint-stop band (rad). Settings of the caller (host/actuator.py actuator_levels), not figures of the reference."""
+    _fields_ = [("tau_level", C.c_float * L.NU), ("vel_level", C.c_float * L.NU), ("pos_lo", C.c_float * L.NU), ("pos_hi", C.c_float * L.NU)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("launches", C.c_int32), ("total_ms", C.c_float), ("flops", C.c_double)]
 
@@ -112,6 +118,7 @@ SIGNATURES = {
     "kbj_episode_stats": (_i, [_vp, C.POINTER(Traj), _vp, _vp]),
     "kbj_tracking_stats": (_i, [_vp, C.POINTER(Traj), _i, _vp, _vp, _vp]),
     "kbj_gait_stats": (_i, [_vp, C.POINTER(Traj), _vp, _vp, _vp]),
+    "kbj_actuator_stats": (_i, [_vp, C.POINTER(Traj), C.POINTER(ActuatorLevels), _vp, _vp, _vp]),
     "kbj_push_recovery": (_i, [_vp, C.POINTER(Traj), _vp, _vp, C.POINTER(PushCriteria), _vp, _vp, _i, _vp]),
     "kbj_step_response": (_i, [_vp, C.POINTER(Traj), _vp, C.POINTER(StepCriteria), _vp, _vp, _vp, _i, _vp]),
     "kbj_ppo_grad": (_i, [_vp, _vp, C.POINTER(Traj), _vp, _i, _vp, _vp, _vp, _vp]),
@@ -360,6 +367,12 @@ class Context:
         """kbj_gait_stats: acc [N, GACC SIZE] float32 (updated in place), stats [GAIT SIZE] float64 (overwritten), env None or
         [N, GENV SIZE] float32 (every env's totals of this call, overwritten), all on the device."""
         self.call("kbj_gait_stats", C.byref(traj), _ptr(acc), _ptr(stats), _ptr(env))
+
+    def actuator_stats(self, traj: Traj, levels: ActuatorLevels, acc, stats, env=None):
+        """kbj_actuator_stats: levels an ActuatorLevels (host), acc [N, AACC SIZE] float32 (updated in place), stats [ACT SIZE] float64
+        (overwritten), env None or [N, AENV SIZE] float32 (every env's totals of this call, overwritten), all on the device. The
+        trajectory needs its state record (qstate_d)."""
+        self.call("kbj_actuator_stats", C.byref(traj) if traj is not None else None, C.byref(levels) if levels is not None else None, _ptr(acc), _ptr(stats), _ptr(env))
 
     def push_recovery(self, traj: Traj, err, sched, criteria: PushCriteria, rec, group=None, G: int = 1, stats=None):
         """kbj_push_recovery: err [T, N, TERR SIZE] float32 (kbj_tracking_stats' per-row output), sched [N, 2] int32 (start row, pushed steps;

@@ -97,6 +97,18 @@ class HumanoidWalkingTaskConfig:
     # default; KBJ_GAIT_STATS in the environment overrides it, for A/B runs with tools/ab_bench.py): nothing is allocated, launched or logged.
     # task.gait_sweep() - the gait table per command - works with the switch off too.
     gait_stats: bool = _env_flag("KBJ_GAIT_STATS")
+    # actuator statistics on the device (kbj_actuator_stats; host/actuator.py): what the policy asks of the motors - per actuator torque against its
+    # level, joint speed, mechanical power, joint stops, action rate - split by the six command modes; merged into scalars() / validate() as
+    # act/<mode>/... (whole-body figures; the per-joint table comes from task.actuator_stats(per_joint=True)), carried per env across rollouts and
+    # through checkpoints. Needs record_state (joint positions and speeds come from the state record). Off (the default; KBJ_ACTUATOR_STATS in the
+    # environment overrides it): nothing is allocated, launched or logged. task.actuator_sweep() works with the switch off too.
+    # The three levels are SETTINGS of this build, not figures of the reference (host/actuator.py actuator_levels): the share of
+    # kbj_model.tau_limit that counts as "at the torque level", a speed limit in rad/s (None: none - the reference gives none; one float or 20)
+    # and how far inside its range, in degrees, a joint counts as "at its stop".
+    actuator_stats: bool = _env_flag("KBJ_ACTUATOR_STATS")
+    actuator_torque_level: float = 0.9
+    actuator_speed_limit: Optional[object] = None
+    actuator_stop_margin_deg: float = 2.0
     # GAE boundary conventions (include/kbj.h kbj_gae). Both off by default - this build's choice: every termination ends the
     # return, V_T := V_{T-1} - and selectable, because SURVEY B.2 believes ksim bootstraps through the episode-length "success" termination:
     # bootstrap_on_truncation: at DONE = +1 (time-out, or a user term's +1) delta = r + gamma V(s_t) - V(s_t) instead of r - V(s_t);
@@ -182,6 +194,9 @@ class HumanoidWalkingTaskConfig:
             if self.record_state:
                 raise ValueError("bootstrap_terminal_value cannot be combined with record_state: no env step kernel writes both the state record and "
                                  "the terminal critic rows")
+        if self.actuator_stats and not self.record_state:
+            raise ValueError("actuator_stats needs record_state=True: joint positions and speeds come from the per-step state record "
+                             "(kbj_traj.qstate_d: 320 bytes per env-step, 262 MB at 8192 envs x 100 steps)")
         if not (0 <= self.extra_actor_obs <= L.MAX_EXTRA_OBS and 0 <= self.extra_critic_obs <= L.MAX_EXTRA_OBS):
             raise ValueError(f"extra_actor_obs / extra_critic_obs must be in 0..{L.MAX_EXTRA_OBS}")
         if self.solver not in ("newton", "cg"):

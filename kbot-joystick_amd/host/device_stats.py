@@ -1,5 +1,5 @@
-"""The host carrier of a statistic the device accumulates over rollouts (kbj_episode_stats, kbj_tracking_stats, kbj_gait_stats;
-host/episode.py, host/tracking.py and host/gait.py construct one each): the per-env rows that live next to the env state, the hand-over of
+"""The host carrier of a statistic the device accumulates over rollouts (kbj_episode_stats, kbj_tracking_stats, kbj_gait_stats, kbj_actuator_stats;
+host/episode.py, host/tracking.py, host/gait.py and host/actuator.py construct one each): the per-env rows that live next to the env state, the hand-over of
 one call's result to the host, the totals - and the same call on rows of its own, for a trajectory that stands alone."""
 from __future__ import annotations
 

@@ -122,3 +122,8 @@ empty_tracking_stats, combine_tracking_stats, reduce_tracking_stats = TRACKING_S
 GAIT_STATS = StatsLayout(L.GAIT["SIZE"], max0_slots=[L.gait_slot(m, "TORQUE_MAX") for m in range(L.CMODE["COUNT"])] +
                          [L.gait_slot(m, k, f) for m in range(L.CMODE["COUNT"]) for f in range(2) for k in ("SWING_MAX", "STANCE_MAX", "CLEAR_MAX", "FORCE_MAX")])
 empty_gait_stats, combine_gait_stats, reduce_gait_stats = GAIT_STATS.empty, GAIT_STATS.combine, GAIT_STATS.reduce
+
+# kbj_actuator_stats vectors (kbj_model.h KBJ_ACT_*, KBJ_AJNT_*): every slot is a count or a sum, except the largest torque, speed, power and
+# action rate of each joint block (all non-negative). HumanoidWalkingTask.actuator_stats() reduces them
+ACTUATOR_STATS = StatsLayout(L.ACT["SIZE"], max0_slots=[L.act_slot(m, k, u) for m in range(L.CMODE["COUNT"]) for u in range(L.NU) for k in L.AJNT_MAX])
+empty_actuator_stats, combine_actuator_stats, reduce_actuator_stats = ACTUATOR_STATS.empty, ACTUATOR_STATS.combine, ACTUATOR_STATS.reduce

@@ -57,11 +57,12 @@ def sweep_terms(task, command=None, events=None) -> UserTerms:
 
 
 @contextlib.contextmanager
-def sweep_rollout(task, n: int, T: int, configure, terms: UserTerms, first_hooks, step_hooks, seed_offset: int):
+def sweep_rollout(task, n: int, T: int, configure, terms: UserTerms, first_hooks, step_hooks, seed_offset: int, record_state: bool = False):
     """Run T control steps of n envs on a context built for the sweep and hand back (ctx, tr) - the context and its TrajBuffers - for the
     sweep's statistics; the context is closed when the block ends. The kbj_config is the task's for n envs and T rows with GAE off (no tail
     pass, no terminal rows), then `configure(vcfg)`. `terms` are bound here; `first_hooks` run on row 0 behind the reset, `step_hooks` behind
     every step (UserTerms.run_hooks / run_steps: the caller's order is kept). Seeds and draw indices start at `seed_offset`.
+    record_state: the TrajBuffers also keep the state record of every step (tr.qstate; the actuator sweep reads joint positions and speeds there).
     Every call builds its context and closes it again (validate() caches its own; a sweep is asked for now and then, and its env count
     follows its cases)."""
     cfg, dev = task.config, task.device
@@ -73,7 +74,7 @@ def sweep_rollout(task, n: int, T: int, configure, terms: UserTerms, first_hooks
     ctx = B.Context(task.model_blob, vcfg, dev.index or 0, torch.cuda.current_stream().cuda_stream)
     try:
         carry = CarryBuffers(n, task.H, task.kcfg.depth, dev, mirror=task.mirror)
-        tr = TrajBuffers(T, n, task.H, task.kcfg.depth, dev, mirror=task.mirror, ld_actor=task.ld_actor, ld_critic=task.ld_critic)
+        tr = TrajBuffers(T, n, task.H, task.kcfg.depth, dev, mirror=task.mirror, ld_actor=task.ld_actor, ld_critic=task.ld_critic, record_state=record_state)
         seed = cfg.seed + seed_offset
         ctx.env_reset_all(seed, tr.actor_obs[0], tr.critic_obs[0], tr.aux[0])
         terms.run_hooks(ctx, tr, 0, seed_offset, first_hooks)
@@ -83,8 +84,8 @@ def sweep_rollout(task, n: int, T: int, configure, terms: UserTerms, first_hooks
         ctx.close()
 
 
-def held_command_rollout(task, n: int, T: int, command, seed_offset: int):
-    """sweep_rollout under the Command term `command` alone (tracking, gait and step sweeps): command_mode = 1, so that the kernel's own
+def held_command_rollout(task, n: int, T: int, command, seed_offset: int, record_state: bool = False):
+    """sweep_rollout under the Command term `command` alone (tracking, gait, step and actuator sweeps): command_mode = 1, so that the kernel's own
     reset writes the context's fixed command and the term's answer then replaces it, and validate()'s hook order - on row 0 the resets, the
     command, then the observation terms that feed a network; behind every step the resets, those observation terms, then the command."""
     terms = sweep_terms(task, command=command)
@@ -94,4 +95,4 @@ def held_command_rollout(task, n: int, T: int, command, seed_offset: int):
         vcfg.command_mode = 1
 
     return sweep_rollout(task, n, T, configure, terms, [terms.apply_resets, terms.apply_command] + feeds,
-                         [terms.apply_resets] + feeds + [terms.apply_command], seed_offset)
+                         [terms.apply_resets] + feeds + [terms.apply_command], seed_offset, record_state)

@@ -25,6 +25,8 @@ from . import ckpt as ckpt_io
 from . import dist as dist_util
 from . import wiring
 from .buffers import CarryBuffers, TrajBuffers
+from .actuator import (ActuatorStats, actuator_joint_table, actuator_scalars, actuator_sweep, format_actuator_joint_table, format_actuator_table,      # noqa: F401 (re-exported)
+                       fresh_actuator_stats, levels_of_config)
 from .ckpt import ModelView
 from .config import HumanoidWalkingTaskConfig, cosine_decay_lr, launch_config      # launch_config: re-exported with the rest
 from .episode import EpisodeStats, episode_stats_scalars, fresh_episode_stats
@@ -155,6 +157,9 @@ class HumanoidWalkingTask:
         self.trk_acc = self.tracking.acc if self.tracking is not None else None
         # gait statistics (config.gait_stats; host/gait.py): `gait.acc`, the per-env carry rows next to the env state; None means off
         self.gait = GaitStats(self.N, self.device) if config.gait_stats else None
+        # actuator statistics (config.actuator_stats; host/actuator.py): `actuator.acc`, the per-env carry rows next to the env state, and the levels
+        # every call is held against; None means off. to_kbj() has refused the switch without record_state
+        self.actuator = ActuatorStats(self.N, levels_of_config(self.model_blob, config), self.device) if config.actuator_stats else None
         # those that are on, in the order of the checkpoint members and of the scalar keys
         dev, dt = self.device, config.ctrl_dt
         self._accounted = [a for a in (
@@ -163,7 +168,9 @@ class HumanoidWalkingTask:
             _Accounted(self.tracking, self.tracking_stats, lambda ctx, traj, n: fresh_tracking_stats(ctx, traj, n, self.tracking.settle_steps, dev),
                        tracking_scalars, "valid/track/"),
             _Accounted(self.gait, self.gait_stats, lambda ctx, traj, n: fresh_gait_stats(ctx, traj, n, dev),
-                       lambda vec, prefix: gait_scalars(vec, dt, prefix), "valid/gait/")) if a.carrier is not None]
+                       lambda vec, prefix: gait_scalars(vec, dt, prefix), "valid/gait/"),
+            _Accounted(self.actuator, self.actuator_stats, lambda ctx, traj, n: fresh_actuator_stats(ctx, traj, self.actuator.levels, n, dev),
+                       lambda vec, prefix: actuator_scalars(vec, self.model_blob, dt, prefix, self.actuator.levels), "valid/act/")) if a.carrier is not None]
         self.opt_step = 0
         self.iteration = 0
         self._perm_gen = torch.Generator(device="cpu")
@@ -203,6 +210,44 @@ class HumanoidWalkingTask:
             self.extra_reward_means = apply_extra_rewards(self.extra_rewards, self._extra_carries, self.trajectory(), self.traj.reward)
         for a in self._accounted:                 # behind the user rewards, so that the episodes count them (tracking and gait read the aux rows alone);
             a.carrier.after_rollout(self.ctx, self.traj.c)      # user terminations are in the DONE column already
+
+    def actuator_stats_vectors(self):
+        """(last, total): this rank's raw KBJ_ACT vectors (float64 numpy, layout.ACT / AJNT) behind actuator_stats() - the rows of the last
+        rollout and all since creation / resume."""
+        if self.actuator is None:
+            raise B.KbjError("actuator_stats_vectors() needs HumanoidWalkingTaskConfig.actuator_stats=True")
+        last, total = self.actuator.vectors()
+        return last.copy(), total.copy()
+
+    def actuator_stats(self, total: bool = False, per_joint: bool = False):
+        """What the policy asks of the motors (needs `actuator_stats=True` and `record_state=True` in the config) over the LAST rollout - or,
+        with `total`, over all rollouts since the task was created or resumed, as `act_total/...`: per command mode that has rows
+        `act/<mode>/power_abs_w`, `power_pos_w`, `cost_of_transport`, `torque_rms`, `at_torque_level_frac`, `at_stop_frac`,
+        `action_rate_rms` / `_max`, `worst_joint`, `worst_joint_frac` (host/actuator.py actuator_scalars; the definitions: include/kbj.h
+        kbj_actuator_stats). With `per_joint` instead the per-joint table of all rows together (actuator_joint_table: a dict per joint;
+        `format_actuator_joint_table` renders it). In a multi-rank job the vectors are reduced over the ranks
+        (dist.reduce_actuator_stats): every rank must call it."""
+        if self.actuator is None:
+            raise B.KbjError("actuator_stats() needs HumanoidWalkingTaskConfig.actuator_stats=True")
+        vec = self.actuator.vectors()[1 if total else 0]
+        if self.world_size > 1 or dist_util.FORCE_COLLECTIVE:
+            vec = dist_util.reduce_actuator_stats(torch.from_numpy(vec).to(self.device), self.world_size).cpu().numpy()
+        if per_joint:
+            return actuator_joint_table(vec, self.model_blob, self.config.ctrl_dt)
+        return actuator_scalars(vec, self.model_blob, self.config.ctrl_dt, "act_total/" if total else "act/", self.actuator.levels)
+
+    def actuator_sweep(self, commands=None, repeats: int = 2, seconds: Optional[float] = None, seed_offset: int = 7919, **levels) -> list:
+        """The actuator table: what the CURRENT policy asks of the motors under each of `commands` (as tracking_sweep takes them; default:
+        host/tracking.default_command_grid). tracking_sweep's rollout - a context of its own with len(commands) * repeats envs (env e follows
+        command e % K), `seconds` (default render_length_seconds) of argmax actions under a scripted Command term, with the state record of
+        every step kept - then ONE kbj_actuator_stats call on a fresh carry with the per-env record. `levels`: keyword arguments of
+        host/actuator.actuator_levels (default: the config's actuator_torque_level, actuator_speed_limit, actuator_stop_margin_deg; settings
+        of this build, not of the reference). Returns one dict per command, pooled over its envs: `command`, `mode`, `power_abs_w`,
+        `power_pos_w`, `cost_of_transport`, `torque_rms`, `at_torque_level_frac`, `at_stop_frac`, `action_rate_rms`, `worst_joint` (by name)
+        and `worst_joint_frac` (its largest torque over its level), `failures_per_s` (nan over nothing). `format_actuator_table` renders
+        it. Works with `actuator_stats` and `record_state` off. Like the gait and push tables, this one has NOT been taken on a trained
+        policy."""
+        return actuator_sweep(self, commands, repeats, seconds, seed_offset, **levels)[0]
 
     def gait_stats_vectors(self):
         """(last, total): this rank's raw KBJ_GAIT vectors (float64 numpy, layout.GAIT / GFOOT) behind gait_stats() - the rows of the last
@@ -651,7 +696,7 @@ class HumanoidWalkingTask:
             vctx = B.Context(self.model_blob, vcfg, self.device.index or 0, torch.cuda.current_stream().cuda_stream)
             self._valid = _Validation(key, vctx, CarryBuffers(num_envs, self.H, self.kcfg.depth, self.device, mirror=self.mirror),
                                       TrajBuffers(T, num_envs, self.H, self.kcfg.depth, self.device, mirror=self.mirror, reward_comps=True,
-                                                  ld_actor=self.ld_actor, ld_critic=self.ld_critic))
+                                                  ld_actor=self.ld_actor, ld_critic=self.ld_critic, record_state=self.actuator is not None))
         _, vctx, carry, tr = self._valid
         seed = self.config.seed + seed_offset
         carry.zero_()

@@ -127,6 +127,22 @@ def gait_slot(mode: int, name: str, foot=None) -> int:
     return base + GAIT[name] if foot is None else base + GAIT["FOOT"] + GAIT["FOOT_STRIDE"] * foot + GFOOT[name]
 
 
+# kbj_model.h KBJ_AACC_* / KBJ_ACT_* / KBJ_AJNT_* / KBJ_AENV_*: the per-env carry row of kbj_actuator_stats (fp32), one call's result (float64: mode
+# m's slot s at m * MODE_STRIDE + s, actuator u's AJNT slot k of the mode at JOINT + AJNT SIZE * u + k, then the episode counter) and one
+# env's totals of a call (fp32)
+AACC = dict(PREV=0, RUNNING=20, SIZE=24)
+ACT = dict(ROWS=0, PAIRS=1, SPEED_SUM=2, ANY_TAU_ROWS=3, ANY_STOP_ROWS=4, JOINT=8, MODE_STRIDE=256, EPISODES=1536, SIZE=1792)
+AJNT = dict(TAU_SQ=0, TAU_MAX=1, TAU_ROWS=2, VEL_SQ=3, VEL_MAX=4, VEL_ROWS=5, POW_ABS=6, POW_POS=7, POW_MAX=8, STOP_ROWS=9, DACT_SQ=10, DACT_MAX=11, SIZE=12)
+AENV = dict(ROWS=0, PAIRS=1, SPEED_SUM=2, TAU_SQ=3, POW_ABS=4, POW_POS=5, DACT_SQ=6, ANY_TAU_ROWS=7, ANY_STOP_ROWS=8, PEAK_FRAC=9, PEAK_JOINT=10, SIZE=12)
+AJNT_MAX = ("TAU_MAX", "VEL_MAX", "POW_MAX", "DACT_MAX")      # the maxima of a joint block (each of a non-negative quantity)
+
+
+def act_slot(mode: int, name: str, joint=None) -> int:
+    """The slot of a KBJ_ACT vector: a head slot (`name` in ACT) of mode block `mode`, or with `joint` (0 .. 19) the joint slot `name` (in AJNT)."""
+    base = mode * ACT["MODE_STRIDE"]
+    return base + ACT[name] if joint is None else base + ACT["JOINT"] + AJNT["SIZE"] * joint + AJNT[name]
+
+
 # kbj_model.h KBJ_PUSH_NEVER / KBJ_POUT_* / KBJ_PREC_* / KBJ_PSTAT_*: the PUSH_NXT value that keeps the built-in push event from drawing, the outcome
 # of a scheduled push, one env's result row of kbj_push_recovery (fp32) and one group's statistics (float64)
 PUSH_NEVER = 16777216.0
