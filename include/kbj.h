@@ -492,6 +492,53 @@ int kbj_step_response(kbj_ctx* ctx, const kbj_traj* traj, const int32_t* sched_d
                       float* sig_d /* [T][N][KBJ_SSIG_SIZE] */, float* rec_d /* [N][KBJ_SREC_SIZE] */,
                       const int32_t* group_d, int G, double* stats_d);
 
+/* ---- command frequency response --------------------------------------------------------------- */
+/* replaces: wiggling the stick at a steady rate and watching how far behind and how much smaller the robot's motion is (the gain and phase
+ * lag a controls engineer asks of a velocity-tracking policy), as sums: for one scheduled window of whole periods per env, the lock-in
+ * sums of the three response channels against the command the trajectory actually recorded and against the same command a quarter period
+ * earlier. Gain, lag, delay, coherence and cross-coupling are formed from these sums on the host (host/frequency.py), none of it here.
+ * Channel k = 0 forward, 1 sideways, 2 yaw is signal word k against command word k. min_amp is a SETTING of the caller, not a measured
+ * threshold.
+ * Stage 1, the signal: kbj_step_response's, bit for bit (the same kernel through the same launch). sig_d [T][N][KBJ_SSIG_SIZE] fp32 is
+ *   OVERWRITTEN. Everything below is an exact function of sig_d.
+ * Stage 2, per env n. sched_d[n] = {s, P, ch, K}: s the first measured row, P the period in rows, ch the driven channel, K the number of
+ * whole periods measured; q = P / 4. All index arithmetic is in 64 bits, K * P in particular: the schedule is the caller's.
+ * The reference r(t) = CMD[ch] of row t; its quadrature d(t) = r(t - q), the same word a quarter period earlier. No sine or cosine is
+ * evaluated on the device: a host restatement reproduces every bit.
+ *   1. s < 0: NONE.
+ *   2. VOID if any of: P < 4, P > 256, P % 4 != 0, ch outside [0, 2], K < 1, s < q, s >= T, a lead row in [s - q, s) has DONE != 0.
+ *   3. Otherwise the rows t = s .. min(T, s + K P) - 1 are scanned in order. On each row, in this order:
+ *        1. DONE < 0: FELL, FALL_STEPS = t - s. Stop.
+ *        2. DONE > 0: CENSORED. Stop.
+ *        3. Accumulate, with y_0, y_1, y_2 = VX, VY, WZ of the row: R_MIN / R_MAX are replaced where r is smaller / greater (they start
+ *           at +inf / -inf; a NaN never replaces them); ROWS += 1; the double sums S_R += r, S_D += d, S_RR += r r, S_DD += d d,
+ *           S_RD += r d, and per channel k S_Y[k] += y_k, S_YY[k] += y_k y_k, S_YR[k] += y_k r, S_YD[k] += y_k d. Every operand is
+ *           converted to double first (the product of two fp32 values is exact in double: fused or not gives the same sum); the adds
+ *           ascend in t.
+ *   4. At the end, for an env that has not stopped: s + K P > T: CENSORED (the trajectory cut the window). Else R_MAX - R_MIN >=
+ *      min_amp[ch] (one fp32 subtraction; false for a NaN): MEASURED. Else FLAT: nobody moved the stick, a gain over nothing is noise.
+ *   5. rec_d [N][KBJ_FREC_SIZE] DOUBLES is OVERWRITTEN (kbj_model.h KBJ_FREC_*): OUTCOME, ROWS, FALL_STEPS, CHANNEL, PERIOD, R_MIN, R_MAX,
+ *      the 5 reference sums, the 12 response sums. The sums are kept as accumulated for FELL, CENSORED, FLAT and MEASURED alike: ROWS says
+ *      over how many rows. Everything but OUTCOME is -1 for NONE and VOID; FALL_STEPS is -1 unless FELL.
+ * stats_d: NULL, or [G][KBJ_FSTAT_SIZE] doubles, overwritten (spare slots 0; kbj_model.h KBJ_FSTAT_*): per group g the envs per outcome;
+ * FALL_SUM over its FELL envs; over its MEASURED envs ONLY the sum of ROWS, of each of the 17 sums, the minimum of R_MIN and the maximum
+ * of R_MAX. A minimum or maximum over nothing is -1. group_d [N] int32 names every env's group (NULL: all in group 0; a value outside
+ * [0, G) puts the env in no group), 1 <= G <= 256. A group's envs are combined in env order, in doubles, without atomics: the same inputs
+ * give the same bytes on every call, with or without stats_d. Pooling the raw sums is deliberate: where the envs of a group share s, P
+ * and the command, the pooled sums are those of the concatenated windows.
+ * Reads rows 0 .. T-1 of traj->aux_d (as kbj_step_response does) and sched_d [N][4] int32; overwrites sig_d, rec_d and stats_d.
+ * Asynchronous on the context's stream; crit is read before the call returns. Fails with a message, before anything is launched, on a
+ * NULL ctx, traj, sched_d, crit, sig_d or rec_d, on a trajectory without aux_d or positive T, N, on a traj->aux_d, sig_d or sched_d that
+ * is not 16-byte aligned, on a rec_d or stats_d that is not 8-byte aligned, on a negative or NaN min_amp, and with stats_d on G outside
+ * [1, 256]. The context stays usable after such a failure. */
+typedef struct kbj_frequency_criteria {
+  float min_amp[3];   /* the smallest swing R_MAX - R_MIN of the driven channel's command that counts as moved: m/s, m/s, rad/s */
+} kbj_frequency_criteria;
+int kbj_sizeof_frequency_criteria(void);   /* sizeof(kbj_frequency_criteria), for a binding's mirror */
+int kbj_frequency_response(kbj_ctx* ctx, const kbj_traj* traj, const int32_t* sched_d /* [N][4] */, const kbj_frequency_criteria* crit,
+                           float* sig_d /* [T][N][KBJ_SSIG_SIZE] */, double* rec_d /* [N][KBJ_FREC_SIZE] */,
+                           const int32_t* group_d, int G, double* stats_d /* NULL or [G][KBJ_FSTAT_SIZE] */);
+
 /* ---- PPO update, rows a9, a12, a13 ---------------------------------------------------------- */
 /* replaces: ksim GAE (gamma, lam: train.py:1769-1770). done from aux; adv_d/target_d [T][N].
  * Per env n, for t = T-1 .. 0, with d = aux[t][n][KBJ_AUX_DONE], v = value[t][n], r = reward[t][n] and A_T = 0:

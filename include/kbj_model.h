@@ -579,6 +579,52 @@ enum {
   KBJ_SSTAT_SIZE          = 48    /* three spare slots, written 0 */
 };
 
+/* ---- command frequency response (kbj_frequency_response) ----
+ * The signal is kbj_step_response's (KBJ_SSIG_*); channel k (0 forward, 1 sideways, 2 yaw) is signal word k and command word k.
+ * Outcome of one env's scheduled lock-in window (kbj.h kbj_frequency_response). Valid = KBJ_FOUT_FELL and above, as with KBJ_SOUT_*. */
+enum {
+  KBJ_FOUT_NONE     = 0,   /* no window scheduled (row < 0) */
+  KBJ_FOUT_VOID     = 1,   /* the schedule says nothing: a period that is no multiple of 4 in [4, 256], no such channel, no whole period, a window that
+                              starts outside the trajectory or without its quarter period of lead rows, or an episode end in the lead rows */
+  KBJ_FOUT_FELL     = 2,   /* a failure (DONE < 0) inside the window */
+  KBJ_FOUT_MEASURED = 3,   /* the whole window was seen and the reference swung by at least min_amp */
+  KBJ_FOUT_FLAT     = 4,   /* the whole window was seen, the reference did not swing: nobody moved the stick */
+  KBJ_FOUT_CENSORED = 5,   /* a time-out (DONE > 0) or the end of the trajectory cut the window */
+  KBJ_FOUT_COUNT    = 6
+};
+/* One env's record ("FREC" record, DOUBLES). Everything but OUTCOME is -1 for NONE and VOID; FALL_STEPS is -1 unless FELL. r = the driven
+ * channel's command word of the row, d = the same word a quarter period earlier, y_k = VX, VY, WZ of the row. */
+enum {
+  KBJ_FREC_OUTCOME    = 0,    /* KBJ_FOUT_* */
+  KBJ_FREC_ROWS       = 1,    /* rows accumulated: all sums below are over these */
+  KBJ_FREC_FALL_STEPS = 2,    /* FELL: rows from the first measured row to the failing row */
+  KBJ_FREC_CHANNEL    = 3,    /* the driven channel */
+  KBJ_FREC_PERIOD     = 4,    /* the period in rows */
+  KBJ_FREC_R_MIN      = 5,    /* smallest r (+inf over no comparable r), */
+  KBJ_FREC_R_MAX      = 6,    /* greatest r (-inf over no comparable r) */
+  KBJ_FREC_S_R        = 7,    /* sum r, */
+  KBJ_FREC_S_D        = 8,    /* sum d, */
+  KBJ_FREC_S_RR       = 9,    /* sum r r, */
+  KBJ_FREC_S_DD       = 10,   /* sum d d, */
+  KBJ_FREC_S_RD       = 11,   /* sum r d */
+  KBJ_FREC_S_Y        = 12,   /* [3] sum y_k, */
+  KBJ_FREC_S_YY       = 15,   /* [3] sum y_k y_k, */
+  KBJ_FREC_S_YR       = 18,   /* [3] sum y_k r, */
+  KBJ_FREC_S_YD       = 21,   /* [3] sum y_k d */
+  KBJ_FREC_SIZE       = 24    /* 192-byte rows */
+};
+#define KBJ_FREC_NSUMS 17 /* the sums of a record: KBJ_FREC_S_R .. KBJ_FREC_SIZE - 1 */
+/* One group's statistics ("FSTAT" record, doubles). A minimum or maximum over nothing is -1; spare slots are 0. */
+enum {
+  KBJ_FSTAT_COUNT    = 0,    /* [6] envs per outcome, KBJ_FOUT_* order */
+  KBJ_FSTAT_FALL_SUM = 6,    /* over the FELL envs: sum of FALL_STEPS */
+  KBJ_FSTAT_ROWS     = 7,    /* over the MEASURED envs: sum of ROWS, */
+  KBJ_FSTAT_SUMS     = 8,    /* [17] of each sum, KBJ_FREC_S_R .. order, */
+  KBJ_FSTAT_R_MIN    = 25,   /* the minimum of R_MIN, */
+  KBJ_FSTAT_R_MAX    = 26,   /* the maximum of R_MAX */
+  KBJ_FSTAT_SIZE     = 32    /* five spare slots, written 0 */
+};
+
 /* reward component order (train.py:1225-1256) */
 enum {
   KBJ_REW_LINVEL = 0, KBJ_REW_ANGVEL, KBJ_REW_ROLL_PITCH, KBJ_REW_BASE_HEIGHT, KBJ_REW_ARM_POS,

@@ -40,6 +40,7 @@ int kbj_sizeof_config(void) { return (int)sizeof(kbj_config); }
 int kbj_sizeof_traj(void) { return (int)sizeof(kbj_traj); }
 int kbj_sizeof_carry(void) { return (int)sizeof(kbj_carry); }
 int kbj_sizeof_step_criteria(void) { return (int)sizeof(kbj_step_criteria); }
+int kbj_sizeof_frequency_criteria(void) { return (int)sizeof(kbj_frequency_criteria); }
 
 // Host-only validation of the sizes the kernels are built for (no device needed; kbj_create runs it first). Besides the plain range
 // checks: the GEMM's interior tiles and the recurrences' hand-off tiles are fetched with buffer loads whose per-thread and scalar byte

@@ -1,7 +1,8 @@
 // kbj_traj_stats.hip — HIP kernels + C-ABI entry points of everything that reads a finished trajectory: kbj_rewards (rewards_kernel below),
 // kbj_episode_stats (kbj_episode_stats.h), kbj_tracking_stats (kbj_tracking_stats.h), kbj_gait_stats (kbj_gait_stats.h), kbj_push_recovery
-// (kbj_push_recovery.h), kbj_step_response (kbj_step_response.h) and kbj_actuator_stats (kbj_actuator_stats.h). None of it
-// is on the hot path, and none of it shares a translation unit with the env kernels (kbj_env.hip): an edit here recompiles no step kernel.
+// (kbj_push_recovery.h), kbj_step_response (kbj_step_response.h), kbj_frequency_response (kbj_frequency_response.h) and kbj_actuator_stats
+// (kbj_actuator_stats.h). None of it is on the hot path, and none of it shares a translation unit with the env kernels (kbj_env.hip): an edit
+// here recompiles no step kernel.
 #include <hip/hip_runtime.h>
 #include <initializer_list>
 #include "kbj_env_core.h"
@@ -13,6 +14,7 @@
 #include "kbj_ctx.h"
 #include "kbj_push_recovery.h"
 #include "kbj_step_response.h"
+#include "kbj_frequency_response.h"
 
 using namespace kbj;
 
@@ -158,6 +160,15 @@ int scan_then_reduce(kbj_ctx* ctx, int blocks, const char* scan_name, const char
   return 0;
 }
 
+// stage 1 of kbj_step_response and kbj_frequency_response: the signal of rows 0 .. T-1 of the trajectory's aux rows into sig_d
+int launch_step_signal(kbj_ctx* ctx, const kbj_traj* tr, float* sig_d) {
+  const size_t rows = (size_t)tr->T * (size_t)tr->N;
+  const size_t sig_blocks = (rows + SR_SIG_THREADS - 1) / SR_SIG_THREADS;
+  hipLaunchKernelGGL(step_signal_kernel, dim3((unsigned)(sig_blocks < (1u << 20) ? sig_blocks : (1u << 20))), dim3(SR_SIG_THREADS), 0, ctx->stream, tr->aux_d, rows, sig_d);
+  KBJ_CHECK_LAUNCH(ctx, "step_signal_kernel");
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -274,15 +285,31 @@ int kbj_step_response(kbj_ctx* ctx, const kbj_traj* tr, const int32_t* sched_d, 
   }
   if (stats_d && (G < 1 || G > GROUP_REDUCE_THREADS)) return kbj_fail(ctx, "kbj_step_response: G must be in [1, 256]");
   KBJ_HIP(ctx, hipSetDevice(ctx->device));      // no kbj_nn_drop_prefetch: no trajectory row is written
-  const size_t rows = (size_t)tr->T * (size_t)tr->N;
-  const size_t sig_blocks = (rows + SR_SIG_THREADS - 1) / SR_SIG_THREADS;
-  hipLaunchKernelGGL(step_signal_kernel, dim3((unsigned)(sig_blocks < (1u << 20) ? sig_blocks : (1u << 20))), dim3(SR_SIG_THREADS), 0, ctx->stream, tr->aux_d, rows, sig_d);
-  KBJ_CHECK_LAUNCH(ctx, "step_signal_kernel");
+  if (launch_step_signal(ctx, tr, sig_d) != 0) return -1;
   hipLaunchKernelGGL(step_scan_kernel, dim3((tr->N + WINDOW_ENVS - 1) / WINDOW_ENVS), dim3(WINDOW_ENVS), 0, ctx->stream, sig_d, tr->T, tr->N, sched_d, *crit, rec_d);
   KBJ_CHECK_LAUNCH(ctx, "step_scan_kernel");
   if (stats_d) {
     hipLaunchKernelGGL(step_reduce_kernel, dim3(1), dim3(GROUP_REDUCE_THREADS), 0, ctx->stream, rec_d, group_d, tr->N, G, stats_d);
     KBJ_CHECK_LAUNCH(ctx, "step_reduce_kernel");
+  }
+  return 0;
+}
+
+int kbj_frequency_response(kbj_ctx* ctx, const kbj_traj* tr, const int32_t* sched_d, const kbj_frequency_criteria* crit, float* sig_d, double* rec_d,
+                           const int32_t* group_d, int G, double* stats_d) {
+  if (!ctx || !tr || !sched_d || !crit || !sig_d || !rec_d) return kbj_fail(ctx, "kbj_frequency_response: null argument");
+  if (check_traj(ctx, "kbj_frequency_response", tr, false) != 0 || check_aligned16(ctx, "kbj_frequency_response", "aux_d, sig_d and sched_d", {tr->aux_d, sig_d, sched_d}) != 0) return -1;
+  if ((reinterpret_cast<uintptr_t>(rec_d) | reinterpret_cast<uintptr_t>(stats_d)) & 7) return kbj_fail(ctx, "kbj_frequency_response: rec_d and stats_d must be 8-byte aligned");
+  for (int k = 0; k < KBJ_NSCH; ++k)
+    if (!(crit->min_amp[k] >= 0.0f)) return kbj_fail(ctx, "kbj_frequency_response: a min_amp is negative or NaN");
+  if (stats_d && (G < 1 || G > GROUP_REDUCE_THREADS)) return kbj_fail(ctx, "kbj_frequency_response: G must be in [1, 256]");
+  KBJ_HIP(ctx, hipSetDevice(ctx->device));      // no kbj_nn_drop_prefetch: no trajectory row is written
+  if (launch_step_signal(ctx, tr, sig_d) != 0) return -1;
+  hipLaunchKernelGGL(freq_scan_kernel, dim3((tr->N + WINDOW_ENVS - 1) / WINDOW_ENVS), dim3(WINDOW_ENVS), 0, ctx->stream, sig_d, tr->T, tr->N, sched_d, *crit, rec_d);
+  KBJ_CHECK_LAUNCH(ctx, "freq_scan_kernel");
+  if (stats_d) {
+    hipLaunchKernelGGL(freq_reduce_kernel, dim3(1), dim3(GROUP_REDUCE_THREADS), 0, ctx->stream, rec_d, group_d, tr->N, G, stats_d);
+    KBJ_CHECK_LAUNCH(ctx, "freq_reduce_kernel");
   }
   return 0;
 }

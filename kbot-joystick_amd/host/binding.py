@@ -58,6 +58,12 @@ class StepCriteria(C.Structure):
                 ("smooth_steps", C.c_int32), ("hold_steps", C.c_int32), ("window_steps", C.c_int32)]
 
 
+class FrequencyCriteria(C.Structure):
+    """kbj_frequency_criteria: per channel (forward, sideways, yaw) the smallest swing of the driven command word over the measured window
+    that counts as a moved stick. A setting of the caller, not a measured threshold."""
+    _fields_ = [("min_amp", C.c_float * L.NSCH)]
+
+
 class ActuatorLevels(C.Structure):
     """kbj_actuator_levels: per actuator (spec/constants.JOINT_NAMES order) the torque level (N m), the speed level (rad/s, +inf counts
     nothing) and the joint-stop band (rad). Settings of the caller (host/actuator.py actuator_levels), not figures of the reference."""
@@ -84,6 +90,7 @@ SIGNATURES = {
     "kbj_sizeof_traj": (_i, []),
     "kbj_sizeof_carry": (_i, []),
     "kbj_sizeof_step_criteria": (_i, []),
+    "kbj_sizeof_frequency_criteria": (_i, []),
     "kbj_synchronize": (_i, [_vp]),
     "kbj_env_reset_all": (_i, [_vp, _u32, _vp, _vp, _vp]),
     "kbj_env_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
@@ -121,6 +128,7 @@ SIGNATURES = {
     "kbj_actuator_stats": (_i, [_vp, C.POINTER(Traj), C.POINTER(ActuatorLevels), _vp, _vp, _vp]),
     "kbj_push_recovery": (_i, [_vp, C.POINTER(Traj), _vp, _vp, C.POINTER(PushCriteria), _vp, _vp, _i, _vp]),
     "kbj_step_response": (_i, [_vp, C.POINTER(Traj), _vp, C.POINTER(StepCriteria), _vp, _vp, _vp, _i, _vp]),
+    "kbj_frequency_response": (_i, [_vp, C.POINTER(Traj), _vp, C.POINTER(FrequencyCriteria), _vp, _vp, _vp, _i, _vp]),
     "kbj_ppo_grad": (_i, [_vp, _vp, C.POINTER(Traj), _vp, _i, _vp, _vp, _vp, _vp]),
     "kbj_ppo_forward": (_i, [_vp, _vp, C.POINTER(Traj), _vp, _i, C.POINTER(PpoVars)]),
     "kbj_stream_wait_actor_grad": (_i, [_vp, _vp]),
@@ -385,6 +393,13 @@ class Context:
         [N, SREC SIZE] float32 (both overwritten), group None or [N] int32 in [0, G), stats None or [G, SSTAT SIZE] float64 (overwritten),
         all on the device."""
         self.call("kbj_step_response", C.byref(traj) if traj is not None else None, _ptr(sched), C.byref(criteria) if criteria is not None else None, _ptr(sig), _ptr(rec),
+                  _ptr(group), int(G), _ptr(stats))
+
+    def frequency_response(self, traj: Traj, sched, criteria: FrequencyCriteria, sig, rec, group=None, G: int = 1, stats=None):
+        """kbj_frequency_response: sched [N, 4] int32 (first measured row, period in rows, driven channel, whole periods; row < 0: no window),
+        sig [T, N, SSIG SIZE] float32 and rec [N, FREC SIZE] float64 (both overwritten), group None or [N] int32 in [0, G), stats None or
+        [G, FSTAT SIZE] float64 (overwritten), all on the device."""
+        self.call("kbj_frequency_response", C.byref(traj) if traj is not None else None, _ptr(sched), C.byref(criteria) if criteria is not None else None, _ptr(sig), _ptr(rec),
                   _ptr(group), int(G), _ptr(stats))
 
     def ppo_grad(self, params, traj: Traj, env_idx, B, adv, target, grad, metrics):

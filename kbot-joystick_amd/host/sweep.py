@@ -1,4 +1,5 @@
-"""What the evaluation sweeps (host/tracking.py tracking_sweep, host/push.py push_sweep, host/gait.py gait_sweep, host/step.py step_sweep) share: a context of their own for n envs and T rows,
+"""What the evaluation sweeps (host/tracking.py tracking_sweep, host/push.py push_sweep, host/gait.py gait_sweep, host/step.py step_sweep,
+host/actuator.py actuator_sweep, host/frequency.py frequency_sweep) share: a context of their own for n envs and T rows,
 one rollout with the task's policy acting with the distribution's mode, the user terms the sweep scripts."""
 from __future__ import annotations
 
@@ -85,7 +86,7 @@ def sweep_rollout(task, n: int, T: int, configure, terms: UserTerms, first_hooks
 
 
 def held_command_rollout(task, n: int, T: int, command, seed_offset: int, record_state: bool = False):
-    """sweep_rollout under the Command term `command` alone (tracking, gait, step and actuator sweeps): command_mode = 1, so that the kernel's own
+    """sweep_rollout under the Command term `command` alone (tracking, gait, step, actuator and frequency sweeps): command_mode = 1, so that the kernel's own
     reset writes the context's fixed command and the term's answer then replaces it, and validate()'s hook order - on row 0 the resets, the
     command, then the observation terms that feed a network; behind every step the resets, those observation terms, then the command."""
     terms = sweep_terms(task, command=command)

@@ -30,6 +30,7 @@ from .actuator import (ActuatorStats, actuator_joint_table, actuator_scalars, ac
 from .ckpt import ModelView
 from .config import HumanoidWalkingTaskConfig, cosine_decay_lr, launch_config      # launch_config: re-exported with the rest
 from .episode import EpisodeStats, episode_stats_scalars, fresh_episode_stats
+from .frequency import FrequencyRecord, SineCommand, format_frequency_table, frequency_sweep      # noqa: F401 (re-exported)
 from .gait import GaitStats, format_gait_table, fresh_gait_stats, gait_scalars, gait_sweep      # noqa: F401 (re-exported)
 from .push import PushRecord, ScriptedPush, format_push_table, push_sweep      # noqa: F401 (re-exported)
 from .step import StepRecord, SteppedCommand, format_step_table, step_sweep      # noqa: F401 (re-exported)
@@ -355,6 +356,29 @@ class HumanoidWalkingTask:
         (nan over nothing), and the StepRecord of the device data. `format_step_table` renders the entries. Like the push and gait
         tables, this one has NOT been taken on a trained policy."""
         return step_sweep(self, transitions, step_at, window, hold, smooth, rise_level, band_frac, band_abs, min_step, repeats, seed_offset)
+
+    def frequency_sweep(self, points=None, periods=None, cycles: int = 4, min_window: float = 4.0, start_at: float = 2.0, settle: float = 2.0,
+                        min_amp=(0.05, 0.05, 0.05), repeats: int = 4, seed_offset: int = 7919):
+        """The frequency-response table: how the CURRENT policy follows a stick that KEEPS MOVING. One case per (operating point, period):
+        an operating point is (base command [<= 16] floats, channel 0 forward / 1 sideways / 2 yaw, amplitude; default:
+        host/frequency.default_frequency_points - each channel around standing at half its range, forward around half speed at a quarter),
+        a period is an int in rows (a multiple of 4 in [4, 256]) or a float frequency in Hz, snapped to P = 4 round(1 / (4 f ctrl_dt))
+        (default 200, 100, 48, 24, 12, 8 rows: 0.25 to 6.25 Hz at 50 Hz control). A context of its own with cases * repeats envs (env e
+        runs case e % cases; at most 256 cases) runs argmax actions through the step-wise loop under the Command term
+        host/frequency.SineCommand: from row round(start_at / ctrl_dt) on the driven word is base + amplitude cos(2 pi (row - start) / P),
+        again after every in-episode reset; the user's Reset and network-input Observation terms apply as in validate(), Event terms do
+        not. After ceil(settle / (P ctrl_dt)) whole periods, K = max(cycles, ceil(min_window / (P ctrl_dt))) whole periods are measured:
+        ONE kbj_frequency_response call, with one group per case, sums every response channel against the recorded command and against
+        the same command a quarter period earlier. A window is VOID when an episode ended in the quarter period in front of it; otherwise
+        the env FELL, was CENSORED by a time-out, left a FLAT window (the recorded command swung by less than `min_amp`) or a MEASURED
+        one. From the sums pooled over a case's MEASURED envs the host forms gain, gain in dB, lag in degrees, delay in ms, coherence
+        and the cross-coupling gain into the two channels that were not driven (host/frequency.case_summary), and per operating point
+        the -3 dB bandwidth by interpolation over log f (`bandwidth_hz`; `bandwidth_below_range` when the gain is below -3 dB already at
+        the lowest frequency). `min_amp` and the grid are SETTINGS, echoed in every entry - not measured thresholds - and the figures
+        are linear-systems language applied to a nonlinear walker: the coherence says how far to trust them. Returns (entries, record):
+        per case the settings and figures (nan over nothing), and the FrequencyRecord of the device data. `format_frequency_table` renders
+        the entries. Like the step table, this one has NOT been taken on a trained policy."""
+        return frequency_sweep(self, points, periods, cycles, min_window, start_at, settle, min_amp, repeats, seed_offset)
 
     def episode_stats_vectors(self):
         """(last, total): this rank's raw KBJ_EPST vectors (float64 numpy, layout.EPST) behind episode_stats() - the episodes that finished in

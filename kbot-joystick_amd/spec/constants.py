@@ -64,6 +64,8 @@ PUSH_OUTCOME_NAMES = ("none", "void", "fell", "recovered", "unrecovered", "censo
 # the outcomes of a scheduled command step (kbj_model.h KBJ_SOUT_*) and the channels kbj_step_response scores: signal word k against command word k
 STEP_OUTCOME_NAMES = ("none", "void", "fell", "settled", "unsettled", "censored")
 STEP_CHANNEL_NAMES = ("forward", "sideways", "yaw")
+# the outcomes of a scheduled lock-in window (kbj_model.h KBJ_FOUT_*); kbj_frequency_response drives and scores the STEP_CHANNEL_NAMES channels
+FREQUENCY_OUTCOME_NAMES = ("none", "void", "fell", "measured", "flat", "censored")
 
 REWARD_NAMES = (
     "linvel", "angvel", "roll_pitch", "base_height", "arm_pos", "single_contact", "no_contact_p",

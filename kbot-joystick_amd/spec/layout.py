@@ -158,6 +158,12 @@ SOUT = dict(NONE=0, VOID=1, FELL=2, SETTLED=3, UNSETTLED=4, CENSORED=5, COUNT=6)
 SREC = dict(OUTCOME=0, SETTLE_STEPS=1, FALL_STEPS=2, ACTIVE=3, TRAVEL_X=4, TRAVEL_Y=5, TRAVEL_YAW=6, SPARE=7, RISE=8, OVER=11, DEV=14, SPARE_TAIL=17, SIZE=20)
 SSTAT = dict(COUNT=0, SETTLE_SUM=6, SETTLE_SUMSQ=7, SETTLE_MAX=8, FALL_SUM=9, FALL_SUMSQ=10, FALL_MAX=11, ACTIVE_N=12, RISE_N=15, RISE_SUM=18, RISE_MAX=21,
              OVER_SUM=24, OVER_MAX=27, DEV_N=30, DEV_SUM=33, DEV_MAX=36, TRAVEL_SUM=39, TRAVEL_ABSMAX=42, SIZE=48)
+# kbj_model.h KBJ_FOUT_* / KBJ_FREC_* / KBJ_FSTAT_*: the outcome of a scheduled lock-in window of kbj_frequency_response (on the SSIG signal), one env's
+# record and one group's statistics (both float64); FREC_NSUMS sums close a record (S_R ..) and fill FSTAT's SUMS block in the same order
+FOUT = dict(NONE=0, VOID=1, FELL=2, MEASURED=3, FLAT=4, CENSORED=5, COUNT=6)
+FREC = dict(OUTCOME=0, ROWS=1, FALL_STEPS=2, CHANNEL=3, PERIOD=4, R_MIN=5, R_MAX=6, S_R=7, S_D=8, S_RR=9, S_DD=10, S_RD=11, S_Y=12, S_YY=15, S_YR=18, S_YD=21, SIZE=24)
+FREC_NSUMS = 17
+FSTAT = dict(COUNT=0, FALL_SUM=6, ROWS=7, SUMS=8, R_MIN=25, R_MAX=26, SIZE=32)
 # pieces of a packed observation row in the reference's concatenation order (kbj_model.h KBJ_OBS_*; train.py:1367-1374, 1410-1430):
 # name -> (offset, width); the first six are common to the actor and the critic row
 OBS = dict(JPOS=(0, 20), JVEL=(20, 20), PG=(40, 5), GYRO=(45, 3), ZEROCMD=(48, 1), CMD=(49, 16), TOUCH=(65, 2), FEETPOS=(67, 6), BASEPOS=(73, 3),
