@@ -5,6 +5,7 @@
 // here recompiles no step kernel.
 #include <hip/hip_runtime.h>
 #include <initializer_list>
+#include <optional>
 #include "kbj_env_core.h"
 #include "kbj_ordered_reduce.h"
 #include "kbj_episode_stats.h"
@@ -148,15 +149,41 @@ int check_aligned16(kbj_ctx* ctx, const char* fn, const char* names, std::initia
   return (bits & 15) ? kbj_fail(ctx, std::string(fn) + ": " + names + " must be 16-byte aligned") : 0;
 }
 
-// a scan that leaves `blocks` workgroup partials of Slots::SIZE doubles, then their ordered reduce into stats_d. launch_scan(partials) queues
-// the scan on the context's stream
+// a scan that leaves `blocks` workgroup partials of Slots::SIZE doubles, then their ordered reduce into stats_d: the wide one where a vector
+// is wider than one workgroup. launch_scan(partials) queues the scan on the context's stream; reduce_kind >= 0 times the reduce as that kind
 template <class Slots, class LaunchScan>
-int scan_then_reduce(kbj_ctx* ctx, int blocks, const char* scan_name, const char* reduce_name, double* stats_d, LaunchScan launch_scan) {
+int scan_then_reduce(kbj_ctx* ctx, int blocks, const char* scan_name, const char* reduce_name, double* stats_d, LaunchScan launch_scan, int reduce_kind = -1) {
   if (stats_partials(ctx, (size_t)blocks * Slots::SIZE) != 0) return -1;
   launch_scan(ctx->stats_part_d);
   KBJ_CHECK_LAUNCH(ctx, scan_name);
-  hipLaunchKernelGGL(ordered_reduce_kernel<Slots>, dim3(1), dim3(ORDERED_REDUCE_THREADS), 0, ctx->stream, ctx->stats_part_d, blocks, stats_d);
+  {
+    std::optional<KbjKernelTimer> timer;
+    if (reduce_kind >= 0) timer.emplace(ctx->stream, reduce_kind, 0.0);
+    if constexpr (Slots::SIZE > ORDERED_REDUCE_THREADS)
+      hipLaunchKernelGGL(ordered_reduce_wide_kernel<Slots>, dim3(Slots::SIZE / ORDERED_REDUCE_THREADS), dim3(ORDERED_REDUCE_THREADS), 0, ctx->stream, ctx->stats_part_d, blocks, stats_d);
+    else
+      hipLaunchKernelGGL(ordered_reduce_kernel<Slots>, dim3(1), dim3(ORDERED_REDUCE_THREADS), 0, ctx->stream, ctx->stats_part_d, blocks, stats_d);
+  }
   KBJ_CHECK_LAUNCH(ctx, reduce_name);
+  return 0;
+}
+
+// "<fn>: G must be in [1, 256]", where the group statistics are asked for
+int check_groups(kbj_ctx* ctx, const char* fn, int G, const double* stats_d) {
+  return (stats_d && (G < 1 || G > GROUP_REDUCE_THREADS)) ? kbj_fail(ctx, std::string(fn) + ": G must be in [1, 256]") : 0;
+}
+
+// a window scan over ceil(N / WINDOW_ENVS) workgroups of one wavefront - launch_scan(grid, block) queues it on the context's stream - then,
+// when stats_d is given, its group reduce: rec_d [N] by group_d into stats_d [G]
+template <class Rec, class LaunchScan>
+int window_scan_then_reduce(kbj_ctx* ctx, int N, const char* scan_name, LaunchScan launch_scan, void (*reduce)(const Rec*, const int32_t*, int, int, double*),
+                            const char* reduce_name, const Rec* rec_d, const int32_t* group_d, int G, double* stats_d) {
+  launch_scan(dim3((N + WINDOW_ENVS - 1) / WINDOW_ENVS), dim3(WINDOW_ENVS));
+  KBJ_CHECK_LAUNCH(ctx, scan_name);
+  if (stats_d) {
+    hipLaunchKernelGGL(reduce, dim3(1), dim3(GROUP_REDUCE_THREADS), 0, ctx->stream, rec_d, group_d, N, G, stats_d);
+    KBJ_CHECK_LAUNCH(ctx, reduce_name);
+  }
   return 0;
 }
 
@@ -235,18 +262,10 @@ int kbj_actuator_stats(kbj_ctx* ctx, const kbj_traj* tr, const kbj_actuator_leve
   }
   KBJ_HIP(ctx, hipSetDevice(ctx->device));      // no kbj_nn_drop_prefetch: no trajectory row is written
   const int blocks = (tr->N + ACT_ENVS - 1) / ACT_ENVS;
-  if (stats_partials(ctx, (size_t)blocks * ActSlots::SIZE) != 0) return -1;
-  {
+  return scan_then_reduce<ActSlots>(ctx, blocks, "actuator_stats_kernel", "ordered_reduce_wide_kernel<ActSlots>", stats_d, [&](double* part_d) {
     KbjKernelTimer timer(ctx->stream, KBJ_KIND_ACTUATOR_STATS, 0.0);
-    hipLaunchKernelGGL(actuator_stats_kernel, dim3(blocks), dim3(ACT_THREADS), 0, ctx->stream, tr->aux_d, tr->qstate_d, tr->action_d, tr->T, tr->N, *lv, acc_d, ctx->stats_part_d, env_d);
-  }
-  KBJ_CHECK_LAUNCH(ctx, "actuator_stats_kernel");
-  {
-    KbjKernelTimer timer(ctx->stream, KBJ_KIND_ACTUATOR_REDUCE, 0.0);
-    hipLaunchKernelGGL(ordered_reduce_wide_kernel<ActSlots>, dim3(ActSlots::SIZE / ORDERED_REDUCE_THREADS), dim3(ORDERED_REDUCE_THREADS), 0, ctx->stream, ctx->stats_part_d, blocks, stats_d);
-  }
-  KBJ_CHECK_LAUNCH(ctx, "ordered_reduce_wide_kernel<ActSlots>");
-  return 0;
+    hipLaunchKernelGGL(actuator_stats_kernel, dim3(blocks), dim3(ACT_THREADS), 0, ctx->stream, tr->aux_d, tr->qstate_d, tr->action_d, tr->T, tr->N, *lv, acc_d, part_d, env_d);
+  }, KBJ_KIND_ACTUATOR_REDUCE);
 }
 
 int kbj_push_recovery(kbj_ctx* ctx, const kbj_traj* tr, const float* err_d, const int32_t* sched_d, const kbj_push_criteria* crit, float* rec_d,
@@ -258,15 +277,11 @@ int kbj_push_recovery(kbj_ctx* ctx, const kbj_traj* tr, const float* err_d, cons
   if (crit->window_steps < 0) return kbj_fail(ctx, "kbj_push_recovery: window_steps must not be negative");
   for (int k = 0; k < KBJ_NTERR; ++k)
     if (crit->tol[k] != crit->tol[k]) return kbj_fail(ctx, "kbj_push_recovery: a tolerance is NaN (+inf ignores a column)");
-  if (stats_d && (G < 1 || G > GROUP_REDUCE_THREADS)) return kbj_fail(ctx, "kbj_push_recovery: G must be in [1, 256]");
+  if (check_groups(ctx, "kbj_push_recovery", G, stats_d) != 0) return -1;
   KBJ_HIP(ctx, hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(push_recovery_kernel, dim3((tr->N + WINDOW_ENVS - 1) / WINDOW_ENVS), dim3(WINDOW_ENVS), 0, ctx->stream, err_d, tr->aux_d, tr->T, tr->N, sched_d, *crit, rec_d);
-  KBJ_CHECK_LAUNCH(ctx, "push_recovery_kernel");
-  if (stats_d) {
-    hipLaunchKernelGGL(push_recovery_reduce_kernel, dim3(1), dim3(GROUP_REDUCE_THREADS), 0, ctx->stream, rec_d, group_d, tr->N, G, stats_d);
-    KBJ_CHECK_LAUNCH(ctx, "push_recovery_reduce_kernel");
-  }
-  return 0;
+  return window_scan_then_reduce<float>(ctx, tr->N, "push_recovery_kernel", [&](dim3 grid, dim3 block) {
+    hipLaunchKernelGGL(push_recovery_kernel, grid, block, 0, ctx->stream, err_d, tr->aux_d, tr->T, tr->N, sched_d, *crit, rec_d);
+  }, push_recovery_reduce_kernel, "push_recovery_reduce_kernel", rec_d, group_d, G, stats_d);
 }
 
 int kbj_step_response(kbj_ctx* ctx, const kbj_traj* tr, const int32_t* sched_d, const kbj_step_criteria* crit, float* sig_d, float* rec_d,
@@ -283,16 +298,12 @@ int kbj_step_response(kbj_ctx* ctx, const kbj_traj* tr, const int32_t* sched_d, 
     if (!(crit->band_abs[k] >= 0.0f)) return kbj_fail(ctx, "kbj_step_response: a band_abs is negative or NaN");
     if (!(crit->min_step[k] >= 0.0f)) return kbj_fail(ctx, "kbj_step_response: a min_step is negative or NaN");
   }
-  if (stats_d && (G < 1 || G > GROUP_REDUCE_THREADS)) return kbj_fail(ctx, "kbj_step_response: G must be in [1, 256]");
+  if (check_groups(ctx, "kbj_step_response", G, stats_d) != 0) return -1;
   KBJ_HIP(ctx, hipSetDevice(ctx->device));      // no kbj_nn_drop_prefetch: no trajectory row is written
   if (launch_step_signal(ctx, tr, sig_d) != 0) return -1;
-  hipLaunchKernelGGL(step_scan_kernel, dim3((tr->N + WINDOW_ENVS - 1) / WINDOW_ENVS), dim3(WINDOW_ENVS), 0, ctx->stream, sig_d, tr->T, tr->N, sched_d, *crit, rec_d);
-  KBJ_CHECK_LAUNCH(ctx, "step_scan_kernel");
-  if (stats_d) {
-    hipLaunchKernelGGL(step_reduce_kernel, dim3(1), dim3(GROUP_REDUCE_THREADS), 0, ctx->stream, rec_d, group_d, tr->N, G, stats_d);
-    KBJ_CHECK_LAUNCH(ctx, "step_reduce_kernel");
-  }
-  return 0;
+  return window_scan_then_reduce<float>(ctx, tr->N, "step_scan_kernel", [&](dim3 grid, dim3 block) {
+    hipLaunchKernelGGL(step_scan_kernel, grid, block, 0, ctx->stream, sig_d, tr->T, tr->N, sched_d, *crit, rec_d);
+  }, step_reduce_kernel, "step_reduce_kernel", rec_d, group_d, G, stats_d);
 }
 
 int kbj_frequency_response(kbj_ctx* ctx, const kbj_traj* tr, const int32_t* sched_d, const kbj_frequency_criteria* crit, float* sig_d, double* rec_d,
@@ -302,16 +313,12 @@ int kbj_frequency_response(kbj_ctx* ctx, const kbj_traj* tr, const int32_t* sche
   if ((reinterpret_cast<uintptr_t>(rec_d) | reinterpret_cast<uintptr_t>(stats_d)) & 7) return kbj_fail(ctx, "kbj_frequency_response: rec_d and stats_d must be 8-byte aligned");
   for (int k = 0; k < KBJ_NSCH; ++k)
     if (!(crit->min_amp[k] >= 0.0f)) return kbj_fail(ctx, "kbj_frequency_response: a min_amp is negative or NaN");
-  if (stats_d && (G < 1 || G > GROUP_REDUCE_THREADS)) return kbj_fail(ctx, "kbj_frequency_response: G must be in [1, 256]");
+  if (check_groups(ctx, "kbj_frequency_response", G, stats_d) != 0) return -1;
   KBJ_HIP(ctx, hipSetDevice(ctx->device));      // no kbj_nn_drop_prefetch: no trajectory row is written
   if (launch_step_signal(ctx, tr, sig_d) != 0) return -1;
-  hipLaunchKernelGGL(freq_scan_kernel, dim3((tr->N + WINDOW_ENVS - 1) / WINDOW_ENVS), dim3(WINDOW_ENVS), 0, ctx->stream, sig_d, tr->T, tr->N, sched_d, *crit, rec_d);
-  KBJ_CHECK_LAUNCH(ctx, "freq_scan_kernel");
-  if (stats_d) {
-    hipLaunchKernelGGL(freq_reduce_kernel, dim3(1), dim3(GROUP_REDUCE_THREADS), 0, ctx->stream, rec_d, group_d, tr->N, G, stats_d);
-    KBJ_CHECK_LAUNCH(ctx, "freq_reduce_kernel");
-  }
-  return 0;
+  return window_scan_then_reduce<double>(ctx, tr->N, "freq_scan_kernel", [&](dim3 grid, dim3 block) {
+    hipLaunchKernelGGL(freq_scan_kernel, grid, block, 0, ctx->stream, sig_d, tr->T, tr->N, sched_d, *crit, rec_d);
+  }, freq_reduce_kernel, "freq_reduce_kernel", rec_d, group_d, G, stats_d);
 }
 
 }  // extern "C"

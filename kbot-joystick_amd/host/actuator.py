@@ -12,9 +12,8 @@ import torch
 from ..spec import constants, layout as L
 from . import binding as B
 from . import dist as dist_util
-from .device_stats import DeviceStats, fresh_stats
-from .sweep import command_label, command_table, failures_per_s, held_command_rollout, table_cell
-from .tracking import ScriptedCommand, command_mode, default_command_grid
+from .device_stats import DeviceStats
+from .sweep import command_sweep, format_command_table, table_cell
 
 V, J, A, E = L.ACT, L.AJNT, L.AACC, L.AENV
 NAN = float("nan")
@@ -147,18 +146,23 @@ def format_actuator_joint_table(table) -> str:
     return "\n".join(lines)
 
 
-def fresh_actuator_stats(ctx, traj, levels, num_envs: int, device, env=None) -> torch.Tensor:
-    """kbj_actuator_stats on a trajectory whose episodes all start with it (every validation and sweep rollout): its KBJ_ACT vector, on the device."""
-    return fresh_stats(dist_util.ACTUATOR_STATS, A["SIZE"], lambda acc, stats: ctx.actuator_stats(traj, levels, acc, stats, env), num_envs, device)
-
-
 class ActuatorStats(DeviceStats):
     """kbj_actuator_stats over the rollouts of a run: every env's previous action and whether its episode runs (KBJ_AACC rows), the KBJ_ACT
-    vectors of the last rollout's rows and of all so far. `levels`: what every call is held against."""
+    vectors of the last rollout's rows and of all so far. `levels`: what every call is held against. `model`, `ctrl_dt`: what `scalars`
+    turns a vector into watts and a cost of transport with."""
+    layout, acc_width, acc_key, total_key = dist_util.ACTUATOR_STATS, A["SIZE"], "act_acc", "act_total"
+    switch, prefix, total_prefix, valid_prefix = "actuator_stats", "act/", "act_total/", "valid/act/"
 
-    def __init__(self, num_envs: int, levels: B.ActuatorLevels, device):
-        self.levels = levels
-        super().__init__(num_envs, A["SIZE"], dist_util.ACTUATOR_STATS, lambda ctx, traj, acc, stats: ctx.actuator_stats(traj, levels, acc, stats), "act_acc", "act_total", device)
+    def __init__(self, num_envs: int, levels: B.ActuatorLevels, device, model=None, ctrl_dt=None):
+        self.levels, self.settings, self.model, self.ctrl_dt = levels, (levels,), model, ctrl_dt
+        super().__init__(num_envs, device)
+
+    @staticmethod
+    def call(ctx, traj, acc, stats, levels, env=None):
+        ctx.actuator_stats(traj, levels, acc, stats, env)
+
+    def scalars(self, vec, prefix: str) -> dict:
+        return actuator_scalars(vec, self.model, self.ctrl_dt, prefix, self.levels)
 
 
 # ---- the sweep ----
@@ -197,29 +201,14 @@ def actuator_sweep(task, commands=None, repeats: int = 2, seconds=None, seed_off
     ScriptedCommand term) with the state record kept; one kbj_actuator_stats call on a fresh carry then gives every env's totals. `levels`:
     keyword arguments of actuator_levels (default: the task config's three level settings). Like the gait and push tables, this one has
     NOT been taken on a trained policy: what a policy fit for the robot looks like in it is not known from this build."""
-    cfg = task.config
-    commands = default_command_grid(task.kcfg) if commands is None else commands
-    if len(commands) == 0 or repeats < 1:
-        raise ValueError("actuator_sweep needs at least one command and one repeat")
+    cfg, dev = task.config, task.device
     lv = actuator_levels(task.model_blob, **levels) if levels else levels_of_config(task.model_blob, cfg)
-    table = command_table(commands)
-    ncmd, n = len(commands), len(commands) * repeats
-    T = max(1, int(round((cfg.render_length_seconds if seconds is None else seconds) / cfg.ctrl_dt)))
-    dev = task.device
-    per_env = torch.from_numpy(np.tile(table, (repeats, 1))).to(dev)                      # env e follows command e % ncmd
-    with held_command_rollout(task, n, T, ScriptedCommand(per_env), seed_offset, record_state=True) as (ctx, tr):
+    with command_sweep(task, "actuator_sweep", commands, repeats, seconds, seed_offset, record_state=True) as (ctx, tr, n, T, entries):
         env = torch.empty(n, E["SIZE"], device=dev)
-        stats = fresh_actuator_stats(ctx, tr.c, lv, n, dev, env)
+        stats = ActuatorStats.fresh(ctx, tr.c, n, dev, lv, env=env)
         ctx.synchronize()
-        rows, done, vec = env.cpu().numpy(), tr.done.cpu().numpy(), stats.cpu().numpy()
-    out = []
-    for i in range(ncmd):
-        envs = list(range(i, n, ncmd))
-        entry = dict(command=tuple(float(x) for x in table[i]), mode=constants.COMMAND_MODE_NAMES[command_mode(table[i])])
-        entry.update(pool_actuator_rows(rows[envs], task.model_blob, cfg.ctrl_dt))
-        entry["failures_per_s"] = failures_per_s(done, envs, repeats * T * cfg.ctrl_dt)
-        out.append(entry)
-    return out, ActuatorRecord(tr.aux, tr.qstate, tr.action, env, vec, lv)
+        rows, vec = env.cpu().numpy(), stats.cpu().numpy()
+    return entries(lambda envs: pool_actuator_rows(rows[envs], task.model_blob, cfg.ctrl_dt)), ActuatorRecord(tr.aux, tr.qstate, tr.action, env, vec, lv)
 
 
 ACTUATOR_TABLE_COLUMNS = (("|P| W", "power_abs_w"), ("P+ W", "power_pos_w"), ("CoT", "cost_of_transport"), ("torque rms", "torque_rms"), ("at level", "at_torque_level_frac"),
@@ -230,9 +219,4 @@ def format_actuator_table(entries) -> str:
     """actuator_sweep's result as a text table: one line per command (its non-zero components by name), then mean |P| and mean positive
     power, the cost of transport, the torque level, the shares of rows with a joint at its torque level and at a stop, the action rate, the
     joint nearest its torque level by fraction and name, and the failures per second ("-" where there was nothing to average)."""
-    labels = [command_label(x["command"]) for x in entries]
-    w = max([len("command")] + [len(s) for s in labels])
-    lines = [f"{'command':{w}s}  {'mode':10s}" + "".join(f"  {title:>10s}" for title, _ in ACTUATOR_TABLE_COLUMNS) + "  worst joint"]
-    for s, x in zip(labels, entries):
-        lines.append(f"{s:{w}s}  {x['mode']:10s}" + "".join(table_cell(x[key]) for _, key in ACTUATOR_TABLE_COLUMNS) + f"  {x['worst_joint']}")
-    return "\n".join(lines)
+    return format_command_table(entries, ACTUATOR_TABLE_COLUMNS, last=("worst joint", "worst_joint"))

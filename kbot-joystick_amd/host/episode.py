@@ -4,11 +4,9 @@ from __future__ import annotations
 
 import math
 
-import torch
-
 from ..spec import constants, layout as L
 from . import dist as dist_util
-from .device_stats import DeviceStats, fresh_stats
+from .device_stats import DeviceStats
 
 
 def episode_stats_scalars(vec, ctrl_dt: float, prefix: str = "episode/", terms: bool = False) -> dict:
@@ -36,15 +34,23 @@ def episode_stats_scalars(vec, ctrl_dt: float, prefix: str = "episode/", terms: 
     return out
 
 
-def fresh_episode_stats(ctx, traj, num_envs: int, device) -> torch.Tensor:
-    """kbj_episode_stats on a trajectory whose episodes all start with it (every validation rollout): its KBJ_EPST vector, on the device."""
-    return fresh_stats(dist_util.EPISODE_STATS, L.EACC["SIZE"], lambda acc, stats: ctx.episode_stats(traj, acc, stats), num_envs, device)
-
-
 class EpisodeStats(DeviceStats):
     """kbj_episode_stats over the rollouts of a run: the episodes in flight per env (KBJ_EACC rows), the KBJ_EPST vectors of the episodes that
-    finished in the last rollout and of all so far."""
+    finished in the last rollout and of all so far. `terms`: the trajectory keeps the reward terms (log_reward_components), so the vectors
+    hold their episodic sums."""
+    layout, acc_width, acc_key, total_key = dist_util.EPISODE_STATS, L.EACC["SIZE"], "ep_acc", "ep_total"
+    switch, prefix, total_prefix, valid_prefix = "episode_stats", "episode/", "episode_total/", "valid/episode/"
 
-    def __init__(self, num_envs: int, device):
-        super().__init__(num_envs, L.EACC["SIZE"], dist_util.EPISODE_STATS, lambda ctx, traj, acc, stats: ctx.episode_stats(traj, acc, stats),
-                         "ep_acc", "ep_total", device)
+    def __init__(self, num_envs: int, ctrl_dt: float, terms: bool, device):
+        self.ctrl_dt, self.terms = ctrl_dt, terms
+        super().__init__(num_envs, device)
+
+    @staticmethod
+    def call(ctx, traj, acc, stats):
+        ctx.episode_stats(traj, acc, stats)
+
+    def scalars(self, vec, prefix: str, terms=None) -> dict:
+        return episode_stats_scalars(vec, self.ctrl_dt, prefix, self.terms if terms is None else terms)
+
+    def valid_scalars(self, vec) -> dict:
+        return self.scalars(vec, self.valid_prefix, terms=True)      # validate()'s trajectory always keeps the reward terms

@@ -19,7 +19,7 @@ import torch
 
 from ..spec import constants, layout as L
 from . import binding as B
-from .sweep import case_of_env, command_label, command_table, held_command_rollout, steps_of, table_cell
+from .sweep import case_envs, command_label, command_table, held_command_rollout, steps_of, table_cell
 
 R, S, O = L.FREC, L.FSTAT, L.FOUT
 CHANNELS = constants.STEP_CHANNEL_NAMES
@@ -141,23 +141,18 @@ def frequency_sweep(task, points=None, periods=None, cycles: int = 4, min_window
     if len(min_amp) != L.NSCH:
         raise ValueError(f"frequency_sweep: min_amp has one value per channel {CHANNELS}")
     cases = [(i, P) for i in range(len(points)) for P in plist]
-    if len(cases) > 256:
-        raise ValueError(f"frequency_sweep: {len(cases)} cases, kbj_frequency_response groups at most 256")
     start, settle_rows = steps_of(start_at, dt), steps_of(settle, dt)
     sk = [case_schedule(P, dt, cycles, min_window, start, settle_rows) for _, P in cases]
     for (_, P), (s, _) in zip(cases, sk):
         if s < P // 4:
             raise ValueError(f"frequency_sweep: start_at + settle puts the first measured row of the {P}-row period on row {s}; it needs {P // 4} rows (a quarter period) in front of it")
-    ncases, n = len(cases), len(cases) * repeats
+    ncases = len(cases)
     T = max(s + K * P for (_, P), (s, K) in zip(cases, sk))
-    dev = task.device
-    env_case = np.arange(n) % ncases                                      # env e runs case e % ncases
-    env_point = np.array([cases[c][0] for c in env_case])
-    sched_h = np.array([[sk[c][0], cases[c][1], chan[cases[c][0]], sk[c][1]] for c in env_case], np.int32)
-    command = SineCommand(torch.from_numpy(base[env_point]).to(dev), [chan[i] for i in env_point], [amps[i] for i in env_point], sched_h[:, 1], start)
+    sched_c = np.array([[s, P, chan[i], K] for (i, P), (s, K) in zip(cases, sk)], np.int32)
+    n, group, (base_env, sched) = case_envs(task, ncases, repeats, f"frequency_sweep: {ncases} cases, kbj_frequency_response", base[[i for i, _ in cases]], sched_c)
+    dev = task.device                                                     # env e runs case e % ncases
+    command = SineCommand(base_env, [chan[i] for i, _ in cases] * repeats, [amps[i] for i, _ in cases] * repeats, [P for _, P in cases] * repeats, start)
     with held_command_rollout(task, n, T, command, seed_offset) as (ctx, tr):
-        sched = torch.from_numpy(sched_h).to(dev)
-        group = case_of_env(n, ncases, dev)
         crit = B.FrequencyCriteria((B.C.c_float * L.NSCH)(*min_amp))
         sig = torch.empty(T, n, L.SSIG["SIZE"], device=dev)
         rec = torch.empty(n, R["SIZE"], dtype=torch.float64, device=dev)

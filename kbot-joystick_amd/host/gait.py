@@ -11,9 +11,8 @@ import torch
 
 from ..spec import constants, layout as L
 from . import dist as dist_util
-from .device_stats import DeviceStats, fresh_stats
-from .sweep import command_label, command_table, failures_per_s, held_command_rollout, table_cell
-from .tracking import ScriptedCommand, command_mode, default_command_grid
+from .device_stats import DeviceStats
+from .sweep import command_sweep, format_command_table
 
 G, F, A, E = L.GAIT, L.GFOOT, L.GACC, L.GENV
 FEET = ("left", "right")
@@ -70,17 +69,22 @@ def gait_scalars(vec, ctrl_dt: float, prefix: str = "gait/") -> dict:
     return out
 
 
-def fresh_gait_stats(ctx, traj, num_envs: int, device, env=None) -> torch.Tensor:
-    """kbj_gait_stats on a trajectory whose episodes all start with it (every validation rollout): its KBJ_GAIT vector, on the device."""
-    return fresh_stats(dist_util.GAIT_STATS, A["SIZE"], lambda acc, stats: ctx.gait_stats(traj, acc, stats, env), num_envs, device)
-
-
 class GaitStats(DeviceStats):
     """kbj_gait_stats over the rollouts of a run: the phase each foot of each env is in and since when (KBJ_GACC rows), the KBJ_GAIT vectors of
     the last rollout's rows and of all so far."""
+    layout, acc_width, acc_key, total_key = dist_util.GAIT_STATS, A["SIZE"], "gait_acc", "gait_total"
+    switch, prefix, total_prefix, valid_prefix = "gait_stats", "gait/", "gait_total/", "valid/gait/"
 
-    def __init__(self, num_envs: int, device):
-        super().__init__(num_envs, A["SIZE"], dist_util.GAIT_STATS, lambda ctx, traj, acc, stats: ctx.gait_stats(traj, acc, stats), "gait_acc", "gait_total", device)
+    def __init__(self, num_envs: int, ctrl_dt: float, device):
+        self.ctrl_dt = ctrl_dt
+        super().__init__(num_envs, device)
+
+    @staticmethod
+    def call(ctx, traj, acc, stats, env=None):
+        ctx.gait_stats(traj, acc, stats, env)
+
+    def scalars(self, vec, prefix: str) -> dict:
+        return gait_scalars(vec, self.ctrl_dt, prefix)
 
 
 # ---- the sweep ----
@@ -119,28 +123,13 @@ def gait_sweep(task, commands=None, repeats: int = 2, seconds=None, seed_offset:
     """The sweep behind HumanoidWalkingTask.gait_sweep (see there): returns (entries, record) - one entry per command, and the GaitRecord of
     what the run left on the device. The rollout is tracking_sweep's (host/sweep.py sweep_rollout under a ScriptedCommand term); one
     kbj_gait_stats call on a fresh carry then gives every env's totals."""
-    cfg = task.config
-    commands = default_command_grid(task.kcfg) if commands is None else commands
-    if len(commands) == 0 or repeats < 1:
-        raise ValueError("gait_sweep needs at least one command and one repeat")
-    table = command_table(commands)
-    ncmd, n = len(commands), len(commands) * repeats
-    T = max(1, int(round((cfg.render_length_seconds if seconds is None else seconds) / cfg.ctrl_dt)))
-    dev = task.device
-    per_env = torch.from_numpy(np.tile(table, (repeats, 1))).to(dev)                      # env e follows command e % ncmd
-    with held_command_rollout(task, n, T, ScriptedCommand(per_env), seed_offset) as (ctx, tr):
+    dev, dt = task.device, task.config.ctrl_dt
+    with command_sweep(task, "gait_sweep", commands, repeats, seconds, seed_offset) as (ctx, tr, n, T, entries):
         env = torch.empty(n, E["SIZE"], device=dev)
-        stats = fresh_gait_stats(ctx, tr.c, n, dev, env)
+        stats = GaitStats.fresh(ctx, tr.c, n, dev, env=env)
         ctx.synchronize()
-        rows, done, vec = env.cpu().numpy(), tr.done.cpu().numpy(), stats.cpu().numpy()
-    out = []
-    for i in range(ncmd):
-        envs = list(range(i, n, ncmd))
-        entry = dict(command=tuple(float(x) for x in table[i]), mode=constants.COMMAND_MODE_NAMES[command_mode(table[i])])
-        entry.update(pool_gait_rows(rows[envs], cfg.ctrl_dt))
-        entry["failures_per_s"] = failures_per_s(done, envs, repeats * T * cfg.ctrl_dt)
-        out.append(entry)
-    return out, GaitRecord(tr.aux, env, vec)
+        rows, vec = env.cpu().numpy(), stats.cpu().numpy()
+    return entries(lambda envs: pool_gait_rows(rows[envs], dt)), GaitRecord(tr.aux, env, vec)
 
 
 GAIT_TABLE_COLUMNS = (("L swing s", "left_swing_s"), ("R swing s", "right_swing_s"), ("L stance s", "left_stance_s"), ("R stance s", "right_stance_s"),
@@ -154,9 +143,4 @@ def format_gait_table(entries) -> str:
     """gait_sweep's result as a text table: one line per command (its non-zero components by name), then per foot the mean swing and stance
     time, mean and largest clearance and peak force, the step rate, the three support shares, the repeat share, the torque level and the
     failures per second ("-" where there was nothing to average)."""
-    labels = [command_label(x["command"]) for x in entries]
-    w = max([len("command")] + [len(s) for s in labels])
-    lines = [f"{'command':{w}s}  {'mode':10s}" + "".join(f"  {title:>10s}" for title, _ in GAIT_TABLE_COLUMNS)]
-    for s, x in zip(labels, entries):
-        lines.append(f"{s:{w}s}  {x['mode']:10s}" + "".join(table_cell(x[key]) for _, key in GAIT_TABLE_COLUMNS))
-    return "\n".join(lines)
+    return format_command_table(entries, GAIT_TABLE_COLUMNS)

@@ -11,8 +11,8 @@ import torch
 
 from ..spec import constants, layout as L
 from . import binding as B
-from .sweep import case_of_env, command_table, steps_of, sweep_rollout, sweep_terms
-from .tracking import fresh_tracking_stats
+from .sweep import case_envs, command_table, steps_of, sweep_rollout, sweep_terms
+from .tracking import TrackingStats
 from .traj_view import PushRequest
 
 P, S, O = L.PREC, L.PSTAT, L.POUT
@@ -80,8 +80,6 @@ def push_sweep(task, forces=(50.0, 100.0, 150.0, 200.0), directions_deg=(0, 45, 
     cases = [(f, a) for f in forces for a in directions_deg]
     if not cases or repeats < 1:
         raise ValueError("push_sweep needs at least one force, one direction and one repeat")
-    if len(cases) > 256:
-        raise ValueError(f"push_sweep: {len(cases)} cases, kbj_push_recovery groups at most 256")
     tol = dict(DEFAULT_TOLERANCES)
     tol.update(tolerances or {})
     if set(tol) != set(constants.TRACKING_ERROR_NAMES):
@@ -91,14 +89,12 @@ def push_sweep(task, forces=(50.0, 100.0, 150.0, 200.0), directions_deg=(0, 45, 
     row, d, win, hld = steps_of(push_at, dt), steps_of(duration, dt), steps_of(window, dt), max(1, steps_of(hold, dt))
     if row < hld or d < 0 or win < 0:
         raise ValueError("push_sweep: push_at must leave room for the hold rows in front of the push; duration and window must not be negative")
-    ncases, n, T = len(cases), len(cases) * repeats, row + d + win
-    dev = task.device
+    ncases, T = len(cases), row + d + win
     tq = np.zeros(3, np.float32) if torque is None else np.asarray(torque, np.float32).reshape(3)
-    local = np.zeros((n, 6), np.float32)
-    for e in range(n):                                                                    # env e runs case e % ncases
-        f, a = cases[e % ncases]
-        local[e] = (f * math.cos(math.radians(a)), f * math.sin(math.radians(a)), 0.0, *tq)
-    event = ScriptedPush(torch.from_numpy(local).to(dev), torch.full((n,), float(d), device=dev), row)
+    wrench = np.array([(f * math.cos(math.radians(a)), f * math.sin(math.radians(a)), 0.0, *tq) for f, a in cases], np.float32)
+    n, group, (local,) = case_envs(task, ncases, repeats, f"push_sweep: {ncases} cases, kbj_push_recovery", wrench)      # env e runs case e % ncases
+    dev = task.device
+    event = ScriptedPush(local, torch.full((n,), float(d), device=dev), row)
     terms = sweep_terms(task, events={"scripted_push": event})
     hooks = [terms.apply_resets, terms.apply_events] + ([terms.observe_rows] if any(task.extra_obs) else [])
     T = max(1, T)
@@ -110,9 +106,8 @@ def push_sweep(task, forces=(50.0, 100.0, 150.0, 200.0), directions_deg=(0, 45, 
 
     with sweep_rollout(task, n, T, configure, terms, hooks, hooks, seed_offset) as (ctx, tr):
         err = torch.empty(T, n, L.TERR["SIZE"], device=dev)
-        fresh_tracking_stats(ctx, tr.c, n, 0, dev, err)
+        TrackingStats.fresh(ctx, tr.c, n, dev, 0, err=err)
         sched = torch.tensor([[row, d]] * n, dtype=torch.int32, device=dev)
-        group = case_of_env(n, ncases, dev)
         crit = B.PushCriteria((B.C.c_float * L.NTERR)(*[tol[k] for k in constants.TRACKING_ERROR_NAMES]), hld, win)
         rec = torch.empty(n, P["SIZE"], device=dev)
         stats = torch.empty(ncases, S["SIZE"], dtype=torch.float64, device=dev)

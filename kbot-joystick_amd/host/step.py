@@ -10,7 +10,7 @@ import torch
 
 from ..spec import constants, layout as L
 from . import binding as B
-from .sweep import case_of_env, command_label, command_table, held_command_rollout, steps_of, table_cell
+from .sweep import case_envs, command_label, command_table, held_command_rollout, steps_of, table_cell
 
 R, S, O = L.SREC, L.SSTAT, L.SOUT
 CHANNELS = constants.STEP_CHANNEL_NAMES
@@ -72,8 +72,6 @@ def step_sweep(task, transitions=None, step_at: float = 3.0, window: float = 4.0
     transitions = default_step_grid(task.kcfg) if transitions is None else list(transitions)
     if not transitions or repeats < 1:
         raise ValueError("step_sweep needs at least one transition and one repeat")
-    if len(transitions) > 256:
-        raise ValueError(f"step_sweep: {len(transitions)} transitions, kbj_step_response groups at most 256")
     if any(len(tr) != 2 for tr in transitions):
         raise ValueError("step_sweep: a transition is a pair (from command, to command)")
     t0, t1 = (command_table([tr[k] for tr in transitions], "step_sweep: the " + end + " command of transition {i}") for k, end in enumerate(("from", "to")))
@@ -87,12 +85,11 @@ def step_sweep(task, transitions=None, step_at: float = 3.0, window: float = 4.0
     band_abs, min_step = [float(x) for x in band_abs], [float(x) for x in min_step]
     if len(band_abs) != L.NSCH or len(min_step) != L.NSCH:
         raise ValueError(f"step_sweep: band_abs and min_step have one value per channel {CHANNELS}")
-    ncases, n, T = len(transitions), len(transitions) * repeats, row + win
+    ncases, T = len(transitions), row + win
+    n, group, (per_env0, per_env1) = case_envs(task, ncases, repeats, f"step_sweep: {ncases} transitions, kbj_step_response", t0, t1)      # env e runs case e % ncases
     dev = task.device
-    per_env0, per_env1 = (torch.from_numpy(np.tile(t, (repeats, 1))).to(dev) for t in (t0, t1))       # env e runs case e % ncases
     with held_command_rollout(task, n, T, SteppedCommand(per_env0, per_env1, row), seed_offset) as (ctx, tr):
         sched = torch.full((n,), row, dtype=torch.int32, device=dev)
-        group = case_of_env(n, ncases, dev)
         crit = B.StepCriteria((B.C.c_float * L.NSCH)(*min_step), (B.C.c_float * L.NSCH)(*band_abs), band_frac, rise_level, m, hld, win)
         sig = torch.empty(T, n, L.SSIG["SIZE"], device=dev)
         rec = torch.empty(n, R["SIZE"], device=dev)

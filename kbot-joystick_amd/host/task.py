@@ -25,16 +25,15 @@ from . import ckpt as ckpt_io
 from . import dist as dist_util
 from . import wiring
 from .buffers import CarryBuffers, TrajBuffers
-from .actuator import (ActuatorStats, actuator_joint_table, actuator_scalars, actuator_sweep, format_actuator_joint_table, format_actuator_table,      # noqa: F401 (re-exported)
-                       fresh_actuator_stats, levels_of_config)
+from .actuator import ActuatorStats, actuator_joint_table, actuator_sweep, format_actuator_joint_table, format_actuator_table, levels_of_config      # noqa: F401 (re-exported)
 from .ckpt import ModelView
 from .config import HumanoidWalkingTaskConfig, cosine_decay_lr, launch_config      # launch_config: re-exported with the rest
-from .episode import EpisodeStats, episode_stats_scalars, fresh_episode_stats
+from .episode import EpisodeStats, episode_stats_scalars      # noqa: F401 (re-exported)
 from .frequency import FrequencyRecord, SineCommand, format_frequency_table, frequency_sweep      # noqa: F401 (re-exported)
-from .gait import GaitStats, format_gait_table, fresh_gait_stats, gait_scalars, gait_sweep      # noqa: F401 (re-exported)
+from .gait import GaitStats, format_gait_table, gait_sweep      # noqa: F401 (re-exported)
 from .push import PushRecord, ScriptedPush, format_push_table, push_sweep      # noqa: F401 (re-exported)
 from .step import StepRecord, SteppedCommand, format_step_table, step_sweep      # noqa: F401 (re-exported)
-from .tracking import TrackingStats, format_tracking_table, fresh_tracking_stats, settle_steps, tracking_scalars, tracking_sweep      # noqa: F401 (re-exported)
+from .tracking import TrackingStats, format_tracking_table, settle_steps, tracking_sweep      # noqa: F401 (re-exported)
 from .user_terms import UserTerms
 
 
@@ -47,15 +46,6 @@ class _Validation(NamedTuple):
     ctx: B.Context
     carry: CarryBuffers
     traj: TrajBuffers
-
-
-class _Accounted(NamedTuple):
-    """One statistic the device keeps over the rollouts, switched on in the config."""
-    carrier: object             # the DeviceStats: per-env rows, the last rollout's vector, the totals
-    logged: object              # () -> dict: the task's own <name>_stats(), what scalars() logs
-    fresh: object               # (ctx, traj, num_envs) -> the vector of a trajectory whose episodes all start with it, on the device
-    as_scalars: object          # (vec, prefix) -> dict: such a vector as logger scalars
-    valid_prefix: str           # the prefix of validate()'s scalars
 
 
 class HumanoidWalkingTask:
@@ -149,29 +139,16 @@ class HumanoidWalkingTask:
                                 terminal_value=bool(self.kcfg.gae_terminal_value))
         if self.kcfg.gae_terminal_value:        # the buffer kbj_rollout writes and kbj_gae reads (bootstrap_terminal_value)
             self.ctx.set_terminal_values(self.traj.value_term)
-        # episode accounting (config.episode_stats; host/episode.py): `ep_acc`, the per-env accumulator rows next to the env state, and
-        # `ep_stats`, one call's result, are the object's own tensors; ep_acc is None means off
-        self.episodes = EpisodeStats(self.N, self.device) if config.episode_stats else None
-        self.ep_acc, self.ep_stats = (self.episodes.acc, self.episodes.stats) if self.episodes is not None else (None, None)
-        # command-tracking errors (config.tracking_stats; host/tracking.py): `trk_acc`, the per-env carry rows next to the env state; None means off
-        self.tracking = TrackingStats(self.N, settle_steps(config.tracking_settle_seconds, config.ctrl_dt), self.device) if config.tracking_stats else None
-        self.trk_acc = self.tracking.acc if self.tracking is not None else None
-        # gait statistics (config.gait_stats; host/gait.py): `gait.acc`, the per-env carry rows next to the env state; None means off
-        self.gait = GaitStats(self.N, self.device) if config.gait_stats else None
-        # actuator statistics (config.actuator_stats; host/actuator.py): `actuator.acc`, the per-env carry rows next to the env state, and the levels
-        # every call is held against; None means off. to_kbj() has refused the switch without record_state
-        self.actuator = ActuatorStats(self.N, levels_of_config(self.model_blob, config), self.device) if config.actuator_stats else None
+        # the statistics the device keeps over the rollouts, each switched on in the config (episode_stats, tracking_stats, gait_stats,
+        # actuator_stats; host/episode.py, tracking.py, gait.py, actuator.py): the carrier's `acc` are the per-env rows next to the env state;
+        # None means off. to_kbj() has refused actuator_stats without record_state
+        N, dev, dt = self.N, self.device, config.ctrl_dt
+        self.episodes = EpisodeStats(N, dt, config.log_reward_components, dev) if config.episode_stats else None
+        self.tracking = TrackingStats(N, settle_steps(config.tracking_settle_seconds, dt), dev) if config.tracking_stats else None
+        self.gait = GaitStats(N, dt, dev) if config.gait_stats else None
+        self.actuator = ActuatorStats(N, levels_of_config(self.model_blob, config), dev, self.model_blob, dt) if config.actuator_stats else None
         # those that are on, in the order of the checkpoint members and of the scalar keys
-        dev, dt = self.device, config.ctrl_dt
-        self._accounted = [a for a in (
-            _Accounted(self.episodes, self.episode_stats, lambda ctx, traj, n: fresh_episode_stats(ctx, traj, n, dev),
-                       lambda vec, prefix: episode_stats_scalars(vec, dt, prefix, terms=True), "valid/episode/"),
-            _Accounted(self.tracking, self.tracking_stats, lambda ctx, traj, n: fresh_tracking_stats(ctx, traj, n, self.tracking.settle_steps, dev),
-                       tracking_scalars, "valid/track/"),
-            _Accounted(self.gait, self.gait_stats, lambda ctx, traj, n: fresh_gait_stats(ctx, traj, n, dev),
-                       lambda vec, prefix: gait_scalars(vec, dt, prefix), "valid/gait/"),
-            _Accounted(self.actuator, self.actuator_stats, lambda ctx, traj, n: fresh_actuator_stats(ctx, traj, self.actuator.levels, n, dev),
-                       lambda vec, prefix: actuator_scalars(vec, self.model_blob, dt, prefix, self.actuator.levels), "valid/act/")) if a.carrier is not None]
+        self._carriers = [c for c in (self.episodes, self.tracking, self.gait, self.actuator) if c is not None]
         self.opt_step = 0
         self.iteration = 0
         self._perm_gen = torch.Generator(device="cpu")
@@ -209,16 +186,35 @@ class HumanoidWalkingTask:
         if self.extra_rewards:
             from .traj_view import apply_extra_rewards
             self.extra_reward_means = apply_extra_rewards(self.extra_rewards, self._extra_carries, self.trajectory(), self.traj.reward)
-        for a in self._accounted:                 # behind the user rewards, so that the episodes count them (tracking and gait read the aux rows alone);
-            a.carrier.after_rollout(self.ctx, self.traj.c)      # user terminations are in the DONE column already
+        for c in self._carriers:                  # behind the user rewards, so that the episodes count them (tracking and gait read the aux rows alone);
+            c.after_rollout(self.ctx, self.traj.c)      # user terminations are in the DONE column already
+
+    def _stats_vectors(self, carrier, cls):
+        """(last, total) of `carrier` (copies) - or the refusal, when the switch of its class `cls` is off."""
+        if carrier is None:
+            raise B.KbjError(f"{cls.switch}_vectors() needs HumanoidWalkingTaskConfig.{cls.switch}=True")
+        last, total = carrier.vectors()
+        return last.copy(), total.copy()
+
+    def _reduced_stats(self, carrier, cls, which) -> np.ndarray:
+        """`carrier`'s vectors()[which] (which = None: both, stacked) over all ranks' envs: ONE StatsLayout.reduce, which every rank must
+        call - or the refusal, when the switch of its class `cls` is off."""
+        if carrier is None:
+            raise B.KbjError(f"{cls.switch}() needs HumanoidWalkingTaskConfig.{cls.switch}=True")
+        vec = np.stack(carrier.vectors()) if which is None else carrier.vectors()[which]
+        if self.world_size > 1 or dist_util.FORCE_COLLECTIVE:
+            vec = carrier.layout.reduce(torch.from_numpy(vec).to(self.device), self.world_size).cpu().numpy()
+        return vec
+
+    def _mode_stats(self, carrier, cls, total: bool) -> dict:
+        """The last rollout's vector of `carrier`, or the totals', reduced over the ranks, as scalars under the prefix that goes with it."""
+        vec = self._reduced_stats(carrier, cls, 1 if total else 0)
+        return carrier.scalars(vec, cls.total_prefix if total else cls.prefix)
 
     def actuator_stats_vectors(self):
         """(last, total): this rank's raw KBJ_ACT vectors (float64 numpy, layout.ACT / AJNT) behind actuator_stats() - the rows of the last
         rollout and all since creation / resume."""
-        if self.actuator is None:
-            raise B.KbjError("actuator_stats_vectors() needs HumanoidWalkingTaskConfig.actuator_stats=True")
-        last, total = self.actuator.vectors()
-        return last.copy(), total.copy()
+        return self._stats_vectors(self.actuator, ActuatorStats)
 
     def actuator_stats(self, total: bool = False, per_joint: bool = False):
         """What the policy asks of the motors (needs `actuator_stats=True` and `record_state=True` in the config) over the LAST rollout - or,
@@ -228,14 +224,9 @@ class HumanoidWalkingTask:
         kbj_actuator_stats). With `per_joint` instead the per-joint table of all rows together (actuator_joint_table: a dict per joint;
         `format_actuator_joint_table` renders it). In a multi-rank job the vectors are reduced over the ranks
         (dist.reduce_actuator_stats): every rank must call it."""
-        if self.actuator is None:
-            raise B.KbjError("actuator_stats() needs HumanoidWalkingTaskConfig.actuator_stats=True")
-        vec = self.actuator.vectors()[1 if total else 0]
-        if self.world_size > 1 or dist_util.FORCE_COLLECTIVE:
-            vec = dist_util.reduce_actuator_stats(torch.from_numpy(vec).to(self.device), self.world_size).cpu().numpy()
         if per_joint:
-            return actuator_joint_table(vec, self.model_blob, self.config.ctrl_dt)
-        return actuator_scalars(vec, self.model_blob, self.config.ctrl_dt, "act_total/" if total else "act/", self.actuator.levels)
+            return actuator_joint_table(self._reduced_stats(self.actuator, ActuatorStats, 1 if total else 0), self.model_blob, self.config.ctrl_dt)
+        return self._mode_stats(self.actuator, ActuatorStats, total)
 
     def actuator_sweep(self, commands=None, repeats: int = 2, seconds: Optional[float] = None, seed_offset: int = 7919, **levels) -> list:
         """The actuator table: what the CURRENT policy asks of the motors under each of `commands` (as tracking_sweep takes them; default:
@@ -253,10 +244,7 @@ class HumanoidWalkingTask:
     def gait_stats_vectors(self):
         """(last, total): this rank's raw KBJ_GAIT vectors (float64 numpy, layout.GAIT / GFOOT) behind gait_stats() - the rows of the last
         rollout and all since creation / resume."""
-        if self.gait is None:
-            raise B.KbjError("gait_stats_vectors() needs HumanoidWalkingTaskConfig.gait_stats=True")
-        last, total = self.gait.vectors()
-        return last.copy(), total.copy()
+        return self._stats_vectors(self.gait, GaitStats)
 
     def gait_stats(self, total: bool = False) -> dict:
         """How the robot walks (needs `gait_stats=True` in the config) over the LAST rollout - or, with `total`, over all rollouts since the
@@ -265,12 +253,7 @@ class HumanoidWalkingTask:
         `left_` / `right_` `swing_s_mean` / `_std` / `_max`, `stance_s_mean` / `_std` / `_max`, `duty`, `clearance_m_mean` / `_max`,
         `force_n_mean` / `_max`, and `swing_asymmetry` (host/gait.py gait_scalars; the definitions: include/kbj.h kbj_gait_stats). In a
         multi-rank job the vectors are reduced over the ranks (dist.reduce_gait_stats): every rank must call it."""
-        if self.gait is None:
-            raise B.KbjError("gait_stats() needs HumanoidWalkingTaskConfig.gait_stats=True")
-        vec = self.gait.vectors()[1 if total else 0]
-        if self.world_size > 1 or dist_util.FORCE_COLLECTIVE:
-            vec = dist_util.reduce_gait_stats(torch.from_numpy(vec).to(self.device), self.world_size).cpu().numpy()
-        return gait_scalars(vec, self.config.ctrl_dt, "gait_total/" if total else "gait/")
+        return self._mode_stats(self.gait, GaitStats, total)
 
     def gait_sweep(self, commands=None, repeats: int = 2, seconds: Optional[float] = None, seed_offset: int = 7919) -> list:
         """The gait table: how the CURRENT policy walks under each of `commands` (as tracking_sweep takes them; default:
@@ -287,10 +270,7 @@ class HumanoidWalkingTask:
     def tracking_stats_vectors(self):
         """(last, total): this rank's raw KBJ_TRK vectors (float64 numpy, layout.TRK) behind tracking_stats() - the rows of the last rollout
         and all since creation / resume."""
-        if self.tracking is None:
-            raise B.KbjError("tracking_stats_vectors() needs HumanoidWalkingTaskConfig.tracking_stats=True")
-        last, total = self.tracking.vectors()
-        return last.copy(), total.copy()
+        return self._stats_vectors(self.tracking, TrackingStats)
 
     def tracking_stats(self, total: bool = False) -> dict:
         """Command-tracking errors (needs `tracking_stats=True` in the config) of the LAST rollout - or, with `total`, of all rollouts since the
@@ -298,12 +278,7 @@ class HumanoidWalkingTask:
         for lin_vel_err (m/s), yaw_rate_err (rad/s), tilt_err, height_err (m), arm_sq_err (rad^2) over the rows whose command has been held
         for `tracking_settle_seconds`, `rows_frac` (the mode's share of all rows) and `settled_frac`. In a multi-rank job the vectors are
         reduced over the ranks (dist.reduce_tracking_stats): every rank must call it."""
-        if self.tracking is None:
-            raise B.KbjError("tracking_stats() needs HumanoidWalkingTaskConfig.tracking_stats=True")
-        vec = self.tracking.vectors()[1 if total else 0]
-        if self.world_size > 1 or dist_util.FORCE_COLLECTIVE:
-            vec = dist_util.reduce_tracking_stats(torch.from_numpy(vec).to(self.device), self.world_size).cpu().numpy()
-        return tracking_scalars(vec, "track_total/" if total else "track/")
+        return self._mode_stats(self.tracking, TrackingStats, total)
 
     def tracking_sweep(self, commands=None, repeats: int = 2, seconds: Optional[float] = None, settle_seconds: Optional[float] = None) -> list:
         """The joystick response table: how well the CURRENT policy follows each of `commands` ([K][<= 16] floats, missing components zero;
@@ -383,26 +358,15 @@ class HumanoidWalkingTask:
     def episode_stats_vectors(self):
         """(last, total): this rank's raw KBJ_EPST vectors (float64 numpy, layout.EPST) behind episode_stats() - the episodes that finished in
         the last rollout and all since creation / resume."""
-        if self.ep_acc is None:
-            raise B.KbjError("episode_stats_vectors() needs HumanoidWalkingTaskConfig.episode_stats=True")
-        last, total = self.episodes.vectors()
-        return last.copy(), total.copy()
+        return self._stats_vectors(self.episodes, EpisodeStats)
 
     def episode_stats(self) -> dict:
         """Episode metrics (needs `episode_stats=True` in the config): `episode/...` over the episodes that finished in the LAST rollout,
         `episode_total/...` over all that finished since the task was created or resumed - count, return mean / std / min / max, length
         and time to failure in seconds, fractions per termination cause and, with `log_reward_components`, the mean episodic sum of every
         reward term. In a multi-rank job the vectors are reduced over the ranks (dist.reduce_episode_stats): every rank must call it."""
-        if self.ep_acc is None:
-            raise B.KbjError("episode_stats() needs HumanoidWalkingTaskConfig.episode_stats=True")
-        last, total = self.episodes.vectors()
-        if self.world_size > 1 or dist_util.FORCE_COLLECTIVE:
-            both = dist_util.reduce_episode_stats(torch.from_numpy(np.stack([last, total])).to(self.device), self.world_size).cpu().numpy()
-            last, total = both[0], both[1]
-        terms = self.traj.comps is not None
-        out = episode_stats_scalars(last, self.config.ctrl_dt, "episode/", terms)
-        out.update(episode_stats_scalars(total, self.config.ctrl_dt, "episode_total/", terms))
-        return out
+        last, total = self._reduced_stats(self.episodes, EpisodeStats, None)      # both from one stacked reduce
+        return {**self.episodes.scalars(last, EpisodeStats.prefix), **self.episodes.scalars(total, EpisodeStats.total_prefix)}
 
     def trajectory(self):
         """The last rollout as the Python reward terms see it: with `config.record_state` a ksim-shaped `host.trajectory.Trajectory`
@@ -595,8 +559,8 @@ class HumanoidWalkingTask:
         if self.mirror:
             extras.update(actor_mirror_hc=self.carry.actor_mirror_hc.cpu().numpy(), critic_mirror_hc=self.carry.critic_mirror_hc.cpu().numpy(),
                           lpf_mirror=self.carry.lpf_mirror.cpu().numpy())
-        for a in self._accounted:
-            extras.update(a.carrier.checkpoint_state())
+        for c in self._carriers:
+            extras.update(c.checkpoint_state())
         # carries of Python StatefulReward terms (extra_rewards): tensors (or tuples / lists of tensors) per term name
         for name, carry in self._extra_carries.items():
             leaves = list(carry) if isinstance(carry, (tuple, list)) else [carry]
@@ -655,8 +619,8 @@ class HumanoidWalkingTask:
         # a resumed run's row 0 already carries the user observation columns and the user command term's commands, its env rows the user Reset terms' state
         self.terms.started = self.iteration > 0
         x = z["extras"]
-        for a in self._accounted:
-            a.carrier.load_checkpoint_state(x)
+        for c in self._carriers:
+            c.load_checkpoint_state(x)
         if "es" not in x:
             return            # a model-only checkpoint (e.g. written by the reference): parameters and optimizer only
         if x["es"].shape[0] != self.N:
@@ -752,7 +716,7 @@ class HumanoidWalkingTask:
             terms.run_steps(vctx, tr, carry, self.params, T, seed=seed, first_step=0, argmax=True, first_index=seed_offset, hooks=hooks)
             vctx.rewards(tr.aux, T, tr.reward, tr.comps)
         # the same kernels on the validation trajectory, on the fused and on the step-wise path: every validation starts its episodes and carries afresh
-        vecs = [a.fresh(vctx, tr.c, num_envs) for a in self._accounted]
+        vecs = [c.fresh(vctx, tr.c, num_envs, self.device, *c.settings) for c in self._carriers]
         vctx.synchronize()
         done = tr.done
         fails, succ = float((done < 0).sum()), float((done > 0).sum())
@@ -760,8 +724,8 @@ class HumanoidWalkingTask:
                "valid/episode_length_s": float(T * num_envs / max(1.0, fails + succ + num_envs) * self.config.ctrl_dt), "valid/value_mean": float(tr.value.mean())}
         for name, v in zip(constants.REWARD_NAMES, tr.comps.mean(dim=(0, 1)).cpu().tolist()):
             out[f"valid/reward/{name}"] = v
-        for a, vec in zip(self._accounted, vecs):
-            out.update(a.as_scalars(vec.cpu().numpy(), a.valid_prefix))
+        for c, vec in zip(self._carriers, vecs):
+            out.update(c.valid_scalars(vec.cpu().numpy()))
         return out
 
     def close_validation(self):
@@ -814,8 +778,8 @@ class HumanoidWalkingTask:
         if self.traj.comps is not None:
             for name, v in self.reward_components().items():
                 out[f"reward/{name}"] = v
-        for a in self._accounted:        # the results came back behind the kernels: the sync above is already past them
-            out.update(a.logged())
+        for c in self._carriers:         # the results came back behind the kernels: the sync above is already past them
+            out.update(self.episode_stats() if c is self.episodes else self._mode_stats(c, type(c), False))      # what <switch>() returns
         return out
 
     def export_actor(self, path: str):

@@ -137,12 +137,12 @@ def test_sweep_entries_are_pooled_from_the_per_env_record_and_the_gait_sweep_is_
     assert len(task.actuator_sweep(commands[:1], repeats=1, seconds=0.1)) == 1                     # the task's own entry point, the config's levels
     # the gait sweep does not pass record_state: it returns what a call that passes the default explicitly returns, and keeps no state record
     first, rec_first = gait.gait_sweep(task, commands, repeats=2, seconds=0.5)
-    seen = []
+    seen, held_command_rollout = [], sweep.held_command_rollout
 
     def explicit(task_, n, T_, command, seed_offset, record_state=None):
         seen.append(record_state)
-        return sweep.held_command_rollout(task_, n, T_, command, seed_offset, record_state=False)
-    monkeypatch.setattr(gait, "held_command_rollout", explicit)
+        return held_command_rollout(task_, n, T_, command, seed_offset, record_state=False)
+    monkeypatch.setattr(sweep, "held_command_rollout", explicit)      # where the command sweeps' rollout is started from
     second, rec_second = gait.gait_sweep(task, commands, repeats=2, seconds=0.5)
     assert seen == [None] and repr(first) == repr(second) and rec_first.stats.tobytes() == rec_second.stats.tobytes()
     assert rec_first.aux.cpu().numpy().tobytes() == rec_second.aux.cpu().numpy().tobytes() and rec_first.env.cpu().numpy().tobytes() == rec_second.env.cpu().numpy().tobytes()

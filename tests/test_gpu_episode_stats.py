@@ -149,9 +149,9 @@ def test_end_to_end_through_the_task():
         assert want[E["EPISODES"]] >= 64 and want[E["TRUNCATED"]] > 0
         R.assert_stats_match(last, want, mags)
         totals.append(want)
-        assert np.array_equal(_bits(task.ep_acc.cpu().numpy()), _bits(acc_ref))
+        assert np.array_equal(_bits(task.episodes.acc.cpu().numpy()), _bits(acc_ref))
         _, es = task.ctx.env_get_state()
-        assert np.array_equal(task.ep_acc[:, A["LENGTH"]].cpu().numpy(), es[:, L.ES["TIME"]])     # kernel and env agree on where episodes start
+        assert np.array_equal(task.episodes.acc[:, A["LENGTH"]].cpu().numpy(), es[:, L.ES["TIME"]])     # kernel and env agree on where episodes start
         sc = task.scalars()
         assert sc["episode/count"] == want[E["EPISODES"]] and sc["episode_total/count"] == sum(w[E["EPISODES"]] for w in totals)
         assert abs(sc["episode/frac_truncated"] + sc["episode/frac_fail_height"] + sc["episode/frac_fail_other"] - 1.0) < 1e-12
@@ -177,7 +177,7 @@ def test_every_step_a_height_failure():
     assert abs(sc["episode/time_to_failure_s_mean"] - task.config.ctrl_dt) < 1e-15
     assert abs(sc["episode/return_mean"] - reward.mean()) <= 1e-6 * abs(reward.mean())
     assert not any(k.startswith("episode/reward/") for k in sc)           # no log_reward_components: no per-term keys
-    assert not task.ep_acc.any()
+    assert not task.episodes.acc.any()
     task.close()
 
 
@@ -194,7 +194,7 @@ def test_checkpoint_carries_the_accounting(tmp_path):
     b = HumanoidWalkingTask(cfg)
     b.load_checkpoint(path)
     b.train_iteration()
-    assert a.ep_acc.any() and torch.equal(a.ep_acc, b.ep_acc)
+    assert a.episodes.acc.any() and torch.equal(a.episodes.acc, b.episodes.acc)
     da, db = a.episode_stats(), b.episode_stats()
     assert da == db and da["episode_total/count"] > da["episode/count"] > 0
     # a checkpoint of a run that did not keep the accounting loads into one that does: it starts from zero
@@ -203,7 +203,7 @@ def test_checkpoint_carries_the_accounting(tmp_path):
     path_off = str(tmp_path / "off.bin")
     off.save_checkpoint(path_off)
     b.load_checkpoint(path_off)
-    assert not b.ep_acc.any() and b.episode_stats() == {"episode/count": 0.0, "episode_total/count": 0.0}
+    assert not b.episodes.acc.any() and b.episode_stats() == {"episode/count": 0.0, "episode_total/count": 0.0}
     b.train_iteration()
     assert b.episode_stats()["episode_total/count"] == b.episode_stats()["episode/count"]
     for t in (a, b, off):
@@ -215,7 +215,7 @@ def test_off_means_off():
     from kbot_joystick_amd.host import binding as B
     from kbot_joystick_amd.host.task import HumanoidWalkingTask
     off, on = HumanoidWalkingTask(_cfg(deterministic=True)), HumanoidWalkingTask(_cfg(deterministic=True, episode_stats=True))
-    assert off.ep_acc is None and off.ep_stats is None
+    assert off.episodes is None
     with pytest.raises(B.KbjError, match="episode_stats=True"):
         off.episode_stats()
     off.train_iteration(); on.train_iteration()

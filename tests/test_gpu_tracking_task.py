@@ -70,7 +70,7 @@ def test_scalars_equal_the_reference_on_the_tasks_own_trajectories():
         last, total = fused.tracking_stats_vectors()
         counts = [m * K["MODE_STRIDE"] + s for m in range(L.CMODE["COUNT"]) for s in (K["ROWS"], K["SETTLED"])] + [K["CHANGES"], K["EPISODES"]]
         assert np.array_equal(last[counts], want[counts]) and np.array_equal(total[counts], sum(totals)[counts])
-        assert np.array_equal(_bits(fused.trk_acc.cpu().numpy()), _bits(acc_ref))
+        assert np.array_equal(_bits(fused.tracking.acc.cpu().numpy()), _bits(acc_ref))
         sc = fused.scalars()
         track = {k: v for k, v in sc.items() if k.startswith("track/")}
         _assert_scalars(track, want, bounds, "track/")
@@ -103,7 +103,7 @@ def test_checkpoint_carries_the_tracking_state(tmp_path):
     b = HumanoidWalkingTask.load_task(path)
     assert b.config.tracking_stats is True and b.config.tracking_settle_seconds == 0.04
     b.train_iteration()
-    assert a.trk_acc.any() and a.trk_acc.cpu().numpy().tobytes() == b.trk_acc.cpu().numpy().tobytes()
+    assert a.tracking.acc.any() and a.tracking.acc.cpu().numpy().tobytes() == b.tracking.acc.cpu().numpy().tobytes()
     for va, vb in zip(a.tracking_stats_vectors(), b.tracking_stats_vectors()):
         assert va.tobytes() == vb.tobytes()
     assert a.tracking_stats() == b.tracking_stats() and a.tracking_stats(total=True) == b.tracking_stats(total=True)
@@ -115,7 +115,7 @@ def test_checkpoint_carries_the_tracking_state(tmp_path):
     path_off = str(tmp_path / "off.bin")
     off.save_checkpoint(path_off)
     b.load_checkpoint(path_off)
-    assert not b.trk_acc.any() and b.tracking_stats() == {} and rows(b.tracking_stats_vectors()[1]) == 0
+    assert not b.tracking.acc.any() and b.tracking_stats() == {} and rows(b.tracking_stats_vectors()[1]) == 0
     for t in (a, b, off):
         t.close()
 
@@ -125,7 +125,7 @@ def test_off_means_off():
     from kbot_joystick_amd.host import binding as B
     from kbot_joystick_amd.host.task import HumanoidWalkingTask
     off, on = HumanoidWalkingTask(_cfg(deterministic=True)), HumanoidWalkingTask(_cfg(deterministic=True, tracking_stats=True, tracking_settle_seconds=0.04))
-    assert off.tracking is None and off.trk_acc is None
+    assert off.tracking is None
     with pytest.raises(B.KbjError, match="tracking_stats=True"):
         off.tracking_stats()
     for _ in range(2):
