@@ -101,6 +101,35 @@ int kbj_env_set_command(kbj_ctx* ctx, const float* mask_d, const float* cmd_d, f
  * just started. Values are taken as they are; the host checks them (host/user_terms.py apply_events). Asynchronous on the context's stream;
  * other envs are untouched. A context with enable_pushes == 0 is refused with that reason: its step kernel ignores the event state. */
 int kbj_env_set_push(kbj_ctx* ctx, const float* mask_d, const float* wrench_d /* [N][6] */, const float* steps_d /* [N] */, const float* next_d /* [N] or NULL */);
+/* replaces: asking what a policy does on a robot that is NOT the model it trained on - the reference's physics randomisers
+ * (get_physics_randomizers, train.py:1097-1132) draw such a robot at every reset, but nobody can hand them one: half the floor friction, a
+ * payload on the torso, motors at 60 % torque, one weak leg. Writes a perturbed model row per env: for every env whose mask_d [N] float entry
+ * is non-zero (NULL = every env) the physics and actuator columns of its KBJ_EP_* row are rewritten from the model blob's nominal values
+ * and the env's record pert_d [N][KBJ_PERT_SIZE] (kbj_model.h KBJ_PERT_*), with m = the model, p = the record:
+ *   MASS[b]       = m.body_mass[b] x p[MASS_SCALE]; for b = m.torso_body then + p[PAYLOAD]: fl(fl(mass x s) + payload), never fused;
+ *   INERTIA[b][k] = m.body_inertia[b][k] x p[MASS_SCALE] (the payload is a point mass at the body's COM: no inertia of its own);
+ *   IPOS[b][k]    = m.body_ipos[b][k] + (b = m.torso_body ? p[COM_SHIFT + k] : 0);
+ *   ARMATURE[d]   = m.dof_armature[d] x p[ARMATURE_SCALE]; FRICLOSS[d] = m.dof_frictionloss[d] x p[FRICLOSS_SCALE];
+ *   KP[u], KD[u], TAULIM[u] = m.kp[u] x p[KP_SCALE + u], m.kd[u] x p[KD_SCALE + u], m.tau_limit[u] x p[TAULIM_SCALE + u];
+ *   ACTBIAS[u]    = p[ACTBIAS + u]; MU = m.contact_mu x p[MU_SCALE];
+ *   CAP_POS = m.cap_pos + 0, CAP_HALF = m.cap_halflen, CAP_RAD = m.cap_radius: the model's capsules;
+ *   LATENCY       = p[LATENCY] when that word is >= 0; a negative word keeps the row's own.
+ * Every written word is ONE fp32 product or ONE fp32 sum rounded to nearest, never contracted: a float32 restatement on the host
+ * reproduces every bit (tests/robustness_ref.py perturbed_row). Left exactly as they are: JPBIAS, PGBIAS, PGLAG (the per-episode sensor
+ * draws), the zero tail behind MU, every other env, the env state (no KBJ_ES_* word) and every observation and aux row. The identity record
+ * (scales 1, additions 0, LATENCY -1) gives the row the reset path writes with enable_randomizers = 0, latency and sensor draws kept.
+ * No observation row needs rewriting: the actor's row (joint positions and speeds, projected gravity, gyroscope, command) depends on none of
+ * the written columns. The critic's privileged columns that do (CINERT and its like, computed from MASS / INERTIA / IPOS) were written for
+ * the next step by the last step or reset and stay as they are: they are one row stale, and right again from the next step's row on.
+ * A record that breaks a "valid" condition of kbj_model.h, or holds a non-finite word among those read (the spare words are not), leaves
+ * its env's row untouched. status_d: NULL, or [N] int32, overwritten for EVERY env: 0 = not masked, 1 = written, -1 = refused.
+ * The step kernel reads the row afresh every control step (nothing derived from it is cached), so the new row acts from the next
+ * kbj_env_step on. An in-step reset (a termination inside kbj_env_step, kbj_env_reset_where) redraws the whole row: a host that pins
+ * parameters writes them again on the envs whose episode has just started, as kbj_env_set_push says of PUSH_NXT.
+ * Asynchronous on the context's stream. Fails with a message, before anything is launched, on a NULL ctx or pert_d and on a pert_d that is
+ * not 16-byte aligned. */
+int kbj_env_perturb(kbj_ctx* ctx, const float* mask_d /* [N] or NULL = all */, const float* pert_d /* [N][KBJ_PERT_SIZE] */,
+                    int32_t* status_d /* [N] or NULL */);
 /* replaces: user-written Reset terms in the reference's protocol (`Reset.__call__(data, curriculum_level, rng) -> data`, train.py:833-844: the in-tree
  * PlaneXYPositionReset reads `data.qpos` and returns the data with a new one), evaluated by the host on the envs that have just been re-initialised
  * (by the step kernel's own terminations, kbj_env_reset_where or kbj_env_reset_all), AFTER the built-in resets of train.py:1146-1153 as in the
@@ -538,6 +567,30 @@ int kbj_sizeof_frequency_criteria(void);   /* sizeof(kbj_frequency_criteria), fo
 int kbj_frequency_response(kbj_ctx* ctx, const kbj_traj* traj, const int32_t* sched_d /* [N][4] */, const kbj_frequency_criteria* crit,
                            float* sig_d /* [T][N][KBJ_SSIG_SIZE] */, double* rec_d /* [N][KBJ_FREC_SIZE] */,
                            const int32_t* group_d, int G, double* stats_d /* NULL or [G][KBJ_FSTAT_SIZE] */);
+
+/* ---- robustness: survival and tracking per case ------------------------------------------------ */
+/* replaces: running the policy on a robot that is not the model (kbj_env_perturb) and watching whether it stays up and still follows the
+ * stick, as numbers: per env over the WHOLE trajectory how often it fell, when first, and how well the settled rows tracked; then the same
+ * per group of envs (one group per case of a sweep). Reads err_d [T][N][KBJ_TERR_SIZE], the per-row output of kbj_tracking_stats on the same
+ * trajectory (the five errors and the SETTLED flag), and the DONE column of rows 0 .. T-1 of traj->aux_d.
+ * Per env n, for t = 0 .. T-1 in ascending order (kbj_model.h KBJ_RREC_*):
+ *   ROWS += 1; DONE[t] < 0: FALLS += 1, and FIRST_FALL = t if it is still -1; DONE[t] > 0: TIMEOUTS += 1;
+ *   if err[t][n][KBJ_TERR_SETTLED] != 0: SETTLED += 1 and per error k < KBJ_NTERR, with e = err[t][n][k]:
+ *     ERR_SUM[k] += (double)e; ERR_SUMSQ[k] += (double)e * (double)e (exact in double: fused or not gives the same sum);
+ *     ERR_MAX[k] = e where e is greater (it starts at -1; a NaN is never greater). A NaN error enters the sums as it is.
+ * rec_d [N][KBJ_RREC_SIZE] DOUBLES is OVERWRITTEN; spare words are 0. A float64 host loop in the same order reproduces every word
+ * (tests/robustness_ref.py).
+ * stats_d: NULL, or [G][KBJ_RSTAT_SIZE] doubles, overwritten (spare slots 0; kbj_model.h KBJ_RSTAT_*): per group g its ENVS, those of them
+ * that fell (FIRST_FALL >= 0), the sums of FALLS, TIMEOUTS, ROWS and SETTLED, over the fell envs the sum and the minimum of FIRST_FALL, the
+ * sums of ERR_SUM and ERR_SUMSQ and the maximum of ERR_MAX. A minimum or maximum over nothing is -1. group_d [N] int32 names every env's
+ * group (NULL: all in group 0; a value outside [0, G) puts the env in no group), 1 <= G <= 256. A group's envs are combined in env order, in
+ * doubles, without atomics: the same inputs give the same bytes on every call, with or without stats_d.
+ * Survival, falls per second and the mean errors are host arithmetic on these slots (host/robustness.py), none of it here.
+ * Writes no trajectory row; asynchronous on the context's stream. Fails with a message, before anything is launched, on a NULL ctx, traj,
+ * err_d or rec_d, on a trajectory without aux_d or positive T, N, on an err_d or rec_d that is not 16-byte aligned, and with stats_d on G
+ * outside [1, 256]. The context stays usable after such a failure. */
+int kbj_robustness(kbj_ctx* ctx, const kbj_traj* traj, const float* err_d /* [T][N][KBJ_TERR_SIZE] */, double* rec_d /* [N][KBJ_RREC_SIZE] */,
+                   const int32_t* group_d, int G, double* stats_d /* NULL or [G][KBJ_RSTAT_SIZE] */);
 
 /* ---- PPO update, rows a9, a12, a13 ---------------------------------------------------------- */
 /* replaces: ksim GAE (gamma, lam: train.py:1769-1770). done from aux; adv_d/target_d [T][N].

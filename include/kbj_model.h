@@ -625,6 +625,52 @@ enum {
   KBJ_FSTAT_SIZE     = 32    /* five spare slots, written 0 */
 };
 
+/* ---- scripted model perturbations and the robustness statistics (kbj_env_perturb, kbj_robustness) ----
+ * One env's perturbation record ("PERT" record, fp32): how its model row (KBJ_EP_*) differs from the model blob's nominal values. Scales
+ * multiply the model's word, additions are added to it; "valid" is what kbj_env_perturb accepts (every word read must be finite). */
+enum {
+  KBJ_PERT_MASS_SCALE     = 0,    /* every body's MASS and its three INERTIA words x s                                        (s > 0)  */
+  KBJ_PERT_PAYLOAD        = 1,    /* kg added to the torso body's mass behind the scaling: a point mass at its COM            (>= 0)   */
+  KBJ_PERT_MU_SCALE       = 2,    /* contact_mu x s                                                                           (s > 0)  */
+  KBJ_PERT_ARMATURE_SCALE = 3,    /* every dof_armature x s                                                                   (s > 0)  */
+  KBJ_PERT_FRICLOSS_SCALE = 4,    /* every dof_frictionloss x s                                                               (s >= 0) */
+  KBJ_PERT_LATENCY        = 5,    /* action latency in substeps, a whole number; any negative value keeps KBJ_EP_LATENCY      (whole, or < 0) */
+  KBJ_PERT_COM_SHIFT      = 6,    /* [3] metres added to the torso body's IPOS                                                (finite) */
+  KBJ_PERT_SPARE          = 9,    /* [3] ignored, whatever they hold */
+  KBJ_PERT_KP_SCALE       = 12,   /* [20] kp[u] x s                                                                           (s > 0)  */
+  KBJ_PERT_KD_SCALE       = 32,   /* [20] kd[u] x s                                                                           (s >= 0) */
+  KBJ_PERT_TAULIM_SCALE   = 52,   /* [20] tau_limit[u] x s                                                                    (s > 0)  */
+  KBJ_PERT_ACTBIAS        = 72,   /* [20] copied into KBJ_EP_ACTBIAS, rad                                                     (finite) */
+  KBJ_PERT_SIZE           = 92    /* 368-byte rows */
+};
+/* One env's record of kbj_robustness ("RREC" record, DOUBLES) over its rows t = 0 .. T-1. Spare words are 0. */
+enum {
+  KBJ_RREC_ROWS       = 0,    /* rows seen: T */
+  KBJ_RREC_FALLS      = 1,    /* rows with DONE < 0 */
+  KBJ_RREC_TIMEOUTS   = 2,    /* rows with DONE > 0 */
+  KBJ_RREC_FIRST_FALL = 3,    /* the first row with DONE < 0, -1 without one */
+  KBJ_RREC_SETTLED    = 4,    /* rows with KBJ_TERR_SETTLED != 0: the sums and maxima below are over these */
+  KBJ_RREC_ERR_SUM    = 8,    /* [5] sum of the fp32 error taken into double, KBJ_TERR_* order (a NaN is taken as it is), */
+  KBJ_RREC_ERR_SUMSQ  = 13,   /* [5] of its square, taken in double, */
+  KBJ_RREC_ERR_MAX    = 18,   /* [5] its maximum: starts at -1, a NaN is never greater */
+  KBJ_RREC_SIZE       = 24    /* 192-byte rows */
+};
+/* One group's statistics of kbj_robustness ("RSTAT" record, doubles). A minimum or maximum over nothing is -1; spare slots are 0. */
+enum {
+  KBJ_RSTAT_ENVS           = 0,    /* envs of the group */
+  KBJ_RSTAT_FELL_ENVS      = 1,    /* of them those with FIRST_FALL >= 0 */
+  KBJ_RSTAT_FALLS          = 2,    /* sum of FALLS, */
+  KBJ_RSTAT_TIMEOUTS       = 3,    /* of TIMEOUTS, */
+  KBJ_RSTAT_ROWS           = 4,    /* of ROWS */
+  KBJ_RSTAT_FIRST_FALL_SUM = 5,    /* over the fell envs: sum of FIRST_FALL, */
+  KBJ_RSTAT_FIRST_FALL_MIN = 6,    /* its minimum */
+  KBJ_RSTAT_SETTLED        = 7,    /* sum of SETTLED */
+  KBJ_RSTAT_ERR_SUM        = 8,    /* [5] sum of ERR_SUM, */
+  KBJ_RSTAT_ERR_SUMSQ      = 13,   /* [5] of ERR_SUMSQ, */
+  KBJ_RSTAT_ERR_MAX        = 18,   /* [5] the maximum of ERR_MAX */
+  KBJ_RSTAT_SIZE           = 24
+};
+
 /* reward component order (train.py:1225-1256) */
 enum {
   KBJ_REW_LINVEL = 0, KBJ_REW_ANGVEL, KBJ_REW_ROLL_PITCH, KBJ_REW_BASE_HEIGHT, KBJ_REW_ARM_POS,

@@ -142,6 +142,89 @@ __global__ __launch_bounds__(256) void env_set_push_kernel(int N, float* __restr
   es[(size_t)env * KBJ_ES_SIZE + KBJ_ES_PUSH + k] = k < 6 ? wrench[(size_t)env * 6 + k] : k == 6 ? steps[env] : next[env];
 }
 
+// one word of a perturbation record against the "valid" column of kbj_model.h KBJ_PERT_*: the spare words are not read; every other word is
+// finite; scales are positive (KD and FRICLOSS: not negative), the payload is not negative, the latency is negative or a whole number
+__device__ inline bool pert_word_valid(int i, float v) {
+  if (i >= KBJ_PERT_SPARE && i < KBJ_PERT_KP_SCALE) return true;
+  if (!(fabsf(v) < INFINITY)) return false;                    // a NaN or an infinity
+  if (i == KBJ_PERT_MASS_SCALE || i == KBJ_PERT_MU_SCALE || i == KBJ_PERT_ARMATURE_SCALE || (i >= KBJ_PERT_KP_SCALE && i < KBJ_PERT_KD_SCALE) ||
+      (i >= KBJ_PERT_TAULIM_SCALE && i < KBJ_PERT_ACTBIAS))
+    return v > 0.0f;
+  if (i == KBJ_PERT_PAYLOAD || i == KBJ_PERT_FRICLOSS_SCALE || (i >= KBJ_PERT_KD_SCALE && i < KBJ_PERT_TAULIM_SCALE)) return v >= 0.0f;
+  if (i == KBJ_PERT_LATENCY) return v < 0.0f || v == floorf(v);
+  return true;                                                 // COM_SHIFT, ACTBIAS: finite
+}
+
+// One fp32 product / one fp32 sum, rounded to nearest, that no pass fuses with its neighbour. __fmul_rn / __fadd_rn are plain * and + to
+// this compiler and carry their header's contraction licence into the caller: the torso's scaled mass plus the payload became one fused
+// multiply-add and missed the two-rounding value by an ulp on one env in ten. Here the licence is withdrawn where the operation is written.
+__device__ inline float pert_mul(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ inline float pert_add(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
+// rewrite the physics and actuator columns of the KBJ_EP row of the envs whose mask entry is non-zero (mask == nullptr: all envs) from the
+// model's nominal values and the env's perturbation record (kbj.h kbj_env_perturb, word for word): every written word is one pert_mul or one
+// pert_add, so nothing is contracted and a float32 restatement reproduces every bit. JPBIAS, PGBIAS, PGLAG and the tail behind MU are not
+// touched, LATENCY only for a record word >= 0. An invalid record leaves the row alone. One wavefront per env: lanes 0 .. 22 fetch the
+// record as 16-byte pieces into LDS and judge their own words, one vote decides, then the lanes share the row's 346 words.
+__global__ __launch_bounds__(64) void env_perturb_kernel(int N, const kbj_model* __restrict__ m, float* __restrict__ ep, const float* __restrict__ mask, const float* __restrict__ pert,
+                                                         int32_t* __restrict__ status) {
+  static_assert(KBJ_PERT_SIZE % 4 == 0 && KBJ_PERT_SIZE / 4 <= 64, "a record is fetched as 16-byte pieces, one per lane");
+  static_assert(KBJ_EP_IPOS == 0 && KBJ_EP_MASS == 3 * KBJ_NBODY && KBJ_EP_INERTIA == KBJ_EP_MASS + KBJ_NBODY && KBJ_EP_ARMATURE == KBJ_EP_INERTIA + 3 * KBJ_NBODY &&
+                KBJ_EP_FRICLOSS == KBJ_EP_ARMATURE + KBJ_NV && KBJ_EP_CAP_POS == KBJ_EP_FRICLOSS + KBJ_NV && KBJ_EP_CAP_HALF == KBJ_EP_CAP_POS + 3 * KBJ_NCAP &&
+                KBJ_EP_CAP_RAD == KBJ_EP_CAP_HALF + KBJ_NCAP && KBJ_EP_KP == KBJ_EP_CAP_RAD + KBJ_NCAP && KBJ_EP_KD == KBJ_EP_KP + KBJ_NU && KBJ_EP_TAULIM == KBJ_EP_KD + KBJ_NU &&
+                KBJ_EP_ACTBIAS == KBJ_EP_TAULIM + KBJ_NU && KBJ_EP_JPBIAS == KBJ_EP_ACTBIAS + KBJ_NU && KBJ_EP_MU == KBJ_EP_LATENCY + 1 && KBJ_EP_MU < KBJ_EP_SIZE,
+                "the columns of the env parameter row, in the order the word dispatch below walks them");
+  __shared__ __align__(16) float p[KBJ_PERT_SIZE];
+  const int env = blockIdx.x, lane = threadIdx.x;              // grid = N: env < N
+  if (mask && mask[env] == 0.0f) {                             // uniform over the workgroup
+    if (status && lane == 0) status[env] = 0;
+    return;
+  }
+  bool ok = true;
+  if (lane < KBJ_PERT_SIZE / 4) {
+    const float4 v = reinterpret_cast<const float4*>(pert + (size_t)env * KBJ_PERT_SIZE)[lane];
+    reinterpret_cast<float4*>(p)[lane] = v;
+    ok = pert_word_valid(4 * lane, v.x) && pert_word_valid(4 * lane + 1, v.y) && pert_word_valid(4 * lane + 2, v.z) && pert_word_valid(4 * lane + 3, v.w);
+  }
+  const bool valid = __all(ok);                                // the workgroup is one wavefront
+  if (status && lane == 0) status[env] = valid ? 1 : -1;
+  if (!valid) return;                                          // uniform
+  __syncthreads();
+  float* row = ep + (size_t)env * KBJ_EP_SIZE;
+  const int torso = m->torso_body;
+  const float* ipos = &m->body_ipos[0][0];
+  const float* inertia = &m->body_inertia[0][0];
+  const float* cap_pos = &m->cap_pos[0][0];
+  for (int k = lane; k <= KBJ_EP_MU; k += 64) {
+    float v;
+    if (k < KBJ_EP_MASS) v = pert_add(ipos[k], k / 3 == torso ? p[KBJ_PERT_COM_SHIFT + k % 3] : 0.0f);
+    else if (k < KBJ_EP_INERTIA) {
+      v = pert_mul(m->body_mass[k - KBJ_EP_MASS], p[KBJ_PERT_MASS_SCALE]);
+      if (k - KBJ_EP_MASS == torso) v = pert_add(v, p[KBJ_PERT_PAYLOAD]);
+    }
+    else if (k < KBJ_EP_ARMATURE) v = pert_mul(inertia[k - KBJ_EP_INERTIA], p[KBJ_PERT_MASS_SCALE]);
+    else if (k < KBJ_EP_FRICLOSS) v = pert_mul(m->dof_armature[k - KBJ_EP_ARMATURE], p[KBJ_PERT_ARMATURE_SCALE]);
+    else if (k < KBJ_EP_CAP_POS) v = pert_mul(m->dof_frictionloss[k - KBJ_EP_FRICLOSS], p[KBJ_PERT_FRICLOSS_SCALE]);
+    else if (k < KBJ_EP_CAP_HALF) v = pert_add(cap_pos[k - KBJ_EP_CAP_POS], 0.0f);      // the reset path's own sum with no jitter
+    else if (k < KBJ_EP_CAP_RAD) v = m->cap_halflen[k - KBJ_EP_CAP_HALF];
+    else if (k < KBJ_EP_KP) v = m->cap_radius[k - KBJ_EP_CAP_RAD];
+    else if (k < KBJ_EP_KD) v = pert_mul(m->kp[k - KBJ_EP_KP], p[KBJ_PERT_KP_SCALE + k - KBJ_EP_KP]);
+    else if (k < KBJ_EP_TAULIM) v = pert_mul(m->kd[k - KBJ_EP_KD], p[KBJ_PERT_KD_SCALE + k - KBJ_EP_KD]);
+    else if (k < KBJ_EP_ACTBIAS) v = pert_mul(m->tau_limit[k - KBJ_EP_TAULIM], p[KBJ_PERT_TAULIM_SCALE + k - KBJ_EP_TAULIM]);
+    else if (k < KBJ_EP_JPBIAS) v = p[KBJ_PERT_ACTBIAS + k - KBJ_EP_ACTBIAS];
+    else if (k < KBJ_EP_LATENCY) continue;                     // JPBIAS, PGBIAS, PGLAG: the episode's sensor draws stay
+    else if (k == KBJ_EP_LATENCY) { if (!(p[KBJ_PERT_LATENCY] >= 0.0f)) continue; v = p[KBJ_PERT_LATENCY]; }
+    else v = pert_mul(m->contact_mu, p[KBJ_PERT_MU_SCALE]);
+    row[k] = v;
+  }
+}
+
 // register budget of the step kernel: 13.4 KB of LDS lets 12 single-wavefront workgroups share a CU (3 waves/SIMD), which
 // needs <= 168 VGPRs. `amdgpu_num_vgpr(N)` makes hipcc allocate 2 N registers for this wave64 kernel (floor 129): N = 84 gives
 // exactly 168 with 61 spilled values. Measured (8192 envs, ms/step): no cap (2 waves/SIMD, no spills) 3.26 -> N = 62 (129 VGPRs,
@@ -325,6 +408,16 @@ int kbj_env_set_push(kbj_ctx* ctx, const float* mask_d, const float* wrench_d, c
   const int N = ctx->cfg_h.num_envs, n = N * 8;
   hipLaunchKernelGGL(env_set_push_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, N, ctx->es_d, mask_d, wrench_d, steps_d, next_d);
   KBJ_CHECK_LAUNCH(ctx, "env_set_push_kernel");
+  return 0;
+}
+
+int kbj_env_perturb(kbj_ctx* ctx, const float* mask_d, const float* pert_d, int32_t* status_d) {
+  if (!ctx || !pert_d) return kbj_fail(ctx, "kbj_env_perturb: null argument");
+  if (reinterpret_cast<uintptr_t>(pert_d) & 15) return kbj_fail(ctx, "kbj_env_perturb: pert_d must be 16-byte aligned");
+  KBJ_HIP(ctx, hipSetDevice(ctx->device));      // no kbj_nn_drop_prefetch: no observation row is written
+  const int N = ctx->cfg_h.num_envs;
+  hipLaunchKernelGGL(env_perturb_kernel, dim3(N), dim3(64), 0, ctx->stream, N, ctx->model_d, ctx->ep_d, mask_d, pert_d, status_d);
+  KBJ_CHECK_LAUNCH(ctx, "env_perturb_kernel");
   return 0;
 }
 

@@ -1,7 +1,7 @@
 // kbj_traj_stats.hip — HIP kernels + C-ABI entry points of everything that reads a finished trajectory: kbj_rewards (rewards_kernel below),
 // kbj_episode_stats (kbj_episode_stats.h), kbj_tracking_stats (kbj_tracking_stats.h), kbj_gait_stats (kbj_gait_stats.h), kbj_push_recovery
-// (kbj_push_recovery.h), kbj_step_response (kbj_step_response.h), kbj_frequency_response (kbj_frequency_response.h) and kbj_actuator_stats
-// (kbj_actuator_stats.h). None of it is on the hot path, and none of it shares a translation unit with the env kernels (kbj_env.hip): an edit
+// (kbj_push_recovery.h), kbj_step_response (kbj_step_response.h), kbj_frequency_response (kbj_frequency_response.h), kbj_actuator_stats
+// (kbj_actuator_stats.h) and kbj_robustness (kbj_robustness.h). None of it is on the hot path, and none of it shares a translation unit with the env kernels (kbj_env.hip): an edit
 // here recompiles no step kernel.
 #include <hip/hip_runtime.h>
 #include <initializer_list>
@@ -16,6 +16,7 @@
 #include "kbj_push_recovery.h"
 #include "kbj_step_response.h"
 #include "kbj_frequency_response.h"
+#include "kbj_robustness.h"
 
 using namespace kbj;
 
@@ -319,6 +320,16 @@ int kbj_frequency_response(kbj_ctx* ctx, const kbj_traj* tr, const int32_t* sche
   return window_scan_then_reduce<double>(ctx, tr->N, "freq_scan_kernel", [&](dim3 grid, dim3 block) {
     hipLaunchKernelGGL(freq_scan_kernel, grid, block, 0, ctx->stream, sig_d, tr->T, tr->N, sched_d, *crit, rec_d);
   }, freq_reduce_kernel, "freq_reduce_kernel", rec_d, group_d, G, stats_d);
+}
+
+int kbj_robustness(kbj_ctx* ctx, const kbj_traj* tr, const float* err_d, double* rec_d, const int32_t* group_d, int G, double* stats_d) {
+  if (!ctx || !tr || !err_d || !rec_d) return kbj_fail(ctx, "kbj_robustness: null argument");
+  if (check_traj(ctx, "kbj_robustness", tr, false) != 0 || check_aligned16(ctx, "kbj_robustness", "err_d and rec_d", {err_d, rec_d}) != 0) return -1;
+  if (check_groups(ctx, "kbj_robustness", G, stats_d) != 0) return -1;
+  KBJ_HIP(ctx, hipSetDevice(ctx->device));      // no kbj_nn_drop_prefetch: no trajectory row is written
+  return window_scan_then_reduce<double>(ctx, tr->N, "robustness_scan_kernel", [&](dim3 grid, dim3 block) {
+    hipLaunchKernelGGL(robustness_scan_kernel, grid, block, 0, ctx->stream, err_d, tr->aux_d, tr->T, tr->N, rec_d);
+  }, robustness_reduce_kernel, "robustness_reduce_kernel", rec_d, group_d, G, stats_d);
 }
 
 }  // extern "C"

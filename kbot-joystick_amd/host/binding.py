@@ -99,6 +99,7 @@ SIGNATURES = {
     "kbj_env_reset_where": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "kbj_env_set_command": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "kbj_env_set_push": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "kbj_env_perturb": (_i, [_vp, _vp, _vp, _vp]),
     "kbj_env_get_qstate": (_i, [_vp, _vp, _vp]),
     "kbj_env_set_qstate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "kbj_env_get_state": (_i, [_vp, _vp, _vp]),
@@ -129,6 +130,7 @@ SIGNATURES = {
     "kbj_push_recovery": (_i, [_vp, C.POINTER(Traj), _vp, _vp, C.POINTER(PushCriteria), _vp, _vp, _i, _vp]),
     "kbj_step_response": (_i, [_vp, C.POINTER(Traj), _vp, C.POINTER(StepCriteria), _vp, _vp, _vp, _i, _vp]),
     "kbj_frequency_response": (_i, [_vp, C.POINTER(Traj), _vp, C.POINTER(FrequencyCriteria), _vp, _vp, _vp, _i, _vp]),
+    "kbj_robustness": (_i, [_vp, C.POINTER(Traj), _vp, _vp, _vp, _i, _vp]),
     "kbj_ppo_grad": (_i, [_vp, _vp, C.POINTER(Traj), _vp, _i, _vp, _vp, _vp, _vp]),
     "kbj_ppo_forward": (_i, [_vp, _vp, C.POINTER(Traj), _vp, _i, C.POINTER(PpoVars)]),
     "kbj_stream_wait_actor_grad": (_i, [_vp, _vp]),
@@ -263,6 +265,12 @@ class Context:
         steps it is applied for [N] and, with `next` [N], the control steps until the built-in event draws again (layout.PUSH_NEVER: never);
         float32 device tensors. Asynchronous; no observation row changes."""
         self.call("kbj_env_set_push", _ptr(mask), _ptr(wrench), _ptr(steps), _ptr(next))
+
+    def env_perturb(self, mask, pert, status=None):
+        """kbj_env_perturb: for the envs of mask [N] float32 (None = every env) the physics and actuator columns of the model row rewritten from
+        the model's nominal values and pert [N, PERT SIZE] float32 (layout.PERT); status None or [N] int32, overwritten for every env (0 not
+        masked, 1 written, -1 refused: an invalid record leaves its row alone); device tensors. Asynchronous; no observation row changes."""
+        self.call("kbj_env_perturb", _ptr(mask), _ptr(pert), _ptr(status))
 
     def env_get_qstate(self, qpos, qvel):
         """kbj_env_get_qstate: every env's qpos [N, 27] / qvel [N, 26] into device tensors (asynchronous)."""
@@ -401,6 +409,11 @@ class Context:
         [G, FSTAT SIZE] float64 (overwritten), all on the device."""
         self.call("kbj_frequency_response", C.byref(traj) if traj is not None else None, _ptr(sched), C.byref(criteria) if criteria is not None else None, _ptr(sig), _ptr(rec),
                   _ptr(group), int(G), _ptr(stats))
+
+    def robustness(self, traj: Traj, err, rec, group=None, G: int = 1, stats=None):
+        """kbj_robustness: err [T, N, TERR SIZE] float32 (kbj_tracking_stats' per-row output), rec [N, RREC SIZE] float64 (overwritten), group
+        None or [N] int32 in [0, G), stats None or [G, RSTAT SIZE] float64 (overwritten), all on the device."""
+        self.call("kbj_robustness", C.byref(traj) if traj is not None else None, _ptr(err), _ptr(rec), _ptr(group), int(G), _ptr(stats))
 
     def ppo_grad(self, params, traj: Traj, env_idx, B, adv, target, grad, metrics):
         self.call("kbj_ppo_grad", _ptr(params), C.byref(traj), _ptr(env_idx), B, _ptr(adv), _ptr(target), _ptr(grad),

@@ -96,18 +96,21 @@ def sweep_rollout(task, n: int, T: int, configure, terms: UserTerms, first_hooks
         ctx.close()
 
 
-def held_command_rollout(task, n: int, T: int, command, seed_offset: int, record_state: bool = False):
-    """sweep_rollout under the Command term `command` alone (tracking, gait, step, actuator and frequency sweeps): command_mode = 1, so that the kernel's own
+def held_command_rollout(task, n: int, T: int, command, seed_offset: int, record_state: bool = False, after_resets=()):
+    """sweep_rollout under the Command term `command` alone (tracking, gait, step, actuator, frequency and robustness sweeps): command_mode = 1, so that the kernel's own
     reset writes the context's fixed command and the term's answer then replaces it, and validate()'s hook order - on row 0 the resets, the
-    command, then the observation terms that feed a network; behind every step the resets, those observation terms, then the command."""
+    command, then the observation terms that feed a network; behind every step the resets, those observation terms, then the command.
+    `after_resets`: further hooks of the sweep's own, run on every row behind the resets and in front of everything else (the robustness
+    sweep writes its model rows there)."""
     terms = sweep_terms(task, command=command)
     feeds = [terms.observe_rows] if any(task.extra_obs) else []
+    own = list(after_resets)
 
     def configure(vcfg):
         vcfg.command_mode = 1
 
-    return sweep_rollout(task, n, T, configure, terms, [terms.apply_resets, terms.apply_command] + feeds,
-                         [terms.apply_resets] + feeds + [terms.apply_command], seed_offset, record_state)
+    return sweep_rollout(task, n, T, configure, terms, [terms.apply_resets] + own + [terms.apply_command] + feeds,
+                         [terms.apply_resets] + own + feeds + [terms.apply_command], seed_offset, record_state)
 
 
 # ---- the command sweeps (tracking, gait, actuator): one held command per env ----

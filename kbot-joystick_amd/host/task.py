@@ -32,6 +32,7 @@ from .episode import EpisodeStats, episode_stats_scalars      # noqa: F401 (re-e
 from .frequency import FrequencyRecord, SineCommand, format_frequency_table, frequency_sweep      # noqa: F401 (re-exported)
 from .gait import GaitStats, format_gait_table, gait_sweep      # noqa: F401 (re-exported)
 from .push import PushRecord, ScriptedPush, format_push_table, push_sweep      # noqa: F401 (re-exported)
+from .robustness import Perturbation, RobustnessRecord, format_robustness_table, in_training_range, robustness_sweep      # noqa: F401 (re-exported)
 from .step import StepRecord, SteppedCommand, format_step_table, step_sweep      # noqa: F401 (re-exported)
 from .tracking import TrackingStats, format_tracking_table, settle_steps, tracking_sweep      # noqa: F401 (re-exported)
 from .user_terms import UserTerms
@@ -354,6 +355,27 @@ class HumanoidWalkingTask:
         per case the settings and figures (nan over nothing), and the FrequencyRecord of the device data. `format_frequency_table` renders
         the entries. Like the step table, this one has NOT been taken on a trained policy."""
         return frequency_sweep(self, points, periods, cycles, min_window, start_at, settle, min_amp, repeats, seed_offset)
+
+    def robustness_sweep(self, perturbations=None, commands=None, repeats: int = 8, seconds: Optional[float] = None, settle_seconds: Optional[float] = None,
+                         seed_offset: int = 7919):
+        """The model-robustness table: what the CURRENT policy does on a robot that is NOT the model it trained on. One case per
+        (perturbation, command): a host/robustness.Perturbation names how the model row differs - mass, a payload on the torso, floor
+        friction, armature, joint friction, action latency, a COM shift, and per joint (or per leg / arm) kp, kd, torque limit and action
+        bias; default: host/robustness.default_perturbations, 16 cases around and beyond the randomisers' ranges, SETTINGS of this build
+        and not measured thresholds - and a command is [<= 16] floats (default: stand, forward at half and full range, turn left at full
+        range). A context of its own with cases * repeats envs (env e runs case e % cases; at most 256 cases) runs `seconds` (default
+        render_length_seconds) of argmax actions through the step-wise loop under a scripted Command term; kbj_env_perturb writes every
+        env's record on row 0 and again, behind every step, on the envs whose episode has just started (an in-step reset redraws the
+        model row); the user's Reset and network-input Observation terms apply as in validate(), Event terms do not. kbj_tracking_stats
+        then gives every row's errors and ONE kbj_robustness call, with one group per case, the falls and the settled-row errors.
+        Returns (entries, record): per case `perturbation`, `changed` (its non-default fields), `command`, `mode`, `in_training_range`
+        (host/robustness.in_training_range: every knob inside what the randomisers draw), `envs`, `survival` (the share of envs that
+        never fell), `falls_per_s`, `first_fall_s_mean` / `first_fall_s_min`, `timeouts`, the five settled-row mean errors (rows whose
+        command has been held for `settle_seconds`, default tracking_settle_seconds) and `settled_rows` (nan over nothing); and the
+        RobustnessRecord of what the run left behind. A refused perturbation raises ValueError naming its field before the device is
+        touched. `format_robustness_table` renders the entries. Like the push, gait, step and frequency tables, this one has NOT been
+        taken on a trained policy."""
+        return robustness_sweep(self, perturbations, commands, repeats, seconds, settle_seconds, seed_offset)
 
     def episode_stats_vectors(self):
         """(last, total): this rank's raw KBJ_EPST vectors (float64 numpy, layout.EPST) behind episode_stats() - the episodes that finished in

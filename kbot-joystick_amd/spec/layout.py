@@ -164,6 +164,12 @@ FOUT = dict(NONE=0, VOID=1, FELL=2, MEASURED=3, FLAT=4, CENSORED=5, COUNT=6)
 FREC = dict(OUTCOME=0, ROWS=1, FALL_STEPS=2, CHANNEL=3, PERIOD=4, R_MIN=5, R_MAX=6, S_R=7, S_D=8, S_RR=9, S_DD=10, S_RD=11, S_Y=12, S_YY=15, S_YR=18, S_YD=21, SIZE=24)
 FREC_NSUMS = 17
 FSTAT = dict(COUNT=0, FALL_SUM=6, ROWS=7, SUMS=8, R_MIN=25, R_MAX=26, SIZE=32)
+# kbj_model.h KBJ_PERT_* / KBJ_RREC_* / KBJ_RSTAT_*: one env's perturbation record of kbj_env_perturb (fp32), one env's record of kbj_robustness and one
+# group's statistics (both float64)
+PERT = dict(MASS_SCALE=0, PAYLOAD=1, MU_SCALE=2, ARMATURE_SCALE=3, FRICLOSS_SCALE=4, LATENCY=5, COM_SHIFT=6, SPARE=9, KP_SCALE=12, KD_SCALE=32, TAULIM_SCALE=52,
+            ACTBIAS=72, SIZE=92)
+RREC = dict(ROWS=0, FALLS=1, TIMEOUTS=2, FIRST_FALL=3, SETTLED=4, ERR_SUM=8, ERR_SUMSQ=13, ERR_MAX=18, SIZE=24)
+RSTAT = dict(ENVS=0, FELL_ENVS=1, FALLS=2, TIMEOUTS=3, ROWS=4, FIRST_FALL_SUM=5, FIRST_FALL_MIN=6, SETTLED=7, ERR_SUM=8, ERR_SUMSQ=13, ERR_MAX=18, SIZE=24)
 # pieces of a packed observation row in the reference's concatenation order (kbj_model.h KBJ_OBS_*; train.py:1367-1374, 1410-1430):
 # name -> (offset, width); the first six are common to the actor and the critic row
 OBS = dict(JPOS=(0, 20), JVEL=(20, 20), PG=(40, 5), GYRO=(45, 3), ZEROCMD=(48, 1), CMD=(49, 16), TOUCH=(65, 2), FEETPOS=(67, 6), BASEPOS=(73, 3),

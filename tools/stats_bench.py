@@ -1,5 +1,5 @@
 """What the statistics benches share (tools/bench_episode_stats.py, bench_tracking_stats.py, bench_gait_stats.py, bench_push_recovery.py,
-bench_step_response.py, bench_frequency_response.py, bench_actuator_stats.py): the timed-call loop and the streaming rate their traffic floors are taken against."""
+bench_step_response.py, bench_frequency_response.py, bench_actuator_stats.py, bench_robustness.py): the timed-call loop and the streaming rate their traffic floors are taken against."""
 import statistics
 
 # The rate this project has measured for a streaming kernel of its own: adamw_kernel moves 63.05 MB per launch (profiles/pmc_traffic.json)
