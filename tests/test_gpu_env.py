@@ -179,6 +179,16 @@ def test_free_running_rollout_statistics(model):
     r_o, c_o = o.rewards(aux_o[:T])
     assert np.abs(comps.cpu().numpy() - c_o).max() < 2e-4
     assert np.abs(rew.cpu().numpy() - r_o).max() < 2e-4
+    # the same rows against the float64 restatement, element by element within the measured factor times each element's condition bound
+    # (tests/test_gpu_rewards.py), discrete terms and carry exactly. These are rollout rows: a row closer to a threshold than 16 x its
+    # float32 error is left out, and tests/test_rewards_ref.py::test_old_criterion_on_the_old_rows shows on the CPU that none is.
+    from tests import rewards_ref as RR
+    P = RR.Params(cfg)
+    ref = RR.scan(aux_o[:T], P, np.array(model.joint_bias, np.float32), RR.initial_carry(N))
+    safe = RR.safe_rows(ref)
+    assert 1 - safe.mean() < 0.01
+    fails = RR.compare((comps.cpu().numpy(), rew.cpu().numpy(), ctx.env_get_reward_carry()), ref, P, rows=safe, carry_want=o.rc)
+    assert fails == [], fails
     ctx.close()
 
 
