@@ -74,10 +74,19 @@ class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("launches", C.c_int32), ("total_ms", C.c_float), ("flops", C.c_double)]
 
 
+# every struct the two headers define: C name -> its mirror
+STRUCTS = {
+    "kbj_model": L.Model, "kbj_config": L.Config, "kbj_carry": Carry, "kbj_traj": Traj, "kbj_ppo_vars": PpoVars,
+    "kbj_deploy_inputs": DeployInputs, "kbj_push_criteria": PushCriteria, "kbj_step_criteria": StepCriteria,
+    "kbj_frequency_criteria": FrequencyCriteria, "kbj_actuator_levels": ActuatorLevels, "kbj_kernel_stat": KernelStat,
+}
+
 _vp, _i, _u32, _f, _sz = C.c_void_p, C.c_int, C.c_uint32, C.c_float, C.c_size_t
 _cfgp = C.POINTER(L.Config)
 
-# every symbol include/kbj.h declares: name -> (restype, argtypes)
+# every symbol include/kbj.h declares: name -> (restype, argtypes). A new entry point needs its entry here (a new struct its entry in
+# STRUCTS) and no test of its own: tests/test_abi_mirror.py takes the arity and every argument's type of each entry, and every field of
+# each struct, from the header through the host compiler, and refuses a declaration of the header that has no entry.
 SIGNATURES = {
     "kbj_create": (_i, [C.POINTER(_vp), _vp, _sz, _cfgp, _i, _vp]),
     "kbj_destroy": (_i, [_vp]),

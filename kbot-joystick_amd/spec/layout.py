@@ -1,7 +1,10 @@
-"""ctypes mirrors of include/kbj_model.h (kbj_model, kbj_config) and the record offsets.
+"""ctypes mirrors of include/kbj_model.h (kbj_model, kbj_config), its record offsets, stream ids and numeric constants.
 
-The C header is the source of truth; tests/test_abi.py checks sizeof() of both structs against the
-compiled library (kbj_sizeof_model / kbj_sizeof_config) so the two cannot drift silently.
+The C header is the source of truth and this module restates it by hand, so that the package imports without the header. What holds the
+two together is tests/test_abi_mirror.py: it has the host C++ compiler print, from the header itself, every field's offset, size and type
+of both structs, the value of every enumerator named below and every constant, compares them one by one, and checks that the header
+has no struct or enumerator without a mirror. (tests/test_abi.py and binding.Context compare sizeof() with the compiled library as
+well: that catches a stale libkbj.so, not a swapped or mistyped field.)
 """
 from __future__ import annotations
 
@@ -177,6 +180,10 @@ OBS = dict(JPOS=(0, 20), JVEL=(20, 20), PG=(40, 5), GYRO=(45, 3), ZEROCMD=(48, 1
 OBS_JVEL_DIV, OBS_ACTFRC_DIV = 10.0, 4.0
 AUX = dict(QVEL=0, BQUAT=6, BASEZ=10, LFZ=11, RFZ=12, LFQUAT=13, RFQUAT=17, ARMQ=21, CTRL=31, TOUCH=51,
            COMDIST=53, CMD=54, DONE=70, SIZE=72)
+# kbj_model.h KBJ_REW_* / KBJ_RNG_*: the slot of every reward term (constants.REWARD_NAMES order) and the threefry stream ids
+REW = dict(LINVEL=0, ANGVEL=1, ROLL_PITCH=2, BASE_HEIGHT=3, ARM_POS=4, SINGLE_CONTACT=5, NO_CONTACT=6, FEET_AIRTIME=7, FEET_ORIENT=8,
+           COM_DISTANCE=9, BASE_ACCEL=10, TORQUE=11)
+RNG = dict(RESET=1, RANDOMIZE=2, OBS_NOISE=3, COMMAND=4, ACTION=5, DROP=6, PUSH=7, INIT=8, SHUFFLE=9)
 
 
 def default_config(**overrides) -> Config:

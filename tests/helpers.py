@@ -5,6 +5,8 @@ import subprocess
 
 import numpy as np
 
+from kbot_joystick_amd.spec.layout import RNG
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # Parity tolerances for ONE control step (5 substeps) started from the identical fp32 state, MEASURED (profiles/parity_r02.json,
@@ -421,8 +423,8 @@ HPARAM_HEAD_CASES = ["max_std=0.35", "min_std=0.2", "var_scale=1.5", "var_scale=
 HPARAM_SHAPES = [(64, 40, 32, 9), (256, 40, 32, 12)]
 
 
-# ---- the counter generator behind the action and init streams (kbj_model.h KBJ_RNG_ACTION = 5, KBJ_RNG_INIT = 8), vectorised ----
-RNG_ACTION, RNG_INIT = 5, 8
+# ---- the counter generator behind the action and init streams (kbj_model.h KBJ_RNG_ACTION, KBJ_RNG_INIT), vectorised ----
+RNG_ACTION, RNG_INIT = RNG["ACTION"], RNG["INIT"]
 # tools/head_check: the largest E_Z of its table (max of the derivable 2.16e-6 and 4 x the host fp32 restatement's error over a case's draws);
 # the device's worst |z - z_ref| measured against it is in EXPERIMENTS.md
 Z_BOUND = 3.3e-6

@@ -2,13 +2,10 @@
 Python mirrors, and the library refuses to run without a HIP device (no CPU fallback)."""
 import ctypes
 import os
-import re
 
 import pytest
 
 from kbot_joystick_amd.spec import compiler, layout as L
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -20,13 +17,9 @@ def lib():
 
 
 def test_every_declared_symbol_is_exported(lib):
-    hdr = open(os.path.join(ROOT, "include", "kbj.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(kbj_[a-z0-9_]+)\s*\(", hdr))
-    assert len(declared) >= 20
-    from kbot_joystick_amd.host import binding
-    assert declared == set(binding.SIGNATURES), declared ^ set(binding.SIGNATURES)
-    for name in declared:
+    from kbot_joystick_amd.host import binding      # SIGNATURES holds exactly the header's declarations: tests/test_abi_mirror.py
+    assert len(binding.SIGNATURES) >= 20
+    for name in binding.SIGNATURES:
         assert hasattr(lib, name), name
 
 

@@ -19,10 +19,7 @@ NU = L.NU
 
 
 def test_layout_mirrors_the_header():
-    hdr = open(os.path.join(ROOT, "include", "kbj_model.h")).read()
-    for prefix, table in (("KBJ_AACC_", L.AACC), ("KBJ_ACT_", L.ACT), ("KBJ_AJNT_", L.AJNT), ("KBJ_AENV_", L.AENV)):
-        found = {m.group(1): int(m.group(2)) for m in re.finditer(r"\b" + prefix + r"([A-Z_]+)\s*=\s*(\d+)", hdr)}
-        assert found == table, (prefix, found, table)
+    # (values against the header: tests/test_abi_mirror.py)
     assert M["COUNT"] * V["MODE_STRIDE"] == V["EPISODES"] < V["SIZE"] == 1792 and V["SIZE"] % 256 == 0 and V["JOINT"] + NU * J["SIZE"] <= V["MODE_STRIDE"] == 256
     assert J["SIZE"] == 12 and sorted(v for k, v in J.items() if k != "SIZE") == list(range(12)) and A == dict(PREV=0, RUNNING=20, SIZE=24) and E["SIZE"] == 12
     assert L.act_slot(2, "ANY_STOP_ROWS") == 516 and L.act_slot(1, "POW_MAX", 19) == 256 + 8 + 12 * 19 + 8

@@ -2,7 +2,6 @@
 mirrors, combining vectors (pure and over gloo), the scalars, the config field and the checkpoint members."""
 import dataclasses
 import os
-import re
 
 import numpy as np
 import torch
@@ -12,7 +11,6 @@ from kbot_joystick_amd.spec import layout as L
 from tests import episode_stats_ref as R
 
 E, A, X = L.EPST, L.EACC, L.AUX
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _random_problem(seed, T, N, p_done=0.3):
@@ -28,10 +26,7 @@ def _random_problem(seed, T, N, p_done=0.3):
 
 
 def test_layout_mirrors_the_header():
-    hdr = open(os.path.join(ROOT, "include", "kbj_model.h")).read()
-    for prefix, table in (("KBJ_EACC_", L.EACC), ("KBJ_EPST_", L.EPST)):
-        found = {m.group(1): int(m.group(2)) for m in re.finditer(prefix + r"([A-Z_]+)\s*=\s*(\d+)", hdr)}
-        assert found == table, (prefix, found, table)
+    # (values against the header: tests/test_abi_mirror.py)
     assert E["SIZE"] >= 24 and E["TERM_SUM"] + L.NREW <= E["SIZE"] and A["TERM"] + L.NREW <= A["SIZE"]
     slots = [E[k] for k in E if k not in ("SIZE", "TERM_SUM")] + list(range(E["TERM_SUM"], E["TERM_SUM"] + L.NREW))
     assert len(set(slots)) == len(slots)

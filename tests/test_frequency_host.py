@@ -5,7 +5,6 @@ points, the summary and the table on hand-made statistics."""
 import ctypes
 import math
 import os
-import re
 import types
 
 import numpy as np
@@ -22,11 +21,7 @@ f32 = np.float32
 
 
 def test_layout_mirrors_the_header():
-    hdr = open(os.path.join(ROOT, "include", "kbj_model.h")).read()
-    for prefix, table in (("KBJ_FOUT_", L.FOUT), ("KBJ_FREC_", L.FREC), ("KBJ_FSTAT_", L.FSTAT)):
-        found = {m.group(1): int(m.group(2)) for m in re.finditer(prefix + r"([A-Z_]+)\s*=\s*(\d+)", hdr)}
-        assert found == table, (prefix, found, table)
-    assert int(re.search(r"#define KBJ_FREC_NSUMS (\d+)", hdr).group(1)) == L.FREC_NSUMS == R["SIZE"] - R["S_R"] == 17
+    assert L.FREC_NSUMS == R["SIZE"] - R["S_R"] == 17                # (values against the header: tests/test_abi_mirror.py)
     assert [O[n.upper()] for n in constants.FREQUENCY_OUTCOME_NAMES] == list(range(O["COUNT"]))
     assert O["FELL"] == L.SOUT["FELL"] and O["CENSORED"] == L.SOUT["CENSORED"] and min(O[k] for k in ("FELL", "MEASURED", "FLAT", "CENSORED")) == O["FELL"]
     assert R["S_Y"] + L.NSCH == R["S_YY"] and R["S_YY"] + L.NSCH == R["S_YR"] and R["S_YR"] + L.NSCH == R["S_YD"] and R["S_YD"] + L.NSCH == R["SIZE"]

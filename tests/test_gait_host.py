@@ -5,7 +5,6 @@ table, the config field and the checkpoint members."""
 import dataclasses
 import math
 import os
-import re
 
 import numpy as np
 import pytest
@@ -19,10 +18,7 @@ DT = 0.02
 
 
 def test_layout_mirrors_the_header():
-    hdr = open(os.path.join(ROOT, "include", "kbj_model.h")).read()
-    for prefix, table in (("KBJ_GACC_", L.GACC), ("KBJ_GAIT_", L.GAIT), ("KBJ_GFOOT_", L.GFOOT), ("KBJ_GENV_", L.GENV)):
-        found = {m.group(1): int(m.group(2)) for m in re.finditer(prefix + r"([A-Z_]+)\s*=\s*(\d+)", hdr)}
-        assert found == table, (prefix, found, table)
+    # (values against the header: tests/test_abi_mirror.py)
     assert M["COUNT"] * G["MODE_STRIDE"] == G["EPISODES"] < G["SIZE"] == 256 and G["FOOT"] + 2 * G["FOOT_STRIDE"] == G["MODE_STRIDE"] == 40
     assert F["SIZE"] == G["FOOT_STRIDE"] and sorted(v for k, v in F.items() if k != "SIZE") == list(range(16))
     assert A["SIZE"] == 16 and A["PEAK"] < A["FOOT_STRIDE"] and 2 * A["FOOT_STRIDE"] == A["RUNNING"] and A["LAST_TD"] == 13

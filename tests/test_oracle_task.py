@@ -184,7 +184,7 @@ def test_command_mode_2_is_the_reference_sampler_on_jax_random_keys(model):
     ranges = dict(vx=(cfg.vx_lo, cfg.vx_hi), vy=(cfg.vy_lo, cfg.vy_hi), wz=(cfg.wz_lo, cfg.wz_hi), bh=(cfg.bh_lo, cfg.bh_hi), rx=(cfg.rx_lo, cfg.rx_hi),
                   ry=(cfg.ry_lo, cfg.ry_hi))
     lo = [model.dof_range[16 + j][0] for j in range(10)]; hi = [model.dof_range[16 + j][1] for j in range(10)]
-    STREAM = 4                                                   # KBJ_RNG_COMMAND (include/kbj_model.h)
+    STREAM = L.RNG["COMMAND"]                                    # KBJ_RNG_COMMAND (include/kbj_model.h)
 
     def call_key(env, a_, b_):
         return O.threefry((seed ^ (STREAM * 0x9E3779B9)) & 0xFFFFFFFF, env, a_, b_)
@@ -210,5 +210,5 @@ def test_command_mode_2_is_the_reference_sampler_on_jax_random_keys(model):
     # PlaneXYPositionReset (train.py:834-836): keyx, keyy = split(rng); uniform(key, (1,), -r, r)
     o2 = O.Oracle(model, cfg, seed=seed, precision="f32"); o2.reset_all()
     for e in range(8):
-        kx, ky = JR.split(O.threefry((seed ^ (1 * 0x9E3779B9)) & 0xFFFFFFFF, e, 1, 43), 2)          # KBJ_RNG_RESET = 1, episode 1, slot 43
+        kx, ky = JR.split(O.threefry((seed ^ (L.RNG["RESET"] * 0x9E3779B9)) & 0xFFFFFFFF, e, 1, 43), 2)          # KBJ_RNG_RESET, episode 1, slot 43
         assert o2.es[e, 0] == JR.uniform(kx, 1, -cfg.reset_xy_range, cfg.reset_xy_range)[0] and o2.es[e, 1] == JR.uniform(ky, 1, -cfg.reset_xy_range, cfg.reset_xy_range)[0]

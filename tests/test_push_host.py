@@ -4,7 +4,6 @@ PushRequest checks, ScriptedPush's schedule through UserTerms.apply_events again
 rotation against a float64 formula, and the table."""
 import math
 import os
-import re
 
 import numpy as np
 import pytest
@@ -19,12 +18,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_layout_mirrors_the_header():
     hdr = open(os.path.join(ROOT, "include", "kbj_model.h")).read()
-    for prefix, table in (("KBJ_POUT_", L.POUT), ("KBJ_PREC_", L.PREC), ("KBJ_PSTAT_", L.PSTAT)):
-        found = {m.group(1): int(m.group(2)) for m in re.finditer(prefix + r"([A-Z_]+)\s*=\s*(\d+)", hdr)}
-        assert found == table, (prefix, found, table)
-    assert float(re.search(r"#define KBJ_PUSH_NEVER ([0-9.]+)f", hdr).group(1)) == L.PUSH_NEVER == 2.0 ** 24
+    assert L.PUSH_NEVER == 2.0 ** 24                                                        # (values against the header: tests/test_abi_mirror.py)
     assert np.float32(L.PUSH_NEVER) - np.float32(1) == L.PUSH_NEVER - 1                     # exactly countable in fp32
-    assert int(re.search(r"#define KBJ_NPEAK (\d+)", hdr).group(1)) == L.NPEAK
     assert [O[n.upper()] for n in constants.PUSH_OUTCOME_NAMES] == list(range(O["COUNT"]))
     assert P["PEAK_LIN"] + L.NPEAK == P["PEAK_ROW"] and S["COUNT"] + O["COUNT"] == S["REC_SUM"] and S["PEAK_MAX"] + L.NPEAK <= S["SIZE"]
     for name in ("KBJ_ES_PUSH_REM", "KBJ_ES_PUSH_NXT"):                                       # counted in control steps, and said so

@@ -197,12 +197,10 @@ def test_observation_packing_order_matches_the_reference(ref):
 
 
 def test_header_observation_offsets_equal_layout():
-    import re
-    hdr = open(os.path.join(os.path.dirname(HERE), "include", "kbj_model.h")).read()
-    enums = {k: int(v) for k, v in re.findall(r"KBJ_OBS_([A-Z]+)\s*=\s*(\d+)", hdr)}
-    assert enums == {k: v[0] for k, v in L.OBS.items()}
-    assert float(re.search(r"KBJ_OBS_JVEL_DIV\s+([0-9.]+)f", hdr).group(1)) == L.OBS_JVEL_DIV
-    assert float(re.search(r"KBJ_OBS_ACTFRC_DIV\s+([0-9.]+)f", hdr).group(1)) == L.OBS_ACTFRC_DIV
+    from tests import abi_probe              # the header as the host compiler reads it; tests/test_abi_mirror.py: it has no KBJ_OBS_* beyond these
+    rep = abi_probe.report()
+    assert {k: rep.enums["KBJ_OBS_" + k] for k in L.OBS} == {k: v[0] for k, v in L.OBS.items()}
+    assert rep.floats["KBJ_OBS_JVEL_DIV"] == L.OBS_JVEL_DIV and rep.floats["KBJ_OBS_ACTFRC_DIV"] == L.OBS_ACTFRC_DIV
 
 
 def reference_mirror_table(ref, m, fn):

@@ -5,7 +5,6 @@ against a context that records its calls, the default transitions, the summary a
 import ctypes
 import math
 import os
-import re
 import types
 
 import numpy as np
@@ -21,12 +20,9 @@ f32 = np.float32
 
 
 def test_layout_mirrors_the_header():
-    hdr = open(os.path.join(ROOT, "include", "kbj_model.h")).read()
-    for prefix, table in (("KBJ_SSIG_", L.SSIG), ("KBJ_SOUT_", L.SOUT), ("KBJ_SREC_", L.SREC), ("KBJ_SSTAT_", L.SSTAT)):
-        found = {m.group(1): int(m.group(2)) for m in re.finditer(prefix + r"([A-Z_]+)\s*=\s*(\d+)", hdr)}
-        assert found == table, (prefix, found, table)
+    for table in (L.SSIG, L.SOUT, L.SREC, L.SSTAT):                  # (values against the header: tests/test_abi_mirror.py)
         assert table.get("SIZE", 0) % 4 == 0
-    assert int(re.search(r"#define KBJ_NSCH (\d+)", hdr).group(1)) == L.NSCH == len(constants.STEP_CHANNEL_NAMES) == 3
+    assert L.NSCH == len(constants.STEP_CHANNEL_NAMES) == 3
     assert constants.STEP_CHANNEL_NAMES == ("forward", "sideways", "yaw")
     assert [O[n.upper()] for n in constants.STEP_OUTCOME_NAMES] == list(range(O["COUNT"]))
     assert O["FELL"] == L.POUT["FELL"] and O["CENSORED"] == L.POUT["CENSORED"] and min(O[k] for k in ("FELL", "SETTLED", "UNSETTLED", "CENSORED")) == O["FELL"]

@@ -3,8 +3,6 @@ scalars, combining vectors, the config fields and checkpoint members, the defaul
 problems of tests/test_gpu_tracking_stats.py must meet for that test to mean something, with the float32-against-float64 spread its
 error bounds are built from."""
 import dataclasses
-import os
-import re
 
 import numpy as np
 
@@ -12,15 +10,10 @@ from kbot_joystick_amd.spec import constants, layout as L
 from tests import tracking_ref as TR
 
 K, A, R, X, M = L.TRK, L.TACC, L.TERR, L.AUX, L.CMODE
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_layout_mirrors_the_header():
-    hdr = open(os.path.join(ROOT, "include", "kbj_model.h")).read()
-    for prefix, table in (("KBJ_TACC_", L.TACC), ("KBJ_TRK_", L.TRK), ("KBJ_TERR_", L.TERR), ("KBJ_CMODE_", L.CMODE)):
-        found = {m.group(1): int(m.group(2)) for m in re.finditer(prefix + r"([A-Z_]+)\s*=\s*(\d+)", hdr)}
-        assert found == table, (prefix, found, table)
-    assert int(re.search(r"#define KBJ_NTERR (\d+)", hdr).group(1)) == L.NTERR == len(constants.TRACKING_ERROR_NAMES)
+    assert L.NTERR == len(constants.TRACKING_ERROR_NAMES)                                     # (values against the header: tests/test_abi_mirror.py)
     assert constants.COMMAND_MODE_NAMES == ("forward", "sideways", "rotate", "omni", "stand_bend", "stand")      # the switch list of train.py:752-762
     assert [M[n.upper()] for n in constants.COMMAND_MODE_NAMES] == list(range(M["COUNT"]))
     assert M["COUNT"] * K["MODE_STRIDE"] == K["CHANGES"] and K["MAX"] + L.NTERR <= K["MODE_STRIDE"] and K["EPISODES"] < K["SIZE"]
